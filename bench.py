@@ -6,7 +6,14 @@ per pixel (= 64 passes of the reference's Config::updateRendering()), from the d
 stream, rendered by the HIP path through the C ABI.  Inputs (seeds, scene tables, camera) are
 resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode parity|fast] [--no-cpu] [--workload c2|c16|c3|c4|c5|...|scn:<scene>]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode parity|fast] [--workload c2|c16|c3|c4|c5|...|scn:<scene>]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-extras]]
+
+A plain run sets up, warms up, times the K steps and prints the headline.  Everything else below (frames in flight, roofline,
+the extra blocks, the CPU baseline and the bit-exact comparison with it, at N > 1 the `c4` block and the in-library path) is
+measured only with --full.  --dump-outputs DIR writes the last timed frame as the caller receives it: DIR/pixels.npy (the packed
+frame of rt_read_pixels, its four bytes per pixel as float32, buffer row 0 = bottom of the image) and at N = 1 DIR/colors.npy
+(rt_read_colors: the running average, float32 RGB); past 64 MB in all, a fixed seeded sample of pixels (DIR/sample_index.npy).
 
 N > 1: one process per GPU (torch.distributed over RCCL); the image is sharded by interleaved 8-row
 tiles and each frame ends with one gather of the packed pixels to rank 0 and the library's
@@ -388,6 +395,30 @@ def cpu_baseline(spheres, cam, w, h, spp, reference_too=True):
     return base, out
 
 
+DUMP_BYTES = 63_000_000        # --dump-outputs: what the arrays may take in all (their .npy headers fit in the rest of 64 MB)
+
+
+def dump_outputs(out_dir, w, h, pixels, colors=None):
+    """--dump-outputs: the last timed frame as its caller receives it, as float32 (exact for both): `pixels` = the packed frame's
+    four bytes per pixel, `colors` = rt_read_colors' running average.  A frame whose arrays exceed DUMP_BYTES is written as a
+    fixed sample of its pixels (seed 0, the same for every run of the same size), their indices in sample_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n_px = w * h
+    arrays = {"pixels": np.ascontiguousarray(pixels).view(np.uint32).reshape(n_px).view(np.uint8).reshape(n_px, 4).astype(np.float32)}
+    if colors is not None:
+        arrays["colors"] = np.asarray(colors, np.float32).reshape(n_px, 3)
+    per_px = sum(a.shape[1] * 4 for a in arrays.values())
+    if per_px * n_px <= DUMP_BYTES:
+        arrays = {k: a.reshape(h, w, a.shape[1]) for k, a in arrays.items()}
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n_px, DUMP_BYTES // (per_px + 8), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as child processes BEFORE this
     process touches a GPU, pass their output through, leave with their exit code."""
@@ -462,9 +493,15 @@ def main():
                          "caustic3, demo_scn, complex, cornell_test, complex_test: sphere array and camera from tests/golden/) at the reference's 800x600, 64 spp")
     ap.add_argument("--frames-in-flight", type=int, default=0,
                     help="frames kept in flight per rank in the throughput region (0 = 2 for N<=2, 3 for N<=4, 6 beyond)")
-    ap.add_argument("--no-extras", action="store_true", help="headline regions only (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline regions only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: frames in flight, roofline, extras, CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame as DIR/<name>.npy (float32)")
     ap.add_argument("--inproc-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.inproc_child:
         return inproc_child(args)
@@ -538,6 +575,7 @@ def main():
     # F contexts, one HIP stream each (the contexts' own: created back to back they land on distinct hardware
     # queues, which streams from torch's pool did not always do)
     F = args.frames_in_flight if args.frames_in_flight > 0 else (2 if world <= 2 else (3 if world <= 4 else 6))
+    extras = args.full and not args.no_extras
 
     class FrameLoop:
         """The frame loop of one workload on this rank: `n_ctx` sharded contexts (one stream each), at N > 1 the gather buffers, the
@@ -562,6 +600,7 @@ def main():
             self.streams = [torch.cuda.ExternalStream(c.stream, device=dev) for c in self.ctxs]
             self.gather, self.want_dev, self.mismatch, self.whole_kernel_ms = None, None, None, None
             self.frame_no, self.frames_checked = 0, 0
+            self.keep_frame, self.kept = None, None     # rank 0 keeps a copy of gathered frame `keep_frame` (--dump-outputs)
             if world > 1:
                 self.gather = rdist.FrameGatherer(h, w, rank, world, TILE_ROWS, dev, slots=2 * n_ctx)
                 self.gather.pending_check = [False] * self.gather.slots
@@ -586,6 +625,8 @@ def main():
             full = g.wait(k)
             if rank == 0 and full is not None and g.pending_check[k % g.slots]:
                 self.mismatch.add_((full != self.want_dev).sum())
+                if k == self.keep_frame:
+                    self.kept = full.clone()
                 full.fill_(-1)
                 g.pending_check[k % g.slots] = False
                 self.frames_checked += 1
@@ -668,7 +709,8 @@ def main():
             dist.all_reduce(t, op=op)
         return [float(v) for v in t.tolist()]
 
-    loop = FrameLoop(spheres, cam, W, H, SPP, F)
+    # (a plain run times one frame at a time on the first context alone: the other F - 1 serve the frames-in-flight region of --full)
+    loop = FrameLoop(spheres, cam, W, H, SPP, F if args.full else 1)
     ctxs, side_streams, ctx = loop.ctxs, loop.streams, loop.ctxs[0]
 
     def timed_region(contexts, streams, in_flight, steps, warmup, with_events=True):
@@ -682,11 +724,17 @@ def main():
         return loop.frame_counters(c)
 
     # ---- the headline: one frame at a time -------------------------------------------------------------
+    if args.dump_outputs and world > 1:
+        loop.keep_frame = loop.frame_no + args.warmup + args.steps - 1
     el1, kernel_ms, last1 = loop.timed_region(1, args.steps, args.warmup, with_events=True)
     last_pixels = last1.read_pixels() if world == 1 else None       # the last TIMED frame (checked against the oracle below)
+    if args.dump_outputs and world == 1:
+        dump_outputs(args.dump_outputs, W, H, last_pixels, last1.read_colors())
+    elif args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, W, H, loop.kept.cpu().numpy())
     # ---- the same K frames with F in flight (throughput) ------------------------------------------------
     elF = None
-    if F > 1 and not args.no_extras:
+    if F > 1 and extras:
         elF, _, _ = loop.timed_region(F, args.steps, args.warmup, with_events=False)
     st = loop.frame_counters(ctx)
     kernel_name = ctx.last_kernel           # the instance the library renders this scene with (rt_last_kernel)
@@ -703,7 +751,7 @@ def main():
 
     # ---- extras, N = 1, outside the headline's timed regions -------------------------------------------
     other, target, in_library, large, unseen, first = None, None, None, None, None, None
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         # The headline renders the SAME frame K times (reset + SPP passes, fixed seed stream: what makes it checkable against the
         # oracle), and the library schedules a launch from what the launch before cost (tile order) -- costs that
         # are exact for a frame rendered again.  The same launch on passes it has NOT seen: SPP more passes of the running image
@@ -833,7 +881,7 @@ def main():
     # 1/2/4/8 curve: a 1080p x 64 frame is short against its slowest wavefront, this one is not.  One frame at a time, every
     # gathered frame compared with the unsharded one on rank 0's GPU, exactly as the headline's ----
     c4_block = None
-    if world > 1 and not args.no_extras and args.workload == "c2":
+    if world > 1 and extras and args.workload == "c2":
         W4, H4, SPP4 = 3840, 2160, 256
         sph4 = host.demo_scene()
         cam4 = host.compute_camera(host.DEMO_ORIG, host.DEMO_TARGET, W4, H4)
@@ -862,7 +910,7 @@ def main():
     if rank != 0:
         return 0
 
-    if world > 1 and not args.no_extras and args.workload == "c2":
+    if world > 1 and extras and args.workload == "c2":
         # the in-library path on the same GPUs, as a child process (the ranks have released their communicator);
         # never allowed to take the headline down with it
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK",
@@ -877,7 +925,7 @@ def main():
             in_library = {"error": repr(e)[:400]}
 
     bound = None
-    if not args.no_extras:
+    if extras:
         try:
             bound = scaling_bound(api, mode, spheres, cam, W, H, SPP, kernel_ms if world == 1 else None, device=local_rank)
         except Exception as e:       # noqa: BLE001 -- a diagnostics figure never takes the headline down
@@ -885,7 +933,7 @@ def main():
     # every shard of a 2 / 4 / 8-way split rendered ALONE on this GPU (tools/shard_prediction.py): what each GPU of an N-GPU run
     # would spend on the frame, imbalance and under-filled GPU included -- for this line's workload and for C4
     shards = None
-    if not args.no_extras:              # (at N > 1 too: rank 0's GPU, alone by now -- the prediction stands beside the measurement it predicts)
+    if extras:                          # (at N > 1 too: rank 0's GPU, alone by now -- the prediction stands beside the measurement it predicts)
         try:
             from tools import shard_prediction
             shards = {args.workload: shard_prediction.predict(api, mode, spheres, cam, W, H, SPP, whole_ms=kernel_ms if world == 1 else None,
@@ -902,18 +950,20 @@ def main():
     value = rays * args.steps / el1_max / 1e6
     # roofline of the dominant (only) kernel, per launch, from this rank's launches in the headline region
     # (HIP events on the stream the kernel is launched on; launches do not overlap there)
-    census = None
-    if world == 1 and "_pairs" in kernel_name:
-        try:
-            census = walk_census(api, spheres, cam, W, H, SPP)
-        except api.RtError:            # (the census instance stages the whole tables in LDS: scenes beyond that have no executed-work count)
-            census = None
-    roofline = roofline_block(kernel_name, kernel_ms, st["sphere_tests"], my_local_rows * W, len(spheres), args.workload, args.mode,
-                              census=census, choice=choice)
-    if world > 1:
-        roofline["traffic"] = None          # the committed counters describe the unsharded launch
-        roofline.pop("executed", None)
-    roofline["kernel_ms_max_rank"] = round(kernel_ms_max, 4)
+    roofline = None
+    if args.full:
+        census = None
+        if world == 1 and "_pairs" in kernel_name:
+            try:
+                census = walk_census(api, spheres, cam, W, H, SPP)
+            except api.RtError:            # (the census instance stages the whole tables in LDS: scenes beyond that have no executed-work count)
+                census = None
+        roofline = roofline_block(kernel_name, kernel_ms, st["sphere_tests"], my_local_rows * W, len(spheres), args.workload, args.mode,
+                                  census=census, choice=choice)
+        if world > 1:
+            roofline["traffic"] = None          # the committed counters describe the unsharded launch
+            roofline.pop("executed", None)
+        roofline["kernel_ms_max_rank"] = round(kernel_ms_max, 4)
     line = {
         "metric": "Mray/s (primary+shadow) at 1080p 64spp" if args.workload == "c2"
                   else f"Mray/s (primary+shadow) at {W}x{H} {SPP}spp",
@@ -936,11 +986,13 @@ def main():
                    "sharding": f"interleaved {TILE_ROWS}-row tiles x {world}",
                    "perfect_balance_estimate": bound,
                    "predicted_from_shards": shards,
+                   "kernel": kernel_name, "kernel_ms_max_rank": round(kernel_ms_max, 4),
                    "rays_per_frame": rays, "all_rays_per_frame": closest + shadow,
                    "Mray_s_all_rays": round((closest + shadow) * args.steps / el1_max / 1e6, 1),
                    "Msample_s": round(samples * args.steps / el1_max / 1e6, 1)},
-        "roofline": roofline,
     }
+    if roofline is not None:
+        line["roofline"] = roofline
     if elF_max is not None:
         line["frames_in_flight"] = {"frames": F, "ms_per_step": round(elF_max / args.steps * 1e3, 4),
                                     "value": round(rays * args.steps / elF_max / 1e6, 1), "unit": "Mray/s",
@@ -959,12 +1011,12 @@ def main():
         line["c4"] = c4_block
     if in_library is not None:
         line["in_library_multi_gpu"] = in_library
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         try:
             line["host_inclusive"] = host_inclusive(spheres, cam, W, H, SPP, kernel_ms)
         except Exception as e:       # noqa: BLE001 -- a side figure never takes the headline down
             line["host_inclusive"] = {"error": repr(e)[:300]}
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         base, cpu_out = cpu_baseline(spheres, cam, W, H, SPP)
         line["cpu_baseline"] = base
         if args.mode == "parity":

@@ -3,10 +3,10 @@
 # counters into profiles/pmc_traffic.json, so that the lines carry `traffic` / `executed`):  tools/bench_records.sh TAG
 set -u
 TAG=${1:-bench}; O=gpurun_out/$TAG; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 rm -f $O/bench_workloads.jsonl
 for wl in c16 c3 c4 c5 box120 r2048; do
-    python bench.py --workload $wl --steps 6 --warmup 3 --no-cpu >> $O/bench_workloads.jsonl 2>> $O/bench_workloads.err
+    python bench.py --full --workload $wl --steps 6 --warmup 3 --no-cpu >> $O/bench_workloads.jsonl 2>> $O/bench_workloads.err
 done
 python - "$O" <<'PY'
 import json, sys

@@ -31,10 +31,10 @@ done
 # the measurement of coop against plain inside a scene's first long frame (what launch_small does NOT do) against the deferred one
 run coop_probe_first_frame.jsonl python tools/first_frame_probe.py
 bash tools/pmc_walk_g.sh r8192 rt_trace_parity_pairs_g,rt_trace_parity_pairs_gq,rt_trace_parity_pairs_gt $TAG/pmc_l2 > $O/l2_walk_pmc.txt 2>&1
-run bench_default.json python bench.py --steps 20 --warmup 5
+run bench_default.json python bench.py --full --steps 20 --warmup 5
 for wl in c16 c3 c4 c5 r8192; do
-    timeout -k 10 400 python bench.py --workload $wl --steps 6 --warmup 3 >> $O/bench_other_workloads.jsonl 2>> $O/bench_other.err
+    timeout -k 10 400 python bench.py --full --workload $wl --steps 6 --warmup 3 >> $O/bench_other_workloads.jsonl 2>> $O/bench_other.err
 done
-RT_BENCH_SINGLE_DEVICE=1 timeout -k 10 400 python bench.py --gpus 2 --steps 6 --warmup 2 > $O/bench_n2_rehearsal.json 2> $O/bench_n2.err
+RT_BENCH_SINGLE_DEVICE=1 timeout -k 10 400 python bench.py --full --gpus 2 --steps 6 --warmup 2 > $O/bench_n2_rehearsal.json 2> $O/bench_n2.err
 raytracing_simple_amd/rt_bench 2 1 0 --w 1920 --h 1080 --spp 64 --oneshot 9 > $O/rt_bench_oneshot.json 2>&1
 echo "records $TAG done"

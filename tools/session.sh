@@ -11,16 +11,16 @@ if [ "$PART" = "A" ]; then
     python -m pytest tests -m gpu -q --timeout 900 --maxfail=12 -p no:cacheprovider > $O/pytest.log 2>&1; rc=$?
     tail -3 $O/pytest.log
     [ $rc -le 1 ] || exit $rc
-    python bench.py --steps 20 --warmup 5 > $O/bench_parity.json 2> $O/bench_parity.err && tail -c 400 $O/bench_parity.json
-    python bench.py --steps 20 --warmup 5 --mode fast --no-cpu > $O/bench_fast.json 2> $O/bench_fast.err
+    python bench.py --full --steps 20 --warmup 5 > $O/bench_parity.json 2> $O/bench_parity.err && tail -c 400 $O/bench_parity.json
+    python bench.py --full --steps 20 --warmup 5 --mode fast --no-cpu > $O/bench_fast.json 2> $O/bench_fast.err
     for wl in c16 c3 c4 c5; do
-        python bench.py --workload $wl --steps 6 --warmup 3 >> $O/bench_other_workloads.jsonl 2>> $O/bench_other.err
+        python bench.py --full --workload $wl --steps 6 --warmup 3 >> $O/bench_other_workloads.jsonl 2>> $O/bench_other.err
     done
     python tools/ab_bench.py --configs c2,c16,c64,c256,c3,c5,c4 --modes 0,1 --rounds 5 > $O/ab_all_configs.jsonl 2>&1
     cut -c1-220 $O/ab_all_configs.jsonl
     raytracing_simple_amd/rt_bench 2 1 0 --w 1920 --h 1080 --spp 64 --oneshot 8 | tee $O/rt_bench_oneshot.json
     raytracing_simple_amd/rt_inflight 1 20 | tee $O/rt_inflight.jsonl; raytracing_simple_amd/rt_inflight 2 20 | tee -a $O/rt_inflight.jsonl
-    RT_BENCH_SINGLE_DEVICE=1 timeout -k 10 300 python bench.py --gpus 2 --steps 6 --warmup 2 > $O/bench_n2_rehearsal.json 2> $O/bench_n2.err; tail -c 300 $O/bench_n2_rehearsal.json
+    RT_BENCH_SINGLE_DEVICE=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 6 --warmup 2 > $O/bench_n2_rehearsal.json 2> $O/bench_n2.err; tail -c 300 $O/bench_n2_rehearsal.json
 elif [ "$PART" = "P" ]; then
     # every shipped parity instance has a stamped record: _w1 (c2), _coop_w1 (c16, c5), _pairs (c3), _coop (box120), _pairs_m (r2048), _pairs_g (r8192),
     # rt_trace_parity_g (nan9800) -- tests/test_abi.py holds the set to the library's build id
