@@ -381,7 +381,11 @@ RT_API int rt_set_mode(rt_ctx *c, int mode) {
     if (!ok) return fail(RT_ERR_ARG, "mode %d", mode);
     if (c->multi) return rt::multi_set_mode(c, mode);
     c->mode = mode;
+#if RT_DIAGNOSTICS
+    return rt::debug_layout_for_mode(c);        // (an A/B instance gets the pair table it reads: rt_debug.hip)
+#else
     return RT_OK;
+#endif
 }
 
 RT_API int rt_reset(rt_ctx *c) {

@@ -1073,9 +1073,9 @@ hipError_t prepare_bvh_build() {
 // the tree is decided here, from the host mirror, with the test the device applies to the same bits: the cut is 16 times the
 // median |radius| and at least an eighth of the scene's extent (ground, walls, lights of the scene's size), non-finite records stay
 // outside as well.
-// After any builder: the top of the tree to the front of the pair table, where the walk will read its tables from HBM / L2 -- i.e. where not even
-// the pairs fit the LDS budget the context gives the hierarchy (rt_launch.hip makes the same comparison per launch).  Costs one small launch per
-// build (20-60 us); trees that are walked from LDS keep the builders' numbering.
+// After any builder, in the diagnostics library and only when asked for (rt_debug_set_bvh_layout): the top of the tree to the front of the pair
+// table, for the A/B walks that stage it (rt_trace_*_pairs_gt, _gtp).  Costs one small launch per build (20-60 us).  By default every tree keeps
+// the builders' numbering -- the layout the product library walks.
 static int promote_top(rt_ctx *c, hipStream_t stream) {
     c->bvh.n_top = 0;
 #if !RT_DIAGNOSTICS
@@ -1084,16 +1084,12 @@ static int promote_top(rt_ctx *c, hipStream_t stream) {
 #else
     if (!c->bvh_ok || c->bvh.n_leaves < 2 || c->bvh_top_pairs <= 0) return RT_OK;
     const uint32_t n_pairs = c->bvh.n_leaves - 1u;
-    const size_t pairs_lds = rt::lds_bytes_pairs(0, 0, false, 64, c->bvh.n_leaves, 0, c->bvh.stack_depth, 256);
-    if (!RT_DIAGNOSTICS && c->bvh_mixed != 0 && pairs_lds <= (size_t)c->bvh_lds_limit) return RT_OK;       // (rt_trace_*_pairs / _pairs_m will walk it: everything it chases is in LDS; the diagnostics library, where any instance may be asked for by name, always promotes)
     const size_t used = rt::bvh_blob_float4s(c->bvh.n_leaves, c->bvh.n_slots);
     const size_t scratch4 = 4 * (size_t)n_pairs + ((size_t)n_pairs * 2 + 15) / 16 + 1;
     if (used + scratch4 > (size_t)c->scene_cap * 6 + 64) return RT_OK;                   // (no room behind the blob: the tree stays as it is, nothing is staged)
     uint32_t top = std::min<uint32_t>((uint32_t)c->bvh_top_pairs, rt::kBvhTopPairs);
-#if RT_DIAGNOSTICS
     if (const char *e = getenv("RT_TOP_PAIRS")) top = std::min<uint32_t>((uint32_t)atoi(e), 256u);       // (experiments: how much of the top is worth staging)
     if (top == 0u) return RT_OK;
-#endif
     hipLaunchKernelGGL(rt_bvh_promote_kernel, dim3(1), dim3(1024), 0, stream, c->d_bvh, c->bvh.n_slots, c->bvh.n_leaves, top, c->d_bvh + used);
     HIP_TRY(hipGetLastError());
     c->bvh.n_top = std::min(top, n_pairs);
@@ -1101,7 +1097,8 @@ static int promote_top(rt_ctx *c, hipStream_t stream) {
 #endif
 }
 
-// ... and the packed pair table behind the blob (where the promotion's scratch was: it is dead by then -- same stream), for the same trees
+// ... and the packed pair table behind the blob (where the promotion's scratch was: it is dead by then -- same stream), for the A/B walks that
+// read it (rt_trace_*_pairs_gq, _gtp), likewise only when asked for
 static int pack_pairs(rt_ctx *c, hipStream_t stream) {
     c->bvh.packed_at = 0;
 #if !RT_DIAGNOSTICS
@@ -1110,8 +1107,6 @@ static int pack_pairs(rt_ctx *c, hipStream_t stream) {
 #else
     if (!c->bvh_ok || c->bvh.n_leaves < 2 || c->bvh_packed == 0) return RT_OK;
     const uint32_t n_pairs = c->bvh.n_leaves - 1u;
-    const size_t pairs_lds = rt::lds_bytes_pairs(0, 0, false, 64, c->bvh.n_leaves, 0, c->bvh.stack_depth, 256);
-    if (!RT_DIAGNOSTICS && c->bvh_mixed != 0 && pairs_lds <= (size_t)c->bvh_lds_limit) return RT_OK;       // (walked from LDS: nothing reads a packed table -- but for an instance asked for by name in the diagnostics library)
     const size_t used = rt::bvh_blob_float4s(c->bvh.n_leaves, c->bvh.n_slots);
     if (used + 2 + 2 * (size_t)n_pairs > (size_t)c->scene_cap * 6 + 64) return RT_OK;
     const unsigned blocks = (unsigned)std::min<size_t>((n_pairs + 255) / 256, 1024);

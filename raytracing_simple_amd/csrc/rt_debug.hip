@@ -253,12 +253,37 @@ static int dbg_set_tree_shape(rt_ctx *c, int v) {
     c->bvh_sah = v < 0 ? 0 : (v > 2 ? 2 : v);
     return dbg_set_bvh_min(c, c->bvh_min);          // (rebuilds the current scene's tables, re-arms the probe)
 }
+// rt_set_mode of an A/B instance that reads a table the product's layout lacks -- ..._gt / _gtp the promoted top, _gq the packed pair table --
+// asks for it as rt_debug_set_bvh_layout would (kept for the context's later scenes) and rebuilds the current scene's tables at once.  Any
+// other instance leaves the layout as it is.  (bind_tables still refuses such an instance on a tree without its table: a layout set back to
+// 0 after the mode, a blob without room behind it.)
+extern "C++" int rt::debug_layout_for_mode(rt_ctx *c) {
+    if (c->mode < 100 || c->mode >= 200) return RT_OK;
+    int n = 0;
+    const rt::Instance &inst = rt::parity_instances(&n)[c->mode - 100];
+    const bool top = inst.tables == rt::kTabPairsTopLds && c->bvh_top_pairs <= 0;
+    const bool packed = inst.tables == rt::kTabPairsPacked && c->bvh_packed == 0;
+    if (!top && !packed) return RT_OK;
+    if (top) c->bvh_top_pairs = (int)rt::kBvhTopPairs;
+    if (packed) c->bvh_packed = 1;
+    return dbg_set_bvh_min(c, c->bvh_min);          // (rebuilds the current scene's tables)
+}
 // The hierarchy's shape.  1 (default): by surface area -- uploads whose choice of form is estimated (below 1500 tree spheres) on the host,
 // larger uploads and every device-resident update on the device; 2: on the device for every upload too; 0: the fixed (halved) shape
 // everywhere.  Takes effect at once.
 RT_API int rt_debug_set_tree_shape(rt_ctx *c, int by_area) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     return dbg_apply(c, dbg_set_tree_shape, by_area);
+}
+static int dbg_set_top_pairs(rt_ctx *c, int v) { c->bvh_top_pairs = v; return RT_OK; }
+static int dbg_set_packed(rt_ctx *c, int v) { c->bvh_packed = v ? 1 : 0; return RT_OK; }
+// The pair table's layout for the A/B walks (rt_bvh.hip promote_top, pack_pairs): top_pairs > 0 promotes the top of the tree to the front of the
+// table, packed != 0 writes the packed pair table.  0, 0 (default) is the product library's layout.  Applies from the next build of the tables.
+RT_API int rt_debug_set_bvh_layout(rt_ctx *c, int top_pairs, int packed) {
+    if (!c || top_pairs < 0 || top_pairs > (int)rt::kBvhTopPairs || packed < 0 || packed > 1)
+        return fail(RT_ERR_ARG, "top_pairs %d (0..%u), packed %d (0 / 1)", top_pairs, rt::kBvhTopPairs, packed);
+    const int rc = dbg_apply(c, dbg_set_top_pairs, top_pairs);
+    return rc != RT_OK ? rc : dbg_apply(c, dbg_set_packed, packed);
 }
 static int dbg_set_walk_gate(rt_ctx *c, int v) { if (v > 0) c->walk_gate = v; return RT_OK; }
 static int dbg_set_walk_round(rt_ctx *c, int v) { c->walk_round = v; return RT_OK; }

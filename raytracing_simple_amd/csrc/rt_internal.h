@@ -54,8 +54,9 @@ struct rt_ctx {
     int bvh_min = 56;                   // scenes with at least this many spheres inside the tree use it (0 = never)
     int bvh_lds_limit = 31 * 1024;      // its tables are staged in LDS while five workgroups of that size fit a CU (2048 spheres: 6.2 ms from L2 with
                                         // 4-5 waves per SIMD against 9.5 ms from LDS with two workgroups per CU); larger ones are read from HBM / L2
-    int bvh_top_pairs = (int)rt::kBvhTopPairs;   // pairs promoted to the front of the table for the walk that reads it from HBM / L2 (rt_bvh.hip promote_top; diagnostics knob: 0 = none)
-    int bvh_packed = 1;                 // the packed pair table is built for trees the walk reads from HBM / L2 (rt_bvh.hip pack_pairs; diagnostics knob: 0 = never)
+    int bvh_top_pairs = 0;              // pairs promoted to the front of the table for the A/B walks that stage the top (rt_bvh.hip promote_top; diagnostics only,
+                                        // rt_debug_set_bvh_layout: 0 = none -- the product's layout, which keeps the builders' numbering)
+    int bvh_packed = 0;                 // the packed pair table behind the blob for the A/B walk that reads it (rt_bvh.hip pack_pairs; diagnostics only, 0 = none)
     int bvh_mixed = 1;                  // tables beyond that limit whose PAIRS fit it: pairs staged, slots from HBM / L2 (rt_trace_*_pairs_m); diagnostics knob: 0 = everything from L2
     int walk_gate = 16, walk_round = 4; // rt_walk.inc.h: ready lanes that make the wavefront shade; pair steps in a row before a leaf step
                                         // (round 4, this kernel: 2 / 3 / 4 / 6 in a row = 5.42 / 5.37 / 5.22 / 5.45 ms on C3, profiles/r04k_walk_sweep.jsonl)
@@ -212,6 +213,7 @@ const char *multi_last_kernel(const rt_ctx *front);
 rt_ctx *multi_first_shard(rt_ctx *front);
 rt_ctx *multi_shard(rt_ctx *front, int r);
 int multi_debug_each(rt_ctx *front, int (*fn)(rt_ctx *, int), int arg);
+int debug_layout_for_mode(rt_ctx *c);                 // diagnostics (rt_debug.hip): rt_set_mode of an A/B instance builds the pair table it reads
 int multi_debug_break(rt_ctx *front);
 int multi_debug_set_rccl(const char *path, int repeated_counts_as_distinct);   // diagnostics build
 

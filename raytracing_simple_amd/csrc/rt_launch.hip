@@ -162,6 +162,8 @@ static int bind_tables(rt_ctx *c, const rt::Instance &inst, int n_samples, rt::L
             lds = rt::lds_bytes_pairs(0, 0, false, n_samples, 1, 0, c->bvh.stack_depth, 64 * inst.waves) + 32;
             break;
         case rt::kTabPairsTopLds:           // header | the promoted top of the tree (n_top pairs = "n_top + 1 leaves") | stacks
+            if (c->bvh.n_top == 0 && c->bvh.n_leaves >= 2)          // (without a promoted top the root is not pair 0: rt_debug_set_bvh_layout asks for one)
+                return fail(RT_ERR_STATE, "%s stages the promoted top of the tree and this scene's hierarchy has none", inst.name);
             p.mat_in_lds = 0;
             lds = rt::lds_bytes_pairs(0, 0, false, n_samples, c->bvh.n_top + 1, 0, c->bvh.stack_depth, 64 * inst.waves);
             break;

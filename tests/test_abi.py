@@ -308,3 +308,76 @@ def test_profile_counters_are_bound_to_the_code_they_describe(tmp_path, monkeypa
     monkeypatch.setattr(bench, "library_build_id", lambda: lib_id)                       # same library, another kernel instance
     other = bench.roofline_block("rt_trace_parity_coop_w1", 2.6, 1788296212, 1920 * 1080, 6, "c2", "parity")
     assert other["traffic"] is None and "executed" not in other
+
+
+def _listing(*insns):
+    """A synthetic kernel listing in llvm-objdump's layout, four bytes per instruction from address 0x100; a branch's operand is written
+    as `@k`, the index of its target, and turned into the dword offset the disassembler prints."""
+    lines = ["0000000000000100 <k>:"]
+    for k, text in enumerate(insns):
+        m = re.search(r"@(\d+)", text)
+        if m:
+            text = text.replace(m.group(0), str((int(m.group(1)) - k - 1) & 0xFFFF))
+        lines.append("\t%-58s // %012X: 00000000" % (text, 0x100 + 4 * k))
+    return lines
+
+
+_CLEAN = ["s_mov_b32 s5, 0",
+          "s_load_dwordx16 s[16:31], s[2:3], 0x0",
+          "s_add_u32 s2, s66, s2",                      # other scalar registers are free
+          "v_writelane_b32 v40, s32, 3",
+          "s_cbranch_vccz @6",
+          "s_mov_b32 s4, s15",
+          "s_waitcnt lgkmcnt(0)",
+          "s_mov_b32 s4, s16",                          # after the wait: the records are there
+          "s_cbranch_scc1 @1",                          # a loop back to the load, behind the wait
+          "s_endpgm"]
+
+
+def test_scalar_load_path_checker_on_synthetic_listings():
+    """tools/scalar_load_paths.py: a clean listing passes; each way of touching the sixteen registers of an s_load_dwordx16 before the
+    s_waitcnt lgkmcnt(0) that makes them valid -- on ANY path: fall-through, taken branch, backward branch -- is flagged."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import scalar_load_paths as S
+    assert S.check_kernel(_listing(*_CLEAN)) == (1, [])
+    assert S.check_kernel(_listing("s_mov_b32 s4, 0", "s_endpgm")) == (0, [])
+
+    def flagged(*insns):
+        n, bad = S.check_kernel(_listing(*insns))
+        return n >= 1 and len(bad) >= 1
+
+    load, wait = "s_load_dwordx16 s[16:31], s[2:3], 0x0", "s_waitcnt lgkmcnt(0)"
+    assert flagged(load, "s_mov_b32 s4, s20", wait, "s_endpgm")                          # a destination register read before the wait
+    assert flagged(load, "s_mov_b32 s31, 0", wait, "s_endpgm")                           # ... written (reused) before it
+    assert flagged(load, "s_add_u32 s2, s[30:31], 1", wait, "s_endpgm")                  # ... named within a range
+    assert flagged(load, "v_writelane_b32 v40, s17, 0", wait, "s_endpgm")                # copied into a lane
+    assert flagged(load, "s_cbranch_vccz @4", wait, "s_endpgm", "s_mov_b32 s4, s16", "s_endpgm")     # a branch past the wait
+    assert flagged(load, "s_cbranch_scc0 @3", wait, "s_endpgm")                          # ... to the end of the program
+    assert flagged(load, "s_waitcnt lgkmcnt(1)", "s_mov_b32 s4, s16", wait, "s_endpgm")  # a wait that leaves one access outstanding
+    assert flagged(load, "s_waitcnt vmcnt(0)", "s_mov_b32 s4, s16", "s_endpgm")          # a wait for vector memory only
+    assert flagged("s_mov_b32 s5, 0", load, "s_add_u32 s5, s5, 1", "s_cbranch_scc1 @1", wait, "s_endpgm")   # the load again, no wait between
+    assert flagged(load, "s_branch @3", wait, "s_mov_b32 s4, s18", "s_endpgm")           # an unconditional branch over the wait
+    assert flagged(load, "s_mov_b32 s4, 0", "s_endpgm")                                  # the program ends, never waited for
+    # a backward branch to before the load that reads the registers there
+    assert flagged("s_mov_b32 s4, s16", load, "s_cbranch_scc1 @0", wait, "s_endpgm")
+    # and a conditional branch whose fall-through is clean but whose target is not (both sides are followed)
+    assert flagged(load, "s_cbranch_execz @5", wait, "s_nop 0", "s_endpgm", "v_mov_b32_e32 v1, s16", "s_endpgm")
+    assert not flagged(load, "s_cbranch_execz @5", wait, "s_nop 0", "s_endpgm", wait, "v_mov_b32_e32 v1, s16", "s_endpgm")
+    assert S.branch_offset("65432") == -104 and S.branch_offset("33") == 33
+    assert S.waits_for_scalar_loads("s_waitcnt", "vmcnt(0) lgkmcnt(0)") and S.waits_for_scalar_loads("s_waitcnt", "0")
+    assert S.waits_for_scalar_loads("s_waitcnt", "0xc07f") and not S.waits_for_scalar_loads("s_waitcnt", "0xc17f")     # (raw: lgkmcnt in bits 11:8)
+
+
+def test_scalar_loads_of_the_shipped_sweeps_are_waited_for_on_every_path():
+    """rt_trace_{parity,fast}_g request four records with s_load_dwordx16 in one asm statement and wait for them in another
+    (rt_trace.inc.h request_four_uniform / arrived): the compiler sees the sixteen registers as defined at the request.  On every
+    path from each such load -- fall-through, both sides of each branch, backward too -- an s_waitcnt lgkmcnt(0) must come before any
+    instruction that names one of them, before the program ends and before the load is reached again.  Read from the product library's
+    gfx950 code objects; each kernel holds at least one such load (four today: two pipelined pairs), so the test is not vacuous."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import scalar_load_paths as S
+    kernels = S.disassemble(api.lib_path())
+    for name in ("rt_trace_parity_g", "rt_trace_fast_g"):
+        n, bad = S.check_kernel(kernels[name])
+        assert n >= 1, name
+        assert bad == [], (name, bad[:5])

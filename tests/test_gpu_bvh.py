@@ -35,6 +35,7 @@ def _render(sph, cam, w, h, spp, bvh_min=1, form=1, mode=api.RT_MODE_PARITY, pas
                 "pick": ctx._lib.rt_debug_bvh_pick(ctx._h)}
 
 
+# (rt_set_mode of the _gq / _gt arms builds the pair table they read; _g and _gp walk the product's layout)
 L2_WALKS = ["rt_trace_parity_pairs_g", "rt_trace_parity_pairs_gq", "rt_trace_parity_pairs_gt", "rt_trace_parity_pairs_gp"]
 
 
@@ -47,37 +48,102 @@ def _same(got, want):
            (o["samples"], o["closest_calls"], o["shadow_calls"], o["sphere_tests"], o["rng_draws"])
 
 
-@pytest.mark.parametrize("maker", [lambda: scenes.random_spheres(1024), lambda: scenes.random_spheres(97),
-                                   lambda: scenes.mirror_box(64), lambda: scenes.demo_plus(16),
-                                   lambda: (host.demo_scene(), host.DEMO_ORIG, host.DEMO_TARGET)])
-def test_device_built_tables_are_a_valid_hierarchy(maker):
+_BUILD_SCENES = [lambda: scenes.random_spheres(1024), lambda: scenes.random_spheres(97), lambda: scenes.mirror_box(64), lambda: scenes.demo_plus(16),
+                 lambda: (host.demo_scene(), host.DEMO_ORIG, host.DEMO_TARGET)]
+
+
+def _every_build(sph, layout=None):
     """All three builds: the device's fixed shape (leaf ranges halved), the host's of a full scene upload (the shape chosen by surface
     area, leaves of up to 8; the default below 1500 tree spheres) and the device's by surface area (cuts between whole leaves; what
     updates and large uploads get) -- every leaf reached once from the root pair the header names, every sphere in one leaf, inside
-    every box above it, lowest scene indices right, the stack deep enough."""
-    sph, _, _ = maker()
-    sph = api.as_spheres(sph)
-    leaves, area = {}, {}
+    every box above it, lowest scene indices right, the stack deep enough.  layout: rt_debug_set_bvh_layout's arguments, None = the library's
+    default.  Returns {by_area: (tables, packed table)}."""
+    out, leaves, area = {}, {}, {}
     for by_area in (0, 1, 2):
         with api.RtContext(64, 64, diag=True) as ctx:
             ctx._check(ctx._lib.rt_debug_set_tree_shape(ctx._h, by_area))
+            if layout is not None:
+                ctx._check(ctx._lib.rt_debug_set_bvh_layout(ctx._h, *layout))
             ctx._check(ctx._lib.rt_debug_set_bvh(ctx._h, 1, 0))
             ctx.set_scene(sph)
             b = bvh_check.read_bvh(ctx)
             pk = bvh_check.read_packed(ctx)
         assert b is not None
         assert bvh_check.check_structure(sph, b) == []
-        if b["n_leaves"] > 1:               # the diagnostics library promotes the top of EVERY tree and packs its pairs (rt_bvh.hip promote_top, pack_pairs)
-            assert b["root"] == 0
-            assert pk is not None and bvh_check.check_packed(b, pk) == []
         assert b["n_always"] + sum(1 for i in b["index"][b["n_always"]:] if i != 0xffffffff) == len(bvh_check.first_of_equals(sph))
         leaves[by_area] = b["n_leaves"]
         area[by_area] = bvh_check.sum_of_box_areas(b)
+        out[by_area] = (b, pk)
     assert leaves[0] <= leaves[1] <= 2 * leaves[0]              # partial leaves only where they pay (below 128 tree spheres both are the device's)
     assert leaves[2] == leaves[0]                               # the device cuts between whole leaves
     n_tree = len(sph) - b["n_always"]
     if n_tree >= 128:                                           # (below that every build is the halved shape)
         assert area[2] < area[0] and area[2] < 1.1 * area[1]    # what the walk pays for: the boxes a ray can meet
+    return out
+
+
+@pytest.mark.parametrize("maker", _BUILD_SCENES)
+def test_device_built_tables_are_a_valid_hierarchy_in_the_product_layout(maker):
+    """The diagnostics library's trees by default are the product's: the builders' numbering -- the halved shape's root is the pair
+    before its middle leaf, a surface-area build's wherever the build put it --, no promoted top, no packed pair table."""
+    sph = api.as_spheres(maker()[0])
+    for by_area, (b, pk) in _every_build(sph).items():
+        assert pk is None
+        if b["n_leaves"] > 1:
+            if by_area == 0 or len(sph) - b["n_always"] < 128:
+                assert b["root"] == b["n_leaves"] // 2 - 1, (by_area, b["root"], b["n_leaves"])
+            else:
+                assert b["root"] < b["n_leaves"] - 1, (by_area, b["root"], b["n_leaves"])
+
+
+def _breadth_first(b):
+    """Pair numbers in breadth-first order from the header's root, side 0 before side 1 (rt_bvh.hip rt_bvh_promote_kernel's order)."""
+    order, queue = [], [b["root"]]
+    while queue:
+        p = queue.pop(0)
+        if p & 0x8000:
+            continue
+        order.append(p)
+        for side in (0, 1):
+            queue.append(int(b["pairs"][4 * p + 2 * side][3:4].view(np.uint32)[0]) & 0xffff)
+    return order
+
+
+@pytest.mark.parametrize("maker", _BUILD_SCENES + [lambda: _many_spheres(5000)])
+def test_the_layout_knob_promotes_the_top_and_packs_the_pairs(maker):
+    """rt_debug_set_bvh_layout(ctx, 255, 1): the A/B arms' tables after every builder -- the top 255 pairs renumbered breadth-first with the
+    root's pair first (a tree of 625 leaves cut off there), the packed pair table behind the blob.  rt_set_mode of an arm that reads one asks
+    for it by itself and renders the oracle's frame; with the layout set back to the product's the arm is refused."""
+    sph, orig, target = maker()
+    sph = api.as_spheres(sph)
+    for by_area, (b, pk) in _every_build(sph, (255, 1)).items():
+        if b["n_leaves"] > 1:
+            assert b["root"] == 0
+            top = min(255, b["n_leaves"] - 1)
+            assert _breadth_first(b)[:top] == list(range(top))
+            assert pk is not None and bvh_check.check_packed(b, pk) == []
+    if len(sph) < 1000:
+        return
+    w, h, spp = 32, 24, 2
+    cam = host.compute_camera(orig, target, w, h)
+    want = O.render(sph, cam, w, h, spp, threads=16)
+    for inst in ("rt_trace_parity_pairs_gt", "rt_trace_parity_pairs_gtp", "rt_trace_parity_pairs_gq"):
+        with api.RtContext(w, h, diag=True) as ctx:
+            ctx._check(ctx._lib.rt_debug_set_bvh(ctx._h, 1, 0))
+            ctx.set_scene(sph)
+            ctx.set_camera(cam)
+            assert bvh_check.read_packed(ctx) is None and bvh_check.read_bvh(ctx)["root"] != 0
+            ctx.set_mode(api.instance_mode(inst))               # the arm's table, built at once
+            assert (bvh_check.read_bvh(ctx)["root"] == 0) == inst.startswith("rt_trace_parity_pairs_gt")
+            assert (bvh_check.read_packed(ctx) is not None) == inst.endswith("_gq")
+            got = {"pixels": ctx.render_pass(spp), "colors": ctx.read_colors(), "seeds": ctx.read_seeds(), "stats": ctx.stats()}
+            assert ctx.last_kernel == inst
+            _same(got, want)
+            ctx._check(ctx._lib.rt_debug_set_bvh_layout(ctx._h, 0, 0))     # a mis-set arm: the tables rebuilt in the product's layout
+            ctx._check(ctx._lib.rt_debug_set_bvh(ctx._h, 1, 0))
+            ctx.reset()
+            with pytest.raises(api.RtError, match="has none"):
+                ctx.render_pass(1)
 
 
 @pytest.mark.parametrize("maker,w,h,spp", [
@@ -685,3 +751,150 @@ def test_the_scene_size_limit():
     with api.RtContext(32, 32) as ctx:
         with pytest.raises(api.RtError):
             ctx.set_scene(too_many)
+
+
+# ---- the product library's own trees: the builders' numbering, no promoted top, no packed table (the suite's other hierarchy tests mostly
+# ---- run the diagnostics library).  Every frame against the oracle, every test asserting the walk it meant to reach.
+def _product(sph, cam, w, h, spp, mode=api.RT_MODE_PARITY):
+    with api.RtContext(w, h) as ctx:
+        ctx.set_scene(sph)
+        ctx.set_camera(cam)
+        ctx.set_mode(mode)
+        return {"pixels": ctx.render_pass(spp), "colors": ctx.read_colors(), "seeds": ctx.read_seeds(), "stats": ctx.stats(),
+                "kernel": ctx.last_kernel}
+
+
+@pytest.mark.parametrize("maker,kernel", [
+    (lambda: scenes.random_spheres(1024), "rt_trace_parity_pairs"),
+    (lambda: _many_spheres(2000), "rt_trace_parity_pairs_m"),
+    (lambda: _many_spheres(2500, seed=3), "rt_trace_parity_pairs_m"),
+    (lambda: _many_spheres(5000), "rt_trace_parity_pairs_g"),
+    (lambda: _many_spheres(9500), "rt_trace_parity_pairs_g"),
+    (lambda: _many_spheres(30000), "rt_trace_parity_pairs_g"),
+])
+def test_product_library_walks_its_own_trees(maker, kernel):
+    """librt_hip.so picks each walk by itself (tables in LDS, pairs in LDS, everything from HBM / L2) on a tree in its own layout:
+    frames, colour plane, seeds and counters are the oracle's."""
+    sph, orig, target = maker()
+    w, h, spp = 48, 32, 2
+    cam = host.compute_camera(orig, target, w, h)
+    got = _product(sph, cam, w, h, spp)
+    assert got["kernel"] == kernel
+    _same(got, O.render(sph, cam, w, h, spp, threads=16))
+
+
+def test_product_library_fast_mode_walk_is_as_close_as_the_fast_sweep():
+    """Fast mode through the product's L2 walk (rt_trace_fast_pairs_g): as close to the parity frame as the fast plain sweep is
+    (test_fast_mode_with_the_hierarchy_is_as_close_as_fast_mode_without's gate).  Among 5000 small spheres a differently rounded
+    bounce or silhouette test changes a path: the fast plain sweep is 23-25 dB from parity here, so the floor is a scene's, not 30 dB."""
+    sph, orig, target = _many_spheres(5000)
+    w, h, spp = 96, 64, 8
+    cam = host.compute_camera(orig, target, w, h)
+    par = _product(sph, cam, w, h, spp)
+    assert par["kernel"] == "rt_trace_parity_pairs_g"
+    _same(par, O.render(sph, cam, w, h, spp, threads=16))
+    plain = _render(sph, cam, w, h, spp, bvh_min=0, mode=api.RT_MODE_FAST)          # (the diagnostics library: no hierarchy at all)
+    base = host.psnr(plain["pixels"], par["pixels"])
+    assert base >= 20.0
+    fast = _product(sph, cam, w, h, spp, mode=api.RT_MODE_FAST)
+    assert fast["kernel"] == "rt_trace_fast_pairs_g"
+    assert fast["stats"]["samples"] == par["stats"]["samples"]
+    assert host.psnr(fast["pixels"], par["pixels"]) >= min(50.0, base - 3.0)
+
+
+def _embedded(records, orig, target, n_fill, seed):
+    """Adversarial records in front of a filler of _many_spheres (its ground and light dropped: the records bring their own), so that
+    the scene is large enough for the product library to walk it from HBM / L2 without being told to."""
+    fill = _many_spheres(n_fill, seed=seed)[0][2:]
+    return np.concatenate([api.as_spheres(records), fill]), orig, target
+
+
+@pytest.mark.parametrize("kind,seed", [("adversarial", 0), ("adversarial", 1), ("adversarial", 2), ("adversarial", 3),
+                                       ("repeats", 0), ("repeats", 1)])
+def test_adversarial_content_in_the_product_layout(kind, seed):
+    """_adversarial / _with_repeats inside thousands of small spheres, through librt_hip.so's own choice: exact ties at higher indices,
+    zero and negative radii, NaN / inf records, a far-away tree member, the camera inside glass (odd adversarial seeds), repeated
+    records with other materials -- in a tree of the builders' numbering walked by _pairs_m (pairs in LDS) and by _pairs_g."""
+    records, orig, target = (_adversarial if kind == "adversarial" else _with_repeats)(seed)
+    w, h, spp = 48, 32, 2
+    cam = host.compute_camera(orig, target, w, h)
+    for n_fill, kernel in ((2200, "rt_trace_parity_pairs_m"), (6000, "rt_trace_parity_pairs_g")):
+        sph, _, _ = _embedded(records, orig, target, n_fill, seed)
+        got = _product(sph, cam, w, h, spp)
+        assert got["kernel"] == kernel, (n_fill, got["kernel"])
+        _same(got, O.render(sph, cam, w, h, spp, threads=16))
+    if kind == "adversarial" and seed % 2:
+        assert records["refl"][3] == api.REFR and np.linalg.norm(np.float32(orig) - records["p"][3]) < records["rad"][3]
+
+
+def _product_frame(ctx, spp):
+    ctx.reset()
+    return {"pixels": ctx.render_pass(spp), "colors": ctx.read_colors(), "seeds": ctx.read_seeds(), "stats": ctx.stats()}
+
+
+def test_product_library_device_resident_updates():
+    """rt_update_spheres_async through librt_hip.so on a scene it walks from HBM / L2: the tables and the tree are rebuilt by the next launch
+    (the device's surface-area builder, rt_bvh.hip), and the records that repeat an earlier one are found again (mark_duplicates) --
+    (a) 200 scattered records moved by 200 calls, then one launch; (b) a record made to repeat an earlier one bit for bit in centre and
+    radius^2 with another material; (c) a repeat of the upload broken by moving the EARLIER record; (d) a record set to NaN, then back.
+    Every frame is the oracle's for the scene as updated."""
+    sph, orig, target = _many_spheres(5000, seed=11)
+    sph = api.as_spheres(sph).copy()
+    sph[4000] = sph[3000]                                   # a repeat in the upload, with another material
+    sph["refl"][4000], sph["c"][4000] = (int(sph["refl"][3000]) + 1) % 3, (0.9, 0.1, 0.1)
+    w, h, spp = 48, 32, 2
+    cam = host.compute_camera(orig, target, w, h)
+    rng = np.random.default_rng(11)
+    with api.RtContext(w, h) as ctx:
+        ctx.set_scene(sph)
+        ctx.set_camera(cam)
+        got = _product_frame(ctx, spp)
+        assert ctx.last_kernel == "rt_trace_parity_pairs_g"
+        _same(got, O.render(sph, cam, w, h, spp, threads=16))
+
+        def step(first, count=1):
+            ctx.update_spheres(first, sph[first:first + count])
+
+        def check(what):
+            got = _product_frame(ctx, spp)
+            assert ctx.last_kernel == "rt_trace_parity_pairs_g", what
+            _same(got, O.render(sph, cam, w, h, spp, threads=16))
+
+        who = rng.choice(np.arange(2, len(sph)), 200, replace=False)                  # (a)
+        sph["p"][who] += rng.uniform(-4, 4, (200, 3)).astype(np.float32)
+        sph["rad"][who[:20]] *= np.float32(1.6)
+        for i in who:
+            step(int(i))
+        check("scattered")
+        j, i = 2500, 1200                                                              # (b)
+        sph["p"][j], sph["rad"][j] = sph["p"][i], -sph["rad"][i]                       # (-r: the same radius^2)
+        sph["refl"][j], sph["e"][j] = (int(sph["refl"][i]) + 1) % 3, (2.0, 2.0, 2.0)
+        step(j)
+        check("made a repeat")
+        sph["p"][3000] += np.float32([0.0, 25.0, 0.0])                                 # (c) record 4000 is the first of its kind now
+        step(3000)
+        check("broke a repeat")
+        keep = sph[1700].copy()                                                        # (d)
+        sph["p"][1700, 1] = np.float32("nan")
+        step(1700)
+        check("NaN")
+        sph[1700] = keep
+        step(1700)
+        check("NaN and back")
+
+
+@pytest.mark.parametrize("n,leaves", [(262144, 32768), (262137, 32767)])
+def test_the_largest_trees(n, leaves):
+    """RT_MAX_SPHERES: 262 143 spheres in the tree, 32 768 leaves -- the last the 15-bit leaf reference numbers (kBvhLeafRef) -- and a tree of
+    one leaf less, built on the host (beyond the device builders) and walked from HBM / L2 by the product library.  One small frame each."""
+    sph, orig, target = _many_spheres(n, seed=n)
+    w, h, spp = 32, 24, 1
+    cam = host.compute_camera(orig, target, w, h)
+    with api.RtContext(8, 8, diag=True) as ctx:
+        ctx.set_scene(sph)
+        counts = (C.c_uint32 * 4)()
+        ctx._check(ctx._lib.rt_debug_read_bvh(ctx._h, None, 0, counts))
+        assert (counts[0], counts[1]) == (1, leaves)                 # (the ground outside; every other sphere in the tree, the light too)
+    got = _product(sph, cam, w, h, spp)
+    assert got["kernel"] == "rt_trace_parity_pairs_g"
+    _same(got, O.render(sph, cam, w, h, spp, threads=16))
