@@ -87,7 +87,7 @@ enum rt_mode {
                               * hit decision, and from that sample on the pixel's one sequential random stream (.cl:143-169)
                               * is consumed differently -- the frames then differ at the noise level although both are correct
                               * renderings.  Use RT_MODE_PARITY where the tolerance matters on such scenes.  Measured per
-                              * configuration by tools/fast_gate.py (profiles/r05_fast_gate.jsonl), held by
+                              * configuration by tools/fast_gate.py (profiles/r06_fast_gate.jsonl), held by
                               * tests/test_gpu_parity.py::test_fast_mode_against_north_star_gate.                        */
 };
 

@@ -200,7 +200,7 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
         c->last_stream = c->stream;
         HIP_TRY(hipEventCreate(&c->ev0));
         HIP_TRY(hipEventCreate(&c->ev1));
-        for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreate(&c->probe_ev[k]));
+        for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreate(&c->probe.ev[k]));
         HIP_TRY(hipEventCreateWithFlags(&c->ev_dep, hipEventDisableTiming));
         for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreateWithFlags(&c->stage_ev[k], hipEventDisableTiming));
         lap(1);
@@ -210,10 +210,10 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
         HIP_TRY(hipMalloc(&c->d_pixels, ((size_t)rows * w + 4) * sizeof(uint32_t)));
         HIP_TRY(hipMalloc(&c->d_counters, 32 * sizeof(unsigned long long)));
         HIP_TRY(hipMalloc(&c->d_stats, rt::kStatReplicas * 8 * sizeof(unsigned long long)));
-        c->n_tiles = (uint32_t)(((w + 7) / 8) * ((rows + rt::kTileH - 1) / rt::kTileH));      // the finest tile shape (8x8)
-        if (c->n_tiles) {
-            HIP_TRY(hipMalloc(&c->d_tile_cost, (size_t)c->n_tiles * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc(&c->d_order, (size_t)c->n_tiles * sizeof(uint32_t)));
+        c->order.n_tiles = (uint32_t)(((w + 7) / 8) * ((rows + rt::kTileH - 1) / rt::kTileH));      // the finest tile shape (8x8)
+        if (c->order.n_tiles) {
+            HIP_TRY(hipMalloc(&c->order.d_tile_cost, (size_t)c->order.n_tiles * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc(&c->order.d_order, (size_t)c->order.n_tiles * sizeof(uint32_t)));
         }
         lap(2);
         // function attributes (dynamic-LDS limit) are per device, not per context
@@ -273,8 +273,8 @@ RT_API void rt_destroy(rt_ctx *c) {
         (void)hipFree(c->d_pixels);
         (void)hipFree(c->d_counters);
         (void)hipFree(c->d_stats);
-        (void)hipFree(c->d_tile_cost);
-        (void)hipFree(c->d_order);
+        (void)hipFree(c->order.d_tile_cost);
+        (void)hipFree(c->order.d_order);
         (void)hipFree(c->d_timelog);
         (void)hipFree(c->d_wavelog);
         (void)hipFree(c->d_blocklog);
@@ -284,7 +284,7 @@ RT_API void rt_destroy(rt_ctx *c) {
         if (c->ev0) (void)hipEventDestroy(c->ev0);
         if (c->ev1) (void)hipEventDestroy(c->ev1);
         for (int k = 0; k < 4; ++k)
-            if (c->probe_ev[k]) (void)hipEventDestroy(c->probe_ev[k]);
+            if (c->probe.ev[k]) (void)hipEventDestroy(c->probe.ev[k]);
         if (c->bvh_stage_ev) (void)hipEventDestroy(c->bvh_stage_ev);
         if (c->dup_ev) (void)hipEventDestroy(c->dup_ev);
         if (c->h_bvh_stage) (void)hipHostFree(c->h_bvh_stage);
@@ -304,9 +304,9 @@ RT_API int rt_scene_choice(rt_ctx *c, double *hierarchy_ms_per_pass, double *swe
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     rt_ctx *s = c->multi ? rt::multi_first_shard(c) : c;
     if (select_device(s) == RT_OK) probe_poll(s, false);
-    if (hierarchy_ms_per_pass) *hierarchy_ms_per_pass = s->probe_ms[0];
-    if (sweep_ms_per_pass) *sweep_ms_per_pass = s->probe_ms[1];
-    return s->bvh_pick;
+    if (hierarchy_ms_per_pass) *hierarchy_ms_per_pass = s->choice.probe_ms[0];
+    if (sweep_ms_per_pass) *sweep_ms_per_pass = s->choice.probe_ms[1];
+    return rt::verdict_number(s->choice.bvh_pick);
 }
 
 RT_API const char *rt_last_kernel(const rt_ctx *c) { return !c ? "" : (c->multi ? rt::multi_last_kernel(c) : c->last_kernel); }
@@ -328,7 +328,7 @@ RT_API int rt_set_scene(rt_ctx *c, const rt_sphere *spheres, uint32_t count) {
     if (rc != RT_OK) return rc;
     c->is_light.assign(c->scene_cap, 0);
     c->h_spheres.assign(spheres, spheres + count);
-    c->cost_valid = c->order_valid = false;
+    c->order.forget();
     rearm_probe(c);                     // a new scene: hierarchy or plain sweep is measured again
     rc = upload_spheres(c, 0, count, spheres, count, c->stream, true);
     if (rc != RT_OK) {
@@ -350,8 +350,7 @@ RT_API int rt_update_spheres_async(rt_ctx *c, uint32_t first, uint32_t count, co
     if (rc != RT_OK) return rc;
     if (count) memcpy(c->h_spheres.data() + first, spheres, (size_t)count * sizeof(rt_sphere));
     // the last frame's costs still predict this one (moving spheres): the order stays in use and the next long launch sorts it again from them
-    c->order_stale = true;
-    if (c->cost_window) c->cost_passes = 0;         // (a window of short launches' costs starts again from the changed scene)
+    c->order.scene_or_camera_moved();
     // (the records go now; tables and hierarchy are rebuilt once, by the next launch -- rt_scene.hip refresh_tables -- however many updates precede it)
     return upload_spheres(c, first, count, spheres, n, (hipStream_t)hip_stream, false);
 }
@@ -359,10 +358,7 @@ RT_API int rt_update_spheres_async(rt_ctx *c, uint32_t first, uint32_t count, co
 RT_API int rt_set_camera(rt_ctx *c, const rt_camera *cam) {
     if (!c || !cam) return fail(RT_ERR_ARG, "null argument");
     if (c->multi) return rt::multi_set_camera(c, cam);
-    if (!c->have_cam || memcmp(&c->cam, cam, sizeof *cam) != 0) {
-        c->order_stale = true;             // a moved camera: the order stays in use, the next long launch sorts it again from the last frame's costs
-        if (c->cost_window) c->cost_passes = 0;     // (... or the next window of short launches, which starts again)
-    }
+    if (!c->have_cam || memcmp(&c->cam, cam, sizeof *cam) != 0) c->order.scene_or_camera_moved();
     c->cam = *cam;                      // a kernel argument: nothing to upload
     c->have_cam = true;
     return RT_OK;
@@ -396,7 +392,7 @@ RT_API int rt_reset(rt_ctx *c) {
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
     c->current_sample = 0;
-    if (c->scene_launches > 0) c->scene_frames += 1;       // (a frame of the current scene has been rendered: rt_launch.hip launch_small)
+    c->choice.frame_ended();
     c->launches = 0;
     c->last_ms = 0.0;
     c->seeds_default = false;
@@ -415,7 +411,7 @@ RT_API int rt_reset_async(rt_ctx *c, void *hip_stream) {
     HIP_TRY(hipGetLastError());
     c->seeds_default = true;            // the next launch reads d_seeds0
     c->current_sample = 0;
-    if (c->scene_launches > 0) c->scene_frames += 1;       // (a frame of the current scene has been rendered: rt_launch.hip launch_small)
+    c->choice.frame_ended();
     c->launches = 0;
     c->last_ms = 0.0;
     return RT_OK;

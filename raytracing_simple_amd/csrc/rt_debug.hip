@@ -157,15 +157,15 @@ RT_API int rt_debug_stage_tables(rt_ctx *c, int n_samples, int repeats) {
     const bool w1 = lds + (coop ? 1536u : 256u) <= 6 * 1024;
     const int tile_w = w1 ? 8 : 32;
     const dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), (unsigned)((c->local_rows + 7) / 8));
-    uint32_t *sink = reinterpret_cast<uint32_t *>(c->d_tile_cost);          // (scratch: n_tiles >= 1024 words are not needed -- index & 1023 of a buffer that large)
-    if (!sink || c->n_tiles < 1024) return fail(RT_ERR_ARG, "image too small for the probe");
+    uint32_t *sink = reinterpret_cast<uint32_t *>(c->order.d_tile_cost);    // (scratch: n_tiles >= 1024 words are not needed -- index & 1023 of a buffer that large)
+    if (!sink || c->order.n_tiles < 1024) return fail(RT_ERR_ARG, "image too small for the probe");
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rt_stage_probe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_debug_stage_tables: %s", hipGetErrorString(e));
     for (int k = 0; k < repeats; ++k) {
         hipLaunchKernelGGL(rt_stage_probe_kernel, grid, dim3(w1 ? 64 : 256), lds, c->stream, c->scene, mat, sink);
         HIP_TRY(hipGetLastError());
     }
-    c->cost_valid = c->order_valid = false;                                 // (the probe scribbled over the tile costs)
+    c->order.forget();                                                      // (the probe scribbled over the tile costs)
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RT_OK;
 }
@@ -190,9 +190,9 @@ static int dbg_set_gate(rt_ctx *c, int v) { c->regen_gate = v; return RT_OK; }
 static int dbg_set_matlds(rt_ctx *c, int v) { c->mat_lds_limit = v; return RT_OK; }
 static int dbg_set_persist(rt_ctx *c, int v) { c->persist = v ? 1 : 0; return RT_OK; }
 static int dbg_set_ncus(rt_ctx *c, int v) { c->n_cus = v; return RT_OK; }
-static int dbg_set_coop(rt_ctx *c, int v) { c->coop_min = v & 0xffffff; c->coop_kmax = v >> 24; c->coop_probe = 0; rearm_probe(c); return RT_OK; }     // (a threshold set by hand decides alone: no measurement)
+static int dbg_set_coop(rt_ctx *c, int v) { c->coop_min = v & 0xffffff; c->coop_kmax = v >> 24; c->choice.coop_probe = 0; rearm_probe(c); return RT_OK; }     // (a threshold set by hand decides alone: no measurement)
 static int dbg_set_wg(rt_ctx *c, int v) { c->wg_waves = v; return RT_OK; }
-static int dbg_set_order(rt_ctx *c, int v) { c->use_order = v ? 1 : 0; c->order_valid = false; return RT_OK; }
+static int dbg_set_order(rt_ctx *c, int v) { c->order.enable(v != 0); return RT_OK; }
 static int dbg_apply(rt_ctx *c, int (*fn)(rt_ctx *, int), int v) { return c->multi ? rt::multi_debug_each(c, fn, v) : fn(c, v); }
 
 // tuning knob (not part of the contract): 0 = automatic, 1 = free-running, n = gate of n lanes
@@ -227,12 +227,12 @@ RT_API int rt_debug_read_tile_order(rt_ctx *c, uint32_t *order_out, uint32_t *co
     if (rc != RT_OK) return rc;
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
-    const uint32_t in_use = c->cost_valid && c->cost_tiles ? c->cost_tiles : c->n_tiles;      // (the tiles of the last launch's workgroup shape)
+    const uint32_t in_use = c->order.tiles_in_use();
     const uint32_t n = cap < in_use ? cap : in_use;
-    if (order_out && n) HIP_TRY(hipMemcpy(order_out, c->d_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (cost_out && n) HIP_TRY(hipMemcpy(cost_out, c->d_tile_cost, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (order_out && n) HIP_TRY(hipMemcpy(order_out, c->order.d_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (cost_out && n) HIP_TRY(hipMemcpy(cost_out, c->order.d_tile_cost, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (n_tiles) *n_tiles = in_use;
-    if (valid) *valid = c->order_valid ? 1 : 0;
+    if (valid) *valid = c->order.has_order() ? 1 : 0;
     return RT_OK;
 }
 // the hierarchy of large scenes: min_spheres = smallest tree that is built and used (0 = never), lds_limit = largest
@@ -347,10 +347,10 @@ RT_API int rt_debug_tree_estimate(rt_ctx *c, double *out4) {
     out4[0] = c->bvh_est_pairs;
     out4[1] = c->bvh_est_leaves;
     out4[2] = c->bvh_est_valid && c->bvh_ok ? estimate_ratio(c) : 0.0;
-    out4[3] = c->pick_estimated ? 1.0 : 0.0;
+    out4[3] = c->choice.pick_estimated ? 1.0 : 0.0;
     return c->bvh_est_valid && c->bvh_ok ? 1 : 0;
 }
-static int dbg_set_estimate(rt_ctx *c, int v) { c->use_estimate = v ? 1 : 0; rearm_probe(c); return RT_OK; }
+static int dbg_set_estimate(rt_ctx *c, int v) { c->choice.use_estimate = v ? 1 : 0; rearm_probe(c); return RT_OK; }
 RT_API int rt_debug_set_choice_estimate(rt_ctx *c, int on) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     return dbg_apply(c, dbg_set_estimate, on);
@@ -358,7 +358,7 @@ RT_API int rt_debug_set_choice_estimate(rt_ctx *c, int on) {
 RT_API int rt_debug_bvh_pick(rt_ctx *c) {
     if (!c || c->multi) return fail(RT_ERR_ARG, "null / multi-device context");
     if (select_device(c) == RT_OK) probe_poll(c, false);
-    return c->bvh_pick;
+    return rt::verdict_number(c->choice.bvh_pick);
 }
 RT_API int rt_debug_set_bvh(rt_ctx *c, int min_spheres, int lds_limit) {
     if (!c || min_spheres < 0 || lds_limit < 0 || lds_limit > 152 * 1024) return fail(RT_ERR_ARG, "min_spheres %d, lds_limit %d", min_spheres, lds_limit);

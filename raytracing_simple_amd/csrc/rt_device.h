@@ -137,7 +137,7 @@ hipError_t launch_pack_fast(const LaunchParams &p, hipStream_t stream);
 
 // ---- the kernel instances ------------------------------------------------------------------------------
 // One row per instance, written next to the instantiations in rt_kernel_parity.hip / rt_kernel_fast.hip: what the
-// instance is and what it needs.  rt_api.hip picks an instance by ROLE, sizes its LDS from `tables` and refuses a
+// instance is and what it needs.  rt_launch.hip picks an instance by ROLE, sizes its LDS from `tables` and refuses a
 // launch whose instance needs a table the context does not have -- nothing in the host code depends on the order of
 // the rows.  The product library holds the shipped rows only; the diagnostics build (librt_hip_diag.so) adds the
 // A/B and verification instances (rt_set_mode 100 + row / 200 + row, or by name: rt_debug_instance).
@@ -150,6 +150,10 @@ enum InstanceTables : uint8_t {
     kTabPairsTopLds = 5,    // ... pairs and slots read where they lie but for the promoted top of the tree (BvhTables::n_top pairs), which is staged
     kTabPairsPacked = 6,    // ... the PACKED pair table (BvhTables::packed_at) and the slots read where they lie; staged: header, frame and stacks
 };
+// the instance walks a hierarchy: it needs the scene's BvhTables
+inline bool walks_hierarchy(uint8_t tables) {
+    return tables == kTabPairsLds || tables == kTabPairsGlobal || tables == kTabPairsLdsSlotsGlobal || tables == kTabPairsTopLds || tables == kTabPairsPacked;
+}
 enum InstanceRole : uint8_t {
     kRoleNone = 0,          // diagnostics: reachable by row / name only
     kRolePlain,             // small scenes

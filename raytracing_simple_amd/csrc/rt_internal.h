@@ -7,8 +7,60 @@
 #include <vector>
 
 #include "rt_device.h"
+#include "rt_tile_order.h"
 
 struct rt_multi;                    // rt_multi.hip
+struct rt_ctx;
+
+namespace rt {
+
+// What a launch renders with: asked of launch_form() (rt_launch.hip), kept as a scene's verdicts, recorded of the last launch.
+//   Auto        the context's own choice from its thresholds.  As a verdict: not decided yet; as the last launch: nothing launched yet
+//   Walk        the hierarchy (if the scene has one)
+//   Sweep       the plain sweep; cooperative any-hit or not as the sphere count says
+//   SweepCoop   the sweep WITH cooperative any-hit whatever the sphere count says (the small-scene measurement); SweepPlain: WITHOUT
+enum class Form : uint8_t { Auto, Walk, Sweep, SweepCoop, SweepPlain };
+inline bool sweeps(Form f) { return f >= Form::Sweep; }
+// the C ABI's number for a hierarchy verdict (rt_scene_choice, rt_debug_bvh_pick): 0 = not decided yet, 1 = hierarchy, 2 = plain sweep
+inline int verdict_number(Form f) { return f == Form::Auto ? 0 : (f == Form::Walk ? 1 : 2); }
+
+// Which form renders this scene, and what the decision rests on (rt_launch.hip launch(), launch_small()).
+struct Choice {
+    // hierarchy or plain sweep?  Decided per scene by measurement (rt_launch.hip launch()): each form once warm and once
+    // timed between events, in the same tile order; whichever took less time per pass renders the rest
+    Form bvh_pick = Form::Auto;         // Auto = not decided yet, Walk, Sweep
+    bool pick_estimated = false;        // ... and it came from the surface-area estimate, not from a measurement
+    int use_estimate = 1;               // diagnostics knob: 0 = every undecided scene is measured
+    double est_ratio = 0.0;             // the estimate's predicted walk / sweep time (0 = none made)
+    uint32_t probe_tree = 0, probe_always = 0;   // the tree the verdict was measured on
+    int probe_updates = 0;              // device-resident updates since the verdict (it is measured again after 256)
+    double probe_ms[2] = { 0.0, 0.0 };  // measured time per pass: hierarchy, plain sweep (0 = not measured)
+    // ... and for a scene WITHOUT a hierarchy and fewer spheres than coop_min: cooperative any-hit or not, timed on the host's own launches (rt_launch.hip launch_small).
+    // Below 12 spheres the threshold alone picks wrongly either way -- the Demo scene is 2 % faster without the sharing, the reference's simple.scn,
+    // caustic.scn and caustic3.scn (6 and 10 records) 7-11 % faster with it (profiles/r06_reference_scenes.jsonl) -- so it is measured.
+    Form coop_pick = Form::Auto;        // Auto = not decided yet, SweepCoop, SweepPlain
+    int coop_probe = 1;                 // diagnostics knob: 0 = the threshold alone decides (round 5's behaviour)
+    uint32_t scene_frames = 0;          // resets since rt_set_scene that followed at least one launch OF THAT SCENE: frames of it already rendered
+    uint64_t scene_launches = 0;        // launches since rt_set_scene
+    rt_ctx *leader = nullptr;           // a shard of a multi-device context: the shard whose verdict it follows (null: its own)
+    Form last = Form::Auto;             // what the last launch was: Walk, SweepCoop (a cooperative any-hit instance) or SweepPlain (any other sweep) --
+                                        // what a multi-device context's other shards follow
+    // rt_reset / rt_reset_async: a frame of the current scene has been rendered, if anything of it was launched (rt_launch.hip launch_small)
+    void frame_ended() { if (scene_launches > 0) scene_frames += 1; }
+};
+
+// The measurement in flight, if any.  Both are four steps on the context's launches -- arm 0 warm, arm 0 timed, arm 1 warm, arm 1 timed; a timed
+// step lies between ev[2 * arm] and ev[2 * arm + 1] -- and differ in what the arms are and in how many passes a step takes (rt_launch.hip).
+struct Probe {
+    enum Which : uint8_t { None, WalkVsSweep, CoopVsPlain };
+    Which which = None;
+    int state = 0;                      // steps finished (0..4)
+    int acc = 0;                        // passes launched so far inside the timed step that is open
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    int samples[2] = { 0, 0 };          // passes between the events of arm 0, arm 1
+};
+
+}  // namespace rt
 
 struct rt_ctx {
     int device = 0;
@@ -30,6 +82,19 @@ struct rt_ctx {
     rt_sphere *d_spheres = nullptr;
     float4 *d_tables = nullptr;         // geom | emis | colr | lightA | lightB, each `scene_cap` entries
     uint32_t scene_cap = 0;
+    std::vector<unsigned char> is_light;   // host mirror of the light test per sphere (sizes the light list)
+    std::vector<rt_sphere> h_spheres;      // host mirror of the records (an identical rt_set_scene uploads nothing)
+    rt_sphere *h_stage = nullptr;       // page-locked staging ring for sphere uploads
+    uint32_t stage_cap = 0;             // records per slot
+    int stage_next = 0;
+    hipEvent_t stage_ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    bool stage_used[4] = { false, false, false, false };
+    rt::SceneTables scene{};
+    rt_camera cam{};
+    bool have_scene = false, have_cam = false;
+    bool tables_stale = false;          // rt_update_spheres_async has changed records since the tables and the hierarchy were built: refresh_tables() builds them
+                                        // ONCE, on the stream of whatever reads them next, however many updates went by (200 moved spheres by 200 calls cost 200
+                                        // rebuilds before: 353 ms a frame at 8192 spheres against 4.9 in one call -- profiles/r06_update_calls.jsonl)
     // hierarchy over the small spheres of a large scene (rt_device.h BvhTables), rebuilt with the tables
     float4 *d_bvh = nullptr;            // blob, sized for scene_cap
     rt::BvhTables bvh{};
@@ -61,56 +126,15 @@ struct rt_ctx {
     int walk_gate = 16, walk_round = 4; // rt_walk.inc.h: ready lanes that make the wavefront shade; pair steps in a row before a leaf step
                                         // (round 4, this kernel: 2 / 3 / 4 / 6 in a row = 5.42 / 5.37 / 5.22 / 5.45 ms on C3, profiles/r04k_walk_sweep.jsonl)
     int walk_tail = 0;                  // lanes that may be left walking when a trip's walk phase ends (0 = none: every walk runs to its end within the trip)
-    int walk_forced = 0;                // 0 = measured choice (below); diagnostics: 1 = the hierarchy whenever the scene has one
-    // hierarchy or plain sweep?  Decided per scene by measurement (rt_api.hip launch()): each form once warm and once
-    // timed between events, in the same tile order; whichever took less time per pass renders the rest
-    int bvh_pick = 0;                   // 0 = not decided yet, 1 = hierarchy, 2 = plain sweep
-    bool pick_estimated = false;        // ... and it came from the surface-area estimate, not from a measurement
-    int use_estimate = 1;               // diagnostics knob: 0 = every undecided scene is measured
-    double est_ratio = 0.0;             // the estimate's predicted walk / sweep time (0 = none made)
-    int probe_state = 0;                // probe launches issued (0..4)
-    // ... and for a scene WITHOUT a hierarchy and fewer spheres than coop_min: cooperative any-hit or not, timed on the host's own launches (rt_launch.hip launch_small).
-    // Below 12 spheres the threshold alone picks wrongly either way -- the Demo scene is 2 % faster without the sharing, the reference's simple.scn,
-    // caustic.scn and caustic3.scn (6 and 10 records) 7-11 % faster with it (profiles/r06_reference_scenes.jsonl) -- so it is measured.
-    int coop_pick = 0;                  // 0 = not decided yet, 1 = cooperative any-hit, 2 = plain
-    bool probing_coop = false;          // the probe launches in flight time coop against plain (not hierarchy against sweep)
-    bool last_coop = false;             // the last launch was a cooperative any-hit instance (what a multi-device context's other shards follow)
-    uint32_t scene_frames = 0;          // resets since rt_set_scene that followed at least one launch OF THAT SCENE: frames of it already rendered
-    uint64_t scene_launches = 0;        // launches since rt_set_scene
-    int probe_acc = 0;                  // passes launched so far inside the timed step of the coop / plain measurement that is open
-    int coop_probe = 1;                 // diagnostics knob: 0 = the threshold alone decides (round 5's behaviour)
-    uint32_t probe_tree = 0, probe_always = 0;   // the tree the verdict was measured on
-    int probe_updates = 0;              // device-resident updates since the verdict (it is measured again after 256)
-    rt_ctx *choice_leader = nullptr;    // a shard of a multi-device context: the shard whose verdict it follows (null: its own)
-    int probe_samples[2] = { 0, 0 };
-    double probe_ms[2] = { 0.0, 0.0 };  // measured time per pass: hierarchy, plain sweep (0 = not measured)
-    hipEvent_t probe_ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    std::vector<unsigned char> is_light;   // host mirror of the light test per sphere (sizes the light list)
-    std::vector<rt_sphere> h_spheres;      // host mirror of the records (an identical rt_set_scene uploads nothing)
-    // heavy-first tile order (rt_trace.inc.h): per-tile cost of the last launch, and the order derived from it
-    uint32_t *d_tile_cost = nullptr, *d_order = nullptr;
-    uint32_t n_tiles = 0;               // capacity of the two arrays (8x8 tiles)
-    uint32_t cost_tiles = 0;            // tile count of the launch the costs come from
+    int walk_forced = 0;                // 0 = measured choice (`choice` below); diagnostics: 1 = the hierarchy whenever the scene has one
+    rt::Choice choice;                  // hierarchy or sweep, cooperative any-hit or not: the verdicts for this scene
+    rt::Probe probe;                    // ... and the measurement behind them, while one runs
+    rt::TileOrder order;                // heavy-first tile schedule (rt_tile_order.h; rt_trace.inc.h reads and writes its arrays)
+    // what a launch is made of besides (rt_launch.hip choose_instance): arithmetic mode, thresholds, diagnostics knobs
     int wg_waves = 0;                   // diagnostics knob: 0 = automatic, 1 / 4 = force the workgroup shape
-    bool cost_valid = false, order_valid = false;
-    uint32_t cost_passes = 0;           // passes behind the costs now in d_tile_cost
-    bool cost_window = false;           // ... which come from a window of SHORT launches (fewer than 8 passes each) adding up, not from one long launch
-    bool order_stale = false;           // scene or camera have changed since the order was sorted: it stays in use until a long launch sorts it again
-    int use_order = 1;
-    rt_sphere *h_stage = nullptr;       // page-locked staging ring for sphere uploads
-    uint32_t stage_cap = 0;             // records per slot
-    int stage_next = 0;
-    hipEvent_t stage_ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    bool stage_used[4] = { false, false, false, false };
-    rt::SceneTables scene{};
-    rt_camera cam{};
-    bool have_scene = false, have_cam = false;
     int mode = RT_MODE_PARITY;
     int regen_gate = 0;                 // 0 = choose from the scene size
     int mat_lds_limit = 24 * 1024;
-    bool tables_stale = false;          // rt_update_spheres_async has changed records since the tables and the hierarchy were built: refresh_tables() builds them
-                                        // ONCE, on the stream of whatever reads them next, however many updates went by (200 moved spheres by 200 calls cost 200
-                                        // rebuilds before: 353 ms a frame at 8192 spheres against 4.9 in one call -- profiles/r06_update_calls.jsonl)
     int sweep_lds_limit = 40 * 1024;    // the plain / cooperative sweep stages its tables while four workgroups of that size fit a CU; beyond, the table is read through the
                                         // scalar cache at six wavefronts per SIMD whatever its size (rt_trace_*_g).  Measured at 1080p on scenes without a hierarchy
                                         // (profiles/r06_g_threshold.jsonl): at 48 KB (3 per CU) rt_trace_*_g takes 0.62 / 0.92 x the staged sweep's time (NaN records / a closed
@@ -122,7 +146,6 @@ struct rt_ctx {
     int current_sample = 0;
     uint64_t launches = 0;
     const char *last_kernel = "";       // symbol of the instance the last launch used
-    int last_form = 0;                  // ... 1 = it walked the hierarchy, 2 = a plain sweep (0 = nothing launched yet)
     double last_ms = 0.0;
     unsigned long long debug_counters[24] = {};   // diagnostic instances only
     hipStream_t stream = nullptr;       // the context's own (non-blocking) stream
@@ -189,7 +212,7 @@ int upload_spheres(rt_ctx *c, uint32_t first, uint32_t count, const rt_sphere *s
 // context's host mirror holds (sets c->bvh / c->bvh_ok; nothing is read back)
 hipError_t prepare_bvh_build();
 int build_bvh(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload = false);
-int render_shard(rt_ctx *c, int n_samples, bool may_block);      // rt_api.hip: one shard's launch on its own stream
+int render_shard(rt_ctx *c, int n_samples, bool may_block);      // rt_launch.hip: one shard's launch on its own stream
 
 // multi-device context (rt_multi.hip); `front` is the rt_ctx whose `multi` points at the record
 void multi_destroy(rt_ctx *front);

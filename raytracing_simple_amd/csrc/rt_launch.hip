@@ -126,10 +126,8 @@ static bool bvh_usable(const rt_ctx *c) { return c->bvh_ok && c->wg_waves != 1 &
 // dynamic LDS and hands out the hierarchy.  An instance whose tables the context lacks is refused (RT_ERR_STATE),
 // whatever route selected it -- the measured choice, a forced form, or a diagnostics mode.
 static int bind_tables(rt_ctx *c, const rt::Instance &inst, int n_samples, rt::LaunchParams &p, size_t *lds_out) {
-    const bool needs_bvh = inst.tables == rt::kTabPairsLds || inst.tables == rt::kTabPairsGlobal || inst.tables == rt::kTabPairsLdsSlotsGlobal ||
-                           inst.tables == rt::kTabPairsTopLds || inst.tables == rt::kTabPairsPacked;
     p.bvh = rt::BvhTables{};
-    if (needs_bvh) {
+    if (rt::walks_hierarchy(inst.tables)) {
         if (!c->bvh_ok || !c->bvh.blob)
             return fail(RT_ERR_STATE, "%s walks a hierarchy and the scene has none (fewer than %d small spheres?)", inst.name, c->bvh_min);
         p.bvh = c->bvh;
@@ -178,43 +176,32 @@ static int bind_tables(rt_ctx *c, const rt::Instance &inst, int n_samples, rt::L
     return RT_OK;
 }
 
-// `form`: 0 = the context's choice, 1 = the hierarchy (if the scene has one), 2 = the plain sweep; 3 / 4 = the sweep WITH / WITHOUT cooperative
-// any-hit whatever the sphere count says (the small-scene measurement below)
-static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, int form, bool natural_order = false) {
-    if (!c->have_scene || !c->have_cam)
-        return fail(RT_ERR_STATE, "rt_set_scene and rt_set_camera must precede rendering");
-    if (n_samples < 0) return fail(RT_ERR_ARG, "n_samples < 0");
-    if (n_samples > 0x7fffffff - c->current_sample)
-        return fail(RT_ERR_ARG, "pass counter would overflow (%d + %d)", c->current_sample, n_samples);
-    if (n_samples == 0 || c->local_rows == 0) return RT_OK;
-    int rc = chain(c, stream);
-    if (rc != RT_OK) return rc;
-
-    rt::LaunchParams p = make_params(c, n_samples);
+// Which instance renders a launch of `form`, and the launch parameters that go with the choice.  Reads the context, changes nothing, calls nothing of HIP.
+struct Chosen { const rt::Instance *inst = nullptr; int mat_in_lds = 0, regen_gate = 0; };      // (regen_gate 0: the context's, make_params)
+static int choose_instance(const rt_ctx *c, int n_samples, Form form, Chosen *out) {
     const size_t lds_all = rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, true, n_samples);
     // materials ride along in LDS only while that keeps at least 6 workgroups per CU resident
     // (160 KiB / 24 KiB); larger scenes read them from L2 once per hit
-    p.mat_in_lds = lds_all <= (size_t)c->mat_lds_limit;
-    const size_t lds_sweep = rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, p.mat_in_lds != 0, n_samples);
+    out->mat_in_lds = lds_all <= (size_t)c->mat_lds_limit;
+    const size_t lds_sweep = rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, out->mat_in_lds != 0, n_samples);
 
     // which instance: arithmetic mode x role x workgroup shape.  Single-wavefront workgroups (8x8 tiles) keep the wave
     // slots of a CU full (a 4-wavefront workgroup waits for four free slots at once) and give the heavy-first order a
     // finer granule; each stages its own copy of the tables, so only while 24 copies fit a CU.
     bool fast = c->mode == RT_MODE_FAST;
-    const bool coop = form == 3 ? true : (form == 4 ? false : (c->coop_min > 0 && c->scene.n_spheres >= (uint32_t)c->coop_min));
+    const bool coop = form == Form::SweepCoop ? true : (form == Form::SweepPlain ? false : (c->coop_min > 0 && c->scene.n_spheres >= (uint32_t)c->coop_min));
     const bool w1 = c->wg_waves == 1 || (c->wg_waves == 0 && lds_sweep + (coop ? 1536u : 256u) <= 6 * 1024);   // + the instance's static LDS
     int role = coop ? rt::kRoleCoop : rt::kRolePlain, waves = w1 ? 1 : 4;
-    if (form != 2 && form < 3 && bvh_usable(c)) {
+    if (!sweeps(form) && bvh_usable(c)) {
         // large scenes: the walk over the hierarchy, from LDS while its tables leave room for five workgroups per CU
         role = bvh_fits_lds(c, n_samples) ? rt::kRolePairs : (bvh_pairs_fit_lds(c, n_samples) ? rt::kRolePairsMixed : rt::kRolePairsGlobal);
         waves = 4;
-        if (c->regen_gate <= 0) p.regen_gate = c->walk_gate;
+        if (c->regen_gate <= 0) out->regen_gate = c->walk_gate;
     } else if (!sweep_stages_tables(c, n_samples)) {
         // no hierarchy (or it lost the measurement) and a table beyond the sweep's LDS budget: the plain sweep over the table in HBM / L2
         role = rt::kRoleSweepGlobal;
         waves = 4;
     }
-    p.walk_round = (c->walk_round & 0xff) | (c->walk_tail << 8);       // (one kernel argument: pair steps in a row | tail lanes << 8)
     const rt::Instance *inst = nullptr;
 #if RT_DIAGNOSTICS
     if (c->persist != 0 && c->mode < 100) {
@@ -232,56 +219,62 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, int form, b
     // launch get here all the same, the cooperative instance of that shape renders any scene -- same bits, it only shares its shadow sweeps)
     if (!inst && role == rt::kRolePlain) inst = find_role(fast, rt::kRoleCoop, waves);
     if (!inst) return fail(RT_ERR_STATE, "this library holds no %s instance of role %d with %d wavefronts per workgroup", fast ? "fast" : "parity", role, waves);
+    out->inst = inst;
+    return RT_OK;
+}
+
+// persistent instances: just enough workgroups to fill the machine; the tile queue (counters[30]) does the rest
+static int persist_grid(rt_ctx *c, int n_tiles, size_t lds_use, hipStream_t stream, dim3 *grid) {
+    size_t per_cu = lds_use > 0 ? (160 * 1024) / (lds_use + 6 * 1024) : 6;
+    if (per_cu > 6) per_cu = 6;
+    if (per_cu < 1) per_cu = 1;
+    size_t blocks = (size_t)c->n_cus * per_cu;
+    const size_t needed = ((size_t)n_tiles + 3) / 4;
+    if (blocks > needed) blocks = needed;
+    *grid = dim3((unsigned)blocks, 1, 1);
+    HIP_TRY(hipMemsetAsync(c->d_counters + 30, 0, sizeof(unsigned long long), stream));
+    return RT_OK;
+}
+
+// One launch of `form` (Form::Auto: whatever the context's thresholds and diagnostics knobs say).  `natural_order`: in image order whatever the
+// tile schedule holds (rt_tile_order.h) -- the hierarchy's probe only.
+static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, Form form, bool natural_order = false) {
+    if (!c->have_scene || !c->have_cam)
+        return fail(RT_ERR_STATE, "rt_set_scene and rt_set_camera must precede rendering");
+    if (n_samples < 0) return fail(RT_ERR_ARG, "n_samples < 0");
+    if (n_samples > 0x7fffffff - c->current_sample)
+        return fail(RT_ERR_ARG, "pass counter would overflow (%d + %d)", c->current_sample, n_samples);
+    if (n_samples == 0 || c->local_rows == 0) return RT_OK;
+    int rc = chain(c, stream);
+    if (rc != RT_OK) return rc;
+
+    Chosen chosen;
+    rc = choose_instance(c, n_samples, form, &chosen);
+    if (rc != RT_OK) return rc;
+    const rt::Instance *inst = chosen.inst;
+    rt::LaunchParams p = make_params(c, n_samples);
+    p.mat_in_lds = chosen.mat_in_lds;
+    if (chosen.regen_gate) p.regen_gate = chosen.regen_gate;
+    p.walk_round = (c->walk_round & 0xff) | (c->walk_tail << 8);       // (one kernel argument: pair steps in a row | tail lanes << 8)
     size_t lds_use = 0;
     rc = bind_tables(c, *inst, n_samples, p, &lds_use);
     if (rc != RT_OK) return rc;
-    const bool persist = (inst->flags & rt::kInstPersistent) != 0;
 
     const int tile_w = 8 * inst->waves * ((inst->flags & rt::kInstTwoRays) ? 2 : 1);
     dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), (unsigned)((c->local_rows + rt::kTileH - 1) / rt::kTileH));
-    // heavy tiles first: launches leave per-tile costs, and a launch of the same scene, camera and tile shape walks the tiles in descending order of
-    // cost (sorted on the device, once per change of scene or camera).  A LONG launch (8 passes and more) replaces the costs with its own and sorts
-    // from the last long launch's.  SHORT launches -- the reference's own regime is a pass per call, the adapter's display loop about a millisecond's
-    // worth -- used to get nothing of this: no costs from fewer than 4 passes, no sort below 8.  Yet once the order exists it is worth as much to them
-    // (complex.scn 12 %, C3 8-13 %, 8192 spheres 12-22 % on launches of 1 / 2 / 4 passes: profiles/r06_order_short_launches.jsonl).  So while the order is
-    // missing or stale, short launches ADD their costs up in a window (launch flag bit 1: the kernel's epilogue adds instead of stores), and the short
-    // launch that finds 16 passes' worth there sorts from them; with a valid order short launches do not touch the costs at all.
-    constexpr int kLongLaunch = 8, kShortWindow = 16;
     const uint32_t n_tiles = grid.x * grid.y;
-    const bool instance_logs_cost = (inst->flags & rt::kInstNoTileCost) == 0;
-    const bool short_launch = n_samples < kLongLaunch;
-    bool accumulate = false;
-    if (c->use_order && c->d_tile_cost && n_tiles <= c->n_tiles && instance_logs_cost) {
-        if (c->cost_tiles != n_tiles) {                                            // another tile shape: start over
-            c->cost_valid = c->order_valid = false;
-            c->cost_passes = 0;
-        }
-        const bool order_wanted = !c->order_valid || c->order_stale;
-        // (a short launch sorts from a long launch's costs whenever the order is stale -- they still predict the next frame -- and from a window's once it is full)
-        if (c->cost_valid && order_wanted && !natural_order && (!short_launch || !c->cost_window || c->cost_passes >= (uint32_t)kShortWindow)) {
-            hipLaunchKernelGGL(rt_order_tiles_kernel, dim3(1), dim3(1024), 0, stream, c->d_tile_cost, c->d_order, n_tiles);
-            HIP_TRY(hipGetLastError());
-            c->order_valid = true;
-            c->order_stale = false;
-            if (short_launch && c->cost_window) c->cost_passes = 0;                 // (the window's costs are spent)
-        }
-        if (c->order_valid && !natural_order) p.order = c->d_order;
-        if (!short_launch || !c->order_valid || c->order_stale) {                   // (a short launch under a valid order leaves the costs alone)
-            p.tile_cost = c->d_tile_cost;
-            accumulate = short_launch && c->cost_window && c->cost_passes > 0;
-            if (accumulate) p.skip_pixels |= 2;
-        }
+    const rt::TileOrder::Plan plan = c->order.plan(n_tiles, n_samples, natural_order, (inst->flags & rt::kInstNoTileCost) == 0);
+    if (plan.sort_now) {
+        hipLaunchKernelGGL(rt_order_tiles_kernel, dim3(1), dim3(1024), 0, stream, c->order.d_tile_cost, c->order.d_order, n_tiles);
+        if (hipPeekAtLastError() != hipSuccess) c->order.forget();      // (no order from a sort that was not queued)
+        HIP_TRY(hipGetLastError());
     }
-    if (persist) {
-        // just enough workgroups to fill the machine; the tile queue (counters[30]) does the rest
-        size_t per_cu = lds_use > 0 ? (160 * 1024) / (lds_use + 6 * 1024) : 6;
-        if (per_cu > 6) per_cu = 6;
-        if (per_cu < 1) per_cu = 1;
-        size_t blocks = (size_t)c->n_cus * per_cu;
-        const size_t needed = ((size_t)p.n_tiles + 3) / 4;
-        if (blocks > needed) blocks = needed;
-        grid = dim3((unsigned)blocks, 1, 1);
-        HIP_TRY(hipMemsetAsync(c->d_counters + 30, 0, sizeof(unsigned long long), stream));
+    if (plan.use_order) p.order = c->order.d_order;
+    if (plan.write_costs) p.tile_cost = c->order.d_tile_cost;
+    if (plan.accumulate) p.skip_pixels |= 2;
+    if (inst->flags & rt::kInstPersistent) {
+        rc = persist_grid(c, p.n_tiles, lds_use, stream, &grid);
+        if (rc != RT_OK) return rc;
     }
 #if RT_DIAGNOSTICS
     if (inst->role == rt::kRoleTimelog && c->d_timelog && c->timelog_used < c->timelog_cap) {
@@ -294,29 +287,135 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, int form, b
     const hipError_t e = rt::launch_instance(*inst, p, grid, lds_use, stream);
     if (e != hipSuccess)
         return fail(RT_ERR_HIP, "kernel launch failed: %s (%s, grid %ux%u, lds %zu B)", hipGetErrorString(e), inst->name, grid.x, grid.y, lds_use);
+    c->order.launched(plan, n_samples, n_tiles);
     c->current_sample += n_samples;
     c->launches += 1;
-    c->scene_launches += 1;
+    c->choice.scene_launches += 1;
     c->last_kernel = inst->name;
-    c->last_coop = inst->role == rt::kRoleCoop || inst->role == rt::kRolePersistCoop;
-    c->last_form = (inst->tables == rt::kTabPairsLds || inst->tables == rt::kTabPairsGlobal || inst->tables == rt::kTabPairsLdsSlotsGlobal ||
-                    inst->tables == rt::kTabPairsTopLds || inst->tables == rt::kTabPairsPacked) ? 1 : 2;
-    if (p.tile_cost) {
-        if (!short_launch) {
-            c->cost_window = false;
-            c->cost_passes = (uint32_t)n_samples;
-        } else if (accumulate) {
-            c->cost_passes += (uint32_t)n_samples;
-        } else {                                    // a short launch has replaced the costs with its own: a new window
-            c->cost_window = true;
-            c->cost_passes = (uint32_t)n_samples;
-        }
-        c->cost_valid = c->cost_passes >= 4;        // (fewer than four passes' worth orders nothing)
-        c->cost_tiles = n_tiles;
-    }
+    const bool coop = inst->role == rt::kRoleCoop || inst->role == rt::kRolePersistCoop;
+    c->choice.last = rt::walks_hierarchy(inst->tables) ? Form::Walk : (coop ? Form::SweepCoop : Form::SweepPlain);
     c->seeds_default = false;           // this launch has written every seed pair the context renders
     c->pixels_current = c->pixel_write != 0;
     return RT_OK;
+}
+
+// A long launch that would walk its tiles in image order although their costs can be had -- the first frame of a scene --
+// renders 4 of its passes first (they are passes of the frame like any other: progressive launches equal one launch bit for bit),
+// which prices the tiles, and the rest heavy first.
+// A renderer that draws one frame per scene would otherwise never leave image order (DESIGN.md section 5, "Heavy tiles first").
+static int launch_priced(rt_ctx *c, int n_samples, hipStream_t stream, Form form) {
+    bool priced = false;
+    if (form != Form::Auto && c->order.wants_pricing(n_samples)) {
+        const int rc = launch_form(c, rt::TileOrder::kPricePasses, stream, form);
+        if (rc != RT_OK) return rc;
+        n_samples -= rt::TileOrder::kPricePasses;
+        priced = true;
+    }
+    const int rc = launch_form(c, n_samples, stream, form);
+    if (rc == RT_OK && priced) c->order.sort_again_from_whole_frame();
+    return rc;
+}
+
+// ---- the two measurements ----
+// Both run as four steps on the context's launches (rt_internal.h Probe): arm 0 warm, arm 0 timed, arm 1 warm, arm 1 timed.
+constexpr int kProbeSteps = 4;
+
+// what arm 0 / arm 1 of the measurement in flight renders with
+static Form probe_arm(const rt::Probe &pr, int arm) {
+    if (pr.which == rt::Probe::CoopVsPlain) return arm == 0 ? Form::SweepCoop : Form::SweepPlain;
+    return arm == 0 ? Form::Walk : Form::Sweep;
+}
+
+// Before a launch of the step that is open: `stream` joins the context's work, and a timed step that holds no passes yet gets its opening event.
+// `skip_warm`: this launch is long enough to warm itself -- an open warm step counts as done.  Yields the arm the launch belongs to.
+static int probe_begin_step(rt_ctx *c, hipStream_t stream, bool skip_warm, int *arm) {
+    rt::Probe &pr = c->probe;
+    if (skip_warm && (pr.state & 1) == 0) pr.state += 1;
+    const int rc = chain(c, stream);
+    if (rc != RT_OK) return rc;
+    *arm = pr.state >> 1;
+    if ((pr.state & 1) != 0 && pr.acc == 0) HIP_TRY(hipEventRecord(pr.ev[2 * *arm], stream));
+    return RT_OK;
+}
+
+// After that launch: a warm step ends with it; a timed step ends, with its closing event, once it holds `passes_needed` passes.
+static int probe_end_step(rt_ctx *c, hipStream_t stream, int n_samples, int passes_needed) {
+    rt::Probe &pr = c->probe;
+    const int arm = pr.state >> 1;
+    if ((pr.state & 1) != 0) {
+        pr.acc += n_samples;
+        if (pr.acc < passes_needed) return RT_OK;
+        HIP_TRY(hipEventRecord(pr.ev[2 * arm + 1], stream));
+        pr.samples[arm] = pr.acc;
+        pr.acc = 0;
+    }
+    pr.state += 1;
+    return RT_OK;
+}
+
+// hierarchy or sweep is settled, by the estimate or by measurement: the tree the verdict is about (rearm_probe_if_changed)
+static void verdict_is_of_this_tree(rt_ctx *c, bool estimated) {
+    c->choice.pick_estimated = estimated;
+    c->choice.probe_tree = c->bvh_n_tree;
+    c->choice.probe_always = c->bvh.n_always;
+    c->choice.probe_updates = 0;
+}
+
+// the verdict of the measurement in flight, if all four steps are queued and the last event has completed (wait: block for it)
+void probe_poll(rt_ctx *c, bool wait) {
+    rt::Probe &pr = c->probe;
+    const bool coop = pr.which == rt::Probe::CoopVsPlain;
+    if ((coop ? c->choice.coop_pick : c->choice.bvh_pick) != Form::Auto || pr.state < kProbeSteps) return;
+    if (wait) {
+        if (hipEventSynchronize(pr.ev[3]) != hipSuccess) return;
+    } else if (hipEventQuery(pr.ev[3]) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    float a = 0.f, b = 0.f;
+    if (hipEventElapsedTime(&a, pr.ev[0], pr.ev[1]) != hipSuccess || hipEventElapsedTime(&b, pr.ev[2], pr.ev[3]) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    const double ta = (double)a / pr.samples[0], tb = (double)b / pr.samples[1];
+    if (coop) {
+        // arm 0 = cooperative any-hit, arm 1 = plain.  The plain instance -- what the threshold says -- keeps anything inside 4 %: the scenes the
+        // sharing is for gain 7-14 %, the Demo scene loses 2-10 %, and a timed probe of a 1/8 shard of a 1080p frame lasts 65 microseconds (two of the
+        // eight shards of profiles/r06_shard_prediction.jsonl's first run picked the slower form on a 2 % dead band)
+        c->choice.coop_pick = ta < 0.96 * tb ? Form::SweepCoop : Form::SweepPlain;
+        return;
+    }
+    c->choice.probe_ms[0] = ta;
+    c->choice.probe_ms[1] = tb;
+    c->choice.bvh_pick = ta <= 1.05 * tb ? Form::Walk : Form::Sweep;      // (a dead band of 5 % towards the usual winner: no flipping on a tie)
+    verdict_is_of_this_tree(c, false);
+}
+
+void rearm_probe(rt_ctx *c) {
+    c->choice.scene_frames = 0;
+    c->choice.scene_launches = 0;
+    c->choice.coop_pick = c->choice.bvh_pick = Form::Auto;
+    c->choice.pick_estimated = false;
+    c->choice.probe_ms[0] = c->choice.probe_ms[1] = 0.0;
+    c->choice.probe_updates = 0;
+    c->probe.which = rt::Probe::None;
+    c->probe.state = c->probe.acc = 0;
+}
+
+// after a device-resident update rebuilt the hierarchy: is the verdict still about this tree?
+void rearm_probe_if_changed(rt_ctx *c) {
+    if (c->probe.which == rt::Probe::CoopVsPlain) return;       // (coop against plain on a scene without a hierarchy: an update cannot change the sphere count -- the verdict stays)
+    if (c->choice.bvh_pick == Form::Auto && c->probe.state == 0) return;
+    if (!c->bvh_ok) {
+        rearm_probe(c);
+        return;
+    }
+    const uint32_t tree = c->bvh_n_tree, always = c->bvh.n_always;        // spheres, not padded slots: the shaped tree of an upload has partial leaves
+    auto moved = [](uint32_t now, uint32_t then) { return 4u * (now > then ? now - then : then - now) > then + 8u; };
+    if (moved(tree, c->choice.probe_tree) || moved(always, c->choice.probe_always) || ++c->choice.probe_updates >= 256) {
+        rearm_probe(c);
+        c->bvh_est_valid = false;               // (the areas were the uploaded tree's: the changed scene is measured)
+    }
 }
 
 // Hierarchy or plain sweep for this scene?  The walk wins by 5x on a thousand spheres scattered over a plane and
@@ -327,104 +426,14 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, int form, b
 // for the verdict before it queues the rest (progressive passes equal one launch bit for bit).  The verdict is kept
 // for the scene; device-resident updates keep it until the tree has changed size by a quarter or 256 updates have
 // gone by (rearm_probe_if_changed).  In a multi-device context only the first shard measures; the others follow it.
-constexpr int kProbeSteps = 4;          // hierarchy warm, hierarchy timed, sweep warm, sweep timed
-
-void probe_poll(rt_ctx *c, bool wait) {
-    if ((c->probing_coop ? c->coop_pick : c->bvh_pick) != 0 || c->probe_state < kProbeSteps) return;
-    if (wait) {
-        if (hipEventSynchronize(c->probe_ev[3]) != hipSuccess) return;
-    } else if (hipEventQuery(c->probe_ev[3]) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    float a = 0.f, b = 0.f;
-    if (hipEventElapsedTime(&a, c->probe_ev[0], c->probe_ev[1]) != hipSuccess || hipEventElapsedTime(&b, c->probe_ev[2], c->probe_ev[3]) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    const double ta = (double)a / c->probe_samples[0], tb = (double)b / c->probe_samples[1];
-    if (c->probing_coop) {
-        // arm 0 = cooperative any-hit, arm 1 = plain.  The plain instance -- what the threshold says -- keeps anything inside 4 %: the scenes the
-        // sharing is for gain 7-14 %, the Demo scene loses 2-10 %, and a timed probe of a 1/8 shard of a 1080p frame lasts 65 microseconds (two of the
-        // eight shards of profiles/r06_shard_prediction.jsonl's first run picked the slower form on a 2 % dead band)
-        c->coop_pick = ta < 0.96 * tb ? 1 : 2;
-        return;
-    }
-    c->probe_ms[0] = ta;
-    c->probe_ms[1] = tb;
-    c->bvh_pick = ta <= 1.05 * tb ? 1 : 2;      // (a dead band of 5 % towards the usual winner: no flipping on a tie)
-    c->pick_estimated = false;
-    c->probe_tree = c->bvh_n_tree;
-    c->probe_always = c->bvh.n_always;
-    c->probe_updates = 0;
-}
-
 static int launch_probe(rt_ctx *c, int n_samples, hipStream_t stream) {
-    const int k = c->probe_state;               // 0, 1: hierarchy (warm, timed); 2, 3: plain sweep (warm, timed)
-    const bool timed = (k & 1) != 0;
-    const int arm = k >> 1;
-    int rc = chain(c, stream);
+    if (c->probe.which == rt::Probe::None) c->probe.which = rt::Probe::WalkVsSweep;
+    int arm = 0;
+    int rc = probe_begin_step(c, stream, false, &arm);
     if (rc != RT_OK) return rc;
-    if (timed) HIP_TRY(hipEventRecord(c->probe_ev[2 * arm], stream));
-    rc = launch_form(c, n_samples, stream, c->probing_coop ? (arm == 0 ? 3 : 4) : (arm == 0 ? 1 : 2), true);
+    rc = launch_form(c, n_samples, stream, probe_arm(c->probe, arm), true);
     if (rc != RT_OK) return rc;
-    if (timed) {
-        HIP_TRY(hipEventRecord(c->probe_ev[2 * arm + 1], stream));
-        c->probe_samples[arm] = n_samples;
-    }
-    c->probe_state = k + 1;
-    return RT_OK;
-}
-
-void rearm_probe(rt_ctx *c) {
-    c->scene_frames = 0;
-    c->scene_launches = 0;
-    c->probe_acc = 0;
-    c->coop_pick = 0;
-    c->probing_coop = false;
-    c->bvh_pick = 0;
-    c->pick_estimated = false;
-    c->probe_state = 0;
-    c->probe_ms[0] = c->probe_ms[1] = 0.0;
-    c->probe_updates = 0;
-}
-
-// after a device-resident update rebuilt the hierarchy: is the verdict still about this tree?
-void rearm_probe_if_changed(rt_ctx *c) {
-    if (c->probing_coop) return;                // (coop against plain on a scene without a hierarchy: an update cannot change the sphere count -- the verdict stays)
-    if (c->bvh_pick == 0 && c->probe_state == 0) return;
-    if (!c->bvh_ok) {
-        rearm_probe(c);
-        return;
-    }
-    const uint32_t tree = c->bvh_n_tree, always = c->bvh.n_always;        // spheres, not padded slots: the shaped tree of an upload has partial leaves
-    auto moved = [](uint32_t now, uint32_t then) { return 4u * (now > then ? now - then : then - now) > then + 8u; };
-    if (moved(tree, c->probe_tree) || moved(always, c->probe_always) || ++c->probe_updates >= 256) {
-        rearm_probe(c);
-        c->bvh_est_valid = false;               // (the areas were the uploaded tree's: the changed scene is measured)
-    }
-}
-
-// A long launch that would walk its tiles in image order although their costs can be had -- the first frame of a scene --
-// renders 4 of its passes first (they are passes of the frame like any other: progressive launches equal one launch bit for bit),
-// which prices the tiles, and the rest heavy first.
-// A renderer that draws one frame per scene would otherwise never leave image order (DESIGN.md section 5, "Heavy tiles first").
-constexpr int kPricePasses = 4, kPriceFrom = 24;
-static int launch_priced(rt_ctx *c, int n_samples, hipStream_t stream, int form) {
-    const bool explicit_mode = form == 0;
-    bool priced = false;
-    if (!explicit_mode && c->use_order && c->d_tile_cost && n_samples >= kPriceFrom && !c->order_valid && !c->cost_valid) {
-        const int rc = launch_form(c, kPricePasses, stream, form);
-        if (rc != RT_OK) return rc;
-        n_samples -= kPricePasses;
-        priced = true;
-    }
-    const int rc = launch_form(c, n_samples, stream, form);
-    // The order this launch walked came from four passes' worth of costs; the launch itself has now left the costs of all its passes,
-    // a better prediction of the next frame: the next long launch sorts once more from those (C2 2.63 -> 2.58 ms per steady frame,
-    // the same on passes not seen before; profiles/r05_resort_after_pricing_ab.jsonl).
-    if (rc == RT_OK && priced && c->order_valid) c->order_stale = true;
-    return rc;
+    return probe_end_step(c, stream, n_samples, 1);             // (any launch is a whole step)
 }
 
 // The same question answered WITHOUT a launch, from the surface areas of the tree the host built at rt_set_scene (rt_bvh.hip):
@@ -444,7 +453,7 @@ double estimate_ratio(const rt_ctx *c) {
     return (kEstPair * c->bvh_est_pairs + kEstAlways * (double)c->bvh.n_always) / ((double)c->scene.n_spheres + kEstSweepFixed);
 }
 
-// Cooperative any-hit or not for a scene of fewer than coop_min spheres (rt_internal.h coop_pick): MEASURED, on the host's own launches as they
+// Cooperative any-hit or not for a scene of fewer than coop_min spheres (rt_internal.h Choice::coop_pick): MEASURED, on the host's own launches as they
 // come -- never split, never reordered, scheduled like any other (heavy tiles first): the sharing's worth depends on the order the tiles run in, so
 // it is timed under the order the frames will run in.  Four steps: coop warm, coop timed, plain warm, plain timed; a step takes whole launches and
 // ends once it holds enough passes -- a warm step one launch, a timed step 16 passes between its two events; a launch of 16 passes or more needs no
@@ -457,38 +466,24 @@ double estimate_ratio(const rt_ctx *c) {
 constexpr uint32_t kCoopProbeFrom = 4;          // (below four spheres a shadow sweep has nothing to share out)
 constexpr int kCoopTimedPasses = 16;
 static int launch_small(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block) {
-    if (c->choice_leader)                       // a shard of a multi-device context: the form the first shard just launched
-        return launch_priced(c, n_samples, stream, c->choice_leader->last_coop ? 3 : 4);
+    if (c->choice.leader)                       // a shard of a multi-device context: the form the first shard just launched
+        return launch_priced(c, n_samples, stream, c->choice.leader->choice.last == Form::SweepCoop ? Form::SweepCoop : Form::SweepPlain);
     const uint32_t n = c->scene.n_spheres;
-    const bool open = c->coop_probe != 0 && c->coop_min > 0 && n >= kCoopProbeFrom && n < (uint32_t)c->coop_min && c->wg_waves == 0 && c->persist == 0 &&
+    const bool open = c->choice.coop_probe != 0 && c->coop_min > 0 && n >= kCoopProbeFrom && n < (uint32_t)c->coop_min && c->wg_waves == 0 && c->persist == 0 &&
                       tables_fit_lds(c, n_samples);
-    if (!open) return launch_priced(c, n_samples, stream, 2);
-    c->probing_coop = true;
+    if (!open) return launch_priced(c, n_samples, stream, Form::Sweep);
+    c->probe.which = rt::Probe::CoopVsPlain;
     probe_poll(c, false);
-    if (c->coop_pick != 0) return launch_priced(c, n_samples, stream, c->coop_pick == 1 ? 3 : 4);
-    if (c->probe_state == kProbeSteps) return launch_priced(c, n_samples, stream, 4);   // both timings queued, not back yet: what the threshold says meanwhile
-    const bool whole_frame = may_block && n_samples >= kCoopTimedPasses;
-    if (whole_frame && c->scene_frames == 0 && c->probe_state == 0) return launch_priced(c, n_samples, stream, 2);
-    if (whole_frame && (c->probe_state & 1) == 0) c->probe_state += 1;                  // (a long launch warms itself)
-    const int k = c->probe_state, arm = k >> 1;
-    const bool timed = (k & 1) != 0;
-    int rc = chain(c, stream);
+    if (c->choice.coop_pick != Form::Auto) return launch_priced(c, n_samples, stream, c->choice.coop_pick);
+    if (c->probe.state == kProbeSteps) return launch_priced(c, n_samples, stream, Form::SweepPlain);   // both timings queued, not back yet: what the threshold says meanwhile
+    const bool whole_frame = may_block && n_samples >= kCoopTimedPasses;        // (a long launch warms itself)
+    if (whole_frame && c->choice.scene_frames == 0 && c->probe.state == 0) return launch_priced(c, n_samples, stream, Form::Sweep);
+    int arm = 0;
+    int rc = probe_begin_step(c, stream, whole_frame, &arm);
     if (rc != RT_OK) return rc;
-    if (timed && c->probe_acc == 0) HIP_TRY(hipEventRecord(c->probe_ev[2 * arm], stream));
-    rc = launch_priced(c, n_samples, stream, arm == 0 ? 3 : 4);
+    rc = launch_priced(c, n_samples, stream, probe_arm(c->probe, arm));
     if (rc != RT_OK) return rc;
-    if (!timed) {
-        c->probe_state = k + 1;
-        return RT_OK;
-    }
-    c->probe_acc += n_samples;
-    if (c->probe_acc >= kCoopTimedPasses) {
-        HIP_TRY(hipEventRecord(c->probe_ev[2 * arm + 1], stream));
-        c->probe_samples[arm] = c->probe_acc;
-        c->probe_acc = 0;
-        c->probe_state = k + 1;
-    }
-    return RT_OK;
+    return probe_end_step(c, stream, n_samples, kCoopTimedPasses);
 }
 
 int launch(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block) {
@@ -496,40 +491,36 @@ int launch(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block) {
         const int rc = refresh_tables(c, stream);
         if (rc != RT_OK) return rc;
     }
-    const bool measured = c->walk_forced == 0 && c->mode < 100;
-    if (measured && n_samples > 0 && c->local_rows != 0 && c->have_scene && c->have_cam && !bvh_usable(c)) return launch_small(c, n_samples, stream, may_block);
-    if (!measured || n_samples <= 0 || c->local_rows == 0 || !c->have_scene || !c->have_cam || !bvh_usable(c))
-        return measured ? launch_priced(c, n_samples, stream, 2) : launch_form(c, n_samples, stream, 0);
+    if (c->walk_forced != 0 || c->mode >= 100) return launch_form(c, n_samples, stream, Form::Auto);      // diagnostics: nothing is measured
+    if (n_samples <= 0 || c->local_rows == 0 || !c->have_scene || !c->have_cam) return launch_priced(c, n_samples, stream, Form::Sweep);   // (nothing to render, or the error)
+    if (!bvh_usable(c)) return launch_small(c, n_samples, stream, may_block);
     // no probe where the answer is known and asking is dear: from 1500 spheres in the tree on the hierarchy won on every
     // scene measured, open or packed, and one pass of the sweep at 1080p costs 2.6 ms at 1024 spheres,
     // 28 ms at 4096, 138 ms at 8192 from staged tables (through the scalar cache, round 6: a fifth of that at 8192 -- still tens of milliseconds a pass)
-    if (c->bvh_n_tree >= kAlwaysWalkFrom || !tables_fit_lds(c, n_samples)) return launch_priced(c, n_samples, stream, 1);
-    if (c->choice_leader)                       // a shard of a multi-device context: the form the first shard just launched
-        return launch_priced(c, n_samples, stream, c->choice_leader->last_form == 2 ? 2 : 1);
+    if (c->bvh_n_tree >= kAlwaysWalkFrom || !tables_fit_lds(c, n_samples)) return launch_priced(c, n_samples, stream, Form::Walk);
+    if (c->choice.leader)                       // a shard of a multi-device context: the form the first shard just launched
+        return launch_priced(c, n_samples, stream, sweeps(c->choice.leader->choice.last) ? Form::Sweep : Form::Walk);
     probe_poll(c, false);
-    if (c->bvh_pick == 0 && c->probe_state == 0 && c->use_estimate && c->bvh_est_valid) {
+    if (c->choice.bvh_pick == Form::Auto && c->probe.state == 0 && c->choice.use_estimate && c->bvh_est_valid) {
         const double r = estimate_ratio(c);
-        c->est_ratio = r;
+        c->choice.est_ratio = r;
         if (r < kEstBandLo || r > kEstBandHi) {
-            c->bvh_pick = r < 1.0 ? 1 : 2;
-            c->pick_estimated = true;
-            c->probe_tree = c->bvh_n_tree;
-            c->probe_always = c->bvh.n_always;
-            c->probe_updates = 0;
+            c->choice.bvh_pick = r < 1.0 ? Form::Walk : Form::Sweep;
+            verdict_is_of_this_tree(c, true);
         }
     }
-    if (c->bvh_pick != 0) return launch_priced(c, n_samples, stream, c->bvh_pick);
-    if (c->probe_state == kProbeSteps) return launch_form(c, n_samples, stream, 1);    // probes in flight: the usual winner meanwhile
+    if (c->choice.bvh_pick != Form::Auto) return launch_priced(c, n_samples, stream, c->choice.bvh_pick);
+    if (c->probe.state == kProbeSteps) return launch_form(c, n_samples, stream, Form::Walk);    // probes in flight: the usual winner meanwhile
     if (may_block && n_samples >= 16) {
         int done = 0;
-        while (c->probe_state < kProbeSteps) {
-            const int k = (c->probe_state & 1) ? 2 : 1;
+        while (c->probe.state < kProbeSteps) {
+            const int k = (c->probe.state & 1) ? 2 : 1;
             const int rc = launch_probe(c, k, stream);
             if (rc != RT_OK) return rc;
             done += k;
         }
         probe_poll(c, true);
-        return launch_priced(c, n_samples - done, stream, c->bvh_pick ? c->bvh_pick : 1);
+        return launch_priced(c, n_samples - done, stream, c->choice.bvh_pick != Form::Auto ? c->choice.bvh_pick : Form::Walk);
     }
     return launch_probe(c, n_samples, stream);
 }
