@@ -281,6 +281,60 @@ RT_API int rt_current_sample(const rt_ctx *ctx);                  /* mCurrentSam
 RT_API int rt_read_colors(rt_ctx *ctx, float *out_host);
 RT_API int rt_read_seeds(rt_ctx *ctx, uint32_t *out_host);
 
+/* ---- render state in and out: seed streams, checkpoints, merged frames ---------------------
+ * A progressive render is three things -- the colour plane, the seed pairs and the pass number: the `colors`, `seeds` and
+ * `currentSample` arguments of the reference's kernel (.cl:551-600), which continues whatever running average it is handed
+ * (.cl:580-590).  rt_read_colors / rt_read_seeds / rt_current_sample read them; the calls below write them.  The render kernels
+ * are the same: a launch reads its first pass's seeds and continues the average from the pass number, whatever put them there.
+ * THIS LIBRARY'S OWN EXTENSION: the reference has one seed stream (OpenCLConfig.cpp:676-680) and never combines frames.  A frame
+ * rendered on a stream other than 0, and a merged frame, are correct renderings of the scene that reproduce NO reference frame;
+ * resuming a render (rt_write_state / rt_load_state of a state read earlier) reproduces the uninterrupted one bit for bit.       */
+
+/* Back to pass 0 of seed stream `stream_id`, without a host round trip: rt_reset_async (pass number, counters, launch count;
+ * the colour plane and packed pixels stay until the next launch overwrites them) plus a small kernel on `hip_stream` that writes
+ * the stream into the context's seed buffer -- one thread and one 8-byte store per pixel, nothing crosses the bus (uploading the
+ * same words would be 16.6 MB per 1080p frame).  The words are rt_stream_seeds(stream_id, ...); stream 0 is the default
+ * stream and is read in place exactly as after rt_reset_async.  The tile order's costs are kept (the scene has not changed).
+ * A host that animates a scene gives frame k stream k + 1 so that the noise does not stand still while the scene moves.
+ * Sharded and multi-device contexts: every shard gets the same full-image stream (a multi-device context on its shards' own
+ * streams; `hip_stream` is not used there).                                                                               */
+RT_API int rt_seed_stream_async(rt_ctx *ctx, uint64_t stream_id, void *hip_stream);
+
+/* Restore a render: `colors_host` (3 floats/px) and `seeds_host` (2 words/px) in exactly the layouts rt_read_colors and
+ * rt_read_seeds return -- the full image, also for a sharded context, which goes on rendering its own rows; a multi-device
+ * context hands them to every shard -- and the pass number the next launch continues from.  seeds_host == NULL means the
+ * default stream; colors_host == NULL is allowed only with current_sample == 0 (pass 0 overwrites the plane, .cl:580-582).
+ * Counters and the launch count restart as by rt_reset.  The packed pixels are NOT written: rt_read_pixels right after the
+ * call packs the restored plane (same toInt, .cl:34,594-596).  Blocking, like rt_reset; the buffers may be reused on return.
+ * A refused call (RT_ERR_ARG: negative pass number, colours missing beyond pass 0) leaves the context as it was.             */
+RT_API int rt_write_state(rt_ctx *ctx, const float *colors_host, const uint32_t *seeds_host, int current_sample);
+
+/* The same through a checkpoint file, so that a long render can be stopped and resumed.  Format (little-endian, no padding):
+ *     bytes 0-7    magic "RTSTATE\0"
+ *     bytes 8-11   uint32 version = 1
+ *     bytes 12-23  int32 w, int32 h, int32 current_sample
+ *     then         float32[3 * w * h]   the colour plane, as rt_read_colors returns it
+ *     then         uint32[2 * w * h]    the seed pairs, as rt_read_seeds returns them
+ * rt_load_state reads and checks the whole file before it touches the context: a file that is short, has the wrong magic or
+ * version, or holds another image size returns RT_ERR_ARG with the reason in rt_last_error, and the context is unchanged.
+ * Scene, camera and mode are not part of the state.                                                                       */
+RT_API int rt_save_state(rt_ctx *ctx, const char *path);
+RT_API int rt_load_state(rt_ctx *ctx, const char *path);
+
+/* Combine independent renders of one scene: afterwards `dst` holds the sample-weighted average of itself and the `n_srcs`
+ * sources.  Per float of the colour plane, in binary32 without contraction, over X = dst, srcs[0], srcs[1], ... with
+ * n_X = rt_current_sample(X) > 0:   acc = c_X * (float)n_X  for the first such X,  acc = acc + c_X * (float)n_X  for the others,
+ * out = acc * (1.0f / (float)N),  N = sum of n_X  -- the multiply by a reciprocal is the reference's own idiom for its running
+ * average (.cl:580-590).  A context at pass 0 is skipped, not weighted by zero: after rt_reset_async its plane still holds an
+ * old frame.  dst's pass number becomes N, its seeds and counters stay, and rt_read_pixels packs the merged plane; the sources
+ * are only read.  One bandwidth-bound kernel on `hip_stream`, ordered behind everything dst and the sources have queued, and
+ * their later work behind it.  The sources should have rendered on seed streams of their own (rt_seed_stream_async):
+ * contexts on one stream render the same frame, and merging them gains nothing.
+ * RT_ERR_ARG: n_srcs outside 1 .. 15, a null entry, dst among the sources, a source listed twice, contexts that differ in
+ * size or sharding (w, h, rank, nranks, tile_rows) or device, any multi-device context.  RT_ERR_STATE: N == 0.
+ * A refused call changes nothing.                                                                                         */
+RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hip_stream);
+
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it
  * from the scene -- "rt_trace_parity_w1" (few spheres: one wavefront per workgroup), "..._coop_w1" / "..._coop"
@@ -315,6 +369,15 @@ RT_API void rt_compute_camera(rt_camera *cam, int w, int h);
 /* The seed initialisation of OpenCLConfig.cpp:676-680 without depending on the host libc:
  * glibc's never-seeded rand() stream restated, each value clamped to >= 2.                   */
 RT_API void rt_default_seeds(uint32_t *seeds, size_t count);
+
+/* Seed stream `stream_id` of this library (an extension: the reference has the one stream above).  stream_id == 0 is
+ * rt_default_seeds.  Otherwise the pair of pixel i -- words 2i and 2i + 1, the flat order of rt_read_seeds -- is the splitmix64
+ * finaliser of (stream_id, i), all arithmetic wrapping in uint64:
+ *     z = stream_id * 0x9E3779B97F4A7C15 + i + 0x9E3779B97F4A7C15
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;   z ^= z >> 31
+ *     seeds[2i] = max(low32(z), 2),  seeds[2i + 1] = max(high32(z), 2)      -- the reference's clamp, OpenCLConfig.cpp:676-680
+ * An odd `count` ends on a low half.  Needs no device; rt_seed_stream_async writes the same words on the device.        */
+RT_API void rt_stream_seeds(uint64_t stream_id, uint32_t *seeds, size_t count);
 
 /* DemoSpheres, Scene.cpp:5-12.  Returns the sphere count (6), or -count if cap is smaller.   */
 RT_API int rt_demo_scene(rt_sphere *out, uint32_t cap);

@@ -39,6 +39,7 @@ UNITS = [
     ("rt_debug.hip", ["-ffp-contract=off"]),
     ("rt_multi.hip", ["-ffp-contract=off"]),
     ("rt_bvh.hip", ["-ffp-contract=off"]),
+    ("rt_state.hip", ["-ffp-contract=off"]),
     ("rt_host.cpp", ["-ffp-contract=off"]),
     ("rt_build_id.cpp", []),
 ]

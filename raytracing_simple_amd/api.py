@@ -20,7 +20,8 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_pin_output", "rt_set_pixel_write", "rt_read_pixels", "rt_read_pixels_async", "rt_throttle", "rt_device_pixels", "rt_set_pixel_buffer", "rt_stream",
            "rt_local_rows", "rt_current_sample", "rt_read_colors",
            "rt_read_seeds", "rt_get_stats", "rt_last_error", "rt_deinterleave_rows", "rt_compute_camera",
-           "rt_default_seeds", "rt_demo_scene", "rt_read_scene", "rt_build_id"]
+           "rt_default_seeds", "rt_demo_scene", "rt_read_scene", "rt_build_id",
+           "rt_stream_seeds", "rt_seed_stream_async", "rt_write_state", "rt_save_state", "rt_load_state", "rt_merge_async"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -106,6 +107,12 @@ def load_library(diag=False):
         "rt_last_error": (C.c_char_p, []),
         "rt_compute_camera": (None, [vp, i32, i32]),
         "rt_default_seeds": (None, [vp, sz]),
+        "rt_stream_seeds": (None, [C.c_uint64, vp, sz]),
+        "rt_seed_stream_async": (i32, [vp, C.c_uint64, vp]),
+        "rt_write_state": (i32, [vp, vp, vp, i32]),
+        "rt_save_state": (i32, [vp, C.c_char_p]),
+        "rt_load_state": (i32, [vp, C.c_char_p]),
+        "rt_merge_async": (i32, [vp, C.POINTER(vp), i32, vp]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -364,6 +371,36 @@ class RtContext:
         self._check(self._lib.rt_read_seeds(self._h, _ptr(out)))
         return out
 
+    # --- render state in and out (rt_state.hip) -------------------------------------------
+    def seed_stream(self, stream_id, stream=None):
+        """rt_seed_stream_async: pass 0 of seed stream `stream_id` (0 = the default stream), seeded on the device."""
+        self._check(self._lib.rt_seed_stream_async(self._h, stream_id, C.c_void_p(stream or 0)))
+
+    def write_state(self, colors, seeds, current_sample):
+        """rt_write_state: colour plane and seeds as read_colors() / read_seeds() return them (None: the default stream;
+        colours may be None only at pass 0), and the pass number the next launch continues from."""
+        def arr(a, dt, n):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+            if a.size != n:
+                raise ValueError("expected %d elements, got %d" % (n, a.size))
+            return a
+        col, sd = arr(colors, np.float32, 3 * self.w * self.h), arr(seeds, np.uint32, 2 * self.w * self.h)
+        self._check(self._lib.rt_write_state(self._h, _ptr(col) if col is not None else None, _ptr(sd) if sd is not None else None,
+                                             current_sample))
+
+    def save_state(self, path):
+        self._check(self._lib.rt_save_state(self._h, os.fsencode(path)))
+
+    def load_state(self, path):
+        self._check(self._lib.rt_load_state(self._h, os.fsencode(path)))
+
+    def merge(self, sources, stream=None):
+        """rt_merge_async: this context becomes the sample-weighted average of itself and `sources` (contexts of the same size)."""
+        srcs = (C.c_void_p * max(len(sources), 1))(*[s._h.value if s is not None else None for s in sources])
+        self._check(self._lib.rt_merge_async(self._h, srcs, len(sources), C.c_void_p(stream or 0)))
+
     def stats(self):
         st = Stats()
         self._check(self._lib.rt_get_stats(self._h, C.byref(st)))
@@ -387,6 +424,13 @@ def deinterleave_rows(full_ptr, gathered_ptr, w, h, nranks, tile_rows, pad_rows,
     """rt_deinterleave_rows on raw device pointers (the gather root's frame assembly)."""
     _check(load_library().rt_deinterleave_rows(C.c_void_p(full_ptr), C.c_void_p(gathered_ptr), w, h, nranks, tile_rows,
                                                pad_rows, device, C.c_void_p(stream or 0)))
+
+
+def stream_seeds(stream_id, count):
+    """rt_stream_seeds: the first `count` words of seed stream `stream_id` (0 = the default stream).  Needs no device."""
+    out = np.zeros(count, np.uint32)
+    load_library().rt_stream_seeds(stream_id, _ptr(out), count)
+    return out
 
 
 def build_id(diag=False):

@@ -120,6 +120,26 @@ void rt_default_seeds(uint32_t *seeds, size_t count) {
     for (size_t i = have; i < count; ++i) seeds[i] = tail.seed();
 }
 
+// Seed stream `stream_id`: 0 is the default stream above; any other id draws pair i from the splitmix64 finaliser of
+// (stream_id, i), clamped like the reference's own seeds (OpenCLConfig.cpp:676-680).  rt_seed_stream_async generates the
+// same words on the device (rt_state.hip rt_seed_stream_kernel).
+void rt_stream_seeds(uint64_t stream_id, uint32_t *seeds, size_t count) {
+    if (!seeds) return;
+    if (stream_id == 0) {
+        rt_default_seeds(seeds, count);
+        return;
+    }
+    for (size_t i = 0; 2 * i < count; ++i) {
+        uint64_t z = stream_id * 0x9E3779B97F4A7C15ull + (uint64_t)i + 0x9E3779B97F4A7C15ull;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        const uint32_t lo = (uint32_t)z, hi = (uint32_t)(z >> 32);
+        seeds[2 * i] = lo < 2 ? 2u : lo;
+        if (2 * i + 1 < count) seeds[2 * i + 1] = hi < 2 ? 2u : hi;      // (an odd count ends on a low half)
+    }
+}
+
 int rt_demo_scene(rt_sphere *out, uint32_t cap) {
     static const rt_sphere demo[6] = {
         { 1000.f, { 0.f, -1000.f, 0.f }, { 0.f, 0.f, 0.f }, { 0.75f, 0.75f, 0.75f }, RT_DIFF },

@@ -4,10 +4,14 @@
 //   rt_bench <framework ID> <CPU/GPU (0/1)> <mem (0/1/2)> [scene.scn]
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
+//            [--stream N] [--save-state FILE] [--load-state FILE]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
 //   --rehearse N  the same with all N shards on device 0 (rt_create_multi_on: the one-GPU rehearsal of that path)
+//   --stream N    render on seed stream N of the library (rt_seed_stream_async; 0 = the reference's default stream)
+//   --load-state FILE   continue the frame a checkpoint holds (rt_load_state): --spp is the number of passes to ADD
+//   --save-state FILE   write the frame's state when the passes are done (rt_save_state)
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
@@ -49,7 +53,8 @@ int main(int argc, char** argv) {
     bool pin = false;
     double readback_ms = 0.0;   // > 0: copy the frame out only when the last copy is this old (the adapter's display cadence)   // SetupGL.cpp:32-33
     bool doubling = true;
-    std::string out, scene_path;
+    std::string out, scene_path, save_state, load_state;
+    unsigned long long seed_stream = 0;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -66,6 +71,9 @@ int main(int argc, char** argv) {
         else if (a == "--gpus") gpus = atoi(next());
         else if (a == "--rehearse") rehearse = atoi(next());
         else if (a == "--out") out = next();
+        else if (a == "--stream") seed_stream = strtoull(next(), nullptr, 0);
+        else if (a == "--save-state") save_state = next();
+        else if (a == "--load-state") load_state = next();
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -117,6 +125,9 @@ int main(int argc, char** argv) {
     if (rt_set_scene(ctx, spheres.data(), n) != RT_OK) return die("rt_set_scene");
     if (rt_set_camera(ctx, &cam) != RT_OK) return die("rt_set_camera");
     if (rt_set_mode(ctx, mode) != RT_OK) return die("rt_set_mode");
+    if (seed_stream != 0 && rt_seed_stream_async(ctx, seed_stream, rt_stream(ctx)) != RT_OK) return die("rt_seed_stream_async");
+    if (!load_state.empty() && rt_load_state(ctx, load_state.c_str()) != RT_OK) return die("rt_load_state");     // (its seeds replace the stream's)
+    const int first_pass = rt_current_sample(ctx);
 
     std::vector<uint32_t> px(static_cast<size_t>(w) * h);
     if (per_launch <= 0) per_launch = spp;
@@ -145,12 +156,13 @@ int main(int argc, char** argv) {
     rt_stats st;
     if (rt_get_stats(ctx, &st) != RT_OK) return die("rt_get_stats");
     if (!out.empty() && !write_ppm(out, px, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
+    if (!save_state.empty() && rt_save_state(ctx, save_state.c_str()) != RT_OK) return die("rt_save_state");
 
     const double rays = (double)(st.samples + st.shadow_rays);
-    printf("{\"spheres\": %u, \"w\": %d, \"h\": %d, \"spp\": %d, \"launches\": %llu, \"kernel_ms\": %.4f, "
+    printf("{\"spheres\": %u, \"w\": %d, \"h\": %d, \"spp\": %d, \"first_pass\": %d, \"seed_stream\": %llu, \"launches\": %llu, \"kernel_ms\": %.4f, "
            "\"wall_ms_with_readback\": %.4f, \"samples\": %llu, \"closest_rays\": %llu, \"shadow_rays\": %llu, "
            "\"sphere_tests\": %llu, \"Mray_s_primary_shadow\": %.1f, \"Msample_s\": %.1f}\n",
-           n, w, h, spp, (unsigned long long)st.launches, kernel_ms, wall_ms, (unsigned long long)st.samples,
+           n, w, h, spp, first_pass, seed_stream, (unsigned long long)st.launches, kernel_ms, wall_ms, (unsigned long long)st.samples,
            (unsigned long long)st.closest_rays, (unsigned long long)st.shadow_rays,
            (unsigned long long)st.sphere_tests, rays / (kernel_ms * 1e3), (double)st.samples / (kernel_ms * 1e3));
     rt_destroy(ctx);
