@@ -335,6 +335,68 @@ RT_API int rt_load_state(rt_ctx *ctx, const char *path);
  * A refused call changes nothing.                                                                                         */
 RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hip_stream);
 
+/* ---- frame error on the device: compare two frames, map the error, render to a PSNR ------------
+ * How far apart the packed frames of two contexts are, computed where the frames live: one bandwidth-bound kernel reads both
+ * pixel buffers once (8 B per pixel) and leaves 48 bytes, instead of two read-backs (8.3 MB each at 1080p) and a host loop.
+ * THIS LIBRARY'S OWN EXTENSION: the reference renders one frame on one seed stream and compares nothing; these calls reproduce
+ * no reference frame.  Their use: two contexts that render the same scene on seed streams of their own (rt_seed_stream_async) are
+ * independent estimates of one image, and the difference between two N-pass estimates measures the noise of an N-pass render.
+ *
+ * The metric is exact integer arithmetic on the packed words (R | G<<8 | B<<16): with p from a and q from b, for channel c
+ * d_c = ((p >> 8c) & 255) - ((q >> 8c) & 255); bits 24-31 are ignored everywhere.                                            */
+typedef struct {              /* 48 bytes, no padding */
+    uint64_t sq_err[3];       /* per channel R, G, B: sum over the compared pixels of d_c^2                                    */
+    uint64_t differing;       /* pixels whose low 24 bits differ                                                               */
+    uint64_t pixels;          /* pixels compared = rt_local_rows * w                                                           */
+    uint32_t max_abs;         /* largest |d_c| of any channel of any pixel                                                     */
+    uint32_t reserved;        /* 0                                                                                             */
+} rt_frame_error;
+
+/* The tile map that goes with it: one uint32 per 8x8 tile of the LOCAL pixel buffer (the render kernels' tile; edge tiles are
+ * partial), tiles[ty * tiles_x + tx] = sum of d_0^2 + d_1^2 + d_2^2 over the tile (at most 64 * 3 * 255^2 = 12 484 800), with
+ * tiles_x = ceil(w / 8), tiles_y = ceil(rt_local_rows / 8).  rt_compare_tiles stores the two (either pointer may be NULL) and
+ * returns tiles_x * tiles_y, the number of words a map holds (0 for a sharded context without rows), or RT_ERR_ARG.           */
+RT_API int rt_compare_tiles(const rt_ctx *ctx, int *tiles_x, int *tiles_y);
+
+/* Compare the frames of `a` and `b` on `hip_stream`, without a host wait.  `result_dev` is a caller-owned DEVICE address of one
+ * rt_frame_error (required); `tiles_dev` a DEVICE address of rt_compare_tiles() words, or NULL for no map.  The call is ordered
+ * behind everything both contexts have queued, on whatever streams, and their later work behind it (as rt_merge_async); it clears
+ * the result on the stream itself, so that two calls in a row give the same answer.  What is compared are the buffers the
+ * contexts' launches write -- the rt_set_pixel_buffer target if one is set, else the context's own -- each first brought up to
+ * date exactly as by rt_read_pixels_async (the pack kernel, if the last launches ran with the pixel store off).  Modes and pass
+ * numbers may differ between a and b (fast against parity is the 50 dB gate).  Nothing else of either context changes: colours,
+ * seeds, pass number, counters, tile-order costs and rt_last_kernel stay.  Sharded contexts compare their local rows (a context
+ * without rows yields zeros and launches nothing); the sums are integers, so the ranks' results add up exactly (max_abs by maximum).
+ * RT_ERR_ARG, and nothing changes: a null context or result, a == b, contexts that differ in size or sharding (w, h, rank,
+ * nranks, tile_rows) or device, any multi-device context.                                                                    */
+RT_API int rt_compare_async(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, void *hip_stream);
+
+/* The same, blocking, into HOST memory (`tiles_host` may be NULL): on a's own stream through scratch that `a` owns (allocated on
+ * first use, freed by rt_destroy), then the 48 bytes -- and the map, if asked for -- are waited for.                           */
+RT_API int rt_compare(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *tiles_host);
+
+/* 10 * log10(255^2 * 3 * pixels / (sq_err[0] + sq_err[1] + sq_err[2])) in binary64: the PSNR over the packed 8-bit channels that
+ * every quality figure of this project is (tools/fast_gate.py, tools/convergence.py).  +infinity when the sum is 0.  Needs no
+ * device.  (NaN, with rt_last_error set, for a null pointer.)                                                                  */
+RT_API double rt_error_psnr(const rt_frame_error *e);
+
+/* Render two contexts in step until the frames agree: repeat { n = min(passes_per_check, max_passes - rt_current_sample) passes
+ * on each context, asynchronously, each on its own rt_stream; rt_compare; wait for the 48 bytes } and return 1 after the first
+ * check whose rt_error_psnr >= target_psnr_db, 0 when max_passes is reached first, a negative rt_status on error.  *last (host,
+ * required) is the last check, *checks (may be NULL) their number; if no pass could be rendered (max_passes equals the pass
+ * number) it is one check of the frames as they are.  The call sets no seed streams and merges nothing: the caller gives each
+ * context a stream before (rt_seed_stream_async) and combines them after (rt_merge_async).
+ * THE FIGURE IS THE PSNR BETWEEN THE TWO HALVES, each an N-pass render.  The merged 2N-pass frame is closer to the converged
+ * image than the halves are to each other: with independent errors of equal variance the difference of the halves carries twice
+ * the variance of one half and four times that of their mean, about 6 dB in the linear colour plane.  How much of that survives
+ * the clamp, the gamma and the rounding to 8 bits has NOT been measured yet (tools/frame_error_probe.py records it): until it
+ * is, treat the pair figure as a lower bound of the merged frame's quality and add nothing to it.
+ * RT_ERR_ARG: a pair rt_compare refuses, a null `last`, passes_per_check < 1, max_passes below the contexts' pass number, a NaN
+ * target.  RT_ERR_STATE: contexts at different pass numbers; both at pass 0 of the default seed stream (they would render the
+ * same frame and "converge" at once).  A refused call changes nothing.                                                       */
+RT_API int rt_render_converged(rt_ctx *a, rt_ctx *b, double target_psnr_db, int passes_per_check, int max_passes,
+                               rt_frame_error *last, int *checks);
+
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it
  * from the scene -- "rt_trace_parity_w1" (few spheres: one wavefront per workgroup), "..._coop_w1" / "..._coop"

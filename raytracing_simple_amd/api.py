@@ -21,7 +21,8 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_local_rows", "rt_current_sample", "rt_read_colors",
            "rt_read_seeds", "rt_get_stats", "rt_last_error", "rt_deinterleave_rows", "rt_compute_camera",
            "rt_default_seeds", "rt_demo_scene", "rt_read_scene", "rt_build_id",
-           "rt_stream_seeds", "rt_seed_stream_async", "rt_write_state", "rt_save_state", "rt_load_state", "rt_merge_async"]
+           "rt_stream_seeds", "rt_seed_stream_async", "rt_write_state", "rt_save_state", "rt_load_state", "rt_merge_async",
+           "rt_compare_tiles", "rt_compare_async", "rt_compare", "rt_error_psnr", "rt_render_converged"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -43,6 +44,20 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FrameError(C.Structure):
+    """include/rt_api.h rt_frame_error (48 bytes): exact integer sums over the 8-bit channels of two packed frames."""
+    _fields_ = [("sq_err", C.c_uint64 * 3), ("differing", C.c_uint64), ("pixels", C.c_uint64), ("max_abs", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"sq_err": [int(v) for v in self.sq_err], "differing": int(self.differing), "pixels": int(self.pixels),
+                "max_abs": int(self.max_abs), "reserved": int(self.reserved)}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls((C.c_uint64 * 3)(*d["sq_err"]), d["differing"], d["pixels"], d["max_abs"], d.get("reserved", 0))
 
 
 class _Scene(C.Structure):
@@ -113,6 +128,11 @@ def load_library(diag=False):
         "rt_save_state": (i32, [vp, C.c_char_p]),
         "rt_load_state": (i32, [vp, C.c_char_p]),
         "rt_merge_async": (i32, [vp, C.POINTER(vp), i32, vp]),
+        "rt_compare_tiles": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "rt_compare_async": (i32, [vp, vp, vp, vp, vp]),
+        "rt_compare": (i32, [vp, vp, C.POINTER(FrameError), vp]),
+        "rt_error_psnr": (C.c_double, [C.POINTER(FrameError)]),
+        "rt_render_converged": (i32, [vp, vp, C.c_double, i32, i32, C.POINTER(FrameError), C.POINTER(i32)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -401,6 +421,43 @@ class RtContext:
         srcs = (C.c_void_p * max(len(sources), 1))(*[s._h.value if s is not None else None for s in sources])
         self._check(self._lib.rt_merge_async(self._h, srcs, len(sources), C.c_void_p(stream or 0)))
 
+    # --- frame error on the device (rt_compare.hip) --------------------------------------
+    def compare_tiles(self):
+        """rt_compare_tiles: (tiles_y, tiles_x) of the tile map of this context's local rows."""
+        tx, ty = C.c_int(), C.c_int()
+        n = self._lib.rt_compare_tiles(self._h, C.byref(tx), C.byref(ty))
+        if n < 0:
+            self._check(n)
+        return ty.value, tx.value
+
+    def compare(self, other, tiles=False):
+        """rt_compare: the error between this context's packed frame and `other`'s as a dict (FrameError.as_dict); with tiles=True
+        also the squared error per 8x8 tile, uint32 [tiles_y, tiles_x]."""
+        err = FrameError()
+        h_other = other._h if other is not None else None
+        if not tiles:
+            self._check(self._lib.rt_compare(self._h, h_other, C.byref(err), None))
+            return err.as_dict()
+        tmap = np.zeros(self.compare_tiles(), np.uint32)
+        self._check(self._lib.rt_compare(self._h, h_other, C.byref(err), _ptr(tmap)))
+        return err.as_dict(), tmap
+
+    def compare_async(self, other, result_ptr, tiles_ptr=None, stream=None):
+        """rt_compare_async: queue the comparison on `stream`; `result_ptr` is the device address of 48 bytes (an rt_frame_error),
+        `tiles_ptr` the device address of the tile map's words, or None."""
+        self._check(self._lib.rt_compare_async(self._h, other._h if other is not None else None, C.c_void_p(result_ptr or 0),
+                                               C.c_void_p(tiles_ptr or 0), C.c_void_p(stream or 0)))
+
+    def render_converged(self, other, target_db, passes_per_check, max_passes):
+        """rt_render_converged: both contexts rendered in step until the PSNR BETWEEN them reaches `target_db` or they hold
+        `max_passes` passes.  Returns (reached, error dict of the last check, number of checks)."""
+        err, checks = FrameError(), C.c_int()
+        rc = self._lib.rt_render_converged(self._h, other._h if other is not None else None, target_db, passes_per_check, max_passes,
+                                           C.byref(err), C.byref(checks))
+        if rc < 0:
+            self._check(rc)
+        return rc == 1, err.as_dict(), checks.value
+
     def stats(self):
         st = Stats()
         self._check(self._lib.rt_get_stats(self._h, C.byref(st)))
@@ -431,6 +488,13 @@ def stream_seeds(stream_id, count):
     out = np.zeros(count, np.uint32)
     load_library().rt_stream_seeds(stream_id, _ptr(out), count)
     return out
+
+
+def error_psnr(err):
+    """rt_error_psnr of a FrameError or of the dict its as_dict() gives: the PSNR over the packed 8-bit channels.  Needs no device."""
+    if not isinstance(err, FrameError):
+        err = FrameError.from_dict(err)
+    return load_library().rt_error_psnr(C.byref(err))
 
 
 def build_id(diag=False):

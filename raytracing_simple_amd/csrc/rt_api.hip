@@ -116,6 +116,17 @@ int wait_all(rt_ctx *c) {
     return RT_OK;
 }
 
+// rt_read_pixels / rt_read_pixels_async / rt_compare_async: if the last launches ran with the pixel store off, a small kernel packs the
+// frame from the running average (same toInt, .cl:34,594-596) into the buffer the launches write
+int refresh_pixels(rt_ctx *c, hipStream_t stream) {
+    if (c->pixels_current || c->current_sample <= 0) return RT_OK;
+    rt::LaunchParams p = make_params(c, 0);
+    hipError_t e = (c->mode == RT_MODE_FAST || c->mode >= 200) ? rt::launch_pack_fast(p, stream) : rt::launch_pack_parity(p, stream);
+    if (e != hipSuccess) return fail(RT_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
+    c->pixels_current = true;
+    return RT_OK;
+}
+
 int upload_default_seeds(rt_ctx *c) {
     const size_t count = 2 * (size_t)c->w * (size_t)c->h;
     const double t0 = now_ms();
@@ -273,6 +284,7 @@ RT_API void rt_destroy(rt_ctx *c) {
         (void)hipFree(c->d_pixels);
         (void)hipFree(c->d_counters);
         (void)hipFree(c->d_stats);
+        (void)hipFree(c->d_compare);
         (void)hipFree(c->order.d_tile_cost);
         (void)hipFree(c->order.d_order);
         (void)hipFree(c->d_timelog);
@@ -396,6 +408,7 @@ RT_API int rt_reset(rt_ctx *c) {
     c->launches = 0;
     c->last_ms = 0.0;
     c->seeds_default = false;
+    c->seeds_custom = false;            // restore_state copies the default stream into d_seeds
     c->pixels_current = true;
     return restore_state(c);
 }
@@ -529,12 +542,8 @@ RT_API int rt_read_pixels(rt_ctx *c, uint32_t *out_host) {
     if (c->local_rows == 0) return RT_OK;
     rc = chain(c, c->stream);
     if (rc != RT_OK) return rc;
-    if (!c->pixels_current && c->current_sample > 0) {
-        rt::LaunchParams p = make_params(c, 0);
-        hipError_t e = (c->mode == RT_MODE_FAST || c->mode >= 200) ? rt::launch_pack_fast(p, c->stream) : rt::launch_pack_parity(p, c->stream);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
-        c->pixels_current = true;
-    }
+    rc = refresh_pixels(c, c->stream);
+    if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out_host, c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels,
                            (size_t)c->local_rows * c->w * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -550,12 +559,8 @@ RT_API int rt_read_pixels_async(rt_ctx *c, uint32_t *out_host, void *hip_stream)
     hipStream_t stream = (hipStream_t)hip_stream;
     rc = chain(c, stream);
     if (rc != RT_OK) return rc;
-    if (!c->pixels_current && c->current_sample > 0) {
-        rt::LaunchParams p = make_params(c, 0);
-        hipError_t e = (c->mode == RT_MODE_FAST || c->mode >= 200) ? rt::launch_pack_fast(p, stream) : rt::launch_pack_parity(p, stream);
-        if (e != hipSuccess) return fail(RT_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
-        c->pixels_current = true;
-    }
+    rc = refresh_pixels(c, stream);
+    if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out_host, c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels, (size_t)c->local_rows * c->w * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, stream));
     return RT_OK;

@@ -1,0 +1,254 @@
+// rt_compare.hip -- frame error on the device (include/rt_api.h, "frame error"): how far apart the packed frames of two contexts are,
+// as exact integer sums over the 8-bit channels, without a read-back --
+//   rt_compare_async / rt_compare   per-channel squared error, differing pixels, largest difference, and a map of the error per 8x8 tile
+//   rt_compare_tiles                the shape of that map
+//   rt_error_psnr                   the PSNR those sums stand for (host arithmetic, no device)
+//   rt_render_converged             two contexts rendered in step until the PSNR between them reaches a target
+// The difference between two independent N-pass renders of one scene is the standard estimate of an N-pass render's noise.  The reference
+// has one seed stream and compares nothing: this is the library's own extension and reproduces no reference frame.
+// The render kernels are not touched: the call reads the buffers their launches write (after the pack kernel, if the pixel store was off).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+#include "rt_internal.h"
+
+using rt::fail;
+
+namespace rt {
+constexpr int kCmpLanes = 128;                  // a workgroup: two wavefronts
+constexpr int kCmpCols = 4;                     // adjacent columns a lane owns: 16 bytes of either frame per row
+constexpr int kCmpRun = kCmpLanes * kCmpCols;   // columns a workgroup covers at a time (a multiple of the tile width)
+static_assert(kCmpRun % 8 == 0 && 8 % kCmpCols == 0, "a tile's columns belong to whole lanes of one wavefront");
+}  // namespace rt
+
+// What one pixel adds: squared differences per channel, the count of differing pixels, the largest difference.
+struct rt_cmp_sums {
+    uint32_t s0 = 0, s1 = 0, s2 = 0, cnt = 0, max_abs = 0;
+    __device__ __forceinline__ void add(uint32_t p, uint32_t q) {
+        const int d0 = (int)(p & 255u) - (int)(q & 255u);
+        const int d1 = (int)((p >> 8) & 255u) - (int)((q >> 8) & 255u);
+        const int d2 = (int)((p >> 16) & 255u) - (int)((q >> 16) & 255u);
+        s0 += (uint32_t)(d0 * d0);
+        s1 += (uint32_t)(d1 * d1);
+        s2 += (uint32_t)(d2 * d2);
+        cnt += ((p ^ q) & 0x00ffffffu) != 0u ? 1u : 0u;
+        max_abs = max(max_abs, (uint32_t)max(max(abs(d0), abs(d1)), abs(d2)));
+    }
+};
+
+// One pass over both frames.  A workgroup takes a strip of 8 local rows by kCmpRun columns at a time (grid-stride over the strips); a lane owns
+// kCmpCols adjacent columns and walks the 8 rows, so every row read of a wavefront is one contiguous segment.  The two lanes of a tile add up
+// by a shuffle and one of them stores the tile's word; the frame's totals stay in registers over all strips of the workgroup, are added up
+// across the wavefront by shuffles and across the workgroup through LDS, and leave as one 64-bit atomic add per channel, one for the count and
+// one atomic maximum: integer atomics, so the result does not depend on the order.  `result` was cleared on the stream before the launch.
+__global__ void __launch_bounds__(rt::kCmpLanes) rt_compare_kernel(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, int w, int rows,
+                                                                 unsigned long long *result, uint32_t *tiles) {
+    const int lane = threadIdx.x;
+    const int runs = (w + rt::kCmpRun - 1) / rt::kCmpRun, strips = (rows + 7) / 8, tiles_x = (w + 7) / 8;
+    unsigned long long sq0 = 0, sq1 = 0, sq2 = 0, differing = 0;
+    uint32_t max_abs = 0;
+    for (int item = blockIdx.x; item < strips * runs; item += gridDim.x) {
+        const int strip = item / runs, x0 = (item - strip * runs) * rt::kCmpRun + lane * rt::kCmpCols;
+        const int n = min(w - x0, rt::kCmpCols);                // columns of this lane inside the image (<= 0: none)
+        const int y0 = strip * 8, ny = min(rows - y0, 8);
+        // Rows start at any multiple of 4 bytes (w = 41: row 1 at byte 164), so the 16-byte loads are of 4-byte alignment -- gfx950's global
+        // loads take that.  A lane that reaches over the row's end reads its one to three pixels word by word: nothing past a row is touched.
+        rt_cmp_sums t;                                          // this strip: at most 8 * 4 * 255^2 per channel
+        const size_t at = (size_t)y0 * (size_t)w + (size_t)x0;
+        if (n == rt::kCmpCols) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                if (r >= ny) break;
+                uint4 p, q;
+                __builtin_memcpy(&p, a + at + (size_t)r * (size_t)w, sizeof p);
+                __builtin_memcpy(&q, b + at + (size_t)r * (size_t)w, sizeof q);
+                t.add(p.x, q.x);
+                t.add(p.y, q.y);
+                t.add(p.z, q.z);
+                t.add(p.w, q.w);
+            }
+        } else if (n > 0) {
+            for (int r = 0; r < ny; ++r)
+                for (int k = 0; k < n; ++k) t.add(a[at + (size_t)r * (size_t)w + k], b[at + (size_t)r * (size_t)w + k]);
+        }
+        max_abs = max(max_abs, t.max_abs);
+        if (tiles) {                                            // (wave-uniform; every lane takes part in the shuffle)
+            uint32_t sum = t.s0 + t.s1 + t.s2;                  // at most 8 * 4 * 3 * 255^2
+            sum += __shfl_xor(sum, 1);
+            if ((lane & 1) == 0 && n > 0) tiles[(size_t)strip * (size_t)tiles_x + (size_t)(x0 >> 3)] = sum;
+        }
+        sq0 += t.s0;
+        sq1 += t.s1;
+        sq2 += t.s2;
+        differing += t.cnt;
+    }
+    // the frame's totals: across the wavefront by shuffles ...
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        sq0 += __shfl_xor(sq0, m);
+        sq1 += __shfl_xor(sq1, m);
+        sq2 += __shfl_xor(sq2, m);
+        differing += __shfl_xor(differing, m);
+        max_abs = max(max_abs, (uint32_t)__shfl_xor((int)max_abs, m));
+    }
+    // ... across the workgroup through LDS, and one set of atomics per workgroup
+    __shared__ unsigned long long part[rt::kCmpLanes / 64][5];
+    if ((lane & 63) == 0) {
+        unsigned long long *mine = part[lane >> 6];
+        mine[0] = sq0;
+        mine[1] = sq1;
+        mine[2] = sq2;
+        mine[3] = differing;
+        mine[4] = max_abs;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        unsigned long long tot[5] = { 0, 0, 0, 0, 0 };
+        for (int v = 0; v < rt::kCmpLanes / 64; ++v) {
+            for (int k = 0; k < 4; ++k) tot[k] += part[v][k];
+            tot[4] = max(tot[4], part[v][4]);
+        }
+        for (int k = 0; k < 4; ++k)
+            if (tot[k]) atomicAdd(result + k, tot[k]);          // rt_frame_error: sq_err[0..2], differing
+        if (tot[4]) atomicMax(reinterpret_cast<uint32_t *>(result + 5), (uint32_t)tot[4]);     // max_abs
+        if (blockIdx.x == 0) result[4] = (unsigned long long)rows * (unsigned long long)w;     // pixels (a plain store: nothing else writes it)
+    }
+}
+
+using namespace rt;
+
+namespace {
+
+static_assert(sizeof(rt_frame_error) == 48, "rt_frame_error is 48 bytes, no padding");
+
+// the pairs rt_compare_async accepts (include/rt_api.h lists the refusals)
+int check_pair(const rt_ctx *a, const rt_ctx *b) {
+    if (!a || !b) return fail(RT_ERR_ARG, "ctx is null");
+    if (a == b) return fail(RT_ERR_ARG, "rt_compare: a context against itself");
+    if (a->multi || b->multi) return fail(RT_ERR_ARG, "rt_compare: a multi-device context cannot be compared");
+    if (a->w != b->w || a->h != b->h || a->rank != b->rank || a->nranks != b->nranks || a->tile_rows != b->tile_rows)
+        return fail(RT_ERR_ARG, "rt_compare: a is %dx%d, rank %d of %d by %d rows; b %dx%d, rank %d of %d by %d rows", a->w, a->h, a->rank, a->nranks,
+                    a->tile_rows, b->w, b->h, b->rank, b->nranks, b->tile_rows);
+    if (a->device != b->device) return fail(RT_ERR_ARG, "rt_compare: a lives on device %d, b on device %d", a->device, b->device);
+    return RT_OK;
+}
+
+size_t tile_count(const rt_ctx *c) { return (size_t)((c->w + 7) / 8) * (size_t)((c->local_rows + 7) / 8); }
+
+// the pair is checked: queue the comparison on `stream`, behind everything both contexts have queued, their later work behind it
+int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, hipStream_t stream) {
+    int rc = select_device(a);
+    if (rc != RT_OK) return rc;
+    rc = chain(a, stream);
+    if (rc == RT_OK) rc = chain(b, stream);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemsetAsync(result_dev, 0, sizeof(rt_frame_error), stream));     // the accumulators; the whole answer of a context without rows
+    if (a->local_rows == 0) return RT_OK;
+    rc = refresh_pixels(a, stream);
+    if (rc == RT_OK) rc = refresh_pixels(b, stream);
+    if (rc != RT_OK) return rc;
+    const size_t items = (size_t)((a->local_rows + 7) / 8) * (size_t)((a->w + kCmpRun - 1) / kCmpRun);
+    const size_t blocks = std::min(items, (size_t)a->n_cus * 8);
+    hipLaunchKernelGGL(rt_compare_kernel, dim3((unsigned)blocks), dim3(kCmpLanes), 0, stream, a->d_pixels_ext ? a->d_pixels_ext : a->d_pixels,
+                       b->d_pixels_ext ? b->d_pixels_ext : b->d_pixels, a->w, a->local_rows, reinterpret_cast<unsigned long long *>(result_dev), tiles_dev);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// the blocking calls' scratch on a's device: one rt_frame_error, then the tile map
+int ensure_scratch(rt_ctx *a) {
+    if (a->d_compare) return RT_OK;
+    HIP_TRY(hipMalloc(&a->d_compare, sizeof(rt_frame_error) + std::max(tile_count(a), (size_t)1) * sizeof(uint32_t)));
+    return RT_OK;
+}
+
+// rt_compare: on a's own stream through a's scratch, then the wait
+int compare_blocking(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *tiles_host) {
+    int rc = select_device(a);
+    if (rc == RT_OK) rc = ensure_scratch(a);
+    if (rc != RT_OK) return rc;
+    rt_frame_error *res = static_cast<rt_frame_error *>(a->d_compare);
+    uint32_t *tiles = reinterpret_cast<uint32_t *>(res + 1);
+    const bool want_tiles = tiles_host && tile_count(a) > 0;
+    rc = compare_on(a, b, res, want_tiles ? tiles : nullptr, a->stream);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out_host, res, sizeof *res, hipMemcpyDeviceToHost, a->stream));
+    if (want_tiles) HIP_TRY(hipMemcpyAsync(tiles_host, tiles, tile_count(a) * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    return RT_OK;
+}
+
+// at pass 0 the next launch would read the default stream (nothing but rt_seed_stream_async / rt_write_state puts another one there)
+bool on_default_stream(const rt_ctx *c) { return c->seeds_default || !c->seeds_custom; }
+
+}  // namespace
+
+extern "C" {
+
+RT_API int rt_compare_tiles(const rt_ctx *c, int *tiles_x, int *tiles_y) {
+    if (!c) return fail(RT_ERR_ARG, "ctx is null");
+    if (c->multi) return fail(RT_ERR_ARG, "rt_compare_tiles: a multi-device context cannot be compared");
+    const int tx = (c->w + 7) / 8, ty = (c->local_rows + 7) / 8;
+    if (tiles_x) *tiles_x = tx;
+    if (tiles_y) *tiles_y = ty;
+    return tx * ty;
+}
+
+RT_API int rt_compare_async(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, void *hip_stream) {
+    int rc = check_pair(a, b);
+    if (rc != RT_OK) return rc;
+    if (!result_dev) return fail(RT_ERR_ARG, "result_dev is null");
+    return compare_on(a, b, result_dev, tiles_dev, (hipStream_t)hip_stream);
+}
+
+RT_API int rt_compare(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *tiles_host) {
+    int rc = check_pair(a, b);
+    if (rc != RT_OK) return rc;
+    if (!out_host) return fail(RT_ERR_ARG, "out_host is null");
+    return compare_blocking(a, b, out_host, tiles_host);
+}
+
+RT_API double rt_error_psnr(const rt_frame_error *e) {
+    if (!e) {
+        (void)fail(RT_ERR_ARG, "the frame error is null");
+        return std::numeric_limits<double>::quiet_NaN();
+    }
+    const double sum = (double)e->sq_err[0] + (double)e->sq_err[1] + (double)e->sq_err[2];
+    if (sum == 0.0) return std::numeric_limits<double>::infinity();
+    return 10.0 * std::log10(255.0 * 255.0 * 3.0 * (double)e->pixels / sum);
+}
+
+RT_API int rt_render_converged(rt_ctx *a, rt_ctx *b, double target_psnr_db, int passes_per_check, int max_passes, rt_frame_error *last, int *checks) {
+    int rc = check_pair(a, b);
+    if (rc != RT_OK) return rc;
+    if (!last) return fail(RT_ERR_ARG, "last is null");
+    if (passes_per_check < 1) return fail(RT_ERR_ARG, "passes_per_check %d", passes_per_check);
+    if (std::isnan(target_psnr_db)) return fail(RT_ERR_ARG, "target_psnr_db is not a number");
+    if (max_passes < a->current_sample || max_passes < b->current_sample)
+        return fail(RT_ERR_ARG, "max_passes %d is below the passes the contexts hold (%d, %d)", max_passes, a->current_sample, b->current_sample);
+    if (a->current_sample != b->current_sample)
+        return fail(RT_ERR_STATE, "rt_render_converged: the contexts hold %d and %d passes", a->current_sample, b->current_sample);
+    if (a->current_sample == 0 && on_default_stream(a) && on_default_stream(b))
+        return fail(RT_ERR_STATE, "rt_render_converged: both contexts are at pass 0 of the default seed stream and would render the same frame "
+                                  "(rt_seed_stream_async gives each a stream of its own)");
+    if (checks) *checks = 0;
+    for (int done = 0;; ++done) {
+        const int n = std::min(passes_per_check, max_passes - a->current_sample);
+        if (n == 0 && done > 0) return 0;                       // max_passes reached: *last is the last check
+        if (n > 0) {
+            rc = rt_render_async(a, n, a->stream);
+            if (rc == RT_OK) rc = rt_render_async(b, n, b->stream);
+            if (rc != RT_OK) return rc;
+        }
+        rc = compare_blocking(a, b, last, nullptr);
+        if (rc != RT_OK) return rc;
+        if (checks) *checks = done + 1;
+        if (rt_error_psnr(last) >= target_psnr_db) return 1;
+        if (n == 0) return 0;                                   // no pass to render: one check of the frames as they are
+    }
+}
+
+}  // extern "C"

@@ -458,6 +458,7 @@ RT_API int rt_debug_reset_by_copy(rt_ctx *c, void *hip_stream, int flags) {
         HIP_TRY(hipGetLastError());
     }
     c->seeds_default = false;
+    c->seeds_custom = false;            // d_seeds holds the default stream again
     c->current_sample = 0;
     return RT_OK;
 }

@@ -76,6 +76,8 @@ struct rt_ctx {
     int pixel_write = 1;                // rt_set_pixel_write
     bool pixels_current = true;         // the packed pixel buffer holds the frame of the running average
     bool seeds_default = false;         // after rt_reset_async: the next launch reads the pristine stream
+    bool seeds_custom = false;          // d_seeds was last filled by rt_seed_stream_async / rt_write_state, not from the default stream (rt_render_converged asks at pass 0)
+    void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; allocated on first use)
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters
     // scene: raw records + the tables the device-side build kernel derives from them, one allocation
@@ -188,6 +190,7 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int select_device(const rt_ctx *c);
 int chain(rt_ctx *c, hipStream_t stream);          // `stream` waits for whatever the context queued last elsewhere (ALL its work runs in issue order)
 int wait_all(rt_ctx *c);                            // host waits for everything the context has queued
+int refresh_pixels(rt_ctx *c, hipStream_t stream); // the packed frame brought up to date on `stream` (already chained): the pack kernel, if the last launches ran with the pixel store off
 const double *create_breakdown();                   // host ms of the last rt_create by phase (rt_debug_create_breakdown)
 
 // ---- rt_launch.hip: one launch of the render kernel ----

@@ -105,6 +105,7 @@ int write_one(rt_ctx *c, const float *colors_host, const uint32_t *seeds_host, i
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, rt::kStatReplicas * 8 * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));               // the caller's buffers may go
     c->seeds_default = seeds_host == nullptr;               // no seeds given: the next launch reads the pristine default stream in place
+    c->seeds_custom = seeds_host != nullptr;
     c->current_sample = current_sample;
     c->choice.frame_ended();
     c->launches = 0;
@@ -135,6 +136,7 @@ RT_API int rt_seed_stream_async(rt_ctx *c, uint64_t stream_id, void *hip_stream)
                            reinterpret_cast<unsigned long long *>(s->d_seeds), px, (unsigned long long)stream_id);
         HIP_TRY(hipGetLastError());
         s->seeds_default = false;                           // the next launch reads d_seeds
+        s->seeds_custom = true;
     }
     return RT_OK;
 }

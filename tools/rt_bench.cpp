@@ -4,7 +4,7 @@
 //   rt_bench <framework ID> <CPU/GPU (0/1)> <mem (0/1/2)> [scene.scn]
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
-//            [--stream N] [--save-state FILE] [--load-state FILE]
+//            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -12,6 +12,10 @@
 //   --stream N    render on seed stream N of the library (rt_seed_stream_async; 0 = the reference's default stream)
 //   --load-state FILE   continue the frame a checkpoint holds (rt_load_state): --spp is the number of passes to ADD
 //   --save-state FILE   write the frame's state when the passes are done (rt_save_state)
+//   --until-psnr DB     render two contexts on seed streams 1 and 2 in step (rt_render_converged) until the PSNR BETWEEN them reaches DB or
+//                       each holds --spp passes, checking every --check-every N passes (default 8); then merge them (rt_merge_async) and
+//                       write --out from the merged frame.  Prints passes per half, checks and the last PSNR of the pair -- the merged
+//                       frame is better than that figure (include/rt_api.h, rt_render_converged)
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
@@ -55,6 +59,9 @@ int main(int argc, char** argv) {
     bool doubling = true;
     std::string out, scene_path, save_state, load_state;
     unsigned long long seed_stream = 0;
+    double until_psnr = 0.0;
+    bool until = false;
+    int check_every = 8;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -74,6 +81,8 @@ int main(int argc, char** argv) {
         else if (a == "--stream") seed_stream = strtoull(next(), nullptr, 0);
         else if (a == "--save-state") save_state = next();
         else if (a == "--load-state") load_state = next();
+        else if (a == "--until-psnr") { until_psnr = atof(next()); until = true; }
+        else if (a == "--check-every") check_every = atoi(next());
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -112,6 +121,35 @@ int main(int argc, char** argv) {
         printf("], \"w\": %d, \"h\": %d, \"spp\": %d, \"spheres\": %u}\n", w, h, spp, n);
         if (!out.empty() && !write_ppm(out, px1, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
         rt_release_cache();
+        return 0;
+    }
+
+    if (until) {                                     // two halves on streams of their own, rendered until they agree, then merged
+        rt_ctx* half[2] = { nullptr, nullptr };
+        for (int k = 0; k < 2; ++k) {
+            if (rt_create(&half[k], w, h) != RT_OK) return die("rt_create");
+            if (rt_set_scene(half[k], spheres.data(), n) != RT_OK) return die("rt_set_scene");
+            if (rt_set_camera(half[k], &cam) != RT_OK) return die("rt_set_camera");
+            if (rt_set_mode(half[k], mode) != RT_OK) return die("rt_set_mode");
+            if (rt_seed_stream_async(half[k], 1 + (unsigned)k, rt_stream(half[k])) != RT_OK) return die("rt_seed_stream_async");
+        }
+        rt_frame_error err{};
+        int checks = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        const int reached = rt_render_converged(half[0], half[1], until_psnr, check_every, spp, &err, &checks);
+        if (reached < 0) return die("rt_render_converged");
+        const int per_half = rt_current_sample(half[0]);
+        if (rt_merge_async(half[0], &half[1], 1, rt_stream(half[0])) != RT_OK) return die("rt_merge_async");
+        std::vector<uint32_t> merged(static_cast<size_t>(w) * h);
+        if (rt_read_pixels(half[0], merged.data()) != RT_OK) return die("rt_read_pixels");
+        const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (!out.empty() && !write_ppm(out, merged, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
+        printf("{\"spheres\": %u, \"w\": %d, \"h\": %d, \"until_psnr\": %.3f, \"reached\": %s, \"passes_per_half\": %d, \"merged_passes\": %d, "
+               "\"checks\": %d, \"check_every\": %d, \"pair_psnr_db\": %.3f, \"differing\": %llu, \"max_abs\": %u, \"wall_ms\": %.4f}\n",
+               n, w, h, until_psnr, reached ? "true" : "false", per_half, rt_current_sample(half[0]), checks, check_every, rt_error_psnr(&err),
+               (unsigned long long)err.differing, err.max_abs, wall_ms);
+        rt_destroy(half[0]);
+        rt_destroy(half[1]);
         return 0;
     }
 
