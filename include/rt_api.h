@@ -332,7 +332,11 @@ RT_API int rt_load_state(rt_ctx *ctx, const char *path);
  * contexts on one stream render the same frame, and merging them gains nothing.
  * RT_ERR_ARG: n_srcs outside 1 .. 15, a null entry, dst among the sources, a source listed twice, contexts that differ in
  * size or sharding (w, h, rank, nranks, tile_rows) or device, any multi-device context.  RT_ERR_STATE: N == 0.
- * A refused call changes nothing.                                                                                         */
+ * A refused call changes nothing.
+ * With a RAGGED context among them (adaptive sampling, below) a second kernel does the same arithmetic with n_X = the pass count X holds
+ * FOR THE TILE THE FLOAT'S PIXEL LIES IN: a context whose tile holds no pass is skipped for that tile, a tile nobody holds a pass of keeps
+ * dst's floats.  dst's tile counts become the per-tile sums, its pass number the sum of the pass numbers as always, and dst is ragged.
+ * With whole contexts only, nothing has changed: the same kernel, the same bits.                                                      */
 RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hip_stream);
 
 /* ---- frame error on the device: compare two frames, map the error, render to a PSNR ------------
@@ -396,6 +400,71 @@ RT_API double rt_error_psnr(const rt_frame_error *e);
  * same frame and "converge" at once).  A refused call changes nothing.                                                       */
 RT_API int rt_render_converged(rt_ctx *a, rt_ctx *b, double target_psnr_db, int passes_per_check, int max_passes,
                                rt_frame_error *last, int *checks);
+
+/* ---- adaptive sampling: render only the 8x8 tiles that are still noisy ----------------------------
+ * rt_render_converged adds whole frames until the frame as a whole has converged; one noisy corner keeps every sky tile rendering.  The
+ * calls below render SUBSETS of the tiles, chosen on the device from rt_compare_async's tile map.  THIS LIBRARY'S OWN EXTENSION, like the
+ * state and compare calls.  The render kernels are the same: they take their tile from a list, and a subset launch is a shorter list and a
+ * smaller grid.
+ * WHAT MAKES IT EXACT: pixels are independent, so a tile that has received p passes holds the colours, seeds and packed pixels of a uniform
+ * p-pass render of its seed stream, bit for bit, whatever happened to the other tiles.  rt_get_stats stays exact too (the kernels count
+ * valid lanes only): samples = sum over the pixels of the pixel's pass count.
+ * THE GROUP RULE: what is selected and rendered is a GROUP -- the 8x8 tiles 4g .. 4g+3 of one tile row: 32x8 pixels aligned at multiples
+ * of 32 in x (fewer tiles and pixels at the right and top edges), the tile of the widest shipped workgroup.  A group is rendered whole or
+ * not at all, so its tiles hold one pass count, and both the one-wavefront (8x8) and the four-wavefront (32x8) instances can render it.
+ * THE FRONT RULE: a launch has ONE first pass number, so only groups whose pass count equals rt_current_sample -- the FRONT -- can be
+ * selected.  A group that was left out of a subset launch has fallen behind and stays retired until the context is whole again.  The
+ * device enforces this (rt_select_tiles reads the counts), not the caller.
+ * A context is RAGGED while some tile holds fewer passes than rt_current_sample.  rt_reset, rt_reset_async, rt_seed_stream_async,
+ * rt_write_state and rt_load_state make it whole again (and drop the selection).  ON A RAGGED CONTEXT these return RT_ERR_STATE and change
+ * nothing: rt_render_pass, rt_render_async, rt_render_converged, rt_render_adaptive (a full-frame launch would continue the retired tiles
+ * from the wrong pass number) and rt_save_state (file format 1 holds one pass number).  rt_read_colors, rt_read_seeds, rt_read_pixels(_async),
+ * rt_compare*, rt_get_stats and rt_set_pixel_write with the pack kernel work as on any context; rt_merge_async weights each tile by its own
+ * count (below).  Multi-device contexts and sharded contexts (nranks > 1) are refused by every call of this section with RT_ERR_ARG.
+ * NOT TIMED ON AN MI355X YET: a subset launch pays the LDS staging per workgroup like any other launch, each rt_select_tiles waits for
+ * 8 bytes, and the list is built once per selection; tools/adaptive_probe.py records what that costs against what it saves
+ * (profiles/r11_adaptive.jsonl).  No speed-up is promised.                                                                            */
+
+/* The pass count of every 8x8 tile: rt_compare_tiles() words in that call's indexing, into HOST memory.  Blocking.  For a context that
+ * is not ragged every word equals rt_current_sample (nothing is stored on the device until a subset launch leaves tiles behind).      */
+RT_API int rt_tile_passes(rt_ctx *ctx, uint32_t *out_host);
+
+/* Select the groups the next rt_render_tiles_async renders.  A group is selected when it is at the front AND (err_dev is NULL, OR some
+ * tile t of it has  err_dev[t] * 64 > above * pixels(t)),  pixels(t) = the image pixels inside tile t: 64 for a full tile -- the rule is
+ * then err > above -- fewer at the right and top edges.  `err_dev` is a DEVICE array of rt_compare_tiles() words in that layout:
+ * rt_compare_async's map, or anything else.  One small kernel on `hip_stream`, ordered behind the context's work, writes one flag per
+ * group into the context; the call then WAITS for 8 bytes: counts[0] = selected groups, counts[1] = the 8x8 tiles they cover (`counts`
+ * may be NULL; the context keeps both).  A new selection replaces the old one; a reset or a merge into the context drops it.
+ * RT_ERR_ARG: a null, multi-device or sharded context.                                                                               */
+RT_API int rt_select_tiles(rt_ctx *ctx, const uint32_t *err_dev, uint32_t above, void *hip_stream, uint32_t counts[2]);
+
+/* n_samples passes on the selected groups and on nothing else, asynchronously on `hip_stream`.  RT_OK and nothing done when the
+ * selection is empty or n_samples == 0.  The launch uses the kernel form the context's last launch used (before any launch: what the
+ * thresholds say for the scene); it starts, advances and times none of the measurements rt_scene_choice reports, and it reads the
+ * heavy-first tile order without touching it or the tile costs.  A small kernel builds the launch's tile list from the selection -- the
+ * selected groups' tiles in heavy-first order where one exists, else in image order -- once per selection, order and tile shape; another
+ * adds n_samples to the pass count of every tile of every selected group.  Afterwards rt_current_sample has grown by n_samples, the
+ * launch count by one, rt_last_kernel names the instance, and the context is ragged unless the selection held every group of the image.
+ * RT_ERR_STATE: no selection; no scene or camera; a kernel instance whose tile is wider than a group (the diagnostics library's
+ * two-pixels-per-lane rows).  RT_ERR_ARG: n_samples < 0 or a pass counter overflow; a null, multi-device or sharded context.            */
+RT_API int rt_render_tiles_async(rt_ctx *ctx, int n_samples, void *hip_stream);
+
+/* rt_render_converged per tile.  Preconditions and refusals are that call's; besides, min_passes >= 0 (RT_ERR_ARG) and neither context
+ * may be ragged on entry (RT_ERR_STATE).
+ *   1. while the pass number is below min(min_passes, max_passes): the shortfall as ordinary full launches on both contexts;
+ *   2. repeat { rt_compare with the tile map (a's scratch); rt_select_tiles on BOTH contexts from that one map with
+ *      above = floor(255^2 * 192 / 10^(tile_psnr_db / 10)) -- the tile's squared error at which the PSNR over its 192 channel values
+ *      equals the target; the same map gives the same selection, so the two contexts stay in step tile for tile;
+ *      no group selected: return 1;  pass number == max_passes: return 0;
+ *      rt_render_tiles_async of min(passes_per_check, max_passes - passes) on each context, each on its own rt_stream }.
+ * *last (host, required) is the last WHOLE-FRAME comparison, *checks (may be NULL) their number.  A negative rt_status on error.
+ * The call merges nothing: rt_merge_async(a, &b, 1, ...) afterwards is exact per tile, and rt_tile_passes gives the sample map.
+ * Everything said above rt_render_converged about the pair figure holds PER TILE: a tile's figure is the PSNR between the two halves, a
+ * lower bound of the merged tile's quality by an offset that has not been measured.  Besides, a tile's figure at few passes is itself
+ * NOISY -- it is a sum over 64 pixels, not over a frame -- so a tile can retire by chance with both halves wrong in the same direction or
+ * simply close; retired is final.  min_passes is the guard against that: no tile is judged before it holds that many passes.          */
+RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
+                              rt_frame_error *last, int *checks);
 
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it

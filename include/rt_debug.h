@@ -76,6 +76,7 @@ RT_API int rt_debug_read_packed_pairs(rt_ctx *ctx, void *out, uint32_t cap_bytes
 RT_API int rt_debug_set_wg_waves(rt_ctx *ctx, int waves);          /* 0 = automatic, 1 or 4 wavefronts per workgroup */
 RT_API int rt_debug_set_tile_order(rt_ctx *ctx, int on);           /* 0 = natural tile order; 1 = heavy first (the default) */
 RT_API int rt_debug_read_tile_order(rt_ctx *ctx, uint32_t *order_out, uint32_t *cost_out, uint32_t cap, uint32_t *n_tiles, int *valid);
+RT_API int rt_debug_read_tile_list(rt_ctx *ctx, uint32_t *list_out, uint32_t cap, uint32_t *n_slots, uint32_t *n_launch, int *by_order);   /* the tile list the last rt_render_tiles_async walked: grid.x * grid.y entries, the sentinel (= *n_launch) at the end; *by_order = 1 if it follows the heavy-first order */
 
 /* raw diagnostic counters (section census of the stamped instances; valid after rt_get_stats) */
 RT_API int rt_debug_counters(rt_ctx *ctx, unsigned long long *out24);

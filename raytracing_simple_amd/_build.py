@@ -41,6 +41,7 @@ UNITS = [
     ("rt_bvh.hip", ["-ffp-contract=off"]),
     ("rt_state.hip", ["-ffp-contract=off"]),
     ("rt_compare.hip", ["-ffp-contract=off"]),
+    ("rt_tiles.hip", ["-ffp-contract=off"]),
     ("rt_host.cpp", ["-ffp-contract=off"]),
     ("rt_build_id.cpp", []),
 ]

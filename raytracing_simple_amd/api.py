@@ -22,11 +22,12 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_read_seeds", "rt_get_stats", "rt_last_error", "rt_deinterleave_rows", "rt_compute_camera",
            "rt_default_seeds", "rt_demo_scene", "rt_read_scene", "rt_build_id",
            "rt_stream_seeds", "rt_seed_stream_async", "rt_write_state", "rt_save_state", "rt_load_state", "rt_merge_async",
-           "rt_compare_tiles", "rt_compare_async", "rt_compare", "rt_error_psnr", "rt_render_converged"]
+           "rt_compare_tiles", "rt_compare_async", "rt_compare", "rt_error_psnr", "rt_render_converged",
+           "rt_tile_passes", "rt_select_tiles", "rt_render_tiles_async", "rt_render_adaptive"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
-                 "rt_debug_set_ncus", "rt_debug_set_coop_min", "rt_debug_set_bvh", "rt_debug_set_tree_shape", "rt_debug_set_bvh_layout", "rt_debug_set_walk", "rt_debug_set_walk_round", "rt_debug_bvh_pick", "rt_debug_tree_estimate", "rt_debug_set_choice_estimate", "rt_debug_create_breakdown", "rt_debug_walk_rays", "rt_debug_read_bvh", "rt_debug_read_packed_pairs", "rt_debug_set_tile_order", "rt_debug_read_tile_order", "rt_debug_set_wg_waves", "rt_debug_counters", "rt_debug_counters_raw",
+                 "rt_debug_set_ncus", "rt_debug_set_coop_min", "rt_debug_set_bvh", "rt_debug_set_tree_shape", "rt_debug_set_bvh_layout", "rt_debug_set_walk", "rt_debug_set_walk_round", "rt_debug_bvh_pick", "rt_debug_tree_estimate", "rt_debug_set_choice_estimate", "rt_debug_create_breakdown", "rt_debug_walk_rays", "rt_debug_read_bvh", "rt_debug_read_packed_pairs", "rt_debug_set_tile_order", "rt_debug_read_tile_order", "rt_debug_read_tile_list", "rt_debug_set_wg_waves", "rt_debug_counters", "rt_debug_counters_raw",
                  "rt_debug_reset_by_copy", "rt_debug_probe_seeds", "rt_debug_sidelog_read", "rt_debug_timelog_enable", "rt_debug_timelog_tag",
                  "rt_debug_timelog_read", "rt_debug_wavelog_read"]
 
@@ -133,6 +134,10 @@ def load_library(diag=False):
         "rt_compare": (i32, [vp, vp, C.POINTER(FrameError), vp]),
         "rt_error_psnr": (C.c_double, [C.POINTER(FrameError)]),
         "rt_render_converged": (i32, [vp, vp, C.c_double, i32, i32, C.POINTER(FrameError), C.POINTER(i32)]),
+        "rt_tile_passes": (i32, [vp, vp]),
+        "rt_select_tiles": (i32, [vp, vp, u32, vp, C.POINTER(u32)]),
+        "rt_render_tiles_async": (i32, [vp, i32, vp]),
+        "rt_render_adaptive": (i32, [vp, vp, C.c_double, i32, i32, i32, C.POINTER(FrameError), C.POINTER(i32)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -169,6 +174,7 @@ def load_library(diag=False):
             "rt_debug_set_tile_order": (i32, [vp, i32]),
             "rt_debug_set_wg_waves": (i32, [vp, i32]),
             "rt_debug_read_tile_order": (i32, [vp, vp, vp, u32, C.POINTER(u32), C.POINTER(i32)]),
+            "rt_debug_read_tile_list": (i32, [vp, vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)]),
             "rt_debug_counters": (i32, [vp, vp]),
             "rt_debug_counters_raw": (i32, [vp, vp]),
             "rt_debug_reset_by_copy": (i32, [vp, vp, i32]),
@@ -458,6 +464,34 @@ class RtContext:
             self._check(rc)
         return rc == 1, err.as_dict(), checks.value
 
+    # --- adaptive sampling (rt_tiles.hip) --------------------------------------------------
+    def tile_passes(self):
+        """rt_tile_passes: the pass count of every 8x8 tile, uint32 [tiles_y, tiles_x]."""
+        out = np.zeros(self.compare_tiles(), np.uint32)
+        self._check(self._lib.rt_tile_passes(self._h, _ptr(out)))
+        return out
+
+    def select_tiles(self, err_ptr, above, stream=None):
+        """rt_select_tiles: select the groups (32x8 pixels) at the front whose error in the DEVICE map at `err_ptr` lies above `above`
+        (None: every group at the front).  Returns (selected groups, the 8x8 tiles they cover)."""
+        counts = (C.c_uint32 * 2)()
+        self._check(self._lib.rt_select_tiles(self._h, C.c_void_p(err_ptr or 0), above, C.c_void_p(stream or 0), counts))
+        return int(counts[0]), int(counts[1])
+
+    def render_tiles_async(self, n_samples, stream=None):
+        """rt_render_tiles_async: `n_samples` passes on the selected groups and nothing else."""
+        self._check(self._lib.rt_render_tiles_async(self._h, n_samples, C.c_void_p(stream or 0)))
+
+    def render_adaptive(self, other, tile_db, min_passes, passes_per_check, max_passes):
+        """rt_render_adaptive: both contexts rendered in step, each group of tiles until the PSNR between its two halves reaches `tile_db`
+        or the contexts hold `max_passes` passes.  Returns (every group retired, error dict of the last whole-frame check, number of checks)."""
+        err, checks = FrameError(), C.c_int()
+        rc = self._lib.rt_render_adaptive(self._h, other._h if other is not None else None, tile_db, min_passes, passes_per_check, max_passes,
+                                          C.byref(err), C.byref(checks))
+        if rc < 0:
+            self._check(rc)
+        return rc == 1, err.as_dict(), checks.value
+
     def stats(self):
         st = Stats()
         self._check(self._lib.rt_get_stats(self._h, C.byref(st)))
@@ -481,6 +515,46 @@ def deinterleave_rows(full_ptr, gathered_ptr, w, h, nranks, tile_rows, pad_rows,
     """rt_deinterleave_rows on raw device pointers (the gather root's frame assembly)."""
     _check(load_library().rt_deinterleave_rows(C.c_void_p(full_ptr), C.c_void_p(gathered_ptr), w, h, nranks, tile_rows,
                                                pad_rows, device, C.c_void_p(stream or 0)))
+
+
+class DeviceWords:
+    """A uint32 array copied into device memory (tests and tools: a hand-made tile map for select_tiles), through hipMalloc / hipMemcpy of
+    the HIP runtime the library itself is linked against -- found among the process's loaded objects, so both share one runtime.
+    `ptr` is the device address; the memory is freed by close() or with the object."""
+
+    _hip = None
+
+    @classmethod
+    def _runtime(cls):
+        if cls._hip is None:
+            load_library()
+            paths = [line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line]
+            if not paths:
+                raise RtError(-2, "the HIP runtime is not loaded in this process")
+            cls._hip = C.CDLL(paths[0])
+        return cls._hip
+
+    def __init__(self, words):
+        hip = self._runtime()
+        a = np.ascontiguousarray(words, dtype=np.uint32)
+        p = C.c_void_p()
+        if hip.hipMalloc(C.byref(p), C.c_size_t(max(a.nbytes, 4))) != 0:
+            raise RtError(-3, "hipMalloc of %d bytes failed" % a.nbytes)
+        self.ptr, self.size = p.value, a.size
+        if a.nbytes and hip.hipMemcpy(C.c_void_p(self.ptr), _ptr(a), C.c_size_t(a.nbytes), 1) != 0:     # hipMemcpyHostToDevice; blocking
+            self.close()
+            raise RtError(-4, "hipMemcpy to the device failed")
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self._hip.hipFree(C.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def stream_seeds(stream_id, count):

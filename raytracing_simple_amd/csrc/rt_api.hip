@@ -285,6 +285,9 @@ RT_API void rt_destroy(rt_ctx *c) {
         (void)hipFree(c->d_counters);
         (void)hipFree(c->d_stats);
         (void)hipFree(c->d_compare);
+        (void)hipFree(c->tiles.d_passes);
+        (void)hipFree(c->tiles.d_selected);
+        (void)hipFree(c->tiles.d_list);
         (void)hipFree(c->order.d_tile_cost);
         (void)hipFree(c->order.d_order);
         (void)hipFree(c->d_timelog);
@@ -404,6 +407,7 @@ RT_API int rt_reset(rt_ctx *c) {
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
     c->current_sample = 0;
+    c->tiles.whole();
     c->choice.frame_ended();
     c->launches = 0;
     c->last_ms = 0.0;
@@ -424,6 +428,7 @@ RT_API int rt_reset_async(rt_ctx *c, void *hip_stream) {
     HIP_TRY(hipGetLastError());
     c->seeds_default = true;            // the next launch reads d_seeds0
     c->current_sample = 0;
+    c->tiles.whole();
     c->choice.frame_ended();
     c->launches = 0;
     c->last_ms = 0.0;
@@ -433,6 +438,7 @@ RT_API int rt_reset_async(rt_ctx *c, void *hip_stream) {
 RT_API int rt_render_async(rt_ctx *c, int n_samples, void *hip_stream) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     if (c->multi) return rt::multi_render(c, nullptr, n_samples, false);
+    if (c->tiles.ragged) return fail(RT_ERR_STATE, "rt_render_async: the tiles hold different pass counts after a subset launch (rt_render_tiles_async goes on; rt_reset makes the frame whole)");
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     if (!c->throttle_on || n_samples <= 0) return launch(c, n_samples, (hipStream_t)hip_stream);
@@ -509,6 +515,7 @@ RT_API int rt_throttle(rt_ctx *c, int max_in_flight, double *ms_per_pass) {
 RT_API int rt_render_pass(rt_ctx *c, uint32_t *out_host, int n_samples) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     if (c->multi) return rt::multi_render(c, out_host, n_samples, true);
+    if (c->tiles.ragged) return fail(RT_ERR_STATE, "rt_render_pass: the tiles hold different pass counts after a subset launch (rt_render_tiles_async goes on; rt_reset makes the frame whole)");
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     rc = chain(c, c->stream);

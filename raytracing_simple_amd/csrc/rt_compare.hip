@@ -234,6 +234,8 @@ RT_API int rt_render_converged(rt_ctx *a, rt_ctx *b, double target_psnr_db, int 
     if (a->current_sample == 0 && on_default_stream(a) && on_default_stream(b))
         return fail(RT_ERR_STATE, "rt_render_converged: both contexts are at pass 0 of the default seed stream and would render the same frame "
                                   "(rt_seed_stream_async gives each a stream of its own)");
+    if (a->tiles.ragged || b->tiles.ragged)
+        return fail(RT_ERR_STATE, "rt_render_converged: the tiles of a context hold different pass counts after a subset launch (rt_reset makes the frame whole)");
     if (checks) *checks = 0;
     for (int done = 0;; ++done) {
         const int n = std::min(passes_per_check, max_passes - a->current_sample);
@@ -248,6 +250,68 @@ RT_API int rt_render_converged(rt_ctx *a, rt_ctx *b, double target_psnr_db, int 
         if (checks) *checks = done + 1;
         if (rt_error_psnr(last) >= target_psnr_db) return 1;
         if (n == 0) return 0;                                   // no pass to render: one check of the frames as they are
+    }
+}
+
+// the tile's squared error at which the PSNR over its 192 channel values equals `db`: floor(255^2 * 192 / 10^(db / 10)), kept inside 32 bits
+static uint32_t tile_error_at(double db) {
+    const double v = std::floor(255.0 * 255.0 * 192.0 / std::pow(10.0, db / 10.0));
+    return v >= 4294967295.0 ? 0xffffffffu : (v > 0.0 ? (uint32_t)v : 0u);
+}
+
+RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes, rt_frame_error *last,
+                              int *checks) {
+    int rc = check_pair(a, b);
+    if (rc != RT_OK) return rc;
+    rc = tiles_refuse(a, "rt_render_adaptive");
+    if (rc == RT_OK) rc = tiles_refuse(b, "rt_render_adaptive");
+    if (rc != RT_OK) return rc;
+    if (!last) return fail(RT_ERR_ARG, "last is null");
+    if (passes_per_check < 1) return fail(RT_ERR_ARG, "passes_per_check %d", passes_per_check);
+    if (min_passes < 0) return fail(RT_ERR_ARG, "min_passes %d", min_passes);
+    if (std::isnan(tile_psnr_db)) return fail(RT_ERR_ARG, "tile_psnr_db is not a number");
+    if (max_passes < a->current_sample || max_passes < b->current_sample)
+        return fail(RT_ERR_ARG, "max_passes %d is below the passes the contexts hold (%d, %d)", max_passes, a->current_sample, b->current_sample);
+    if (a->current_sample != b->current_sample)
+        return fail(RT_ERR_STATE, "rt_render_adaptive: the contexts hold %d and %d passes", a->current_sample, b->current_sample);
+    if (a->current_sample == 0 && on_default_stream(a) && on_default_stream(b))
+        return fail(RT_ERR_STATE, "rt_render_adaptive: both contexts are at pass 0 of the default seed stream and would render the same frame "
+                                  "(rt_seed_stream_async gives each a stream of its own)");
+    if (a->tiles.ragged || b->tiles.ragged)
+        return fail(RT_ERR_STATE, "rt_render_adaptive: the tiles of a context hold different pass counts already (rt_reset makes the frame whole)");
+    if (checks) *checks = 0;
+    rc = select_device(a);
+    if (rc == RT_OK) rc = ensure_scratch(a);
+    if (rc != RT_OK) return rc;
+    // 1. the passes every tile gets, as ordinary full launches
+    const int floor_passes = std::min(min_passes, max_passes);
+    if (a->current_sample < floor_passes) {
+        const int n = floor_passes - a->current_sample;
+        rc = rt_render_async(a, n, a->stream);
+        if (rc == RT_OK) rc = rt_render_async(b, n, b->stream);
+        if (rc != RT_OK) return rc;
+    }
+    // 2. compare, select on both contexts from the one map, render the selected groups
+    const uint32_t above = tile_error_at(tile_psnr_db);
+    rt_frame_error *res = static_cast<rt_frame_error *>(a->d_compare);
+    uint32_t *map = reinterpret_cast<uint32_t *>(res + 1);
+    for (int done = 0;; ++done) {
+        rc = compare_on(a, b, res, map, a->stream);
+        if (rc != RT_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(last, res, sizeof *res, hipMemcpyDeviceToHost, a->stream));
+        uint32_t counts_a[2] = { 0, 0 }, counts_b[2] = { 0, 0 };
+        rc = rt_select_tiles(a, map, above, a->stream, counts_a);      // (waits for a's stream: *last has landed too)
+        if (rc == RT_OK) rc = rt_select_tiles(b, map, above, b->stream, counts_b);
+        if (rc != RT_OK) return rc;
+        if (checks) *checks = done + 1;
+        if (counts_a[0] != counts_b[0] || counts_a[1] != counts_b[1])
+            return fail(RT_ERR_STATE, "rt_render_adaptive: the contexts selected %u and %u groups from one map (their tile pass counts differ)", counts_a[0], counts_b[0]);
+        if (counts_a[0] == 0) return 1;                         // every group has retired
+        const int n = std::min(passes_per_check, max_passes - a->current_sample);
+        if (n == 0) return 0;                                   // max_passes reached with groups still above the target
+        rc = rt_render_tiles_async(a, n, a->stream);
+        if (rc == RT_OK) rc = rt_render_tiles_async(b, n, b->stream);
+        if (rc != RT_OK) return rc;
     }
 }
 

@@ -235,6 +235,22 @@ RT_API int rt_debug_read_tile_order(rt_ctx *c, uint32_t *order_out, uint32_t *co
     if (valid) *valid = c->order.has_order() ? 1 : 0;
     return RT_OK;
 }
+// the tile list the last subset launch walked (rt_render_tiles_async): its entries -- the launch's grid.x * grid.y, the sentinel n_launch at the end --
+// the launch tiles of the instance's shape, and whether it was compacted from the heavy-first order (1) or from image order (0)
+RT_API int rt_debug_read_tile_list(rt_ctx *c, uint32_t *list_out, uint32_t cap, uint32_t *n_slots, uint32_t *n_launch, int *by_order) {
+    if (!c || c->multi) return fail(RT_ERR_ARG, "null / multi-device context");
+    if (!c->tiles.list_valid) return fail(RT_ERR_STATE, "rt_debug_read_tile_list: no subset launch has built a list (or the selection, the order or a reset made it stale)");
+    int rc = select_device(c);
+    if (rc != RT_OK) return rc;
+    rc = wait_all(c);
+    if (rc != RT_OK) return rc;
+    const uint32_t n = cap < c->tiles.list_slots ? cap : c->tiles.list_slots;
+    if (list_out && n) HIP_TRY(hipMemcpy(list_out, c->tiles.d_list, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_slots) *n_slots = c->tiles.list_slots;
+    if (n_launch) *n_launch = c->tiles.list_tiles;
+    if (by_order) *by_order = c->tiles.list_by_order ? 1 : 0;
+    return RT_OK;
+}
 // the hierarchy of large scenes: min_spheres = smallest tree that is built and used (0 = never), lds_limit = largest
 // LDS footprint it is used at (0 = keep).  Takes effect at once: the current scene's tables are rebuilt.
 static int dbg_set_bvh_lds(rt_ctx *c, int v) { if (v > 0) c->bvh_lds_limit = v; return RT_OK; }

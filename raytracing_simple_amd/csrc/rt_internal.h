@@ -60,6 +60,28 @@ struct Probe {
     int samples[2] = { 0, 0 };          // passes between the events of arm 0, arm 1
 };
 
+constexpr int kMergeMax = 16;           // rt_merge_async: dst + 15 sources
+
+// Adaptive sampling (rt_tiles.hip; include/rt_api.h "adaptive sampling").  A GROUP is the 8x8 tiles 4g .. 4g+3 of one tile row -- the 32x8 tile of
+// the widest shipped workgroup; it is rendered whole or not at all, so its tiles hold one pass count.
+struct TileSubset {
+    uint32_t *d_passes = nullptr;       // one word per 8x8 tile of the local pixel buffer (rt_compare_tiles' indexing); allocated on first use.  Its content
+                                        // means something only while `ragged`: otherwise every tile holds current_sample passes and nothing is stored
+    bool ragged = false;                // some tile holds fewer passes than current_sample
+    uint32_t *d_selected = nullptr;     // one flag per group (rt_select_tiles), then two words: selected groups, the 8x8 tiles they cover
+    uint32_t *d_list = nullptr;         // the subset launch's tile list: the launch tiles of the selected groups, padded with the sentinel to whole grid rows
+    bool have_selection = false;
+    uint32_t counts[2] = { 0, 0 };      // host copy of the two words
+    uint64_t selection_serial = 0;      // counts rt_select_tiles calls
+    // what d_list was built from (it is rebuilt only when one of these changes; a new sort of the order clears list_valid: rt_launch.hip)
+    bool list_valid = false, list_by_order = false;
+    uint64_t list_serial = 0;
+    uint32_t list_tiles = 0;            // launch tiles of the instance's shape
+    uint32_t list_slots = 0;            // entries: the launch's grid.x * grid.y
+    // every tile holds current_sample passes again (rt_reset and the calls that write a whole state); a selection does not outlive that
+    void whole() { ragged = false; have_selection = false; list_valid = false; }
+};
+
 }  // namespace rt
 
 struct rt_ctx {
@@ -77,6 +99,8 @@ struct rt_ctx {
     bool pixels_current = true;         // the packed pixel buffer holds the frame of the running average
     bool seeds_default = false;         // after rt_reset_async: the next launch reads the pristine stream
     bool seeds_custom = false;          // d_seeds was last filled by rt_seed_stream_async / rt_write_state, not from the default stream (rt_render_converged asks at pass 0)
+    // adaptive sampling (rt_tiles.hip): a pass count per 8x8 tile, the selected groups, the launch list of a subset launch
+    rt::TileSubset tiles;
     void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; allocated on first use)
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters
@@ -216,6 +240,15 @@ int upload_spheres(rt_ctx *c, uint32_t first, uint32_t count, const rt_sphere *s
 hipError_t prepare_bvh_build();
 int build_bvh(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload = false);
 int render_shard(rt_ctx *c, int n_samples, bool may_block);      // rt_launch.hip: one shard's launch on its own stream
+
+// ---- rt_tiles.hip: the subset launch's device side ----
+inline uint32_t group_count(const rt_ctx *c) { return (uint32_t)(((c->w + 31) / 32) * ((c->local_rows + 7) / 8)); }
+int tiles_refuse(const rt_ctx *c, const char *call);                  // RT_ERR_ARG for the contexts the adaptive calls do not take (null, multi-device, sharded)
+int tiles_ensure(rt_ctx *c);                                          // the three device arrays of rt_ctx::tiles, on first use
+int merge_by_tile(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, int total, hipStream_t stream);   // rt_merge_async with a ragged context among them (checked by the caller)
+int tiles_build_list(rt_ctx *c, int waves, bool by_order, uint32_t n_launch, uint32_t slots, hipStream_t stream);   // d_list for an instance of `waves` wavefronts
+int tiles_advance(rt_ctx *c, int n_samples, hipStream_t stream);      // + n_samples on every tile of every selected group (the array made explicit first)
+int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream);       // rt_launch.hip: n_samples passes on the selected groups
 
 // multi-device context (rt_multi.hip); `front` is the rt_ctx whose `multi` points at the record
 void multi_destroy(rt_ctx *front);

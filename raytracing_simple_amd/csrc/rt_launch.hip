@@ -268,6 +268,7 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, Form form, 
         hipLaunchKernelGGL(rt_order_tiles_kernel, dim3(1), dim3(1024), 0, stream, c->order.d_tile_cost, c->order.d_order, n_tiles);
         if (hipPeekAtLastError() != hipSuccess) c->order.forget();      // (no order from a sort that was not queued)
         HIP_TRY(hipGetLastError());
+        c->tiles.list_valid = false;                                    // (a subset launch's list follows the order: launch_tiles builds it again)
     }
     if (plan.use_order) p.order = c->order.d_order;
     if (plan.write_costs) p.tile_cost = c->order.d_tile_cost;
@@ -296,6 +297,83 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, Form form, 
     c->choice.last = rt::walks_hierarchy(inst->tables) ? Form::Walk : (coop ? Form::SweepCoop : Form::SweepPlain);
     c->seeds_default = false;           // this launch has written every seed pair the context renders
     c->pixels_current = c->pixel_write != 0;
+    return RT_OK;
+}
+
+// rt_render_tiles_async: n_samples passes on the groups rt_select_tiles selected, and on nothing else (rt_tiles.hip).  The render kernels take their
+// tile from LaunchParams::order, so the launch is a list of the selected groups' tiles and a grid just large enough for it: (tiles_x, ceil(m / tiles_x))
+// -- grid.x stays the instance's tiles per row, because the kernels form tile_by and tile_bx with gridDim.x -- the list padded to whole grid rows with
+// the SENTINEL id tiles_x * tiles_y.  A workgroup that draws the sentinel has tile_by = tiles_y, so lrow >= local_rows in every lane: no lane is valid,
+// nothing is loaded or stored, zeros are added to the counters, and with tile_cost null there is no other store (rt_trace.inc.h, rt_walk.inc.h: the
+// `valid` / `valid_e` tests and the epilogue).  The instance is the one the context's last launch used (choice.last; before any launch what the thresholds
+// say); no probe is started, advanced or timed, and the heavy-first schedule is read, never written: no plan(), no launched(), no costs.
+int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream) {
+    if (!c->have_scene || !c->have_cam) return fail(RT_ERR_STATE, "rt_set_scene and rt_set_camera must precede rendering");
+    if (n_samples < 0) return fail(RT_ERR_ARG, "n_samples < 0");
+    if (n_samples > 0x7fffffff - c->current_sample) return fail(RT_ERR_ARG, "pass counter would overflow (%d + %d)", c->current_sample, n_samples);
+    rt::TileSubset &sub = c->tiles;
+    if (!sub.have_selection) return fail(RT_ERR_STATE, "rt_render_tiles_async: no selection (rt_select_tiles comes first; a reset drops it)");
+    if (n_samples == 0 || sub.counts[0] == 0) return RT_OK;
+    int rc = RT_OK;
+    if (c->tables_stale) {
+        rc = refresh_tables(c, stream);
+        if (rc != RT_OK) return rc;
+    }
+    rc = chain(c, stream);
+    if (rc != RT_OK) return rc;
+
+    Chosen chosen;
+    rc = choose_instance(c, n_samples, c->choice.last, &chosen);
+    if (rc != RT_OK) return rc;
+    const rt::Instance *inst = chosen.inst;
+    if ((inst->flags & (rt::kInstTwoRays | rt::kInstPersistent | rt::kInstNoTileCost)) != 0 || (inst->waves != 1 && inst->waves != 4))
+        return fail(RT_ERR_STATE, "rt_render_tiles_async: %s does not render a 32x8 group from a tile list (a wider tile, or no list at all)", inst->name);
+    rt::LaunchParams p = make_params(c, n_samples);
+    p.mat_in_lds = chosen.mat_in_lds;
+    if (chosen.regen_gate) p.regen_gate = chosen.regen_gate;
+    p.walk_round = (c->walk_round & 0xff) | (c->walk_tail << 8);
+    size_t lds_use = 0;
+    rc = bind_tables(c, *inst, n_samples, p, &lds_use);
+    if (rc != RT_OK) return rc;
+
+    const uint32_t tiles_x = (uint32_t)((c->w + 8 * inst->waves - 1) / (8 * inst->waves)), tiles_y = (uint32_t)((c->local_rows + rt::kTileH - 1) / rt::kTileH);
+    const uint32_t n_launch = tiles_x * tiles_y;
+    const uint32_t m = inst->waves == 4 ? sub.counts[0] : sub.counts[1];       // launch tiles kept: a group is one 32x8 tile, or the 8x8 tiles it covers
+    dim3 grid(tiles_x, (m + tiles_x - 1) / tiles_x);
+    const bool by_order = c->order.use_order != 0 && c->order.has_order() && c->order.cost_tiles == n_launch;      // a schedule sorted for this tile shape
+    if (!sub.list_valid || sub.list_serial != sub.selection_serial || sub.list_tiles != n_launch || sub.list_by_order != by_order) {
+        rc = tiles_build_list(c, inst->waves, by_order, n_launch, grid.x * grid.y, stream);
+        if (rc != RT_OK) return rc;
+    }
+    const bool all = sub.counts[0] == group_count(c);       // every group selected means every group at the front: the frame stays (or is again) whole
+    if (c->seeds_default && !all) {
+        // after rt_reset_async the first launch reads the pristine stream in place and writes the context's buffer; the tiles this launch leaves out
+        // must hold that stream too (a tile at 0 passes holds the seeds of a 0-pass render): the copy rt_reset makes, now
+        HIP_TRY(hipMemcpyAsync(c->d_seeds, c->d_seeds0, 2 * (size_t)c->w * (size_t)c->h * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        c->seeds_default = false;
+        p.seeds_in = c->d_seeds;
+    }
+    p.order = sub.d_list;
+    p.tile_cost = nullptr;
+    const hipError_t e = rt::launch_instance(*inst, p, grid, lds_use, stream);
+    if (e != hipSuccess)
+        return fail(RT_ERR_HIP, "kernel launch failed: %s (%s, grid %ux%u, lds %zu B)", hipGetErrorString(e), inst->name, grid.x, grid.y, lds_use);
+    if (!all) {
+        rc = tiles_advance(c, n_samples, stream);           // (reads current_sample as it was: the count the selected groups come from)
+        if (rc != RT_OK) return rc;
+    }
+    sub.ragged = !all;
+    // (a timed step of the cooperative-or-plain measurement that is open lies between an event and the full launches still to come: this launch
+    // would be timed with them, so the step starts again with the next full launch -- nothing of the measurement is started, advanced or timed here)
+    if ((c->probe.state & 1) != 0 && c->probe.acc > 0) c->probe.acc = 0;
+    c->current_sample += n_samples;
+    c->launches += 1;
+    c->choice.scene_launches += 1;
+    c->last_kernel = inst->name;
+    const bool coop = inst->role == rt::kRoleCoop || inst->role == rt::kRolePersistCoop;
+    c->choice.last = rt::walks_hierarchy(inst->tables) ? Form::Walk : (coop ? Form::SweepCoop : Form::SweepPlain);
+    c->seeds_default = false;
+    c->pixels_current = c->pixel_write != 0 && (all || c->pixels_current);      // (the tiles left out keep the packed pixels they had)
     return RT_OK;
 }
 

@@ -39,7 +39,6 @@ __global__ void __launch_bounds__(256) rt_seed_stream_kernel(unsigned long long 
 // before it writes that element.  Pointers and weights travel by value; the loop over them is wave-uniform and unrolled, so the
 // argument arrays are only ever indexed by constants.
 namespace rt {
-constexpr int kMergeMax = 16;           // dst + 15 sources
 struct MergeArgs {
     const float *plane[kMergeMax];
     float weight[kMergeMax];
@@ -107,6 +106,7 @@ int write_one(rt_ctx *c, const float *colors_host, const uint32_t *seeds_host, i
     c->seeds_default = seeds_host == nullptr;               // no seeds given: the next launch reads the pristine default stream in place
     c->seeds_custom = seeds_host != nullptr;
     c->current_sample = current_sample;
+    c->tiles.whole();                                       // a written state is a whole frame at one pass number
     c->choice.frame_ended();
     c->launches = 0;
     c->last_ms = 0.0;
@@ -160,6 +160,7 @@ RT_API int rt_write_state(rt_ctx *c, const float *colors_host, const uint32_t *s
 RT_API int rt_save_state(rt_ctx *c, const char *path) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     if (!path) return fail(RT_ERR_ARG, "path is null");
+    if (c->tiles.ragged) return fail(RT_ERR_STATE, "rt_save_state: the tiles hold different pass counts after a subset launch, and the file format holds one pass number");
     const size_t px = (size_t)c->w * (size_t)c->h;
     std::vector<float> colors(3 * px);
     std::vector<uint32_t> seeds(2 * px);
@@ -244,6 +245,10 @@ RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hi
     a.inv_total = 1.0f / (float)total;
     int rc = select_device(dst);
     if (rc != RT_OK) return rc;
+    bool ragged = dst->tiles.ragged;
+    for (int k = 0; k < n_srcs; ++k) ragged = ragged || srcs[k]->tiles.ragged;
+    if (ragged)                                             // tiles at different pass counts (after subset launches): every float by its own tile's weights
+        return merge_by_tile(dst, srcs, n_srcs, (int)total, (hipStream_t)hip_stream);
     // behind everything the destination and the sources it reads have queued; their later work behind the merge
     hipStream_t stream = (hipStream_t)hip_stream;
     rc = chain(dst, stream);
@@ -257,6 +262,7 @@ RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hi
     hipLaunchKernelGGL(rt_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dst->d_colors, a, n_floats);
     HIP_TRY(hipGetLastError());
     dst->current_sample = (int)total;
+    dst->tiles.have_selection = false;                      // (a selection was made at another pass number)
     dst->pixels_current = false;                            // rt_read_pixels packs the merged plane
     return RT_OK;
 }

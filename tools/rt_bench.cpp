@@ -4,7 +4,7 @@
 //   rt_bench <framework ID> <CPU/GPU (0/1)> <mem (0/1/2)> [scene.scn]
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
-//            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N]]
+//            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -16,10 +16,14 @@
 //                       each holds --spp passes, checking every --check-every N passes (default 8); then merge them (rt_merge_async) and
 //                       write --out from the merged frame.  Prints passes per half, checks and the last PSNR of the pair -- the merged
 //                       frame is better than that figure (include/rt_api.h, rt_render_converged)
+//   --adaptive          with --until-psnr: DB is the target PER 8x8 TILE and only the groups of tiles still below it are rendered
+//                       (rt_render_adaptive), after --min-passes M passes on every tile (default 16).  A second line gives the checks, the
+//                       samples rendered against w * h * passes of both halves, and the smallest, median and largest tile pass count
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
 // Prints one JSON line with frame time and ray throughput.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -62,6 +66,8 @@ int main(int argc, char** argv) {
     double until_psnr = 0.0;
     bool until = false;
     int check_every = 8;
+    bool adaptive = false;      // --until-psnr per 8x8 tile: rt_render_adaptive instead of rt_render_converged
+    int min_passes = 16;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -83,6 +89,8 @@ int main(int argc, char** argv) {
         else if (a == "--load-state") load_state = next();
         else if (a == "--until-psnr") { until_psnr = atof(next()); until = true; }
         else if (a == "--check-every") check_every = atoi(next());
+        else if (a == "--adaptive") adaptive = true;
+        else if (a == "--min-passes") min_passes = atoi(next());
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -136,9 +144,19 @@ int main(int argc, char** argv) {
         rt_frame_error err{};
         int checks = 0;
         const auto t0 = std::chrono::steady_clock::now();
-        const int reached = rt_render_converged(half[0], half[1], until_psnr, check_every, spp, &err, &checks);
-        if (reached < 0) return die("rt_render_converged");
+        const int reached = adaptive ? rt_render_adaptive(half[0], half[1], until_psnr, min_passes, check_every, spp, &err, &checks)
+                                     : rt_render_converged(half[0], half[1], until_psnr, check_every, spp, &err, &checks);
+        if (reached < 0) return die(adaptive ? "rt_render_adaptive" : "rt_render_converged");
         const int per_half = rt_current_sample(half[0]);
+        // adaptive: what was rendered against what whole frames to that pass number would have been, and the sample map
+        rt_stats st_half[2];
+        std::vector<uint32_t> tile_passes((size_t)rt_compare_tiles(half[0], nullptr, nullptr));
+        if (adaptive) {
+            for (int k = 0; k < 2; ++k)
+                if (rt_get_stats(half[k], &st_half[k]) != RT_OK) return die("rt_get_stats");
+            if (rt_tile_passes(half[0], tile_passes.data()) != RT_OK) return die("rt_tile_passes");
+            std::sort(tile_passes.begin(), tile_passes.end());
+        }
         if (rt_merge_async(half[0], &half[1], 1, rt_stream(half[0])) != RT_OK) return die("rt_merge_async");
         std::vector<uint32_t> merged(static_cast<size_t>(w) * h);
         if (rt_read_pixels(half[0], merged.data()) != RT_OK) return die("rt_read_pixels");
@@ -148,6 +166,11 @@ int main(int argc, char** argv) {
                "\"checks\": %d, \"check_every\": %d, \"pair_psnr_db\": %.3f, \"differing\": %llu, \"max_abs\": %u, \"wall_ms\": %.4f}\n",
                n, w, h, until_psnr, reached ? "true" : "false", per_half, rt_current_sample(half[0]), checks, check_every, rt_error_psnr(&err),
                (unsigned long long)err.differing, err.max_abs, wall_ms);
+        if (adaptive)
+            printf("{\"adaptive\": true, \"min_passes\": %d, \"checks\": %d, \"samples_rendered\": %llu, \"samples_of_whole_frames\": %llu, "
+                   "\"tile_passes_min\": %u, \"tile_passes_median\": %u, \"tile_passes_max\": %u}\n",
+                   min_passes, checks, (unsigned long long)(st_half[0].samples + st_half[1].samples), 2ull * (unsigned long long)w * h * per_half,
+                   tile_passes.front(), tile_passes[tile_passes.size() / 2], tile_passes.back());
         rt_destroy(half[0]);
         rt_destroy(half[1]);
         return 0;
