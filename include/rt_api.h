@@ -466,6 +466,73 @@ RT_API int rt_render_tiles_async(rt_ctx *ctx, int n_samples, void *hip_stream);
 RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
                               rt_frame_error *last, int *checks);
 
+/* ---- denoising: a non-local-means filter steered by the difference of two halves ------------------
+ * The last step of the pipeline above: two contexts render one scene on seed streams of their own, are compared, rendered until they agree
+ * and merged -- and the merged frame still carries the residual noise.  The two halves are the standard input of a filter for it: their
+ * difference is a per-pixel estimate of the variance, and a non-local-means filter whose weights are steered by that estimate is what
+ * Rousselle, Knaus and Zwicker pair with adaptive sampling (2012).  THIS LIBRARY'S OWN EXTENSION: the reference filters nothing,
+ * and these calls reproduce no reference frame.  A FILTERED FRAME IS BIASED: it is no longer the average of its passes, and rendering on
+ * from it (rt_render_async on dst afterwards) continues a biased average.  Filter the frame you show, not the state you keep.
+ *
+ * THE ARITHMETIC, the same in rt_denoise_async's kernel and in rt_denoise_planes, all binary32, uncontracted, in this order, IEEE division.
+ * Planes are [h][w][3] floats as rt_read_colors returns them; cl(y, x) clamps both coordinates to the image; D is the image, A and B the
+ * halves; R = search_radius, P = patch_radius, kk = k * k, inv = 1.0f / (float)(3 * (2P + 1) * (2P + 1)).
+ *   1. V[y][x][c] = d * d with d = (A - B) * 0.5f                    (the variance of the mean of two equal halves)
+ *   2. Vs[y][x][c] = (sum of V[cl(y + j, x + i)][c], j = -1..1 outer, i = -1..1 inner, from its first term) * (1.0f / 9.0f)
+ *   3. for an offset o = (oy, ox), a pixel p inside the image and q' = cl(p + o), per channel: t = D[p][c] - D[q'][c],
+ *      m = Vs[q'][c] < Vs[p][c] ? Vs[q'][c] : Vs[p][c],
+ *      dc = (t * t - alpha * (Vs[p][c] + m)) / (1e-10f + kk * (Vs[p][c] + Vs[q'][c]));     e(p, o) = (d0 + d1) + d2
+ *   4. S(p, o) = sum of e(cl(p + delta), o), dy = -P..P outer, dx inner, from its first term;  T = S * inv.  e is taken at the clamped
+ *      position AND THAT POSITION'S OWN clamped partner -- not at cl(p + delta + o); the two differ at the border
+ *   5. offsets run oy = -R..R outer, ox inner.  o = (0, 0): wgt = 1.0f.  p + o outside the image: skipped.  T a NaN, or any of the three
+ *      D[p + o][c] not finite: skipped.  Otherwise g = T > 0 ? T : 0 and wgt = 1.0f / (1.0f + g * (1.0f + g * 0.5f))
+ *   6. num[c] and den start at 0.0f; every offset that is not skipped adds wgt * D[p + o][c] and wgt, in offset order;
+ *      out[p][c] = num[c] / den.  den >= 1.  A non-finite pixel stays non-finite and spreads to no neighbour.
+ * With R = 0 the output is the image, bit for bit.
+ * MEASURED, in numpy on a CPU, with frames of this project's oracle (the arithmetic above before any kernel existed): the Demo scene at 96x64,
+ * halves on seed streams 1 and 2, against a 4096-pass frame of the default stream (32 768 passes for the two larger N), PSNR over 8-bit
+ * channels packed by numpy's clip, **(1 / 2.2), * 255 + 0.5:
+ *     passes per half     pair      merged    filtered (R 5, P 1, alpha 1, k 0.45)
+ *           4           14.8 dB      20.4        27.7
+ *          16           20.9         26.5        31.6
+ *          64           26.4         31.3        35.8
+ *         256           31.3         36.3        40.3
+ * R = 3 gives the same within 0.4 dB; k = 1.0 and P = 2 are 1 - 2.5 dB worse.  tools/denoise_probe.py measures the gain and the kernel's time
+ * on the device (profiles/r12_denoise.jsonl); no time is promised.                                                                     */
+typedef struct {              /* 16 bytes */
+    int32_t search_radius;    /* R: the window is (2R + 1)^2 offsets; 0 .. 8                                                    */
+    int32_t patch_radius;     /* P: patches of (2P + 1)^2 pixels; 0 .. 2                                                        */
+    float alpha;              /* how much of the noise's own share is taken off a squared difference; finite, >= 0             */
+    float k;                  /* the filter's strength: distances are measured in units of k^2 * variance; finite, > 0         */
+} rt_denoise_params;
+
+/* {5, 1, 1.0f, 0.45f}.  Needs no device.                                                                                       */
+RT_API void rt_denoise_defaults(rt_denoise_params *p);
+
+/* Filter dst's colour plane -- the image D -- steered by the colour planes of `a` and `b`, the two independent halves A and B, on
+ * `hip_stream`, without a host wait.  The intended use: dst is a third context that holds their merge, rt_merge_async(dst, {a, b}, 2, s) with
+ * dst at pass 0.  That also holds after rt_render_adaptive: the merge is then per tile, the variance estimate is per pixel.  `p` == NULL
+ * means the defaults.  The call is ordered behind everything the three contexts have queued, on whatever streams, and their later work
+ * behind it (as rt_merge_async).  Two kernels: the smoothed variance (rule 2) into a plane that dst owns, then the filter -- a workgroup per
+ * 32x8 pixels, D and Vs of the tile and its halo of R + P staged in LDS, e(., o) formed once per offset for the tile and its P-halo and
+ * shared by the patches that cover it -- into a SCRATCH PLANE THAT dst OWNS (both allocated on first use, freed by rt_destroy).  The
+ * scratch plane then BECOMES the colour plane BY EXCHANGING THE TWO POINTERS; nothing is copied, and the old plane is the next call's scratch.
+ * Afterwards dst's colour plane holds the filtered image and its packed pixels are stale: rt_read_pixels and rt_compare* pack the plane with
+ * the same toInt as after a merge.  Nothing else of dst changes and nothing at all of a or b: pass number, seeds, counters, tile counts,
+ * selection, tile order and rt_last_kernel stay.  search_radius == 0 launches nothing and leaves dst as it is.
+ * Ragged contexts are accepted.  The arithmetic weights the halves equally, which is right when a and b hold equal counts tile for tile;
+ * rt_render_adaptive leaves them that way and checks it.  THAT IS NOT CHECKED HERE.
+ * RT_ERR_ARG: a null context; dst equal to a or b, or a == b; contexts that differ in size or device; any multi-device or sharded context
+ * (the halo would cross shards); search_radius outside 0 .. 8, patch_radius outside 0 .. 2; alpha negative or not finite; k not finite
+ * or <= 0.  RT_ERR_STATE: rt_current_sample(a) != rt_current_sample(b); either of them 0; rt_current_sample(dst) different from their sum
+ * (dst is not their merge).  A refused call changes nothing.                                                                            */
+RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_params *p, void *hip_stream);
+
+/* The same arithmetic on HOST planes of w x h pixels, as plain loops: the readable statement of the rules above, and what the device is
+ * tested against bit for bit.  `out` may not overlap the inputs.  Needs no device.  RT_ERR_ARG: a null plane, w or h < 1, parameters
+ * rt_denoise_async refuses.                                                                                                           */
+RT_API int rt_denoise_planes(float *out, const float *merged, const float *a, const float *b, int w, int h, const rt_denoise_params *p);
+
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it
  * from the scene -- "rt_trace_parity_w1" (few spheres: one wavefront per workgroup), "..._coop_w1" / "..._coop"

@@ -42,6 +42,7 @@ UNITS = [
     ("rt_state.hip", ["-ffp-contract=off"]),
     ("rt_compare.hip", ["-ffp-contract=off"]),
     ("rt_tiles.hip", ["-ffp-contract=off"]),
+    ("rt_denoise.hip", ["-ffp-contract=off"]),
     ("rt_host.cpp", ["-ffp-contract=off"]),
     ("rt_build_id.cpp", []),
 ]

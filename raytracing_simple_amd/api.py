@@ -23,7 +23,8 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_default_seeds", "rt_demo_scene", "rt_read_scene", "rt_build_id",
            "rt_stream_seeds", "rt_seed_stream_async", "rt_write_state", "rt_save_state", "rt_load_state", "rt_merge_async",
            "rt_compare_tiles", "rt_compare_async", "rt_compare", "rt_error_psnr", "rt_render_converged",
-           "rt_tile_passes", "rt_select_tiles", "rt_render_tiles_async", "rt_render_adaptive"]
+           "rt_tile_passes", "rt_select_tiles", "rt_render_tiles_async", "rt_render_adaptive",
+           "rt_denoise_defaults", "rt_denoise_async", "rt_denoise_planes"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -59,6 +60,14 @@ class FrameError(C.Structure):
     @classmethod
     def from_dict(cls, d):
         return cls((C.c_uint64 * 3)(*d["sq_err"]), d["differing"], d["pixels"], d["max_abs"], d.get("reserved", 0))
+
+
+class DenoiseParams(C.Structure):
+    """include/rt_api.h rt_denoise_params (16 bytes): search radius R, patch radius P, alpha, k."""
+    _fields_ = [("search_radius", C.c_int32), ("patch_radius", C.c_int32), ("alpha", C.c_float), ("k", C.c_float)]
+
+    def as_dict(self):
+        return {"search_radius": int(self.search_radius), "patch_radius": int(self.patch_radius), "alpha": float(self.alpha), "k": float(self.k)}
 
 
 class _Scene(C.Structure):
@@ -138,6 +147,9 @@ def load_library(diag=False):
         "rt_select_tiles": (i32, [vp, vp, u32, vp, C.POINTER(u32)]),
         "rt_render_tiles_async": (i32, [vp, i32, vp]),
         "rt_render_adaptive": (i32, [vp, vp, C.c_double, i32, i32, i32, C.POINTER(FrameError), C.POINTER(i32)]),
+        "rt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
+        "rt_denoise_async": (i32, [vp, vp, vp, C.POINTER(DenoiseParams), vp]),
+        "rt_denoise_planes": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(DenoiseParams)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -492,6 +504,13 @@ class RtContext:
             self._check(rc)
         return rc == 1, err.as_dict(), checks.value
 
+    # --- denoising (rt_denoise.hip) ----------------------------------------------------------
+    def denoise(self, a, b, params=None, stream=None):
+        """rt_denoise_async: this context's colour plane (the merge of `a` and `b`) filtered by non-local means, steered by the difference of
+        the two halves.  `params`: a DenoiseParams, a dict of its fields over the defaults, or None for the defaults."""
+        self._check(self._lib.rt_denoise_async(self._h, a._h if a is not None else None, b._h if b is not None else None,
+                                               _denoise_params(params), C.c_void_p(stream or 0)))
+
     def stats(self):
         st = Stats()
         self._check(self._lib.rt_get_stats(self._h, C.byref(st)))
@@ -561,6 +580,37 @@ def stream_seeds(stream_id, count):
     """rt_stream_seeds: the first `count` words of seed stream `stream_id` (0 = the default stream).  Needs no device."""
     out = np.zeros(count, np.uint32)
     load_library().rt_stream_seeds(stream_id, _ptr(out), count)
+    return out
+
+
+def denoise_defaults():
+    """rt_denoise_defaults: DenoiseParams {5, 1, 1.0, 0.45}.  Needs no device."""
+    p = DenoiseParams()
+    load_library().rt_denoise_defaults(C.byref(p))
+    return p
+
+
+def _denoise_params(params):
+    """None (the library's defaults), a DenoiseParams, or a dict of fields laid over the defaults -> what the C call takes."""
+    if params is None or isinstance(params, DenoiseParams):
+        return C.byref(params) if params is not None else None
+    p = denoise_defaults()
+    for name, value in dict(params).items():
+        if name not in ("search_radius", "patch_radius", "alpha", "k"):
+            raise ValueError("rt_denoise_params has no field %r" % name)
+        setattr(p, name, value)
+    return C.byref(p)
+
+
+def denoise_planes(merged, a, b, w, h, params=None):
+    """rt_denoise_planes: the filter of RtContext.denoise on HOST planes ([h][w][3] float32, as read_colors() returns them); returns the
+    filtered plane, float32 [3 * w * h].  Needs no device."""
+    planes = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (merged, a, b)]
+    for x in planes:
+        if x.size != 3 * w * h:
+            raise ValueError("expected %d floats, got %d" % (3 * w * h, x.size))
+    out = np.zeros(3 * w * h, np.float32)
+    _check(load_library().rt_denoise_planes(_ptr(out), _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), w, h, _denoise_params(params)))
     return out
 
 

@@ -204,4 +204,101 @@ int rt_read_scene(const char *path, rt_sphere *out, uint32_t cap, uint32_t *coun
     return RT_OK;
 }
 
+// ---- rt_denoise_planes: the non-local-means filter of include/rt_api.h ("denoising"), rules 1-6, as plain loops ----
+// rt_denoise_async runs the same arithmetic on the device (rt_denoise.hip) and is tested against this function bit for bit.
+
+void rt_denoise_defaults(rt_denoise_params *p) {
+    if (!p) return;
+    p->search_radius = 5;
+    p->patch_radius = 1;
+    p->alpha = 1.0f;
+    p->k = 0.45f;
+}
+
+// the parameter rules both entry points share (`p` == null: the defaults); hidden, like rt_host_set_error
+int rt_host_denoise_params(const rt_denoise_params *p, rt_denoise_params *out) {
+    rt_denoise_defaults(out);
+    if (p) *out = *p;
+    if (out->search_radius < 0 || out->search_radius > 8) return host_fail("rt_denoise: search_radius %d (0 .. 8)", out->search_radius);
+    if (out->patch_radius < 0 || out->patch_radius > 2) return host_fail("rt_denoise: patch_radius %d (0 .. 2)", out->patch_radius);
+    if (!std::isfinite(out->alpha) || out->alpha < 0.f) return host_fail("rt_denoise: alpha %g (finite, >= 0)", (double)out->alpha);
+    if (!std::isfinite(out->k) || out->k <= 0.f) return host_fail("rt_denoise: k %g (finite, > 0)", (double)out->k);
+    return RT_OK;
+}
+
+int rt_denoise_planes(float *out, const float *merged, const float *a, const float *b, int w, int h, const rt_denoise_params *p) {
+    if (!out || !merged || !a || !b) return host_fail("rt_denoise_planes: null plane");
+    if (w < 1 || h < 1) return host_fail("rt_denoise_planes: %dx%d", w, h);
+    rt_denoise_params q;
+    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
+    const int R = q.search_radius, P = q.patch_radius;
+    const float alpha = q.alpha, kk = q.k * q.k, inv = 1.0f / (float)(3 * (2 * P + 1) * (2 * P + 1));
+    const auto cl = [](int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); };
+    const auto at = [w](int y, int x) { return 3 * ((size_t)y * (size_t)w + (size_t)x); };
+    const size_t px = (size_t)w * (size_t)h;
+    // 1. the variance of the mean of the two halves; 2. smoothed over 3x3, clamped
+    std::vector<float> V(3 * px), Vs(3 * px);
+    for (size_t i = 0; i < 3 * px; ++i) {
+        const float d = (a[i] - b[i]) * 0.5f;
+        V[i] = d * d;
+    }
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x)
+            for (int c = 0; c < 3; ++c) {
+                float sum = 0.f;
+                for (int j = -1; j <= 1; ++j)
+                    for (int i = -1; i <= 1; ++i) {
+                        const float v = V[at(cl(y + j, h), cl(x + i, w)) + c];
+                        sum = (j == -1 && i == -1) ? v : sum + v;
+                    }
+                Vs[at(y, x) + c] = sum * (1.0f / 9.0f);
+            }
+    std::vector<float> num(3 * px, 0.0f), den(px, 0.0f), e(px);
+    for (int oy = -R; oy <= R; ++oy)
+        for (int ox = -R; ox <= R; ++ox) {
+            if (oy == 0 && ox == 0) {                        // 5. the pixel itself: weight 1, whatever it holds
+                for (size_t i = 0; i < px; ++i) {
+                    for (int c = 0; c < 3; ++c) num[3 * i + c] = num[3 * i + c] + 1.0f * merged[3 * i + c];
+                    den[i] = den[i] + 1.0f;
+                }
+                continue;
+            }
+            // 3. e(x, o) for every pixel x: it depends on x and o only, so one evaluation serves every patch that covers x
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    const size_t ip = at(y, x), iq = at(cl(y + oy, h), cl(x + ox, w));
+                    float d[3];
+                    for (int c = 0; c < 3; ++c) {
+                        const float t = merged[ip + c] - merged[iq + c];
+                        const float vp = Vs[ip + c], vq = Vs[iq + c];
+                        const float m = vq < vp ? vq : vp;
+                        d[c] = (t * t - alpha * (vp + m)) / (1e-10f + kk * (vp + vq));
+                    }
+                    e[(size_t)y * w + x] = (d[0] + d[1]) + d[2];
+                }
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    const int qy = y + oy, qx = x + ox;
+                    if (qy < 0 || qy >= h || qx < 0 || qx >= w) continue;     // 5. p + o outside the image
+                    float S = 0.f;                                            // 4. the patch sum, at clamped positions
+                    for (int dy = -P; dy <= P; ++dy)
+                        for (int dx = -P; dx <= P; ++dx) {
+                            const float v = e[(size_t)cl(y + dy, h) * w + cl(x + dx, w)];
+                            S = (dy == -P && dx == -P) ? v : S + v;
+                        }
+                    const float T = S * inv;
+                    const float *dq = merged + at(qy, qx);
+                    if (std::isnan(T) || !std::isfinite(dq[0]) || !std::isfinite(dq[1]) || !std::isfinite(dq[2])) continue;
+                    const float g = T > 0.f ? T : 0.f;
+                    const float wgt = 1.0f / (1.0f + g * (1.0f + g * 0.5f));
+                    const size_t i = (size_t)y * w + x;
+                    for (int c = 0; c < 3; ++c) num[3 * i + c] = num[3 * i + c] + wgt * dq[c];
+                    den[i] = den[i] + wgt;
+                }
+        }
+    for (size_t i = 0; i < px; ++i)                                           // 6.
+        for (int c = 0; c < 3; ++c) out[3 * i + c] = num[3 * i + c] / den[i];
+    return RT_OK;
+}
+
 }  // extern "C"

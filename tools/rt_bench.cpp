@@ -4,7 +4,8 @@
 //   rt_bench <framework ID> <CPU/GPU (0/1)> <mem (0/1/2)> [scene.scn]
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
-//            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]]
+//            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]
+//             [--denoise [--denoise-radius R]]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -19,6 +20,9 @@
 //   --adaptive          with --until-psnr: DB is the target PER 8x8 TILE and only the groups of tiles still below it are rendered
 //                       (rt_render_adaptive), after --min-passes M passes on every tile (default 16).  A second line gives the checks, the
 //                       samples rendered against w * h * passes of both halves, and the smallest, median and largest tile pass count
+//   --denoise           with --until-psnr: the halves are merged into a THIRD context, that frame is filtered (rt_denoise_async: non-local
+//                       means steered by the difference of the halves) and --out is written from it; --denoise-radius R sets the search
+//                       radius (0 .. 8, default 5).  A further line gives the parameters and the call's wall time (queue, kernels, pack, read-back)
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
@@ -68,6 +72,9 @@ int main(int argc, char** argv) {
     int check_every = 8;
     bool adaptive = false;      // --until-psnr per 8x8 tile: rt_render_adaptive instead of rt_render_converged
     int min_passes = 16;
+    bool denoise = false;       // --until-psnr: merge into a third context and filter it (rt_denoise_async)
+    rt_denoise_params dn;
+    rt_denoise_defaults(&dn);
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -91,6 +98,8 @@ int main(int argc, char** argv) {
         else if (a == "--check-every") check_every = atoi(next());
         else if (a == "--adaptive") adaptive = true;
         else if (a == "--min-passes") min_passes = atoi(next());
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-radius") dn.search_radius = atoi(next());
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -102,6 +111,10 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (pos.size() >= 4) scene_path = pos[3];
+    if (denoise && !until) {
+        fprintf(stderr, "--denoise filters the merge of two halves: it needs --until-psnr\n");
+        return 1;
+    }
 
     std::vector<rt_sphere> spheres(16384);
     uint32_t n = 0;
@@ -157,20 +170,40 @@ int main(int argc, char** argv) {
             if (rt_tile_passes(half[0], tile_passes.data()) != RT_OK) return die("rt_tile_passes");
             std::sort(tile_passes.begin(), tile_passes.end());
         }
-        if (rt_merge_async(half[0], &half[1], 1, rt_stream(half[0])) != RT_OK) return die("rt_merge_async");
+        rt_ctx* frame = half[0];                     // the context --out is written from: the first half, or with --denoise a third one
+        double denoise_ms = 0.0;
         std::vector<uint32_t> merged(static_cast<size_t>(w) * h);
-        if (rt_read_pixels(half[0], merged.data()) != RT_OK) return die("rt_read_pixels");
+        if (denoise) {                               // the halves stay as they are: the filter reads them
+            if (rt_create(&frame, w, h) != RT_OK) return die("rt_create");
+            if (rt_set_scene(frame, spheres.data(), n) != RT_OK) return die("rt_set_scene");
+            if (rt_set_camera(frame, &cam) != RT_OK) return die("rt_set_camera");
+            if (rt_set_mode(frame, mode) != RT_OK) return die("rt_set_mode");
+            if (rt_merge_async(frame, half, 2, rt_stream(frame)) != RT_OK) return die("rt_merge_async");
+            if (rt_read_pixels(frame, merged.data()) != RT_OK) return die("rt_read_pixels");   // (the merge has finished: the filter is timed alone)
+            const auto d0 = std::chrono::steady_clock::now();
+            if (rt_denoise_async(frame, half[0], half[1], &dn, rt_stream(frame)) != RT_OK) return die("rt_denoise_async");
+            if (rt_read_pixels(frame, merged.data()) != RT_OK) return die("rt_read_pixels");
+            denoise_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - d0).count();
+        } else if (rt_merge_async(half[0], &half[1], 1, rt_stream(half[0])) != RT_OK) {
+            return die("rt_merge_async");
+        }
+        if (!denoise && rt_read_pixels(frame, merged.data()) != RT_OK) return die("rt_read_pixels");
         const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (!out.empty() && !write_ppm(out, merged, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
         printf("{\"spheres\": %u, \"w\": %d, \"h\": %d, \"until_psnr\": %.3f, \"reached\": %s, \"passes_per_half\": %d, \"merged_passes\": %d, "
                "\"checks\": %d, \"check_every\": %d, \"pair_psnr_db\": %.3f, \"differing\": %llu, \"max_abs\": %u, \"wall_ms\": %.4f}\n",
-               n, w, h, until_psnr, reached ? "true" : "false", per_half, rt_current_sample(half[0]), checks, check_every, rt_error_psnr(&err),
+               n, w, h, until_psnr, reached ? "true" : "false", per_half, rt_current_sample(frame), checks, check_every, rt_error_psnr(&err),
                (unsigned long long)err.differing, err.max_abs, wall_ms);
         if (adaptive)
             printf("{\"adaptive\": true, \"min_passes\": %d, \"checks\": %d, \"samples_rendered\": %llu, \"samples_of_whole_frames\": %llu, "
                    "\"tile_passes_min\": %u, \"tile_passes_median\": %u, \"tile_passes_max\": %u}\n",
                    min_passes, checks, (unsigned long long)(st_half[0].samples + st_half[1].samples), 2ull * (unsigned long long)w * h * per_half,
                    tile_passes.front(), tile_passes[tile_passes.size() / 2], tile_passes.back());
+        if (denoise) {
+            printf("{\"denoise\": true, \"search_radius\": %d, \"patch_radius\": %d, \"alpha\": %.3f, \"k\": %.3f, \"denoise_wall_ms\": %.4f}\n",
+                   dn.search_radius, dn.patch_radius, (double)dn.alpha, (double)dn.k, denoise_ms);
+            rt_destroy(frame);
+        }
         rt_destroy(half[0]);
         rt_destroy(half[1]);
         return 0;
