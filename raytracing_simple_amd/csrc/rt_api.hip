@@ -119,16 +119,36 @@ int wait_all(rt_ctx *c) {
 // rt_read_pixels / rt_read_pixels_async / rt_compare_async: if the last launches ran with the pixel store off, a small kernel packs the
 // frame from the running average (same toInt, .cl:34,594-596) into the buffer the launches write
 int refresh_pixels(rt_ctx *c, hipStream_t stream) {
-    if (c->pixels_current || c->current_sample <= 0) return RT_OK;
+    if (c->frame.pixels_current || c->frame.current_sample <= 0) return RT_OK;
     rt::LaunchParams p = make_params(c, 0);
     hipError_t e = (c->mode == RT_MODE_FAST || c->mode >= 200) ? rt::launch_pack_fast(p, stream) : rt::launch_pack_parity(p, stream);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
-    c->pixels_current = true;
+    c->frame.pixels_packed();
+    return RT_OK;
+}
+
+int read_back(rt_ctx *c, void *host, const void *dev, size_t bytes, bool wait) {
+    int rc = select_device(c);
+    if (rc == RT_OK) rc = chain(c, c->stream);          // behind everything the context has queued, on whatever stream
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (wait) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+int same_frame(const rt_ctx *a, const rt_ctx *b, const char *call, const char *a_name, const char *b_name, bool sharding) {
+    if (!a || !b) return fail(RT_ERR_ARG, "%s: %s is null", call, a ? b_name : a_name);
+    if (a == b) return fail(RT_ERR_ARG, "%s: %s is %s itself", call, a_name, b_name);
+    if (a->multi || b->multi) return fail(RT_ERR_ARG, "%s: %s is a multi-device context", call, a->multi ? a_name : b_name);
+    if (a->w != b->w || a->h != b->h || (sharding && (a->rank != b->rank || a->nranks != b->nranks || a->tile_rows != b->tile_rows)))
+        return fail(RT_ERR_ARG, "%s: %s is %dx%d, rank %d of %d by %d rows; %s %dx%d, rank %d of %d by %d rows", call, a_name, a->w, a->h, a->rank, a->nranks,
+                    a->tile_rows, b_name, b->w, b->h, b->rank, b->nranks, b->tile_rows);
+    if (a->device != b->device) return fail(RT_ERR_ARG, "%s: %s lives on device %d, %s on device %d", call, a_name, a->device, b_name, b->device);
     return RT_OK;
 }
 
 int upload_default_seeds(rt_ctx *c) {
-    const size_t count = 2 * (size_t)c->w * (size_t)c->h;
+    const size_t count = 2 * image_pixels(c);
     const double t0 = now_ms();
     std::vector<uint32_t> host(count);
     rt_default_seeds(host.data(), count);
@@ -141,12 +161,12 @@ int upload_default_seeds(rt_ctx *c) {
 int restore_state(rt_ctx *c) {                          // rt_create / rt_reset: blocking
     int rc = chain(c, c->stream);
     if (rc != RT_OK) return rc;
-    const size_t px = (size_t)c->w * (size_t)c->h;
+    const size_t px = image_pixels(c);
     size_t blocks = (3 * px + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(rt_restore_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, reinterpret_cast<unsigned long long *>(c->d_seeds),
                        reinterpret_cast<const unsigned long long *>(c->d_seeds0), px, reinterpret_cast<uint32_t *>(c->d_colors), 3 * px,
-                       c->d_pixels, (size_t)c->local_rows * (size_t)c->w, c->d_counters, c->d_stats);
+                       c->d_pixels, local_pixels(c), c->d_counters, c->d_stats);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RT_OK;
@@ -202,7 +222,7 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
     c->local_rows = rows;
 
     int rc = select_device(c);
-    const size_t px = (size_t)w * (size_t)h;
+    const size_t px = image_pixels(c);
     g_create_ms[0] = now_ms() - t_begin;
     auto alloc_all = [&]() -> int {
         double t = now_ms();
@@ -218,10 +238,10 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
         HIP_TRY(hipMalloc(&c->d_seeds, 2 * px * sizeof(uint32_t)));
         HIP_TRY(hipMalloc(&c->d_seeds0, 2 * px * sizeof(uint32_t)));
         HIP_TRY(hipMalloc(&c->d_colors, 3 * px * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->d_pixels, ((size_t)rows * w + 4) * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&c->d_pixels, (local_pixels(c) + 4) * sizeof(uint32_t)));
         HIP_TRY(hipMalloc(&c->d_counters, 32 * sizeof(unsigned long long)));
         HIP_TRY(hipMalloc(&c->d_stats, rt::kStatReplicas * 8 * sizeof(unsigned long long)));
-        c->order.n_tiles = (uint32_t)(((w + 7) / 8) * ((rows + rt::kTileH - 1) / rt::kTileH));      // the finest tile shape (8x8)
+        c->order.n_tiles = tile_count(c);           // the finest tile shape (8x8)
         if (c->order.n_tiles) {
             HIP_TRY(hipMalloc(&c->order.d_tile_cost, (size_t)c->order.n_tiles * sizeof(uint32_t)));
             HIP_TRY(hipMalloc(&c->order.d_order, (size_t)c->order.n_tiles * sizeof(uint32_t)));
@@ -408,14 +428,7 @@ RT_API int rt_reset(rt_ctx *c) {
     if (rc != RT_OK) return rc;
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
-    c->current_sample = 0;
-    c->tiles.whole();
-    c->choice.frame_ended();
-    c->launches = 0;
-    c->last_ms = 0.0;
-    c->seeds_default = false;
-    c->seeds_custom = false;            // restore_state copies the default stream into d_seeds
-    c->pixels_current = true;
+    end_frame(c).reset_blocking();      // restore_state copies the default stream into d_seeds
     return restore_state(c);
 }
 
@@ -428,19 +441,14 @@ RT_API int rt_reset_async(rt_ctx *c, void *hip_stream) {
     if (rc != RT_OK) return rc;
     hipLaunchKernelGGL(rt_zero_counters_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, c->d_counters, c->d_stats);
     HIP_TRY(hipGetLastError());
-    c->seeds_default = true;            // the next launch reads d_seeds0
-    c->current_sample = 0;
-    c->tiles.whole();
-    c->choice.frame_ended();
-    c->launches = 0;
-    c->last_ms = 0.0;
+    end_frame(c).reset_in_place();      // the next launch reads d_seeds0
     return RT_OK;
 }
 
 RT_API int rt_render_async(rt_ctx *c, int n_samples, void *hip_stream) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     if (c->multi) return rt::multi_render(c, nullptr, n_samples, false);
-    if (c->tiles.ragged) return fail(RT_ERR_STATE, "rt_render_async: the tiles hold different pass counts after a subset launch (rt_render_tiles_async goes on; rt_reset makes the frame whole)");
+    if (c->frame.ragged) return fail(RT_ERR_STATE, "rt_render_async: the tiles hold different pass counts after a subset launch (rt_render_tiles_async goes on; rt_reset makes the frame whole)");
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     if (!c->throttle_on || n_samples <= 0) return launch(c, n_samples, (hipStream_t)hip_stream);
@@ -517,7 +525,7 @@ RT_API int rt_throttle(rt_ctx *c, int max_in_flight, double *ms_per_pass) {
 RT_API int rt_render_pass(rt_ctx *c, uint32_t *out_host, int n_samples) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     if (c->multi) return rt::multi_render(c, out_host, n_samples, true);
-    if (c->tiles.ragged) return fail(RT_ERR_STATE, "rt_render_pass: the tiles hold different pass counts after a subset launch (rt_render_tiles_async goes on; rt_reset makes the frame whole)");
+    if (c->frame.ragged) return fail(RT_ERR_STATE, "rt_render_pass: the tiles hold different pass counts after a subset launch (rt_render_tiles_async goes on; rt_reset makes the frame whole)");
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     rc = chain(c, c->stream);
@@ -527,12 +535,11 @@ RT_API int rt_render_pass(rt_ctx *c, uint32_t *out_host, int n_samples) {
     if (rc != RT_OK) return rc;
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
     if (out_host && c->local_rows > 0)
-        HIP_TRY(hipMemcpyAsync(out_host, c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels,
-                               (size_t)c->local_rows * c->w * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out_host, frame_pixels(c), local_pixels(c) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last_ms = ms;
+    c->frame.timed(ms);
     return RT_OK;
 }
 
@@ -553,10 +560,7 @@ RT_API int rt_read_pixels(rt_ctx *c, uint32_t *out_host) {
     if (rc != RT_OK) return rc;
     rc = refresh_pixels(c, c->stream);
     if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_host, c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels,
-                           (size_t)c->local_rows * c->w * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RT_OK;
+    return read_back(c, out_host, frame_pixels(c), local_pixels(c) * sizeof(uint32_t));
 }
 
 RT_API int rt_read_pixels_async(rt_ctx *c, uint32_t *out_host, void *hip_stream) {
@@ -570,8 +574,7 @@ RT_API int rt_read_pixels_async(rt_ctx *c, uint32_t *out_host, void *hip_stream)
     if (rc != RT_OK) return rc;
     rc = refresh_pixels(c, stream);
     if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_host, c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels, (size_t)c->local_rows * c->w * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out_host, frame_pixels(c), local_pixels(c) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     return RT_OK;
 }
 
@@ -586,9 +589,8 @@ RT_API int rt_pin_output(rt_ctx *c, uint32_t *out_host, size_t count) {
         (void)hipHostUnregister(c->pinned_out);
         c->pinned_out = nullptr;
     }
-    if (!out_host || (size_t)c->local_rows * (size_t)c->w == 0) return RT_OK;    // nothing to pin (a rank without rows)
-    if (count < (size_t)c->local_rows * (size_t)c->w)
-        return fail(RT_ERR_ARG, "output buffer of %zu < %zu elements", count, (size_t)c->local_rows * (size_t)c->w);
+    if (!out_host || local_pixels(c) == 0) return RT_OK;    // nothing to pin (a rank without rows)
+    if (count < local_pixels(c)) return fail(RT_ERR_ARG, "output buffer of %zu < %zu elements", count, local_pixels(c));
     HIP_TRY(hipHostRegister(out_host, count * sizeof(uint32_t), hipHostRegisterDefault));
     c->pinned_out = out_host;
     return RT_OK;
@@ -597,8 +599,7 @@ RT_API int rt_pin_output(rt_ctx *c, uint32_t *out_host, size_t count) {
 RT_API int rt_set_pixel_buffer(rt_ctx *c, void *dptr, size_t count) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     if (c->multi) return fail(RT_ERR_ARG, "rt_set_pixel_buffer: a multi-device context assembles its frame in its own buffer");
-    if (dptr && count < (size_t)c->local_rows * (size_t)c->w)
-        return fail(RT_ERR_ARG, "pixel buffer of %zu < %zu elements", count, (size_t)c->local_rows * (size_t)c->w);
+    if (dptr && count < local_pixels(c)) return fail(RT_ERR_ARG, "pixel buffer of %zu < %zu elements", count, local_pixels(c));
     c->d_pixels_ext = static_cast<uint32_t *>(dptr);
     return RT_OK;
 }
@@ -611,51 +612,33 @@ RT_API void *rt_stream(rt_ctx *c) { return !c ? nullptr : (c->multi ? rt::multi_
 RT_API int rt_device_pixels(rt_ctx *c, void **dptr, size_t *count) {
     if (!c || !dptr || !count) return fail(RT_ERR_ARG, "null argument");
     if (c->multi) return rt::multi_device_pixels(c, dptr, count);
-    *dptr = c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels;
-    *count = (size_t)c->local_rows * (size_t)c->w;
+    *dptr = frame_pixels(c);
+    *count = local_pixels(c);
     return RT_OK;
 }
 
 RT_API int rt_local_rows(const rt_ctx *c) { return c ? c->local_rows : RT_ERR_ARG; }
-RT_API int rt_current_sample(const rt_ctx *c) { return c ? c->current_sample : RT_ERR_ARG; }
+RT_API int rt_current_sample(const rt_ctx *c) { return c ? c->frame.current_sample : RT_ERR_ARG; }
 
 RT_API int rt_read_colors(rt_ctx *c, float *out_host) {
     if (!c || !out_host) return fail(RT_ERR_ARG, "null argument");
     if (c->multi) return rt::multi_read_colors(c, out_host);
-    int rc = select_device(c);
-    if (rc != RT_OK) return rc;
-    rc = chain(c, c->stream);           // behind everything the context has queued, on whatever stream
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_host, c->d_colors, 3 * (size_t)c->w * c->h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RT_OK;
+    return read_back(c, out_host, c->d_colors, color_floats(c) * sizeof(float));
 }
 
 RT_API int rt_read_seeds(rt_ctx *c, uint32_t *out_host) {
     if (!c || !out_host) return fail(RT_ERR_ARG, "null argument");
     if (c->multi) return rt::multi_read_seeds(c, out_host);
-    int rc = select_device(c);
-    if (rc != RT_OK) return rc;
-    rc = chain(c, c->stream);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_host, c->seeds_default ? c->d_seeds0 : c->d_seeds, 2 * (size_t)c->w * c->h * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RT_OK;
+    return read_back(c, out_host, c->frame.seeds_default ? c->d_seeds0 : c->d_seeds, 2 * image_pixels(c) * sizeof(uint32_t));
 }
 
 RT_API int rt_get_stats(rt_ctx *c, rt_stats *out) {
     if (!c || !out) return fail(RT_ERR_ARG, "null argument");
     if (c->multi) return rt::multi_get_stats(c, out);
-    int rc = select_device(c);
+    unsigned long long v[32], part[rt::kStatReplicas * 8], sum[5] = { 0, 0, 0, 0, 0 };
+    int rc = read_back(c, v, c->d_counters, sizeof v, false);       // two copies, one wait
+    if (rc == RT_OK) rc = read_back(c, part, c->d_stats, sizeof part);
     if (rc != RT_OK) return rc;
-    rc = chain(c, c->stream);
-    if (rc != RT_OK) return rc;
-    unsigned long long v[32];
-    HIP_TRY(hipMemcpyAsync(v, c->d_counters, sizeof v, hipMemcpyDeviceToHost, c->stream));
-    unsigned long long part[rt::kStatReplicas * 8], sum[5] = { 0, 0, 0, 0, 0 };
-    HIP_TRY(hipMemcpyAsync(part, c->d_stats, sizeof part, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
     for (int r = 0; r < rt::kStatReplicas; ++r)
         for (int k = 0; k < 5; ++k) sum[k] += part[r * 8 + k];
     out->samples = sum[0];
@@ -664,8 +647,8 @@ RT_API int rt_get_stats(rt_ctx *c, rt_stats *out) {
     out->sphere_tests = sum[3];
     out->rng_draws = sum[4];
     memcpy(c->debug_counters, v + 8, sizeof c->debug_counters);
-    out->launches = c->launches;
-    out->last_kernel_ms = c->last_ms;
+    out->launches = c->frame.launches;
+    out->last_kernel_ms = c->frame.last_ms;
     return RT_OK;
 }
 

@@ -124,19 +124,6 @@ namespace {
 
 static_assert(sizeof(rt_frame_error) == 48, "rt_frame_error is 48 bytes, no padding");
 
-// the pairs rt_compare_async accepts (include/rt_api.h lists the refusals)
-int check_pair(const rt_ctx *a, const rt_ctx *b) {
-    if (!a || !b) return fail(RT_ERR_ARG, "ctx is null");
-    if (a == b) return fail(RT_ERR_ARG, "rt_compare: a context against itself");
-    if (a->multi || b->multi) return fail(RT_ERR_ARG, "rt_compare: a multi-device context cannot be compared");
-    if (a->w != b->w || a->h != b->h || a->rank != b->rank || a->nranks != b->nranks || a->tile_rows != b->tile_rows)
-        return fail(RT_ERR_ARG, "rt_compare: a is %dx%d, rank %d of %d by %d rows; b %dx%d, rank %d of %d by %d rows", a->w, a->h, a->rank, a->nranks,
-                    a->tile_rows, b->w, b->h, b->rank, b->nranks, b->tile_rows);
-    if (a->device != b->device) return fail(RT_ERR_ARG, "rt_compare: a lives on device %d, b on device %d", a->device, b->device);
-    return RT_OK;
-}
-
-size_t tile_count(const rt_ctx *c) { return (size_t)((c->w + 7) / 8) * (size_t)((c->local_rows + 7) / 8); }
 
 // the pair is checked: queue the comparison on `stream`, behind everything both contexts have queued, their later work behind it
 int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, hipStream_t stream) {
@@ -150,10 +137,9 @@ int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles
     rc = refresh_pixels(a, stream);
     if (rc == RT_OK) rc = refresh_pixels(b, stream);
     if (rc != RT_OK) return rc;
-    const size_t items = (size_t)((a->local_rows + 7) / 8) * (size_t)((a->w + kCmpRun - 1) / kCmpRun);
+    const size_t items = (size_t)tile_row_count(a) * (size_t)((a->w + kCmpRun - 1) / kCmpRun);
     const size_t blocks = std::min(items, (size_t)a->n_cus * 8);
-    hipLaunchKernelGGL(rt_compare_kernel, dim3((unsigned)blocks), dim3(kCmpLanes), 0, stream, a->d_pixels_ext ? a->d_pixels_ext : a->d_pixels,
-                       b->d_pixels_ext ? b->d_pixels_ext : b->d_pixels, a->w, a->local_rows, reinterpret_cast<unsigned long long *>(result_dev), tiles_dev);
+    hipLaunchKernelGGL(rt_compare_kernel, dim3((unsigned)blocks), dim3(kCmpLanes), 0, stream, frame_pixels(a), frame_pixels(b), a->w, a->local_rows, reinterpret_cast<unsigned long long *>(result_dev), tiles_dev);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -161,7 +147,7 @@ int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles
 // the blocking calls' scratch on a's device: one rt_frame_error, then the tile map
 int ensure_scratch(rt_ctx *a) {
     if (a->d_compare) return RT_OK;
-    HIP_TRY(hipMalloc(&a->d_compare, sizeof(rt_frame_error) + std::max(tile_count(a), (size_t)1) * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&a->d_compare, sizeof(rt_frame_error) + std::max<size_t>(tile_count(a), 1) * sizeof(uint32_t)));
     return RT_OK;
 }
 
@@ -176,13 +162,27 @@ int compare_blocking(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *t
     rc = compare_on(a, b, res, want_tiles ? tiles : nullptr, a->stream);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out_host, res, sizeof *res, hipMemcpyDeviceToHost, a->stream));
-    if (want_tiles) HIP_TRY(hipMemcpyAsync(tiles_host, tiles, tile_count(a) * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+    if (want_tiles) HIP_TRY(hipMemcpyAsync(tiles_host, tiles, (size_t)tile_count(a) * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
     HIP_TRY(hipStreamSynchronize(a->stream));
     return RT_OK;
 }
 
-// at pass 0 the next launch would read the default stream (nothing but rt_seed_stream_async / rt_write_state puts another one there)
-bool on_default_stream(const rt_ctx *c) { return c->seeds_default || !c->seeds_custom; }
+// what rt_render_converged and rt_render_adaptive ask of their arguments alike: a place for the last check, a step, a target that is a number, and two
+// whole frames at one pass number below max_passes that will not render the same image
+int check_paired_render(const rt_ctx *a, const rt_ctx *b, const char *call, const rt_frame_error *last, int passes_per_check, double target_db, int max_passes) {
+    const int na = a->frame.current_sample, nb = b->frame.current_sample;
+    if (!last) return fail(RT_ERR_ARG, "last is null");
+    if (passes_per_check < 1) return fail(RT_ERR_ARG, "passes_per_check %d", passes_per_check);
+    if (std::isnan(target_db)) return fail(RT_ERR_ARG, "%s: the target in dB is not a number", call);
+    if (max_passes < na || max_passes < nb) return fail(RT_ERR_ARG, "max_passes %d is below the passes the contexts hold (%d, %d)", max_passes, na, nb);
+    if (na != nb) return fail(RT_ERR_STATE, "%s: the contexts hold %d and %d passes", call, na, nb);
+    if (na == 0 && a->frame.on_default_stream() && b->frame.on_default_stream())
+        return fail(RT_ERR_STATE, "%s: both contexts are at pass 0 of the default seed stream and would render the same frame "
+                                  "(rt_seed_stream_async gives each a stream of its own)", call);
+    if (a->frame.ragged || b->frame.ragged)
+        return fail(RT_ERR_STATE, "%s: the tiles of a context hold different pass counts after a subset launch (rt_reset makes the frame whole)", call);
+    return RT_OK;
+}
 
 }  // namespace
 
@@ -191,21 +191,21 @@ extern "C" {
 RT_API int rt_compare_tiles(const rt_ctx *c, int *tiles_x, int *tiles_y) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     if (c->multi) return fail(RT_ERR_ARG, "rt_compare_tiles: a multi-device context cannot be compared");
-    const int tx = (c->w + 7) / 8, ty = (c->local_rows + 7) / 8;
+    const int tx = (int)tiles_per_row(c), ty = (int)tile_row_count(c);
     if (tiles_x) *tiles_x = tx;
     if (tiles_y) *tiles_y = ty;
     return tx * ty;
 }
 
 RT_API int rt_compare_async(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, void *hip_stream) {
-    int rc = check_pair(a, b);
+    int rc = same_frame(a, b, "rt_compare_async", "a", "b");
     if (rc != RT_OK) return rc;
     if (!result_dev) return fail(RT_ERR_ARG, "result_dev is null");
     return compare_on(a, b, result_dev, tiles_dev, (hipStream_t)hip_stream);
 }
 
 RT_API int rt_compare(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *tiles_host) {
-    int rc = check_pair(a, b);
+    int rc = same_frame(a, b, "rt_compare", "a", "b");
     if (rc != RT_OK) return rc;
     if (!out_host) return fail(RT_ERR_ARG, "out_host is null");
     return compare_blocking(a, b, out_host, tiles_host);
@@ -222,23 +222,12 @@ RT_API double rt_error_psnr(const rt_frame_error *e) {
 }
 
 RT_API int rt_render_converged(rt_ctx *a, rt_ctx *b, double target_psnr_db, int passes_per_check, int max_passes, rt_frame_error *last, int *checks) {
-    int rc = check_pair(a, b);
+    int rc = same_frame(a, b, "rt_render_converged", "a", "b");
+    if (rc == RT_OK) rc = check_paired_render(a, b, "rt_render_converged", last, passes_per_check, target_psnr_db, max_passes);
     if (rc != RT_OK) return rc;
-    if (!last) return fail(RT_ERR_ARG, "last is null");
-    if (passes_per_check < 1) return fail(RT_ERR_ARG, "passes_per_check %d", passes_per_check);
-    if (std::isnan(target_psnr_db)) return fail(RT_ERR_ARG, "target_psnr_db is not a number");
-    if (max_passes < a->current_sample || max_passes < b->current_sample)
-        return fail(RT_ERR_ARG, "max_passes %d is below the passes the contexts hold (%d, %d)", max_passes, a->current_sample, b->current_sample);
-    if (a->current_sample != b->current_sample)
-        return fail(RT_ERR_STATE, "rt_render_converged: the contexts hold %d and %d passes", a->current_sample, b->current_sample);
-    if (a->current_sample == 0 && on_default_stream(a) && on_default_stream(b))
-        return fail(RT_ERR_STATE, "rt_render_converged: both contexts are at pass 0 of the default seed stream and would render the same frame "
-                                  "(rt_seed_stream_async gives each a stream of its own)");
-    if (a->tiles.ragged || b->tiles.ragged)
-        return fail(RT_ERR_STATE, "rt_render_converged: the tiles of a context hold different pass counts after a subset launch (rt_reset makes the frame whole)");
     if (checks) *checks = 0;
     for (int done = 0;; ++done) {
-        const int n = std::min(passes_per_check, max_passes - a->current_sample);
+        const int n = std::min(passes_per_check, max_passes - a->frame.current_sample);
         if (n == 0 && done > 0) return 0;                       // max_passes reached: *last is the last check
         if (n > 0) {
             rc = rt_render_async(a, n, a->stream);
@@ -261,32 +250,21 @@ static uint32_t tile_error_at(double db) {
 
 RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes, rt_frame_error *last,
                               int *checks) {
-    int rc = check_pair(a, b);
-    if (rc != RT_OK) return rc;
-    rc = tiles_refuse(a, "rt_render_adaptive");
+    int rc = same_frame(a, b, "rt_render_adaptive", "a", "b");
+    if (rc == RT_OK) rc = tiles_refuse(a, "rt_render_adaptive");
     if (rc == RT_OK) rc = tiles_refuse(b, "rt_render_adaptive");
     if (rc != RT_OK) return rc;
-    if (!last) return fail(RT_ERR_ARG, "last is null");
-    if (passes_per_check < 1) return fail(RT_ERR_ARG, "passes_per_check %d", passes_per_check);
-    if (min_passes < 0) return fail(RT_ERR_ARG, "min_passes %d", min_passes);
-    if (std::isnan(tile_psnr_db)) return fail(RT_ERR_ARG, "tile_psnr_db is not a number");
-    if (max_passes < a->current_sample || max_passes < b->current_sample)
-        return fail(RT_ERR_ARG, "max_passes %d is below the passes the contexts hold (%d, %d)", max_passes, a->current_sample, b->current_sample);
-    if (a->current_sample != b->current_sample)
-        return fail(RT_ERR_STATE, "rt_render_adaptive: the contexts hold %d and %d passes", a->current_sample, b->current_sample);
-    if (a->current_sample == 0 && on_default_stream(a) && on_default_stream(b))
-        return fail(RT_ERR_STATE, "rt_render_adaptive: both contexts are at pass 0 of the default seed stream and would render the same frame "
-                                  "(rt_seed_stream_async gives each a stream of its own)");
-    if (a->tiles.ragged || b->tiles.ragged)
-        return fail(RT_ERR_STATE, "rt_render_adaptive: the tiles of a context hold different pass counts already (rt_reset makes the frame whole)");
+    if (min_passes < 0) return fail(RT_ERR_ARG, "min_passes %d", min_passes);      // (every refusal ahead of the pass counts' is RT_ERR_ARG: their order does not show)
+    rc = check_paired_render(a, b, "rt_render_adaptive", last, passes_per_check, tile_psnr_db, max_passes);
+    if (rc != RT_OK) return rc;
     if (checks) *checks = 0;
     rc = select_device(a);
     if (rc == RT_OK) rc = ensure_scratch(a);
     if (rc != RT_OK) return rc;
     // 1. the passes every tile gets, as ordinary full launches
     const int floor_passes = std::min(min_passes, max_passes);
-    if (a->current_sample < floor_passes) {
-        const int n = floor_passes - a->current_sample;
+    if (a->frame.current_sample < floor_passes) {
+        const int n = floor_passes - a->frame.current_sample;
         rc = rt_render_async(a, n, a->stream);
         if (rc == RT_OK) rc = rt_render_async(b, n, b->stream);
         if (rc != RT_OK) return rc;
@@ -307,7 +285,7 @@ RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min
         if (counts_a[0] != counts_b[0] || counts_a[1] != counts_b[1])
             return fail(RT_ERR_STATE, "rt_render_adaptive: the contexts selected %u and %u groups from one map (their tile pass counts differ)", counts_a[0], counts_b[0]);
         if (counts_a[0] == 0) return 1;                         // every group has retired
-        const int n = std::min(passes_per_check, max_passes - a->current_sample);
+        const int n = std::min(passes_per_check, max_passes - a->frame.current_sample);
         if (n == 0) return 0;                                   // max_passes reached with groups still above the target
         rc = rt_render_tiles_async(a, n, a->stream);
         if (rc == RT_OK) rc = rt_render_tiles_async(b, n, b->stream);

@@ -156,7 +156,7 @@ RT_API int rt_debug_stage_tables(rt_ctx *c, int n_samples, int repeats) {
     const bool coop = c->coop_min > 0 && c->scene.n_spheres >= (uint32_t)c->coop_min;
     const bool w1 = lds + (coop ? 1536u : 256u) <= 6 * 1024;
     const int tile_w = w1 ? 8 : 32;
-    const dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), (unsigned)((c->local_rows + 7) / 8));
+    const dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), tile_row_count(c));
     uint32_t *sink = reinterpret_cast<uint32_t *>(c->order.d_tile_cost);    // (scratch: n_tiles >= 1024 words are not needed -- index & 1023 of a buffer that large)
     if (!sink || c->order.n_tiles < 1024) return fail(RT_ERR_ARG, "image too small for the probe");
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rt_stage_probe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
@@ -239,16 +239,16 @@ RT_API int rt_debug_read_tile_order(rt_ctx *c, uint32_t *order_out, uint32_t *co
 // the launch tiles of the instance's shape, and whether it was compacted from the heavy-first order (1) or from image order (0)
 RT_API int rt_debug_read_tile_list(rt_ctx *c, uint32_t *list_out, uint32_t cap, uint32_t *n_slots, uint32_t *n_launch, int *by_order) {
     if (!c || c->multi) return fail(RT_ERR_ARG, "null / multi-device context");
-    if (!c->tiles.list_valid) return fail(RT_ERR_STATE, "rt_debug_read_tile_list: no subset launch has built a list (or the selection, the order or a reset made it stale)");
+    if (!c->frame.list_valid) return fail(RT_ERR_STATE, "rt_debug_read_tile_list: no subset launch has built a list (or the selection, the order or a reset made it stale)");
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
-    const uint32_t n = cap < c->tiles.list_slots ? cap : c->tiles.list_slots;
+    const uint32_t n = cap < c->frame.list_slots ? cap : c->frame.list_slots;
     if (list_out && n) HIP_TRY(hipMemcpy(list_out, c->tiles.d_list, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (n_slots) *n_slots = c->tiles.list_slots;
-    if (n_launch) *n_launch = c->tiles.list_tiles;
-    if (by_order) *by_order = c->tiles.list_by_order ? 1 : 0;
+    if (n_slots) *n_slots = c->frame.list_slots;
+    if (n_launch) *n_launch = c->frame.list_tiles;
+    if (by_order) *by_order = c->frame.list_by_order ? 1 : 0;
     return RT_OK;
 }
 // the hierarchy of large scenes: min_spheres = smallest tree that is built and used (0 = never), lds_limit = largest
@@ -462,7 +462,7 @@ RT_API int rt_debug_reset_by_copy(rt_ctx *c, void *hip_stream, int flags) {
     if (!c || c->multi) return fail(RT_ERR_ARG, "null / multi-device context");
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
-    const size_t n = 2 * (size_t)c->w * (size_t)c->h;
+    const size_t n = 2 * image_pixels(c);
     if (flags & 1) {
         HIP_TRY(hipMemcpyAsync(c->d_seeds, c->d_seeds0, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
     } else {
@@ -473,9 +473,7 @@ RT_API int rt_debug_reset_by_copy(rt_ctx *c, void *hip_stream, int flags) {
                            c->timelog_tag, bl, flags);
         HIP_TRY(hipGetLastError());
     }
-    c->seeds_default = false;
-    c->seeds_custom = false;            // d_seeds holds the default stream again
-    c->current_sample = 0;
+    c->frame.debug_reset_by_copy();     // d_seeds holds the default stream again
     return RT_OK;
 }
 
@@ -489,7 +487,7 @@ RT_API int rt_debug_probe_seeds(rt_ctx *c, void *hip_stream, int flags) {
     unsigned long long *tl = timelog_next(c, &seq);
     uint32_t *sl = (tl && c->d_stalelog) ? c->d_stalelog + (size_t)seq * 64 : nullptr;
     hipLaunchKernelGGL(rt_debug_probe_seeds_kernel, dim3(256), dim3(256), 0, (hipStream_t)hip_stream, c->d_seeds, c->d_seeds0,
-                       2 * (size_t)c->w * (size_t)c->h, c->d_counters + 28, tl, c->timelog_tag, sl, flags);
+                       2 * image_pixels(c), c->d_counters + 28, tl, c->timelog_tag, sl, flags);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }

@@ -170,15 +170,11 @@ int check_three(const rt_ctx *dst, const rt_ctx *a, const rt_ctx *b) {
     int rc = tiles_refuse(dst, "rt_denoise_async");
     if (rc == RT_OK) rc = tiles_refuse(a, "rt_denoise_async");
     if (rc == RT_OK) rc = tiles_refuse(b, "rt_denoise_async");
-    if (rc != RT_OK) return rc;
-    if (dst == a || dst == b) return fail(RT_ERR_ARG, "rt_denoise_async: the destination is one of the halves");
-    if (a == b) return fail(RT_ERR_ARG, "rt_denoise_async: the two halves are one context");
-    for (const rt_ctx *x : { a, b }) {
-        if (x->w != dst->w || x->h != dst->h)
-            return fail(RT_ERR_ARG, "rt_denoise_async: a half is %dx%d, the destination %dx%d", x->w, x->h, dst->w, dst->h);
-        if (x->device != dst->device) return fail(RT_ERR_ARG, "rt_denoise_async: a half lives on device %d, the destination on device %d", x->device, dst->device);
-    }
-    return RT_OK;
+    // (no context is sharded by now: rows per tile say nothing about an unsharded frame)
+    if (rc == RT_OK) rc = same_frame(a, dst, "rt_denoise_async", "the first half", "the destination", false);
+    if (rc == RT_OK) rc = same_frame(b, dst, "rt_denoise_async", "the second half", "the destination", false);
+    if (rc == RT_OK) rc = same_frame(a, b, "rt_denoise_async", "the first half", "the second half", false);
+    return rc;
 }
 
 }  // namespace
@@ -190,16 +186,16 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
     if (rc != RT_OK) return rc;
     rt_denoise_params q;
     if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
-    if (a->current_sample != b->current_sample)
-        return fail(RT_ERR_STATE, "rt_denoise_async: the halves hold %d and %d passes", a->current_sample, b->current_sample);
-    if (a->current_sample <= 0) return fail(RT_ERR_STATE, "rt_denoise_async: the halves hold no pass");
-    if ((long long)dst->current_sample != 2ll * a->current_sample)
-        return fail(RT_ERR_STATE, "rt_denoise_async: the destination holds %d passes, the halves %d each: it is not their merge", dst->current_sample,
-                    a->current_sample);
+    if (a->frame.current_sample != b->frame.current_sample)
+        return fail(RT_ERR_STATE, "rt_denoise_async: the halves hold %d and %d passes", a->frame.current_sample, b->frame.current_sample);
+    if (a->frame.current_sample <= 0) return fail(RT_ERR_STATE, "rt_denoise_async: the halves hold no pass");
+    if ((long long)dst->frame.current_sample != 2ll * a->frame.current_sample)
+        return fail(RT_ERR_STATE, "rt_denoise_async: the destination holds %d passes, the halves %d each: it is not their merge", dst->frame.current_sample,
+                    a->frame.current_sample);
     if (q.search_radius == 0) return RT_OK;                 // the window is the pixel itself: the image, bit for bit
     rc = select_device(dst);
     if (rc != RT_OK) return rc;
-    const size_t n_floats = 3 * (size_t)dst->w * (size_t)dst->h;
+    const size_t n_floats = color_floats(dst);
     if (!dst->d_denoise) HIP_TRY(hipMalloc(&dst->d_denoise, n_floats * sizeof(float)));
     if (!dst->d_denoise_var) HIP_TRY(hipMalloc(&dst->d_denoise_var, n_floats * sizeof(float)));
     // behind everything the three contexts have queued; their later work behind the filter
@@ -221,7 +217,7 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
     }
     HIP_TRY(hipGetLastError());
     std::swap(dst->d_colors, dst->d_denoise);               // the filtered plane IS the colour plane now; the old one is the next call's scratch
-    dst->pixels_current = false;                            // rt_read_pixels packs the filtered plane
+    dst->frame.colours_replaced();                          // rt_read_pixels packs the filtered plane
     return RT_OK;
 }
 

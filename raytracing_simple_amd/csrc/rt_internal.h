@@ -1,5 +1,6 @@
-// rt_internal.h -- what the translation units of the library share behind the C ABI: the context
-// record, error reporting, and the hooks of the multi-device context (rt_multi.hip).
+// rt_internal.h -- what the translation units of the library share behind the C ABI: the context record and the records embedded in it
+// (Choice, Probe, TileOrder, FrameState), the frame's geometry said once, error reporting, the checks and the blocking read several units
+// share, and the hooks of the multi-device context (rt_multi.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "rt_device.h"
+#include "rt_frame_state.h"
 #include "rt_tile_order.h"
 
 struct rt_multi;                    // rt_multi.hip
@@ -62,24 +64,13 @@ struct Probe {
 
 constexpr int kMergeMax = 16;           // rt_merge_async: dst + 15 sources
 
-// Adaptive sampling (rt_tiles.hip; include/rt_api.h "adaptive sampling").  A GROUP is the 8x8 tiles 4g .. 4g+3 of one tile row -- the 32x8 tile of
-// the widest shipped workgroup; it is rendered whole or not at all, so its tiles hold one pass count.
+// Adaptive sampling (rt_tiles.hip; include/rt_api.h "adaptive sampling"): the device arrays.  What they currently mean -- ragged, the selection, what
+// the list was built from -- is host state of the frame: rt_frame_state.h.
 struct TileSubset {
     uint32_t *d_passes = nullptr;       // one word per 8x8 tile of the local pixel buffer (rt_compare_tiles' indexing); allocated on first use.  Its content
-                                        // means something only while `ragged`: otherwise every tile holds current_sample passes and nothing is stored
-    bool ragged = false;                // some tile holds fewer passes than current_sample
+                                        // means something only while the frame is ragged: otherwise every tile holds current_sample passes and nothing is stored
     uint32_t *d_selected = nullptr;     // one flag per group (rt_select_tiles), then two words: selected groups, the 8x8 tiles they cover
     uint32_t *d_list = nullptr;         // the subset launch's tile list: the launch tiles of the selected groups, padded with the sentinel to whole grid rows
-    bool have_selection = false;
-    uint32_t counts[2] = { 0, 0 };      // host copy of the two words
-    uint64_t selection_serial = 0;      // counts rt_select_tiles calls
-    // what d_list was built from (it is rebuilt only when one of these changes; a new sort of the order clears list_valid: rt_launch.hip)
-    bool list_valid = false, list_by_order = false;
-    uint64_t list_serial = 0;
-    uint32_t list_tiles = 0;            // launch tiles of the instance's shape
-    uint32_t list_slots = 0;            // entries: the launch's grid.x * grid.y
-    // every tile holds current_sample passes again (rt_reset and the calls that write a whole state); a selection does not outlive that
-    void whole() { ragged = false; have_selection = false; list_valid = false; }
 };
 
 }  // namespace rt
@@ -96,11 +87,8 @@ struct rt_ctx {
     uint32_t *d_pixels_ext = nullptr;   // caller-owned target of rt_set_pixel_buffer, or null
     void *pinned_out = nullptr;         // host buffer page-locked by rt_pin_output, or null
     int pixel_write = 1;                // rt_set_pixel_write
-    bool pixels_current = true;         // the packed pixel buffer holds the frame of the running average
-    bool seeds_default = false;         // after rt_reset_async: the next launch reads the pristine stream
-    bool seeds_custom = false;          // d_seeds was last filled by rt_seed_stream_async / rt_write_state, not from the default stream (rt_render_converged asks at pass 0)
-    // adaptive sampling (rt_tiles.hip): a pass count per 8x8 tile, the selected groups, the launch list of a subset launch
-    rt::TileSubset tiles;
+    rt::FrameState frame;               // what the progressive frame currently is: pass number, seed stream, packed pixels, launch count, tile bookkeeping
+    rt::TileSubset tiles;               // adaptive sampling (rt_tiles.hip): a pass count per 8x8 tile, the selected groups, the launch list of a subset launch
     float *d_denoise = nullptr;         // rt_denoise_async (rt_denoise.hip): the plane the filter writes, EXCHANGED with d_colors after every call; allocated on first use
     float *d_denoise_var = nullptr;     // ... and the smoothed variance plane it is steered by
     void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; allocated on first use)
@@ -171,10 +159,7 @@ struct rt_ctx {
     int coop_min = 12;                  // scenes with at least this many spheres use the cooperative any-hit instance (0 = never)
     int persist = 0;                    // diagnostics: persistent-wavefront instances
     int n_cus = 256;
-    int current_sample = 0;
-    uint64_t launches = 0;
     const char *last_kernel = "";       // symbol of the instance the last launch used
-    double last_ms = 0.0;
     unsigned long long debug_counters[24] = {};   // diagnostic instances only
     hipStream_t stream = nullptr;       // the context's own (non-blocking) stream
     hipStream_t last_stream = nullptr;  // stream of the most recent launch / update (what readers wait for)
@@ -202,6 +187,20 @@ struct rt_ctx {
 
 namespace rt {
 
+// ---- the frame's geometry on the host (the kernels keep their own arithmetic) ----
+inline uint32_t tiles_per_row(const rt_ctx *c) { return (uint32_t)((c->w + 7) / 8); }                  // 8x8 tiles
+inline uint32_t tile_row_count(const rt_ctx *c) { return (uint32_t)((c->local_rows + 7) / 8); }        // ... of the local pixel buffer
+inline uint32_t tile_count(const rt_ctx *c) { return tiles_per_row(c) * tile_row_count(c); }
+inline uint32_t groups_per_row(const rt_ctx *c) { return (tiles_per_row(c) + 3) / 4; }                 // groups of four tiles (rt_tiles.hip)
+inline uint32_t group_count(const rt_ctx *c) { return groups_per_row(c) * tile_row_count(c); }
+inline size_t image_pixels(const rt_ctx *c) { return (size_t)c->w * (size_t)c->h; }                    // the full image, whatever rows the context renders
+inline size_t local_pixels(const rt_ctx *c) { return (size_t)c->local_rows * (size_t)c->w; }
+inline size_t color_floats(const rt_ctx *c) { return 3 * image_pixels(c); }
+inline uint32_t *frame_pixels(const rt_ctx *c) { return c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels; }     // the buffer launches write
+
+// a reset or a written state ends a frame of the current scene for the form choice too (Choice::frame_ended): end_frame(c).reset_in_place()
+inline FrameState &end_frame(rt_ctx *c) { c->choice.frame_ended(); return c->frame; }
+
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define HIP_TRY(call)                                                                          \
@@ -218,6 +217,11 @@ int chain(rt_ctx *c, hipStream_t stream);          // `stream` waits for whateve
 int wait_all(rt_ctx *c);                            // host waits for everything the context has queued
 int refresh_pixels(rt_ctx *c, hipStream_t stream); // the packed frame brought up to date on `stream` (already chained): the pack kernel, if the last launches ran with the pixel store off
 const double *create_breakdown();                   // host ms of the last rt_create by phase (rt_debug_create_breakdown)
+// blocking read of `bytes` from the context's device: behind everything it has queued, on its own stream (wait = false: the copy is queued, a later call waits)
+int read_back(rt_ctx *c, void *host, const void *dev, size_t bytes, bool wait = true);
+// `a` and `b` show the same frame on the same device: non-null, distinct, neither multi-device, same size (`sharding`: and rank, ranks, rows per
+// tile), same device -- or RT_ERR_ARG with a message that names `call`, the two contexts as the caller knows them, and the property that differs
+int same_frame(const rt_ctx *a, const rt_ctx *b, const char *call, const char *a_name, const char *b_name, bool sharding = true);
 
 // ---- rt_launch.hip: one launch of the render kernel ----
 constexpr uint32_t kAlwaysWalkFrom = 1500;          // tree spheres from which the hierarchy is walked without estimate or measurement (rt_launch.hip)
@@ -244,7 +248,6 @@ int build_bvh(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload 
 int render_shard(rt_ctx *c, int n_samples, bool may_block);      // rt_launch.hip: one shard's launch on its own stream
 
 // ---- rt_tiles.hip: the subset launch's device side ----
-inline uint32_t group_count(const rt_ctx *c) { return (uint32_t)(((c->w + 31) / 32) * ((c->local_rows + 7) / 8)); }
 int tiles_refuse(const rt_ctx *c, const char *call);                  // RT_ERR_ARG for the contexts the adaptive calls do not take (null, multi-device, sharded)
 int tiles_ensure(rt_ctx *c);                                          // the three device arrays of rt_ctx::tiles, on first use
 int merge_by_tile(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, int total, hipStream_t stream);   // rt_merge_async with a ragged context among them (checked by the caller)

@@ -59,14 +59,14 @@ rt::LaunchParams make_params(rt_ctx *c, int n_samples) {
     p.scene = c->scene;
     p.cam = c->cam;
     p.seeds = c->d_seeds;
-    p.seeds_in = c->seeds_default ? c->d_seeds0 : c->d_seeds;
+    p.seeds_in = c->frame.seeds_default ? c->d_seeds0 : c->d_seeds;
     p.colors = c->d_colors;
-    p.pixels = c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels;
+    p.pixels = frame_pixels(c);
     p.counters = c->d_counters;
     p.stats = c->d_stats;
     p.w = c->w;
     p.h = c->h;
-    p.first_sample = c->current_sample;
+    p.first_sample = c->frame.current_sample;
     p.n_samples = n_samples;
     p.rank = c->rank;
     p.nranks = c->nranks;
@@ -77,8 +77,8 @@ rt::LaunchParams make_params(rt_ctx *c, int n_samples) {
     p.inv_h = 1.f / (float)c->h;
     p.regen_gate = c->regen_gate > 0 ? c->regen_gate : (c->scene.n_spheres <= 512 ? 8 : 1);
     p.coop_kmax = c->coop_kmax;
-    p.tiles_x = (c->w + 7) / 8;
-    p.n_tiles = p.tiles_x * ((c->local_rows + 7) / 8);
+    p.tiles_x = (int)tiles_per_row(c);
+    p.n_tiles = (int)tile_count(c);
     return p;
 }
 
@@ -223,6 +223,42 @@ static int choose_instance(const rt_ctx *c, int n_samples, Form form, Chosen *ou
     return RT_OK;
 }
 
+// What launch_form and launch_tiles refuse alike ...
+static int check_launch_args(const rt_ctx *c, int n_samples) {
+    if (!c->have_scene || !c->have_cam) return fail(RT_ERR_STATE, "rt_set_scene and rt_set_camera must precede rendering");
+    if (n_samples < 0) return fail(RT_ERR_ARG, "n_samples < 0");
+    if (n_samples > 0x7fffffff - c->frame.current_sample)
+        return fail(RT_ERR_ARG, "pass counter would overflow (%d + %d)", c->frame.current_sample, n_samples);
+    return RT_OK;
+}
+
+// ... and what both make of `form` once something is to be launched: the instance, its parameters, its tables and its LDS.  `from_list`: the launch
+// takes its tiles from a subset launch's list, which an instance of a wider tile, or one that walks no list at all, cannot render.
+struct Prepared { const rt::Instance *inst = nullptr; rt::LaunchParams p{}; size_t lds = 0; };
+static int prepare_launch(rt_ctx *c, int n_samples, Form form, bool from_list, Prepared *out) {
+    Chosen chosen;
+    int rc = choose_instance(c, n_samples, form, &chosen);
+    if (rc != RT_OK) return rc;
+    const rt::Instance *inst = out->inst = chosen.inst;
+    if (from_list && ((inst->flags & (rt::kInstTwoRays | rt::kInstPersistent | rt::kInstNoTileCost)) != 0 || (inst->waves != 1 && inst->waves != 4)))
+        return fail(RT_ERR_STATE, "rt_render_tiles_async: %s does not render a 32x8 group from a tile list (a wider tile, or no list at all)", inst->name);
+    out->p = make_params(c, n_samples);
+    out->p.mat_in_lds = chosen.mat_in_lds;
+    if (chosen.regen_gate) out->p.regen_gate = chosen.regen_gate;
+    out->p.walk_round = (c->walk_round & 0xff) | (c->walk_tail << 8);       // (one kernel argument: pair steps in a row | tail lanes << 8)
+    return bind_tables(c, *inst, n_samples, out->p, &out->lds);
+}
+
+// The launch is queued: the frame has its passes, and the form choice knows what rendered them
+static void after_launch(rt_ctx *c, const rt::Instance &inst, int n_samples, const bool *all_groups) {
+    if (all_groups) c->frame.launched_subset(n_samples, c->pixel_write != 0, *all_groups);
+    else c->frame.launched(n_samples, c->pixel_write != 0);
+    c->choice.scene_launches += 1;
+    c->last_kernel = inst.name;
+    const bool coop = inst.role == rt::kRoleCoop || inst.role == rt::kRolePersistCoop;
+    c->choice.last = rt::walks_hierarchy(inst.tables) ? Form::Walk : (coop ? Form::SweepCoop : Form::SweepPlain);
+}
+
 // persistent instances: just enough workgroups to fill the machine; the tile queue (counters[30]) does the rest
 static int persist_grid(rt_ctx *c, int n_tiles, size_t lds_use, hipStream_t stream, dim3 *grid) {
     size_t per_cu = lds_use > 0 ? (160 * 1024) / (lds_use + 6 * 1024) : 6;
@@ -239,36 +275,26 @@ static int persist_grid(rt_ctx *c, int n_tiles, size_t lds_use, hipStream_t stre
 // One launch of `form` (Form::Auto: whatever the context's thresholds and diagnostics knobs say).  `natural_order`: in image order whatever the
 // tile schedule holds (rt_tile_order.h) -- the hierarchy's probe only.
 static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, Form form, bool natural_order = false) {
-    if (!c->have_scene || !c->have_cam)
-        return fail(RT_ERR_STATE, "rt_set_scene and rt_set_camera must precede rendering");
-    if (n_samples < 0) return fail(RT_ERR_ARG, "n_samples < 0");
-    if (n_samples > 0x7fffffff - c->current_sample)
-        return fail(RT_ERR_ARG, "pass counter would overflow (%d + %d)", c->current_sample, n_samples);
-    if (n_samples == 0 || c->local_rows == 0) return RT_OK;
-    int rc = chain(c, stream);
+    int rc = check_launch_args(c, n_samples);
+    if (rc != RT_OK || n_samples == 0 || c->local_rows == 0) return rc;
+    rc = chain(c, stream);
     if (rc != RT_OK) return rc;
-
-    Chosen chosen;
-    rc = choose_instance(c, n_samples, form, &chosen);
+    Prepared prep;
+    rc = prepare_launch(c, n_samples, form, false, &prep);
     if (rc != RT_OK) return rc;
-    const rt::Instance *inst = chosen.inst;
-    rt::LaunchParams p = make_params(c, n_samples);
-    p.mat_in_lds = chosen.mat_in_lds;
-    if (chosen.regen_gate) p.regen_gate = chosen.regen_gate;
-    p.walk_round = (c->walk_round & 0xff) | (c->walk_tail << 8);       // (one kernel argument: pair steps in a row | tail lanes << 8)
-    size_t lds_use = 0;
-    rc = bind_tables(c, *inst, n_samples, p, &lds_use);
-    if (rc != RT_OK) return rc;
+    const rt::Instance *inst = prep.inst;
+    rt::LaunchParams &p = prep.p;
+    const size_t lds_use = prep.lds;
 
     const int tile_w = 8 * inst->waves * ((inst->flags & rt::kInstTwoRays) ? 2 : 1);
-    dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), (unsigned)((c->local_rows + rt::kTileH - 1) / rt::kTileH));
+    dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), tile_row_count(c));
     const uint32_t n_tiles = grid.x * grid.y;
     const rt::TileOrder::Plan plan = c->order.plan(n_tiles, n_samples, natural_order, (inst->flags & rt::kInstNoTileCost) == 0);
     if (plan.sort_now) {
         hipLaunchKernelGGL(rt_order_tiles_kernel, dim3(1), dim3(1024), 0, stream, c->order.d_tile_cost, c->order.d_order, n_tiles);
         if (hipPeekAtLastError() != hipSuccess) c->order.forget();      // (no order from a sort that was not queued)
         HIP_TRY(hipGetLastError());
-        c->tiles.list_valid = false;                                    // (a subset launch's list follows the order: launch_tiles builds it again)
+        c->frame.order_resorted();                                      // (a subset launch's list follows the order: launch_tiles builds it again)
     }
     if (plan.use_order) p.order = c->order.d_order;
     if (plan.write_costs) p.tile_cost = c->order.d_tile_cost;
@@ -289,14 +315,7 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, Form form, 
     if (e != hipSuccess)
         return fail(RT_ERR_HIP, "kernel launch failed: %s (%s, grid %ux%u, lds %zu B)", hipGetErrorString(e), inst->name, grid.x, grid.y, lds_use);
     c->order.launched(plan, n_samples, n_tiles);
-    c->current_sample += n_samples;
-    c->launches += 1;
-    c->choice.scene_launches += 1;
-    c->last_kernel = inst->name;
-    const bool coop = inst->role == rt::kRoleCoop || inst->role == rt::kRolePersistCoop;
-    c->choice.last = rt::walks_hierarchy(inst->tables) ? Form::Walk : (coop ? Form::SweepCoop : Form::SweepPlain);
-    c->seeds_default = false;           // this launch has written every seed pair the context renders
-    c->pixels_current = c->pixel_write != 0;
+    after_launch(c, *inst, n_samples, nullptr);
     return RT_OK;
 }
 
@@ -308,52 +327,42 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, Form form, 
 // `valid` / `valid_e` tests and the epilogue).  The instance is the one the context's last launch used (choice.last; before any launch what the thresholds
 // say); no probe is started, advanced or timed, and the heavy-first schedule is read, never written: no plan(), no launched(), no costs.
 int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream) {
-    if (!c->have_scene || !c->have_cam) return fail(RT_ERR_STATE, "rt_set_scene and rt_set_camera must precede rendering");
-    if (n_samples < 0) return fail(RT_ERR_ARG, "n_samples < 0");
-    if (n_samples > 0x7fffffff - c->current_sample) return fail(RT_ERR_ARG, "pass counter would overflow (%d + %d)", c->current_sample, n_samples);
-    rt::TileSubset &sub = c->tiles;
-    if (!sub.have_selection) return fail(RT_ERR_STATE, "rt_render_tiles_async: no selection (rt_select_tiles comes first; a reset drops it)");
-    if (n_samples == 0 || sub.counts[0] == 0) return RT_OK;
-    int rc = RT_OK;
+    int rc = check_launch_args(c, n_samples);
+    if (rc != RT_OK) return rc;
+    const rt::FrameState &frame = c->frame;
+    if (!frame.have_selection) return fail(RT_ERR_STATE, "rt_render_tiles_async: no selection (rt_select_tiles comes first; a reset drops it)");
+    if (n_samples == 0 || frame.counts[0] == 0) return RT_OK;
     if (c->tables_stale) {
         rc = refresh_tables(c, stream);
         if (rc != RT_OK) return rc;
     }
     rc = chain(c, stream);
     if (rc != RT_OK) return rc;
-
-    Chosen chosen;
-    rc = choose_instance(c, n_samples, c->choice.last, &chosen);
+    Prepared prep;
+    rc = prepare_launch(c, n_samples, c->choice.last, true, &prep);
     if (rc != RT_OK) return rc;
-    const rt::Instance *inst = chosen.inst;
-    if ((inst->flags & (rt::kInstTwoRays | rt::kInstPersistent | rt::kInstNoTileCost)) != 0 || (inst->waves != 1 && inst->waves != 4))
-        return fail(RT_ERR_STATE, "rt_render_tiles_async: %s does not render a 32x8 group from a tile list (a wider tile, or no list at all)", inst->name);
-    rt::LaunchParams p = make_params(c, n_samples);
-    p.mat_in_lds = chosen.mat_in_lds;
-    if (chosen.regen_gate) p.regen_gate = chosen.regen_gate;
-    p.walk_round = (c->walk_round & 0xff) | (c->walk_tail << 8);
-    size_t lds_use = 0;
-    rc = bind_tables(c, *inst, n_samples, p, &lds_use);
-    if (rc != RT_OK) return rc;
+    const rt::Instance *inst = prep.inst;
+    rt::LaunchParams &p = prep.p;
+    const size_t lds_use = prep.lds;
 
-    const uint32_t tiles_x = (uint32_t)((c->w + 8 * inst->waves - 1) / (8 * inst->waves)), tiles_y = (uint32_t)((c->local_rows + rt::kTileH - 1) / rt::kTileH);
+    const uint32_t tiles_x = (uint32_t)((c->w + 8 * inst->waves - 1) / (8 * inst->waves)), tiles_y = tile_row_count(c);
     const uint32_t n_launch = tiles_x * tiles_y;
-    const uint32_t m = inst->waves == 4 ? sub.counts[0] : sub.counts[1];       // launch tiles kept: a group is one 32x8 tile, or the 8x8 tiles it covers
+    const uint32_t m = inst->waves == 4 ? frame.counts[0] : frame.counts[1];       // launch tiles kept: a group is one 32x8 tile, or the 8x8 tiles it covers
     dim3 grid(tiles_x, (m + tiles_x - 1) / tiles_x);
     const bool by_order = c->order.use_order != 0 && c->order.has_order() && c->order.cost_tiles == n_launch;      // a schedule sorted for this tile shape
-    if (!sub.list_valid || sub.list_serial != sub.selection_serial || sub.list_tiles != n_launch || sub.list_by_order != by_order) {
+    if (frame.list_is_stale(by_order, n_launch)) {
         rc = tiles_build_list(c, inst->waves, by_order, n_launch, grid.x * grid.y, stream);
         if (rc != RT_OK) return rc;
     }
-    const bool all = sub.counts[0] == group_count(c);       // every group selected means every group at the front: the frame stays (or is again) whole
-    if (c->seeds_default && !all) {
+    const bool all = frame.counts[0] == group_count(c);       // every group selected means every group at the front: the frame stays (or is again) whole
+    if (frame.seeds_default && !all) {
         // after rt_reset_async the first launch reads the pristine stream in place and writes the context's buffer; the tiles this launch leaves out
         // must hold that stream too (a tile at 0 passes holds the seeds of a 0-pass render): the copy rt_reset makes, now
-        HIP_TRY(hipMemcpyAsync(c->d_seeds, c->d_seeds0, 2 * (size_t)c->w * (size_t)c->h * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-        c->seeds_default = false;
+        HIP_TRY(hipMemcpyAsync(c->d_seeds, c->d_seeds0, 2 * image_pixels(c) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        c->frame.default_seeds_copied();
         p.seeds_in = c->d_seeds;
     }
-    p.order = sub.d_list;
+    p.order = c->tiles.d_list;
     p.tile_cost = nullptr;
     const hipError_t e = rt::launch_instance(*inst, p, grid, lds_use, stream);
     if (e != hipSuccess)
@@ -362,18 +371,10 @@ int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream) {
         rc = tiles_advance(c, n_samples, stream);           // (reads current_sample as it was: the count the selected groups come from)
         if (rc != RT_OK) return rc;
     }
-    sub.ragged = !all;
     // (a timed step of the cooperative-or-plain measurement that is open lies between an event and the full launches still to come: this launch
     // would be timed with them, so the step starts again with the next full launch -- nothing of the measurement is started, advanced or timed here)
     if ((c->probe.state & 1) != 0 && c->probe.acc > 0) c->probe.acc = 0;
-    c->current_sample += n_samples;
-    c->launches += 1;
-    c->choice.scene_launches += 1;
-    c->last_kernel = inst->name;
-    const bool coop = inst->role == rt::kRoleCoop || inst->role == rt::kRolePersistCoop;
-    c->choice.last = rt::walks_hierarchy(inst->tables) ? Form::Walk : (coop ? Form::SweepCoop : Form::SweepPlain);
-    c->seeds_default = false;
-    c->pixels_current = c->pixel_write != 0 && (all || c->pixels_current);      // (the tiles left out keep the packed pixels they had)
+    after_launch(c, *inst, n_samples, &all);
     return RT_OK;
 }
 

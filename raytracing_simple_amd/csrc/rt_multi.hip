@@ -449,7 +449,7 @@ int multi_reset(rt_ctx *front, bool async) {
     rt_multi *m = front->multi;
     m->launches = 0;
     m->last_ms = 0.0;
-    front->current_sample = 0;
+    front->frame.front_follows(0);
     EACH_SHARD(async ? rt_reset_async(s, s->stream) : rt_reset(s));
 }
 
@@ -497,7 +497,7 @@ int multi_render(rt_ctx *front, uint32_t *out_host, int n_samples, bool blocking
         if (rc != RT_OK) return rc;
         if (blocking) HIP_TRY(hipEventRecord(s->ev1, s->stream));
     }
-    front->current_sample = m->shard[0]->current_sample;
+    front->frame.front_follows(m->shard[0]->frame.current_sample);
     if (n_samples > 0) m->launches += 1;
     if (frame_wanted) {
         int rc = gather_and_assemble(m);
@@ -515,7 +515,7 @@ int multi_render(rt_ctx *front, uint32_t *out_host, int n_samples, bool blocking
         HIP_TRY(hipStreamSynchronize(s->stream));
         float ms = 0.f;
         if (n_samples > 0 && s->local_rows > 0) HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-        s->last_ms = ms;
+        s->frame.timed(ms);
         worst = ms > worst ? ms : worst;
     }
     m->last_ms = worst;                 // the frame's kernel time = its slowest shard
@@ -530,7 +530,7 @@ int multi_read_pixels(rt_ctx *front, uint32_t *out_host) {
     }
     // shards whose last launches skipped the pixel store pack their rows now; then the usual gather
     bool stale = false;
-    for (rt_ctx *s : m->shard) stale = stale || (!s->pixels_current && s->current_sample > 0);
+    for (rt_ctx *s : m->shard) stale = stale || (!s->frame.pixels_current && s->frame.current_sample > 0);
     if (stale) {
         int rb = begin_frame(m);                        // (the root packs into the receive slot of the frame about to be gathered)
         if (rb != RT_OK) return rb;

@@ -97,20 +97,13 @@ int write_one(rt_ctx *c, const float *colors_host, const uint32_t *seeds_host, i
     if (rc != RT_OK) return rc;
     rc = chain(c, c->stream);
     if (rc != RT_OK) return rc;
-    const size_t px = (size_t)c->w * (size_t)c->h;
+    const size_t px = image_pixels(c);
     if (colors_host) HIP_TRY(hipMemcpyAsync(c->d_colors, colors_host, 3 * px * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (seeds_host) HIP_TRY(hipMemcpyAsync(c->d_seeds, seeds_host, 2 * px * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, 32 * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, rt::kStatReplicas * 8 * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));               // the caller's buffers may go
-    c->seeds_default = seeds_host == nullptr;               // no seeds given: the next launch reads the pristine default stream in place
-    c->seeds_custom = seeds_host != nullptr;
-    c->current_sample = current_sample;
-    c->tiles.whole();                                       // a written state is a whole frame at one pass number
-    c->choice.frame_ended();
-    c->launches = 0;
-    c->last_ms = 0.0;
-    c->pixels_current = false;                              // rt_read_pixels packs the frame from the restored plane
+    end_frame(c).state_written(current_sample, seeds_host != nullptr);
     return RT_OK;
 }
 
@@ -131,12 +124,11 @@ RT_API int rt_seed_stream_async(rt_ctx *c, uint64_t stream_id, void *hip_stream)
         if (rc != RT_OK) return rc;
         rc = chain(s, stream);
         if (rc != RT_OK) return rc;
-        const size_t px = (size_t)s->w * (size_t)s->h;      // the full image, whatever rows the context renders
+        const size_t px = image_pixels(s);
         hipLaunchKernelGGL(rt_seed_stream_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream,
                            reinterpret_cast<unsigned long long *>(s->d_seeds), px, (unsigned long long)stream_id);
         HIP_TRY(hipGetLastError());
-        s->seeds_default = false;                           // the next launch reads d_seeds
-        s->seeds_custom = true;
+        s->frame.custom_seeds_written();                    // the next launch reads d_seeds
     }
     return RT_OK;
 }
@@ -153,15 +145,15 @@ RT_API int rt_write_state(rt_ctx *c, const float *colors_host, const uint32_t *s
         rc = write_one(rt::multi_shard(c, r), colors_host, seeds_host, current_sample);
         if (rc != RT_OK) return rc;
     }
-    c->current_sample = current_sample;
+    c->frame.front_follows(current_sample);
     return RT_OK;
 }
 
 RT_API int rt_save_state(rt_ctx *c, const char *path) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     if (!path) return fail(RT_ERR_ARG, "path is null");
-    if (c->tiles.ragged) return fail(RT_ERR_STATE, "rt_save_state: the tiles hold different pass counts after a subset launch, and the file format holds one pass number");
-    const size_t px = (size_t)c->w * (size_t)c->h;
+    if (c->frame.ragged) return fail(RT_ERR_STATE, "rt_save_state: the tiles hold different pass counts after a subset launch, and the file format holds one pass number");
+    const size_t px = image_pixels(c);
     std::vector<float> colors(3 * px);
     std::vector<uint32_t> seeds(2 * px);
     int rc = rt_read_colors(c, colors.data());
@@ -172,7 +164,7 @@ RT_API int rt_save_state(rt_ctx *c, const char *path) {
     hd.version = kStateVersion;
     hd.w = c->w;
     hd.h = c->h;
-    hd.current_sample = c->current_sample;
+    hd.current_sample = c->frame.current_sample;
     FILE *f = fopen(path, "wb");
     if (!f) return fail(RT_ERR_ARG, "rt_save_state: cannot open %s for writing", path);
     bool ok = fwrite(&hd, sizeof hd, 1, f) == 1 && fwrite(colors.data(), sizeof(float), colors.size(), f) == colors.size() &&
@@ -187,7 +179,7 @@ RT_API int rt_load_state(rt_ctx *c, const char *path) {
     if (!path) return fail(RT_ERR_ARG, "path is null");
     FILE *f = fopen(path, "rb");
     if (!f) return fail(RT_ERR_ARG, "rt_load_state: cannot open %s", path);
-    const size_t px = (size_t)c->w * (size_t)c->h;
+    const size_t px = image_pixels(c);
     std::vector<float> colors;
     std::vector<uint32_t> seeds;
     StateHeader hd;
@@ -214,18 +206,13 @@ RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hi
     if (!dst) return fail(RT_ERR_ARG, "ctx is null");
     if (!srcs) return fail(RT_ERR_ARG, "srcs is null");
     if (n_srcs < 1 || n_srcs > rt::kMergeMax - 1) return fail(RT_ERR_ARG, "n_srcs %d (1 .. %d)", n_srcs, rt::kMergeMax - 1);
-    if (dst->multi) return fail(RT_ERR_ARG, "rt_merge_async: a multi-device context cannot be merged");
     for (int k = 0; k < n_srcs; ++k) {
-        const rt_ctx *s = srcs[k];
-        if (!s) return fail(RT_ERR_ARG, "srcs[%d] is null", k);
-        if (s == dst) return fail(RT_ERR_ARG, "srcs[%d] is the destination", k);
+        char name[16];
+        snprintf(name, sizeof name, "srcs[%d]", k);
+        const int rc = same_frame(srcs[k], dst, "rt_merge_async", name, "the destination");
+        if (rc != RT_OK) return rc;
         for (int j = 0; j < k; ++j)
-            if (srcs[j] == s) return fail(RT_ERR_ARG, "srcs[%d] repeats srcs[%d]", k, j);
-        if (s->multi) return fail(RT_ERR_ARG, "rt_merge_async: srcs[%d] is a multi-device context", k);
-        if (s->w != dst->w || s->h != dst->h || s->rank != dst->rank || s->nranks != dst->nranks || s->tile_rows != dst->tile_rows)
-            return fail(RT_ERR_ARG, "srcs[%d] is %dx%d, rank %d of %d by %d rows; the destination %dx%d, rank %d of %d by %d rows", k, s->w, s->h, s->rank,
-                        s->nranks, s->tile_rows, dst->w, dst->h, dst->rank, dst->nranks, dst->tile_rows);
-        if (s->device != dst->device) return fail(RT_ERR_ARG, "srcs[%d] lives on device %d, the destination on device %d", k, s->device, dst->device);
+            if (srcs[j] == srcs[k]) return fail(RT_ERR_ARG, "srcs[%d] repeats srcs[%d]", k, j);
     }
     // the contexts that hold passes, destination first: one at pass 0 is skipped, not weighted by zero (its plane may hold an old frame, or nothing)
     rt::MergeArgs a{};
@@ -233,20 +220,20 @@ RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hi
     long long total = 0;
     for (int k = -1; k < n_srcs; ++k) {
         rt_ctx *x = k < 0 ? dst : srcs[k];
-        if (x->current_sample <= 0) continue;
+        if (x->frame.current_sample <= 0) continue;
         used[a.count] = x;
         a.plane[a.count] = x->d_colors;
-        a.weight[a.count] = (float)x->current_sample;
+        a.weight[a.count] = (float)x->frame.current_sample;
         a.count += 1;
-        total += x->current_sample;
+        total += x->frame.current_sample;
     }
     if (total == 0) return fail(RT_ERR_STATE, "rt_merge_async: none of the %d contexts holds a pass", n_srcs + 1);
     if (total > INT_MAX) return fail(RT_ERR_ARG, "rt_merge_async: the pass counter would overflow (%lld)", total);
     a.inv_total = 1.0f / (float)total;
     int rc = select_device(dst);
     if (rc != RT_OK) return rc;
-    bool ragged = dst->tiles.ragged;
-    for (int k = 0; k < n_srcs; ++k) ragged = ragged || srcs[k]->tiles.ragged;
+    bool ragged = dst->frame.ragged;
+    for (int k = 0; k < n_srcs; ++k) ragged = ragged || srcs[k]->frame.ragged;
     if (ragged)                                             // tiles at different pass counts (after subset launches): every float by its own tile's weights
         return merge_by_tile(dst, srcs, n_srcs, (int)total, (hipStream_t)hip_stream);
     // behind everything the destination and the sources it reads have queued; their later work behind the merge
@@ -255,15 +242,13 @@ RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hi
     for (int k = 0; k < a.count && rc == RT_OK; ++k)
         if (used[k] != dst) rc = chain(used[k], stream);
     if (rc != RT_OK) return rc;
-    const size_t n_floats = 3 * (size_t)dst->w * (size_t)dst->h;
+    const size_t n_floats = color_floats(dst);
     size_t blocks = (n_floats / 4 + 255) / 256, cap = (size_t)dst->n_cus * 8;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(rt_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dst->d_colors, a, n_floats);
     HIP_TRY(hipGetLastError());
-    dst->current_sample = (int)total;
-    dst->tiles.have_selection = false;                      // (a selection was made at another pass number)
-    dst->pixels_current = false;                            // rt_read_pixels packs the merged plane
+    dst->frame.merged((int)total);
     return RT_OK;
 }
 

@@ -150,18 +150,12 @@ __global__ void __launch_bounds__(256) rt_merge_tile_counts_kernel(uint32_t *out
 
 using namespace rt;
 
-namespace {
-
-uint32_t tile_count(const rt_ctx *c) { return (uint32_t)(((c->w + 7) / 8) * ((c->local_rows + 7) / 8)); }
-
-}  // namespace
-
 namespace rt {
 
 // the three device arrays, on first use (rt_destroy frees them)
 int tiles_ensure(rt_ctx *c) {
     rt::TileSubset &s = c->tiles;
-    const size_t tiles = std::max<size_t>(tile_count(c), 1), tiles_x = (size_t)((c->w + 7) / 8);
+    const size_t tiles = std::max<size_t>(tile_count(c), 1), tiles_x = tiles_per_row(c);
     if (!s.d_passes) HIP_TRY(hipMalloc(&s.d_passes, tiles * sizeof(uint32_t)));
     if (!s.d_selected) HIP_TRY(hipMalloc(&s.d_selected, ((size_t)group_count(c) + 2) * sizeof(uint32_t)));
     if (!s.d_list) HIP_TRY(hipMalloc(&s.d_list, (tiles + tiles_x) * sizeof(uint32_t)));      // every tile, and the padding of the last grid row
@@ -176,25 +170,20 @@ int tiles_refuse(const rt_ctx *c, const char *call) {
 }
 
 int tiles_build_list(rt_ctx *c, int waves, bool by_order, uint32_t n_launch, uint32_t slots, hipStream_t stream) {
-    rt::TileSubset &s = c->tiles;
-    const uint32_t tiles_x = (uint32_t)((c->w + 7) / 8), groups_x = (tiles_x + 3) / 4;
+    const rt::TileSubset &s = c->tiles;
+    const uint32_t tiles_x = tiles_per_row(c), groups_x = groups_per_row(c);
     if (slots > tile_count(c) + tiles_x) return fail(RT_ERR_STATE, "rt_render_tiles_async: a list of %u entries for %u tiles", slots, tile_count(c));
     hipLaunchKernelGGL(rt_tile_list_kernel, dim3(1), dim3(1024), 0, stream, by_order ? c->order.d_order : nullptr, n_launch,
                        waves == 4 ? groups_x : tiles_x, waves == 4 ? 1u : 4u, groups_x, s.d_selected, s.d_list, slots, n_launch);
     HIP_TRY(hipGetLastError());
-    s.list_valid = true;
-    s.list_by_order = by_order;
-    s.list_serial = s.selection_serial;
-    s.list_tiles = n_launch;
-    s.list_slots = slots;
+    c->frame.list_built(by_order, n_launch, slots);
     return RT_OK;
 }
 
 int tiles_advance(rt_ctx *c, int n_samples, hipStream_t stream) {
-    rt::TileSubset &s = c->tiles;
-    const uint32_t n = tile_count(c), tiles_x = (uint32_t)((c->w + 7) / 8);
-    hipLaunchKernelGGL(rt_tile_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, s.d_passes, s.ragged ? 1 : 0, (uint32_t)c->current_sample,
-                       s.d_selected, n, tiles_x, (tiles_x + 3) / 4, (uint32_t)n_samples);
+    const uint32_t n = tile_count(c);
+    hipLaunchKernelGGL(rt_tile_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, c->tiles.d_passes, c->frame.ragged ? 1 : 0,
+                       (uint32_t)c->frame.current_sample, c->tiles.d_selected, n, tiles_per_row(c), groups_per_row(c), (uint32_t)n_samples);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -209,23 +198,19 @@ int merge_by_tile(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, int total, hipSt
         rt_ctx *x = k < 0 ? dst : srcs[k];
         if (k >= 0) rc = chain(x, stream);
         t.plane[t.count] = x->d_colors;
-        t.passes[t.count] = x->tiles.ragged ? x->tiles.d_passes : nullptr;
-        t.cur[t.count] = (uint32_t)x->current_sample;
+        t.passes[t.count] = x->frame.ragged ? x->tiles.d_passes : nullptr;
+        t.cur[t.count] = (uint32_t)x->frame.current_sample;
         t.count += 1;
     }
     if (rc != RT_OK) return rc;
-    const size_t n_floats = 3 * (size_t)dst->w * (size_t)dst->h;
+    const size_t n_floats = color_floats(dst);
     const size_t blocks = std::max<size_t>(1, std::min((n_floats + 255) / 256, (size_t)dst->n_cus * 8));
     hipLaunchKernelGGL(rt_merge_tiles_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dst->d_colors, t, dst->w, dst->h, n_floats);
     HIP_TRY(hipGetLastError());
     const uint32_t n_tiles = tile_count(dst);
     hipLaunchKernelGGL(rt_merge_tile_counts_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, stream, dst->tiles.d_passes, t, n_tiles);
     HIP_TRY(hipGetLastError());
-    dst->current_sample = total;
-    dst->tiles.ragged = true;
-    dst->tiles.have_selection = false;                      // (dst's front has moved)
-    dst->tiles.list_valid = false;
-    dst->pixels_current = false;                            // rt_read_pixels packs the merged plane
+    dst->frame.merged_by_tile(total);
     return RT_OK;
 }
 
@@ -242,22 +227,18 @@ RT_API int rt_select_tiles(rt_ctx *c, const uint32_t *err_dev, uint32_t above, v
     hipStream_t stream = (hipStream_t)hip_stream;
     rc = chain(c, stream);
     if (rc != RT_OK) return rc;
-    rt::TileSubset &s = c->tiles;
+    const rt::TileSubset &s = c->tiles;
     const uint32_t groups = group_count(c);
     uint32_t *d_counts = s.d_selected + groups;
     HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(rt_select_tiles_kernel, dim3((groups + 255) / 256), dim3(256), 0, stream, err_dev, above, s.ragged ? s.d_passes : nullptr,
-                       (uint32_t)c->current_sample, c->w, c->local_rows, s.d_selected, d_counts);
+    hipLaunchKernelGGL(rt_select_tiles_kernel, dim3((groups + 255) / 256), dim3(256), 0, stream, err_dev, above, c->frame.ragged ? s.d_passes : nullptr,
+                       (uint32_t)c->frame.current_sample, c->w, c->local_rows, s.d_selected, d_counts);
     HIP_TRY(hipGetLastError());
-    s.have_selection = false;                               // (the flags are being rewritten: no selection until the counts are back)
-    s.list_valid = false;
+    c->frame.selection_started();                           // (the flags are being rewritten: no selection until the counts are back)
     uint32_t got[2] = { 0, 0 };
     HIP_TRY(hipMemcpyAsync(got, d_counts, sizeof got, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    s.counts[0] = got[0];
-    s.counts[1] = got[1];
-    s.selection_serial += 1;
-    s.have_selection = true;
+    c->frame.selection_landed(got[0], got[1]);
     if (counts) {
         counts[0] = got[0];
         counts[1] = got[1];
@@ -278,17 +259,11 @@ RT_API int rt_tile_passes(rt_ctx *c, uint32_t *out_host) {
     if (rc != RT_OK) return rc;
     if (!out_host) return fail(RT_ERR_ARG, "out_host is null");
     const uint32_t n = tile_count(c);
-    if (!c->tiles.ragged) {                                 // implicit: nothing is stored while every tile holds current_sample passes
-        std::fill(out_host, out_host + n, (uint32_t)c->current_sample);
+    if (!c->frame.ragged) {                                 // implicit: nothing is stored while every tile holds current_sample passes
+        std::fill(out_host, out_host + n, (uint32_t)c->frame.current_sample);
         return RT_OK;
     }
-    rc = select_device(c);
-    if (rc != RT_OK) return rc;
-    rc = chain(c, c->stream);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_host, c->tiles.d_passes, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RT_OK;
+    return read_back(c, out_host, c->tiles.d_passes, (size_t)n * sizeof(uint32_t));
 }
 
 }  // extern "C"
