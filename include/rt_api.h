@@ -226,7 +226,8 @@ RT_API int rt_set_pixel_write(rt_ctx *ctx, int enable);
 /* getPixels() for hosts that skip pixel stores: brings the packed frame up to date -- if the last
  * launches ran with the pixel store off, a small kernel packs the frame from the running average
  * (same toInt, .cl:34,594-596) -- and copies it to `out_host` (local rows x w uint32).  Waits for
- * the launches issued on this context.                                                        */
+ * the launches issued on this context.  While the context is at pass 0 nothing is packed and the
+ * pixels are unspecified: whatever the buffer held (rt_reset clears it, the other calls do not).  */
 RT_API int rt_read_pixels(rt_ctx *ctx, uint32_t *out_host);
 
 /* Same launch, asynchronous on `hip_stream` (a hipStream_t, NULL = default stream), no copy
@@ -305,7 +306,10 @@ RT_API int rt_seed_stream_async(rt_ctx *ctx, uint64_t stream_id, void *hip_strea
  * context hands them to every shard -- and the pass number the next launch continues from.  seeds_host == NULL means the
  * default stream; colors_host == NULL is allowed only with current_sample == 0 (pass 0 overwrites the plane, .cl:580-582).
  * Counters and the launch count restart as by rt_reset.  The packed pixels are NOT written: rt_read_pixels right after the
- * call packs the restored plane (same toInt, .cl:34,594-596).  Blocking, like rt_reset; the buffers may be reused on return.
+ * call packs the restored plane (same toInt, .cl:34,594-596) -- of a state beyond pass 0.  AT PASS 0 THE PACKED PIXELS ARE
+ * UNSPECIFIED: pass 0 means that the plane holds nothing (rt_reset_async leaves an old frame there, rt_merge_async skips such a
+ * context), so nothing is packed from it and rt_read_pixels returns whatever the buffer held before the call.  The same holds
+ * for the tiles of a ragged context that hold no pass.  Blocking, like rt_reset; the buffers may be reused on return.
  * A refused call (RT_ERR_ARG: negative pass number, colours missing beyond pass 0) leaves the context as it was.             */
 RT_API int rt_write_state(rt_ctx *ctx, const float *colors_host, const uint32_t *seeds_host, int current_sample);
 

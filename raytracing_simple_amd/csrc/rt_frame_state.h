@@ -36,7 +36,8 @@ struct FrameState {
     void reset_blocking() { restart(0); seeds_default = seeds_custom = false; pixels_current = true; }
     void reset_in_place() { restart(0); seeds_default = true; }                     // rt_reset_async: nothing is copied, the next launch reads d_seeds0
     void custom_seeds_written() { seeds_default = false; seeds_custom = true; }     // rt_seed_stream_async, stream id != 0, after its reset
-    // rt_write_state; without seeds the default stream is read in place, and the frame is packed from the written plane when somebody reads it
+    // rt_write_state; without seeds the default stream is read in place, and the frame is packed from the written plane when somebody reads it --
+    // beyond pass 0: refresh_pixels packs nothing while current_sample is 0 (the plane holds nothing), and the packed pixels are unspecified there
     void state_written(int pass, bool with_seeds) { restart(pass); seeds_default = !with_seeds; seeds_custom = with_seeds; pixels_current = false; }
     void debug_reset_by_copy() { current_sample = 0; seeds_default = seeds_custom = false; }    // the round-1 reset (rt_debug.hip): seeds and pass, nothing else
 
