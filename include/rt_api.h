@@ -398,7 +398,8 @@ RT_API double rt_error_psnr(const rt_frame_error *e);
  * image than the halves are to each other: with independent errors of equal variance the difference of the halves carries twice
  * the variance of one half and four times that of their mean, about 6 dB in the linear colour plane.  How much of that survives
  * the clamp, the gamma and the rounding to 8 bits has NOT been measured yet (tools/frame_error_probe.py records it): until it
- * is, treat the pair figure as a lower bound of the merged frame's quality and add nothing to it.
+ * is, treat the pair figure as a lower bound of the merged frame's quality and add nothing to it.  (For the FILTERED merge the offset is
+ * about 13 dB, and "the error of the filtered frame" below has a figure of its own for it: rt_render_converged_filtered.)
  * RT_ERR_ARG: a pair rt_compare refuses, a null `last`, passes_per_check < 1, max_passes below the contexts' pass number, a NaN
  * target.  RT_ERR_STATE: contexts at different pass numbers; both at pass 0 of the default seed stream (they would render the
  * same frame and "converge" at once).  A refused call changes nothing.                                                       */
@@ -536,6 +537,85 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
  * tested against bit for bit.  `out` may not overlap the inputs.  Needs no device.  RT_ERR_ARG: a null plane, w or h < 1, parameters
  * rt_denoise_async refuses.                                                                                                           */
 RT_API int rt_denoise_planes(float *out, const float *merged, const float *a, const float *b, int w, int h, const rt_denoise_params *p);
+
+/* ---- the error of the filtered frame: cross-filtered halves, render to ITS PSNR -------------------
+ * The pipeline above judges one frame and shows another: rt_render_converged and rt_render_adaptive measure the PSNR between the UNFILTERED halves,
+ * and the frame the user looks at is the filtered merge, for which nothing above has an error figure.  Rousselle, Knaus and Zwicker (2012)
+ * close the gap with dual buffers: half A is filtered with weights taken from half B, and B with weights taken from A.  Each half's weights are then
+ * independent of its own noise, and the difference of the two filtered halves estimates the error of the filtered result.  THIS LIBRARY'S OWN
+ * EXTENSION; it reproduces no reference frame.  No call above changes behaviour.
+ *
+ * THE ARITHMETIC, the same in rt_denoise_pair_async's kernel and in rt_denoise_pair_planes: all binary32, uncontracted, in the written order, IEEE
+ * division; the symbols are those of the denoising section.
+ *   7. Vs comes from rules 1-2 unchanged.  Vh = Vs + Vs is the variance of ONE half: (A - B)^2 / 4 estimates the variance of the mean, which is half
+ *      of one half's variance.
+ *   8. For X in {A, B} with the guide G = the other half, FX follows rules 3-6 with three substitutions: in rule 3  t = G[p][c] - G[q'][c]  and every
+ *      Vs is Vh;  rule 5's finiteness test reads X[p + o][c];  rule 6 accumulates wgt * X[p + o][c].  Everything else holds as written: the double
+ *      clamp of rule 4, the offset order, the centre weight 1.0f, a NaN T skipped.
+ *   9. With R = 0, FX = X bit for bit.  Exchanging a and b exchanges FA and FB bit for bit.  A non-finite value of X stays at its place in FX and
+ *      spreads nowhere; a NaN in the guide removes only the offsets whose patches touch it.
+ * MEASURED, in numpy on a CPU, with frames of this project's oracle alone (before any kernel existed): 96x64, the halves on seed streams 1 and 2 and
+ * packed by the oracle's toInt, truth a 4096-pass frame of the default stream (2048 passes for the 16-sphere scene), the defaults; PSNR in dB:
+ *     scene               passes per half   pair A/B (the loops above)   filtered merge vs truth (what is shown)   cross-filtered pair FA/FB
+ *     Demo                      4                 14.78                          27.69                                    28.00
+ *     Demo                     16                 20.90                          31.60                                    32.44
+ *     Demo                     64                 26.41                          35.43                                    35.83
+ *     c16_demo_plus_10          4                 15.00                          27.23                                    27.21
+ *     c16_demo_plus_10         16                 20.82                          31.42                                    31.86
+ * The cross-filtered pair figure lands within 0.9 dB of the true quality of the frame shown, where the raw pair is about 13 dB away: a host that
+ * wants a 28 dB picture and stops on the raw pair renders about twenty times the passes it needs.  Summed squared error, Demo at 4 passes: 1.90 M
+ * for the cross pair against a true 2.04 M and 39.8 M for the raw pair.  Per 8x8 tile, the rank correlation of the map with the filtered frame's
+ * true tile error is 0.90 / 0.87 / 0.94 for the cross pair and 0.71 / 0.89 / 0.91 for the raw pair (Demo, 4 / 16 / 64 passes).
+ * TWO THINGS THE SAME RUNS SHOWED:
+ *   - The mean of FA and FB is about 1 dB WORSE than rt_denoise_async of the merge (27.09 against 27.69, 30.63 against 31.60).  The cross-filtered
+ *     planes are an estimator, not the picture.  The picture stays rt_denoise_async's.
+ *   - The estimate sees variance, not the filter's bias, because both halves blur the same edge.  It is up to 0.85 dB optimistic in the table and
+ *     will be more so where bias dominates.  IT IS AN ESTIMATE, NOT A BOUND.
+ * ON THE DEVICE: tools/filtered_error_probe.py records the pair kernel's time beside rt_denoise_async's and the table above from rendered contexts
+ * (profiles/r14_filtered_error.jsonl); no time is promised.  The pair call does two filters' arithmetic on shared staging.                        */
+
+/* Each half filtered with the other half's weights, on `hip_stream`, without a host wait.  FA goes into a float plane that `a` owns, FB into one
+ * that `b` owns, laid out like the colour planes; beside each goes the plane packed by the library's toInt (.cl:34 -- the function the pack
+ * kernel of that context's mode uses), one uint32 per pixel in the PIXEL BUFFER's layout (row 0 = bottom), which is what rt_compare_filtered
+ * reads.  The four planes are allocated on first use and freed by rt_destroy.  `p` == NULL means rt_denoise_defaults.  Ordering, ragged contexts
+ * and refusals are rt_denoise_async's: behind everything both contexts have queued, their later work behind it.  Two kernels: rule 2's variance
+ * (into scratch that `a` owns), then ONE kernel that forms FA and FB together -- a workgroup per 32x8 pixels; A, B and Vh of the tile and its halo
+ * of R + P in LDS; rule 3's alpha * (Vh[p] + m) and 1e-10f + kk * (Vh[p] + Vh[q']) formed once and shared by both directions.
+ * Nothing else of either context changes: colour planes, seeds, pass numbers, packed pixels, counters, tile counts, selection, tile order and
+ * rt_last_kernel stay.  search_radius == 0 copies the halves (and packs them).
+ * A context's cross-filtered plane is CURRENT from this call until anything moves its colour plane: a launch, a reset, rt_seed_stream_async,
+ * rt_write_state / rt_load_state, a merge or rt_denoise_async into it.
+ * RT_ERR_ARG: a null context, a == b, contexts that differ in size or device, any multi-device or sharded context, parameters rt_denoise_async
+ * refuses.  RT_ERR_STATE: pass numbers that differ, or zero.  A refused call changes nothing.                                                    */
+RT_API int rt_denoise_pair_async(rt_ctx *a, rt_ctx *b, const rt_denoise_params *p, void *hip_stream);
+
+/* The same arithmetic on HOST planes of w x h pixels, as plain loops, FA into `out_a` and FB into `out_b`: what the device is tested against bit
+ * for bit.  The outputs may not overlap the inputs or each other.  Needs no device.  Refusals are rt_denoise_planes'.                          */
+RT_API int rt_denoise_pair_planes(float *out_a, float *out_b, const float *a, const float *b, int w, int h, const rt_denoise_params *p);
+
+/* The context's cross-filtered plane, 3 floats per pixel as rt_read_colors lays them out, into HOST memory.  Blocking.  RT_ERR_STATE when the
+ * plane is not current; RT_ERR_ARG for a null, multi-device or sharded context or a null buffer.                                               */
+RT_API int rt_read_filtered(rt_ctx *ctx, float *out_host);
+
+/* rt_compare_async / rt_compare over the two PACKED CROSS-FILTERED PLANES instead of the packed frames: the same kernel, the same exact integer
+ * metric, the same tile map in rt_compare_tiles' indexing.  Nothing is packed or refreshed and nothing of either context changes.
+ * RT_ERR_ARG as rt_compare, and for sharded contexts.  RT_ERR_STATE when either plane is not current or the two were not made by ONE
+ * rt_denoise_pair_async call.                                                                                                                  */
+RT_API int rt_compare_filtered_async(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, void *hip_stream);
+RT_API int rt_compare_filtered(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *tiles_host);
+
+/* rt_render_converged's loop and refusals with the check replaced: rt_denoise_pair_async(a, b, p) on a's stream, the comparison of the packed
+ * cross-filtered planes, a wait for the 48 bytes.  The target is then the estimated PSNR of the FILTERED merge.  The call merges and filters
+ * nothing: the caller goes on with rt_merge_async and rt_denoise_async, USING THE SAME PARAMETERS.  Besides that call's refusals, RT_ERR_ARG for
+ * sharded contexts and for parameters rt_denoise_async refuses; a check at pass 0 (max_passes == 0) is RT_ERR_STATE.                            */
+RT_API int rt_render_converged_filtered(rt_ctx *a, rt_ctx *b, double target_psnr_db, int passes_per_check, int max_passes,
+                                        const rt_denoise_params *p, rt_frame_error *last, int *checks);
+
+/* rt_render_adaptive with the tile map taken from the cross-filtered pair: the group rule, the front rule and `above` are unchanged, and one map
+ * selects on both contexts, so they stay in step tile for tile.  A tile then retires when the FILTERED tile is estimated to have reached
+ * tile_psnr_db; what is said above about a tile's figure being noisy, and about min_passes, holds as it stands.                               */
+RT_API int rt_render_adaptive_filtered(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
+                                       const rt_denoise_params *p, rt_frame_error *last, int *checks);
 
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it

@@ -24,7 +24,9 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_stream_seeds", "rt_seed_stream_async", "rt_write_state", "rt_save_state", "rt_load_state", "rt_merge_async",
            "rt_compare_tiles", "rt_compare_async", "rt_compare", "rt_error_psnr", "rt_render_converged",
            "rt_tile_passes", "rt_select_tiles", "rt_render_tiles_async", "rt_render_adaptive",
-           "rt_denoise_defaults", "rt_denoise_async", "rt_denoise_planes"]
+           "rt_denoise_defaults", "rt_denoise_async", "rt_denoise_planes",
+           "rt_denoise_pair_async", "rt_denoise_pair_planes", "rt_read_filtered", "rt_compare_filtered_async", "rt_compare_filtered",
+           "rt_render_converged_filtered", "rt_render_adaptive_filtered"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -150,6 +152,13 @@ def load_library(diag=False):
         "rt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
         "rt_denoise_async": (i32, [vp, vp, vp, C.POINTER(DenoiseParams), vp]),
         "rt_denoise_planes": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(DenoiseParams)]),
+        "rt_denoise_pair_async": (i32, [vp, vp, C.POINTER(DenoiseParams), vp]),
+        "rt_denoise_pair_planes": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(DenoiseParams)]),
+        "rt_read_filtered": (i32, [vp, vp]),
+        "rt_compare_filtered_async": (i32, [vp, vp, vp, vp, vp]),
+        "rt_compare_filtered": (i32, [vp, vp, C.POINTER(FrameError), vp]),
+        "rt_render_converged_filtered": (i32, [vp, vp, C.c_double, i32, i32, C.POINTER(DenoiseParams), C.POINTER(FrameError), C.POINTER(i32)]),
+        "rt_render_adaptive_filtered": (i32, [vp, vp, C.c_double, i32, i32, i32, C.POINTER(DenoiseParams), C.POINTER(FrameError), C.POINTER(i32)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -511,6 +520,53 @@ class RtContext:
         self._check(self._lib.rt_denoise_async(self._h, a._h if a is not None else None, b._h if b is not None else None,
                                                _denoise_params(params), C.c_void_p(stream or 0)))
 
+    # --- the error of the filtered frame (rt_denoise.hip, rt_compare.hip) ------------------------
+    def denoise_pair(self, other, params=None, stream=None):
+        """rt_denoise_pair_async: this context's colour plane filtered with weights from `other`'s and the reverse, each into a plane its
+        context owns beside the colour plane (read_filtered, compare_filtered).  `params` as for denoise()."""
+        self._check(self._lib.rt_denoise_pair_async(self._h, other._h if other is not None else None, _denoise_params(params), C.c_void_p(stream or 0)))
+
+    def read_filtered(self):
+        """rt_read_filtered: the cross-filtered plane, float32 [3 * w * h] as read_colors() lays it out."""
+        out = np.zeros(3 * self.w * self.h, np.float32)
+        self._check(self._lib.rt_read_filtered(self._h, _ptr(out)))
+        return out
+
+    def compare_filtered(self, other, tiles=False):
+        """rt_compare_filtered: compare() over the packed cross-filtered planes of one denoise_pair call."""
+        err = FrameError()
+        h_other = other._h if other is not None else None
+        if not tiles:
+            self._check(self._lib.rt_compare_filtered(self._h, h_other, C.byref(err), None))
+            return err.as_dict()
+        tmap = np.zeros(self.compare_tiles(), np.uint32)
+        self._check(self._lib.rt_compare_filtered(self._h, h_other, C.byref(err), _ptr(tmap)))
+        return err.as_dict(), tmap
+
+    def compare_filtered_async(self, other, result_ptr, tiles_ptr=None, stream=None):
+        """rt_compare_filtered_async: compare_async() over the packed cross-filtered planes."""
+        self._check(self._lib.rt_compare_filtered_async(self._h, other._h if other is not None else None, C.c_void_p(result_ptr or 0),
+                                                        C.c_void_p(tiles_ptr or 0), C.c_void_p(stream or 0)))
+
+    def render_converged_filtered(self, other, target_db, passes_per_check, max_passes, params=None):
+        """rt_render_converged_filtered: render_converged() with the cross-filtered pair's PSNR -- the estimate for the FILTERED merge -- as
+        the check.  Returns (reached, error dict of the last check, number of checks)."""
+        err, checks = FrameError(), C.c_int()
+        rc = self._lib.rt_render_converged_filtered(self._h, other._h if other is not None else None, target_db, passes_per_check, max_passes,
+                                                    _denoise_params(params), C.byref(err), C.byref(checks))
+        if rc < 0:
+            self._check(rc)
+        return rc == 1, err.as_dict(), checks.value
+
+    def render_adaptive_filtered(self, other, tile_db, min_passes, passes_per_check, max_passes, params=None):
+        """rt_render_adaptive_filtered: render_adaptive() with the tile map taken from the cross-filtered pair."""
+        err, checks = FrameError(), C.c_int()
+        rc = self._lib.rt_render_adaptive_filtered(self._h, other._h if other is not None else None, tile_db, min_passes, passes_per_check,
+                                                   max_passes, _denoise_params(params), C.byref(err), C.byref(checks))
+        if rc < 0:
+            self._check(rc)
+        return rc == 1, err.as_dict(), checks.value
+
     def stats(self):
         st = Stats()
         self._check(self._lib.rt_get_stats(self._h, C.byref(st)))
@@ -612,6 +668,17 @@ def denoise_planes(merged, a, b, w, h, params=None):
     out = np.zeros(3 * w * h, np.float32)
     _check(load_library().rt_denoise_planes(_ptr(out), _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), w, h, _denoise_params(params)))
     return out
+
+
+def denoise_pair_planes(a, b, w, h, params=None):
+    """rt_denoise_pair_planes: the two cross-filtered planes (FA, FB) of HOST planes, float32 [3 * w * h] each.  Needs no device."""
+    planes = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (a, b)]
+    for x in planes:
+        if x.size != 3 * w * h:
+            raise ValueError("expected %d floats, got %d" % (3 * w * h, x.size))
+    out_a, out_b = np.zeros(3 * w * h, np.float32), np.zeros(3 * w * h, np.float32)
+    _check(load_library().rt_denoise_pair_planes(_ptr(out_a), _ptr(out_b), _ptr(planes[0]), _ptr(planes[1]), w, h, _denoise_params(params)))
+    return out_a, out_b
 
 
 def error_psnr(err):

@@ -307,6 +307,8 @@ RT_API void rt_destroy(rt_ctx *c) {
         (void)hipFree(c->d_compare);
         (void)hipFree(c->d_denoise);
         (void)hipFree(c->d_denoise_var);
+        (void)hipFree(c->d_filtered);
+        (void)hipFree(c->d_filtered_px);
         (void)hipFree(c->tiles.d_passes);
         (void)hipFree(c->tiles.d_selected);
         (void)hipFree(c->tiles.d_list);

@@ -4,6 +4,8 @@
 //   rt_compare_tiles                the shape of that map
 //   rt_error_psnr                   the PSNR those sums stand for (host arithmetic, no device)
 //   rt_render_converged             two contexts rendered in step until the PSNR between them reaches a target
+//   rt_compare_filtered(_async)     the same metric and map over the packed cross-filtered planes of rt_denoise_pair_async (rt_denoise.hip)
+//   rt_render_converged_filtered    ... and the same loop (and rt_render_adaptive's, rt_tiles.hip's calls) with that figure as the check
 // The difference between two independent N-pass renders of one scene is the standard estimate of an N-pass render's noise.  The reference
 // has one seed stream and compares nothing: this is the library's own extension and reproduces no reference frame.
 // The render kernels are not touched: the call reads the buffers their launches write (after the pack kernel, if the pixel store was off).
@@ -16,6 +18,8 @@
 #include "rt_internal.h"
 
 using rt::fail;
+
+extern "C" int rt_host_denoise_params(const rt_denoise_params *p, rt_denoise_params *out);     // rt_host.cpp: the parameter rules (null = defaults)
 
 namespace rt {
 constexpr int kCmpLanes = 128;                  // a workgroup: two wavefronts
@@ -125,8 +129,11 @@ namespace {
 static_assert(sizeof(rt_frame_error) == 48, "rt_frame_error is 48 bytes, no padding");
 
 
+// What a comparison reads: the packed frames of the two contexts, or the packed cross-filtered planes rt_denoise_pair_async left beside them.
+enum class Of { Frames, FilteredPlanes };
+
 // the pair is checked: queue the comparison on `stream`, behind everything both contexts have queued, their later work behind it
-int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, hipStream_t stream) {
+int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, hipStream_t stream, Of what = Of::Frames) {
     int rc = select_device(a);
     if (rc != RT_OK) return rc;
     rc = chain(a, stream);
@@ -134,12 +141,15 @@ int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemsetAsync(result_dev, 0, sizeof(rt_frame_error), stream));     // the accumulators; the whole answer of a context without rows
     if (a->local_rows == 0) return RT_OK;
-    rc = refresh_pixels(a, stream);
-    if (rc == RT_OK) rc = refresh_pixels(b, stream);
-    if (rc != RT_OK) return rc;
+    if (what == Of::Frames) {
+        rc = refresh_pixels(a, stream);
+        if (rc == RT_OK) rc = refresh_pixels(b, stream);
+        if (rc != RT_OK) return rc;
+    }
+    const uint32_t *pa = what == Of::Frames ? frame_pixels(a) : a->d_filtered_px, *pb = what == Of::Frames ? frame_pixels(b) : b->d_filtered_px;
     const size_t items = (size_t)tile_row_count(a) * (size_t)((a->w + kCmpRun - 1) / kCmpRun);
     const size_t blocks = std::min(items, (size_t)a->n_cus * 8);
-    hipLaunchKernelGGL(rt_compare_kernel, dim3((unsigned)blocks), dim3(kCmpLanes), 0, stream, frame_pixels(a), frame_pixels(b), a->w, a->local_rows, reinterpret_cast<unsigned long long *>(result_dev), tiles_dev);
+    hipLaunchKernelGGL(rt_compare_kernel, dim3((unsigned)blocks), dim3(kCmpLanes), 0, stream, pa, pb, a->w, a->local_rows, reinterpret_cast<unsigned long long *>(result_dev), tiles_dev);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -152,14 +162,14 @@ int ensure_scratch(rt_ctx *a) {
 }
 
 // rt_compare: on a's own stream through a's scratch, then the wait
-int compare_blocking(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *tiles_host) {
+int compare_blocking(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *tiles_host, Of what = Of::Frames) {
     int rc = select_device(a);
     if (rc == RT_OK) rc = ensure_scratch(a);
     if (rc != RT_OK) return rc;
     rt_frame_error *res = static_cast<rt_frame_error *>(a->d_compare);
     uint32_t *tiles = reinterpret_cast<uint32_t *>(res + 1);
     const bool want_tiles = tiles_host && tile_count(a) > 0;
-    rc = compare_on(a, b, res, want_tiles ? tiles : nullptr, a->stream);
+    rc = compare_on(a, b, res, want_tiles ? tiles : nullptr, a->stream, what);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out_host, res, sizeof *res, hipMemcpyDeviceToHost, a->stream));
     if (want_tiles) HIP_TRY(hipMemcpyAsync(tiles_host, tiles, (size_t)tile_count(a) * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
@@ -182,6 +192,64 @@ int check_paired_render(const rt_ctx *a, const rt_ctx *b, const char *call, cons
     if (a->frame.ragged || b->frame.ragged)
         return fail(RT_ERR_STATE, "%s: the tiles of a context hold different pass counts after a subset launch (rt_reset makes the frame whole)", call);
     return RT_OK;
+}
+
+// the pair rt_compare_filtered* takes: one frame on one device, neither sharded, both planes current and made by one rt_denoise_pair_async call
+int check_filtered_pair(const rt_ctx *a, const rt_ctx *b, const char *call) {
+    int rc = same_frame(a, b, call, "a", "b");
+    if (rc == RT_OK) rc = tiles_refuse(a, call);
+    if (rc == RT_OK) rc = tiles_refuse(b, call);
+    if (rc != RT_OK) return rc;
+    if (!a->frame.filtered_with(b->frame))
+        return fail(RT_ERR_STATE, "%s: the cross-filtered planes are not current, or were not made by one rt_denoise_pair_async call (whatever moves a colour plane ends its plane)", call);
+    return RT_OK;
+}
+
+// What a check of the two paired loops compares.  filter == null: the packed frames, as they are.  Else: rt_denoise_pair_async with these
+// (checked) parameters on `stream` first, then its packed planes -- the estimate of the FILTERED frame's error.
+int check_on(rt_ctx *a, rt_ctx *b, const rt_denoise_params *filter, rt_frame_error *result_dev, uint32_t *tiles_dev, hipStream_t stream) {
+    if (!filter) return compare_on(a, b, result_dev, tiles_dev, stream);
+    int rc = denoise_pair_refuse(a, b, "rt_denoise_pair_async");
+    if (rc == RT_OK) rc = denoise_pair(a, b, *filter, stream);
+    if (rc == RT_OK) rc = compare_on(a, b, result_dev, tiles_dev, stream, Of::FilteredPlanes);
+    return rc;
+}
+
+// the filtered loops' own refusals, ahead of the shared ones: contexts the filter does not take, parameters it does not take (`q`: the checked copy)
+int check_filtered_loop(const rt_ctx *a, const rt_ctx *b, const char *call, const rt_denoise_params *p, rt_denoise_params *q) {
+    int rc = same_frame(a, b, call, "a", "b");
+    if (rc == RT_OK) rc = tiles_refuse(a, call);
+    if (rc == RT_OK) rc = tiles_refuse(b, call);
+    if (rc == RT_OK && rt_host_denoise_params(p, q) != RT_OK) rc = RT_ERR_ARG;
+    return rc;
+}
+
+// rt_render_converged and rt_render_converged_filtered: the loop, over what makes the figure
+int render_converged(rt_ctx *a, rt_ctx *b, const char *call, const rt_denoise_params *filter, double target_psnr_db, int passes_per_check, int max_passes,
+                     rt_frame_error *last, int *checks) {
+    int rc = same_frame(a, b, call, "a", "b");
+    if (rc == RT_OK) rc = check_paired_render(a, b, call, last, passes_per_check, target_psnr_db, max_passes);
+    if (rc == RT_OK) rc = select_device(a);
+    if (rc == RT_OK) rc = ensure_scratch(a);
+    if (rc != RT_OK) return rc;
+    if (checks) *checks = 0;
+    rt_frame_error *res = static_cast<rt_frame_error *>(a->d_compare);
+    for (int done = 0;; ++done) {
+        const int n = std::min(passes_per_check, max_passes - a->frame.current_sample);
+        if (n == 0 && done > 0) return 0;                       // max_passes reached: *last is the last check
+        if (n > 0) {
+            rc = rt_render_async(a, n, a->stream);
+            if (rc == RT_OK) rc = rt_render_async(b, n, b->stream);
+            if (rc != RT_OK) return rc;
+        }
+        rc = check_on(a, b, filter, res, nullptr, a->stream);
+        if (rc != RT_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(last, res, sizeof *res, hipMemcpyDeviceToHost, a->stream));
+        HIP_TRY(hipStreamSynchronize(a->stream));
+        if (checks) *checks = done + 1;
+        if (rt_error_psnr(last) >= target_psnr_db) return 1;
+        if (n == 0) return 0;                                   // no pass to render: one check of the frames as they are
+    }
 }
 
 }  // namespace
@@ -222,24 +290,29 @@ RT_API double rt_error_psnr(const rt_frame_error *e) {
 }
 
 RT_API int rt_render_converged(rt_ctx *a, rt_ctx *b, double target_psnr_db, int passes_per_check, int max_passes, rt_frame_error *last, int *checks) {
-    int rc = same_frame(a, b, "rt_render_converged", "a", "b");
-    if (rc == RT_OK) rc = check_paired_render(a, b, "rt_render_converged", last, passes_per_check, target_psnr_db, max_passes);
+    return render_converged(a, b, "rt_render_converged", nullptr, target_psnr_db, passes_per_check, max_passes, last, checks);
+}
+
+RT_API int rt_render_converged_filtered(rt_ctx *a, rt_ctx *b, double target_psnr_db, int passes_per_check, int max_passes, const rt_denoise_params *p,
+                                        rt_frame_error *last, int *checks) {
+    rt_denoise_params q;
+    const int rc = check_filtered_loop(a, b, "rt_render_converged_filtered", p, &q);
     if (rc != RT_OK) return rc;
-    if (checks) *checks = 0;
-    for (int done = 0;; ++done) {
-        const int n = std::min(passes_per_check, max_passes - a->frame.current_sample);
-        if (n == 0 && done > 0) return 0;                       // max_passes reached: *last is the last check
-        if (n > 0) {
-            rc = rt_render_async(a, n, a->stream);
-            if (rc == RT_OK) rc = rt_render_async(b, n, b->stream);
-            if (rc != RT_OK) return rc;
-        }
-        rc = compare_blocking(a, b, last, nullptr);
-        if (rc != RT_OK) return rc;
-        if (checks) *checks = done + 1;
-        if (rt_error_psnr(last) >= target_psnr_db) return 1;
-        if (n == 0) return 0;                                   // no pass to render: one check of the frames as they are
-    }
+    return render_converged(a, b, "rt_render_converged_filtered", &q, target_psnr_db, passes_per_check, max_passes, last, checks);
+}
+
+RT_API int rt_compare_filtered_async(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, void *hip_stream) {
+    int rc = check_filtered_pair(a, b, "rt_compare_filtered_async");
+    if (rc != RT_OK) return rc;
+    if (!result_dev) return fail(RT_ERR_ARG, "result_dev is null");
+    return compare_on(a, b, result_dev, tiles_dev, (hipStream_t)hip_stream, Of::FilteredPlanes);
+}
+
+RT_API int rt_compare_filtered(rt_ctx *a, rt_ctx *b, rt_frame_error *out_host, uint32_t *tiles_host) {
+    int rc = check_filtered_pair(a, b, "rt_compare_filtered");
+    if (rc != RT_OK) return rc;
+    if (!out_host) return fail(RT_ERR_ARG, "out_host is null");
+    return compare_blocking(a, b, out_host, tiles_host, Of::FilteredPlanes);
 }
 
 // the tile's squared error at which the PSNR over its 192 channel values equals `db`: floor(255^2 * 192 / 10^(db / 10)), kept inside 32 bits
@@ -248,14 +321,15 @@ static uint32_t tile_error_at(double db) {
     return v >= 4294967295.0 ? 0xffffffffu : (v > 0.0 ? (uint32_t)v : 0u);
 }
 
-RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes, rt_frame_error *last,
-                              int *checks) {
-    int rc = same_frame(a, b, "rt_render_adaptive", "a", "b");
-    if (rc == RT_OK) rc = tiles_refuse(a, "rt_render_adaptive");
-    if (rc == RT_OK) rc = tiles_refuse(b, "rt_render_adaptive");
+// rt_render_adaptive and rt_render_adaptive_filtered: the loop, over what makes the map
+static int render_adaptive(rt_ctx *a, rt_ctx *b, const char *call, const rt_denoise_params *filter, double tile_psnr_db, int min_passes, int passes_per_check,
+                           int max_passes, rt_frame_error *last, int *checks) {
+    int rc = same_frame(a, b, call, "a", "b");
+    if (rc == RT_OK) rc = tiles_refuse(a, call);
+    if (rc == RT_OK) rc = tiles_refuse(b, call);
     if (rc != RT_OK) return rc;
     if (min_passes < 0) return fail(RT_ERR_ARG, "min_passes %d", min_passes);      // (every refusal ahead of the pass counts' is RT_ERR_ARG: their order does not show)
-    rc = check_paired_render(a, b, "rt_render_adaptive", last, passes_per_check, tile_psnr_db, max_passes);
+    rc = check_paired_render(a, b, call, last, passes_per_check, tile_psnr_db, max_passes);
     if (rc != RT_OK) return rc;
     if (checks) *checks = 0;
     rc = select_device(a);
@@ -274,7 +348,7 @@ RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min
     rt_frame_error *res = static_cast<rt_frame_error *>(a->d_compare);
     uint32_t *map = reinterpret_cast<uint32_t *>(res + 1);
     for (int done = 0;; ++done) {
-        rc = compare_on(a, b, res, map, a->stream);
+        rc = check_on(a, b, filter, res, map, a->stream);
         if (rc != RT_OK) return rc;
         HIP_TRY(hipMemcpyAsync(last, res, sizeof *res, hipMemcpyDeviceToHost, a->stream));
         uint32_t counts_a[2] = { 0, 0 }, counts_b[2] = { 0, 0 };
@@ -283,7 +357,7 @@ RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min
         if (rc != RT_OK) return rc;
         if (checks) *checks = done + 1;
         if (counts_a[0] != counts_b[0] || counts_a[1] != counts_b[1])
-            return fail(RT_ERR_STATE, "rt_render_adaptive: the contexts selected %u and %u groups from one map (their tile pass counts differ)", counts_a[0], counts_b[0]);
+            return fail(RT_ERR_STATE, "%s: the contexts selected %u and %u groups from one map (their tile pass counts differ)", call, counts_a[0], counts_b[0]);
         if (counts_a[0] == 0) return 1;                         // every group has retired
         const int n = std::min(passes_per_check, max_passes - a->frame.current_sample);
         if (n == 0) return 0;                                   // max_passes reached with groups still above the target
@@ -291,6 +365,19 @@ RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min
         if (rc == RT_OK) rc = rt_render_tiles_async(b, n, b->stream);
         if (rc != RT_OK) return rc;
     }
+}
+
+RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes, rt_frame_error *last,
+                              int *checks) {
+    return render_adaptive(a, b, "rt_render_adaptive", nullptr, tile_psnr_db, min_passes, passes_per_check, max_passes, last, checks);
+}
+
+RT_API int rt_render_adaptive_filtered(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
+                                       const rt_denoise_params *p, rt_frame_error *last, int *checks) {
+    rt_denoise_params q;
+    const int rc = check_filtered_loop(a, b, "rt_render_adaptive_filtered", p, &q);
+    if (rc != RT_OK) return rc;
+    return render_adaptive(a, b, "rt_render_adaptive_filtered", &q, tile_psnr_db, min_passes, passes_per_check, max_passes, last, checks);
 }
 
 }  // extern "C"

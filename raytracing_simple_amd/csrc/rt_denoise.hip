@@ -3,6 +3,10 @@
 //   rt_denoise_async         dst's colour plane filtered on the device, the colour planes of a and b as the variance estimate
 // and the two kernels behind it.  rt_denoise_planes (rt_host.cpp) is the same arithmetic as plain loops; the header states it as rules 1-6, and the
 // comments below name the rule a line implements.  The reference filters nothing: this is the library's own extension.
+// "The error of the filtered frame" of the same header lives here too --
+//   rt_denoise_pair_async    each half filtered with weights taken from the OTHER half, into planes of their own beside the colour planes
+//   rt_read_filtered         that plane of one context
+// and one kernel that forms both planes together (rt_denoise_pair_planes is its host statement).  rt_compare.hip compares the packed planes.
 // The render kernels are not touched, and nothing here reads or writes anything but colour planes.
 // This unit is compiled with -ffp-contract=off: every multiply, add and IEEE division below is an operation of its own, in the written order.
 #include <hip/hip_runtime.h>
@@ -11,6 +15,9 @@
 #include <cfloat>
 #include <cmath>
 
+#include <atomic>
+
+#include "rt_detmath.h"
 #include "rt_internal.h"
 
 using rt::fail;
@@ -156,6 +163,157 @@ __global__ void __launch_bounds__(kDnLanes) rt_denoise_kernel(float *__restrict_
     out[at + 2] = num2 / den;
 }
 
+namespace {
+
+// .cl:34, the pack kernel's toInt (rt_trace.inc.h to_int): parity's restated powf, or fast mode's exp2 / log2 with the fused multiply-add that
+// unit's contraction makes of g * 255 + .5 (this unit contracts nothing, so it is written out)
+__device__ __forceinline__ uint32_t dn_to_int(float v, bool fast) {
+    const float c = fminf(fmaxf(v, 0.f), 1.f);
+    if (fast) return (uint32_t)(int)__builtin_fmaf(rt::fm_powf(c, 1.f / 2.2f), 255.f, .5f);
+    return (uint32_t)(int)(rt::dm_powf(c, 1.f / 2.2f) * 255.f + .5f);
+}
+
+__device__ __forceinline__ bool dn_finite3(float a, float b, float c) { return fabsf(a) <= FLT_MAX && fabsf(b) <= FLT_MAX && fabsf(c) <= FLT_MAX; }
+
+}  // namespace
+
+// The cross-filtered halves: FA = A filtered with weights from B, FB = B with weights from A, rules 3 to 6 with the header's three substitutions,
+// both in one pass.  The shape is rt_denoise_kernel's -- a workgroup per 32x8 pixels, H = R + P, one barrier per offset -- with
+//   LDS: NINE planes (A, B and Vh = Vs + Vs, three channels each) of LW x LH floats, then FOUR buffers of EW x EH floats: e(., o) of guide A and of
+//   guide B, each twice, so that offset n + 1 writes the other pair while slower lanes still read this one (as the two buffers there).
+//   (9 * 52 * 28 + 4 * 36 * 12) * 4 = 59 328 bytes at R 8, P 2: below 64 KiB, no attribute call.
+//   Rule 3's alpha * (Vh[p] + m) and 1e-10f + kk * (Vh[p] + Vh[q']) are formed once per position and offset and serve both directions; t, the
+//   square and the division are per direction.
+// The index arithmetic and its bounds are that kernel's, line for line: every coordinate that indexes LDS or a plane is clamped to the image first,
+// and a clamped coordinate lies inside the staged window.  The packed words go to the pixel buffer's row (row 0 = bottom: plane row h - 1 - y).
+template <int P>
+__global__ void __launch_bounds__(kDnLanes) rt_denoise_pair_kernel(float *__restrict__ out_a, float *__restrict__ out_b, uint32_t *__restrict__ px_a,
+                                                                   uint32_t *__restrict__ px_b, const float *__restrict__ a, const float *__restrict__ b,
+                                                                   const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, int fast_a,
+                                                                   int fast_b) {
+    extern __shared__ float dn_lds[];
+    constexpr int EW = kDnTileW + 2 * P, EH = kDnTileH + 2 * P, EN = EW * EH;
+    const int H = R + P, LW = kDnTileW + 2 * H, LH = kDnTileH + 2 * H, LN = LW * LH;
+    float *const sA = dn_lds, *const sB = dn_lds + 3 * LN, *const sV = dn_lds + 6 * LN, *const sE = dn_lds + 9 * LN;
+    const int tid = (int)threadIdx.x, x0 = (int)blockIdx.x * kDnTileW, y0 = (int)blockIdx.y * kDnTileH;
+    const int wx0 = x0 - H, wy0 = y0 - H;
+
+    for (int l = tid; l < LN; l += kDnLanes) {
+        const int ly = l / LW, lx = l - ly * LW;
+        const size_t at = 3 * ((size_t)dn_clamp(wy0 + ly, h) * (size_t)w + (size_t)dn_clamp(wx0 + lx, w));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = vs[at + c];
+            sA[c * LN + l] = a[at + c];
+            sB[c * LN + l] = b[at + c];
+            sV[c * LN + l] = v + v;                         // Vh: the variance of one half
+        }
+    }
+    __syncthreads();
+
+    int ex[2], ey[2];
+    float pa[2][3], pb[2][3], pv[2][3];
+    bool have[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        have[s] = tid + s * kDnLanes < EN;
+        const int idx = have[s] ? tid + s * kDnLanes : 0, iy = idx / EW, ix = idx - iy * EW;
+        ex[s] = dn_clamp(x0 - P + ix, w);
+        ey[s] = dn_clamp(y0 - P + iy, h);
+        const int l = (ey[s] - wy0) * LW + (ex[s] - wx0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            pa[s][c] = sA[c * LN + l];
+            pb[s][c] = sB[c * LN + l];
+            pv[s][c] = sV[c * LN + l];
+        }
+    }
+
+    const int tx = tid & (kDnTileW - 1), ty = tid / kDnTileW, px = x0 + tx, py = y0 + ty;
+    const bool inside = px < w && py < h;
+    const float inv = 1.0f / (float)(3 * (2 * P + 1) * (2 * P + 1));
+    float na0 = 0.0f, na1 = 0.0f, na2 = 0.0f, da = 0.0f, nb0 = 0.0f, nb1 = 0.0f, nb2 = 0.0f, db = 0.0f;
+    int buf = 0;
+    for (int oy = -R; oy <= R; ++oy)
+        for (int ox = -R; ox <= R; ++ox) {
+            const bool centre = oy == 0 && ox == 0;
+            float *const e_ga = sE + (2 * buf) * EN, *const e_gb = e_ga + EN;      // e(., o) of guide A (it weights FB), of guide B (it weights FA)
+            if (!centre) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    if (!have[s]) continue;
+                    const int l = (dn_clamp(ey[s] + oy, h) - wy0) * LW + (dn_clamp(ex[s] + ox, w) - wx0);    // q' = cl(x + o)
+                    float d_ga[3], d_gb[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {           // rule 3, G = A and G = B
+                        const float qv = sV[c * LN + l];
+                        const float m = qv < pv[s][c] ? qv : pv[s][c];
+                        const float off = alpha * (pv[s][c] + m), dnm = 1e-10f + kk * (pv[s][c] + qv);
+                        const float t_a = pa[s][c] - sA[c * LN + l], t_b = pb[s][c] - sB[c * LN + l];
+                        d_ga[c] = (t_a * t_a - off) / dnm;
+                        d_gb[c] = (t_b * t_b - off) / dnm;
+                    }
+                    e_ga[tid + s * kDnLanes] = (d_ga[0] + d_ga[1]) + d_ga[2];
+                    e_gb[tid + s * kDnLanes] = (d_gb[0] + d_gb[1]) + d_gb[2];
+                }
+            }
+            __syncthreads();
+            buf ^= 1;
+            const int qx = px + ox, qy = py + oy;
+            if (inside && qx >= 0 && qx < w && qy >= 0 && qy < h) {   // rule 5: p + o outside the image is skipped
+                const int l = (qy - wy0) * LW + (qx - wx0);
+                const float a0 = sA[l], a1 = sA[LN + l], a2 = sA[2 * LN + l], b0 = sB[l], b1 = sB[LN + l], b2 = sB[2 * LN + l];
+                float w_a = 1.0f, w_b = 1.0f;               // the weight FA's sum takes (from guide B), FB's (from guide A)
+                bool take_a = true, take_b = true;
+                if (!centre) {
+                    float s_ga = 0.f, s_gb = 0.f;           // rule 4
+#pragma unroll
+                    for (int dy = 0; dy <= 2 * P; ++dy)
+#pragma unroll
+                        for (int dx = 0; dx <= 2 * P; ++dx) {
+                            const float v_ga = e_ga[(ty + dy) * EW + tx + dx], v_gb = e_gb[(ty + dy) * EW + tx + dx];
+                            s_ga = (dy == 0 && dx == 0) ? v_ga : s_ga + v_ga;
+                            s_gb = (dy == 0 && dx == 0) ? v_gb : s_gb + v_gb;
+                        }
+                    const float t_ga = s_ga * inv, t_gb = s_gb * inv;
+                    take_a = t_gb == t_gb && dn_finite3(a0, a1, a2);
+                    take_b = t_ga == t_ga && dn_finite3(b0, b1, b2);
+                    const float g_a = t_gb > 0.f ? t_gb : 0.f, g_b = t_ga > 0.f ? t_ga : 0.f;
+                    w_a = 1.0f / (1.0f + g_a * (1.0f + g_a * 0.5f));
+                    w_b = 1.0f / (1.0f + g_b * (1.0f + g_b * 0.5f));
+                }
+                if (take_a) {                               // rule 6
+                    na0 = na0 + w_a * a0;
+                    na1 = na1 + w_a * a1;
+                    na2 = na2 + w_a * a2;
+                    da = da + w_a;
+                }
+                if (take_b) {
+                    nb0 = nb0 + w_b * b0;
+                    nb1 = nb1 + w_b * b1;
+                    nb2 = nb2 + w_b * b2;
+                    db = db + w_b;
+                }
+            }
+        }
+    if (!inside) return;
+    float fa0 = na0 / da, fa1 = na1 / da, fa2 = na2 / da, fb0 = nb0 / db, fb1 = nb1 / db, fb2 = nb2 / db;
+    if (R == 0) {                                           // the window is the pixel itself: the halves, bit for bit
+        const int l = (py - wy0) * LW + (px - wx0);
+        fa0 = sA[l], fa1 = sA[LN + l], fa2 = sA[2 * LN + l];
+        fb0 = sB[l], fb1 = sB[LN + l], fb2 = sB[2 * LN + l];
+    }
+    const size_t at = 3 * ((size_t)py * (size_t)w + (size_t)px), word = (size_t)(h - 1 - py) * (size_t)w + (size_t)px;
+    out_a[at] = fa0;
+    out_a[at + 1] = fa1;
+    out_a[at + 2] = fa2;
+    out_b[at] = fb0;
+    out_b[at + 1] = fb1;
+    out_b[at + 2] = fb2;
+    px_a[word] = dn_to_int(fa0, fast_a != 0) | (dn_to_int(fa1, fast_a != 0) << 8) | (dn_to_int(fa2, fast_a != 0) << 16);
+    px_b[word] = dn_to_int(fb0, fast_b != 0) | (dn_to_int(fb1, fast_b != 0) << 8) | (dn_to_int(fb2, fast_b != 0) << 16);
+}
+
 using namespace rt;
 
 namespace {
@@ -178,6 +336,71 @@ int check_three(const rt_ctx *dst, const rt_ctx *a, const rt_ctx *b) {
 }
 
 }  // namespace
+
+namespace {
+
+std::atomic<uint64_t> g_pair_calls{0};                     // numbers the rt_denoise_pair_async calls of the process (FrameState::filtered_pair)
+
+size_t denoise_pair_lds_bytes(int R, int P) {
+    const int H = R + P;
+    return ((size_t)9 * (kDnTileW + 2 * H) * (kDnTileH + 2 * H) + (size_t)4 * (kDnTileW + 2 * P) * (kDnTileH + 2 * P)) * sizeof(float);
+}
+
+bool packs_fast(const rt_ctx *c) { return c->mode == RT_MODE_FAST || c->mode >= 200; }     // which pack kernel refresh_pixels launches (rt_api.hip)
+
+}  // namespace
+
+namespace rt {
+
+int denoise_pair_refuse(const rt_ctx *a, const rt_ctx *b, const char *call) {
+    if (!a || !b) return fail(RT_ERR_ARG, "%s: ctx is null", call);
+    int rc = tiles_refuse(a, call);
+    if (rc == RT_OK) rc = tiles_refuse(b, call);
+    if (rc == RT_OK) rc = same_frame(a, b, call, "the first half", "the second half", false);
+    if (rc != RT_OK) return rc;
+    if (a->frame.current_sample != b->frame.current_sample)
+        return fail(RT_ERR_STATE, "%s: the halves hold %d and %d passes", call, a->frame.current_sample, b->frame.current_sample);
+    if (a->frame.current_sample <= 0) return fail(RT_ERR_STATE, "%s: the halves hold no pass", call);
+    return RT_OK;
+}
+
+int denoise_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream) {
+    int rc = select_device(a);
+    if (rc != RT_OK) return rc;
+    const size_t n_floats = color_floats(a), n_words = image_pixels(a);
+    for (rt_ctx *c : { a, b }) {
+        if (!c->d_filtered) HIP_TRY(hipMalloc(&c->d_filtered, n_floats * sizeof(float)));
+        if (!c->d_filtered_px) HIP_TRY(hipMalloc(&c->d_filtered_px, n_words * sizeof(uint32_t)));
+    }
+    if (!a->d_denoise_var) HIP_TRY(hipMalloc(&a->d_denoise_var, n_floats * sizeof(float)));
+    // behind everything the two contexts have queued; their later work behind the filter
+    rc = chain(a, stream);
+    if (rc == RT_OK) rc = chain(b, stream);
+    if (rc != RT_OK) return rc;
+    hipLaunchKernelGGL(rt_denoise_variance_kernel, dim3((unsigned)((3 * (size_t)a->w + 255) / 256), (unsigned)std::min(a->h, 65535)), dim3(256), 0, stream,
+                       a->d_denoise_var, a->d_colors, b->d_colors, a->w, a->h);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid((unsigned)((a->w + kDnTileW - 1) / kDnTileW), (unsigned)((a->h + kDnTileH - 1) / kDnTileH));
+    const size_t lds = denoise_pair_lds_bytes(q.search_radius, q.patch_radius);
+    const float kk = q.k * q.k;
+    const int fast_a = packs_fast(a), fast_b = packs_fast(b);
+#define RT_PAIR_LAUNCH(P)                                                                                                                                     \
+    hipLaunchKernelGGL(rt_denoise_pair_kernel<P>, grid, dim3(kDnLanes), lds, stream, a->d_filtered, b->d_filtered, a->d_filtered_px, b->d_filtered_px,          \
+                       a->d_colors, b->d_colors, a->d_denoise_var, a->w, a->h, q.search_radius, q.alpha, kk, fast_a, fast_b)
+    switch (q.patch_radius) {
+    case 0: RT_PAIR_LAUNCH(0); break;
+    case 1: RT_PAIR_LAUNCH(1); break;
+    default: RT_PAIR_LAUNCH(2); break;
+    }
+#undef RT_PAIR_LAUNCH
+    HIP_TRY(hipGetLastError());
+    const uint64_t call = g_pair_calls.fetch_add(1) + 1;
+    a->frame.pair_filtered(call);
+    b->frame.pair_filtered(call);
+    return RT_OK;
+}
+
+}  // namespace rt
 
 extern "C" {
 
@@ -219,6 +442,23 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
     std::swap(dst->d_colors, dst->d_denoise);               // the filtered plane IS the colour plane now; the old one is the next call's scratch
     dst->frame.colours_replaced();                          // rt_read_pixels packs the filtered plane
     return RT_OK;
+}
+
+RT_API int rt_denoise_pair_async(rt_ctx *a, rt_ctx *b, const rt_denoise_params *p, void *hip_stream) {
+    int rc = denoise_pair_refuse(a, b, "rt_denoise_pair_async");
+    if (rc != RT_OK) return rc;
+    rt_denoise_params q;
+    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
+    return denoise_pair(a, b, q, (hipStream_t)hip_stream);
+}
+
+RT_API int rt_read_filtered(rt_ctx *c, float *out_host) {
+    int rc = tiles_refuse(c, "rt_read_filtered");
+    if (rc != RT_OK) return rc;
+    if (!out_host) return fail(RT_ERR_ARG, "rt_read_filtered: out_host is null");
+    if (c->frame.filtered_pair == 0)
+        return fail(RT_ERR_STATE, "rt_read_filtered: the context holds no current cross-filtered plane (rt_denoise_pair_async makes one; whatever moves the colour plane ends it)");
+    return read_back(c, out_host, c->d_filtered, color_floats(c) * sizeof(float));
 }
 
 }  // extern "C"

@@ -26,10 +26,15 @@ struct FrameState {
     uint64_t list_serial = 0;
     uint32_t list_tiles = 0;            // launch tiles of the instance's shape
     uint32_t list_slots = 0;            // entries: the launch's grid.x * grid.y
+    // The error of the filtered frame (rt_denoise.hip rt_denoise_pair_async): the call that made this context's cross-filtered plane, numbered per
+    // process from 1 and shared by the two contexts of that call; 0 while the plane is stale -- never made, or the colour plane has moved since
+    uint64_t filtered_pair = 0;
 
     // at pass 0 the next launch would read the default stream (nothing but a custom stream or a written state puts another one there)
     bool on_default_stream() const { return seeds_default || !seeds_custom; }
     bool list_is_stale(bool by_order, uint32_t tiles) const { return !list_valid || list_serial != selection_serial || list_tiles != tiles || list_by_order != by_order; }
+    // the cross-filtered planes of this context and of `other` are current and were made by one rt_denoise_pair_async call
+    bool filtered_with(const FrameState &other) const { return filtered_pair != 0 && filtered_pair == other.filtered_pair; }
 
     // ---- resets and written states: a whole frame at one pass number again ----
     // rt_reset: the restore kernel copies the default stream into d_seeds and clears the pixels
@@ -61,16 +66,19 @@ struct FrameState {
     }
 
     // ---- the colour plane written by something else than a launch: rt_read_pixels packs it ----
-    void merged(int total) { current_sample = total; have_selection = false; pixels_current = false; }     // (a selection was made at another pass number)
+    void merged(int total) { current_sample = total; have_selection = false; pixels_current = false; filtered_pair = 0; }     // (a selection was made at another pass number)
     void merged_by_tile(int total) { merged(total); ragged = true; list_valid = false; }                    // every tile by its own weights: dst's front has moved
-    void colours_replaced() { pixels_current = false; }         // rt_denoise_async
+    void colours_replaced() { pixels_current = false; filtered_pair = 0; }     // rt_denoise_async
     void pixels_packed() { pixels_current = true; }             // refresh_pixels
+    // rt_denoise_pair_async: the cross-filtered plane beside the colour plane is current, until anything moves the colour plane (a launch, a reset,
+    // a written state, a merge or a filter into it); nothing else of the frame changes
+    void pair_filtered(uint64_t call) { filtered_pair = call; }
 
 private:
     // every tile holds `pass` passes; a selection does not outlive that, and the launch count starts again
-    void restart(int pass) { current_sample = pass; launches = 0; last_ms = 0.0; ragged = have_selection = list_valid = false; }
+    void restart(int pass) { current_sample = pass; launches = 0; last_ms = 0.0; ragged = have_selection = list_valid = false; filtered_pair = 0; }
     // a launch has written every seed pair it renders: the default stream is no longer read in place
-    void advance(int n_samples) { current_sample += n_samples; launches += 1; seeds_default = false; }
+    void advance(int n_samples) { current_sample += n_samples; launches += 1; seeds_default = false; filtered_pair = 0; }
 };
 
 }  // namespace rt

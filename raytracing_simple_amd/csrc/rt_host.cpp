@@ -226,17 +226,16 @@ int rt_host_denoise_params(const rt_denoise_params *p, rt_denoise_params *out) {
     return RT_OK;
 }
 
-int rt_denoise_planes(float *out, const float *merged, const float *a, const float *b, int w, int h, const rt_denoise_params *p) {
-    if (!out || !merged || !a || !b) return host_fail("rt_denoise_planes: null plane");
-    if (w < 1 || h < 1) return host_fail("rt_denoise_planes: %dx%d", w, h);
-    rt_denoise_params q;
-    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
-    const int R = q.search_radius, P = q.patch_radius;
-    const float alpha = q.alpha, kk = q.k * q.k, inv = 1.0f / (float)(3 * (2 * P + 1) * (2 * P + 1));
-    const auto cl = [](int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); };
+}  // extern "C"
+
+namespace {
+
+inline int dn_cl(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
+
+// rules 1 and 2: the variance of the mean of the two halves, smoothed over 3x3, clamped
+std::vector<float> smoothed_variance(const float *a, const float *b, int w, int h) {
     const auto at = [w](int y, int x) { return 3 * ((size_t)y * (size_t)w + (size_t)x); };
     const size_t px = (size_t)w * (size_t)h;
-    // 1. the variance of the mean of the two halves; 2. smoothed over 3x3, clamped
     std::vector<float> V(3 * px), Vs(3 * px);
     for (size_t i = 0; i < 3 * px; ++i) {
         const float d = (a[i] - b[i]) * 0.5f;
@@ -248,17 +247,28 @@ int rt_denoise_planes(float *out, const float *merged, const float *a, const flo
                 float sum = 0.f;
                 for (int j = -1; j <= 1; ++j)
                     for (int i = -1; i <= 1; ++i) {
-                        const float v = V[at(cl(y + j, h), cl(x + i, w)) + c];
+                        const float v = V[at(dn_cl(y + j, h), dn_cl(x + i, w)) + c];
                         sum = (j == -1 && i == -1) ? v : sum + v;
                     }
                 Vs[at(y, x) + c] = sum * (1.0f / 9.0f);
             }
+    return Vs;
+}
+
+// rules 3 to 6 with the image and the guide apart: the weights come from `guide` (rule 3's t) and the variance plane `var`, the values that are
+// tested (rule 5) and averaged (rule 6) from `img`.  rt_denoise_planes: img == guide == the merged frame, var = Vs.  rt_denoise_pair_planes: img
+// one half, guide the other, var = Vh
+void nlm_planes(float *out, const float *img, const float *guide, const std::vector<float> &var, int w, int h, const rt_denoise_params &q) {
+    const int R = q.search_radius, P = q.patch_radius;
+    const float alpha = q.alpha, kk = q.k * q.k, inv = 1.0f / (float)(3 * (2 * P + 1) * (2 * P + 1));
+    const auto at = [w](int y, int x) { return 3 * ((size_t)y * (size_t)w + (size_t)x); };
+    const size_t px = (size_t)w * (size_t)h;
     std::vector<float> num(3 * px, 0.0f), den(px, 0.0f), e(px);
     for (int oy = -R; oy <= R; ++oy)
         for (int ox = -R; ox <= R; ++ox) {
             if (oy == 0 && ox == 0) {                        // 5. the pixel itself: weight 1, whatever it holds
                 for (size_t i = 0; i < px; ++i) {
-                    for (int c = 0; c < 3; ++c) num[3 * i + c] = num[3 * i + c] + 1.0f * merged[3 * i + c];
+                    for (int c = 0; c < 3; ++c) num[3 * i + c] = num[3 * i + c] + 1.0f * img[3 * i + c];
                     den[i] = den[i] + 1.0f;
                 }
                 continue;
@@ -266,11 +276,11 @@ int rt_denoise_planes(float *out, const float *merged, const float *a, const flo
             // 3. e(x, o) for every pixel x: it depends on x and o only, so one evaluation serves every patch that covers x
             for (int y = 0; y < h; ++y)
                 for (int x = 0; x < w; ++x) {
-                    const size_t ip = at(y, x), iq = at(cl(y + oy, h), cl(x + ox, w));
+                    const size_t ip = at(y, x), iq = at(dn_cl(y + oy, h), dn_cl(x + ox, w));
                     float d[3];
                     for (int c = 0; c < 3; ++c) {
-                        const float t = merged[ip + c] - merged[iq + c];
-                        const float vp = Vs[ip + c], vq = Vs[iq + c];
+                        const float t = guide[ip + c] - guide[iq + c];
+                        const float vp = var[ip + c], vq = var[iq + c];
                         const float m = vq < vp ? vq : vp;
                         d[c] = (t * t - alpha * (vp + m)) / (1e-10f + kk * (vp + vq));
                     }
@@ -283,11 +293,11 @@ int rt_denoise_planes(float *out, const float *merged, const float *a, const flo
                     float S = 0.f;                                            // 4. the patch sum, at clamped positions
                     for (int dy = -P; dy <= P; ++dy)
                         for (int dx = -P; dx <= P; ++dx) {
-                            const float v = e[(size_t)cl(y + dy, h) * w + cl(x + dx, w)];
+                            const float v = e[(size_t)dn_cl(y + dy, h) * w + dn_cl(x + dx, w)];
                             S = (dy == -P && dx == -P) ? v : S + v;
                         }
                     const float T = S * inv;
-                    const float *dq = merged + at(qy, qx);
+                    const float *dq = img + at(qy, qx);
                     if (std::isnan(T) || !std::isfinite(dq[0]) || !std::isfinite(dq[1]) || !std::isfinite(dq[2])) continue;
                     const float g = T > 0.f ? T : 0.f;
                     const float wgt = 1.0f / (1.0f + g * (1.0f + g * 0.5f));
@@ -298,6 +308,38 @@ int rt_denoise_planes(float *out, const float *merged, const float *a, const flo
         }
     for (size_t i = 0; i < px; ++i)                                           // 6.
         for (int c = 0; c < 3; ++c) out[3 * i + c] = num[3 * i + c] / den[i];
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_denoise_planes(float *out, const float *merged, const float *a, const float *b, int w, int h, const rt_denoise_params *p) {
+    if (!out || !merged || !a || !b) return host_fail("rt_denoise_planes: null plane");
+    if (w < 1 || h < 1) return host_fail("rt_denoise_planes: %dx%d", w, h);
+    rt_denoise_params q;
+    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
+    nlm_planes(out, merged, merged, smoothed_variance(a, b, w, h), w, h, q);
+    return RT_OK;
+}
+
+// ---- rt_denoise_pair_planes: the cross-filtered halves of include/rt_api.h ("the error of the filtered frame"), as plain loops ----
+// rt_denoise_pair_async runs the same arithmetic on the device (rt_denoise.hip) and is tested against this function bit for bit.
+int rt_denoise_pair_planes(float *out_a, float *out_b, const float *a, const float *b, int w, int h, const rt_denoise_params *p) {
+    if (!out_a || !out_b || !a || !b) return host_fail("rt_denoise_pair_planes: null plane");
+    if (w < 1 || h < 1) return host_fail("rt_denoise_pair_planes: %dx%d", w, h);
+    rt_denoise_params q;
+    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
+    const size_t n = 3 * (size_t)w * (size_t)h;
+    if (q.search_radius == 0) {                              // the window is the pixel itself: the halves, bit for bit
+        memcpy(out_a, a, n * sizeof(float));
+        memcpy(out_b, b, n * sizeof(float));
+        return RT_OK;
+    }
+    std::vector<float> Vh = smoothed_variance(a, b, w, h);
+    for (size_t i = 0; i < n; ++i) Vh[i] = Vh[i] + Vh[i];    // the variance of ONE half: twice that of the mean
+    nlm_planes(out_a, a, b, Vh, w, h, q);                    // FA: A's values, weights from B
+    nlm_planes(out_b, b, a, Vh, w, h, q);                    // FB: B's values, weights from A
     return RT_OK;
 }
 

@@ -90,7 +90,10 @@ struct rt_ctx {
     rt::FrameState frame;               // what the progressive frame currently is: pass number, seed stream, packed pixels, launch count, tile bookkeeping
     rt::TileSubset tiles;               // adaptive sampling (rt_tiles.hip): a pass count per 8x8 tile, the selected groups, the launch list of a subset launch
     float *d_denoise = nullptr;         // rt_denoise_async (rt_denoise.hip): the plane the filter writes, EXCHANGED with d_colors after every call; allocated on first use
-    float *d_denoise_var = nullptr;     // ... and the smoothed variance plane it is steered by
+    float *d_denoise_var = nullptr;     // ... and the smoothed variance plane it is steered by (rt_denoise_pair_async: the first context's, for both halves)
+    float *d_filtered = nullptr;        // rt_denoise_pair_async: this half filtered with the other half's weights, a plane like d_colors; allocated on first use.
+                                        // Whether it is current is frame.filtered_pair
+    uint32_t *d_filtered_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom): what rt_compare_filtered reads
     void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; allocated on first use)
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters
@@ -246,6 +249,10 @@ int upload_spheres(rt_ctx *c, uint32_t first, uint32_t count, const rt_sphere *s
 hipError_t prepare_bvh_build();
 int build_bvh(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload = false);
 int render_shard(rt_ctx *c, int n_samples, bool may_block);      // rt_launch.hip: one shard's launch on its own stream
+
+// ---- rt_denoise.hip: the cross-filtered halves, for the paired loops of rt_compare.hip ----
+int denoise_pair_refuse(const rt_ctx *a, const rt_ctx *b, const char *call);     // the contexts rt_denoise_pair_async does not take, and pass numbers that differ or are zero
+int denoise_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream);    // a checked pair, checked parameters: the planes made on `stream`, both marked current
 
 // ---- rt_tiles.hip: the subset launch's device side ----
 int tiles_refuse(const rt_ctx *c, const char *call);                  // RT_ERR_ARG for the contexts the adaptive calls do not take (null, multi-device, sharded)

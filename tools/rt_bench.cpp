@@ -5,7 +5,7 @@
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
 //            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]
-//             [--denoise [--denoise-radius R]]]
+//             [--denoise [--denoise-radius R]] [--filtered]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -23,6 +23,9 @@
 //   --denoise           with --until-psnr: the halves are merged into a THIRD context, that frame is filtered (rt_denoise_async: non-local
 //                       means steered by the difference of the halves) and --out is written from it; --denoise-radius R sets the search
 //                       radius (0 .. 8, default 5).  A further line gives the parameters and the call's wall time (queue, kernels, pack, read-back)
+//   --filtered          with --until-psnr: DB is the target for the FILTERED merge.  The check is the PSNR between the two cross-filtered halves
+//                       (rt_render_converged_filtered; with --adaptive per tile, rt_render_adaptive_filtered) -- an estimate of the filtered
+//                       frame's quality, not a bound -- and the halves are then merged and filtered as by --denoise, with the same parameters
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
@@ -73,6 +76,7 @@ int main(int argc, char** argv) {
     bool adaptive = false;      // --until-psnr per 8x8 tile: rt_render_adaptive instead of rt_render_converged
     int min_passes = 16;
     bool denoise = false;       // --until-psnr: merge into a third context and filter it (rt_denoise_async)
+    bool filtered = false;      // --until-psnr judged on the cross-filtered halves: the *_filtered loops, then merge and filter
     rt_denoise_params dn;
     rt_denoise_defaults(&dn);
     std::vector<const char*> pos;
@@ -100,6 +104,7 @@ int main(int argc, char** argv) {
         else if (a == "--min-passes") min_passes = atoi(next());
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-radius") dn.search_radius = atoi(next());
+        else if (a == "--filtered") filtered = denoise = true;
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -157,9 +162,11 @@ int main(int argc, char** argv) {
         rt_frame_error err{};
         int checks = 0;
         const auto t0 = std::chrono::steady_clock::now();
-        const int reached = adaptive ? rt_render_adaptive(half[0], half[1], until_psnr, min_passes, check_every, spp, &err, &checks)
-                                     : rt_render_converged(half[0], half[1], until_psnr, check_every, spp, &err, &checks);
-        if (reached < 0) return die(adaptive ? "rt_render_adaptive" : "rt_render_converged");
+        const int reached = filtered ? (adaptive ? rt_render_adaptive_filtered(half[0], half[1], until_psnr, min_passes, check_every, spp, &dn, &err, &checks)
+                                                 : rt_render_converged_filtered(half[0], half[1], until_psnr, check_every, spp, &dn, &err, &checks))
+                                     : (adaptive ? rt_render_adaptive(half[0], half[1], until_psnr, min_passes, check_every, spp, &err, &checks)
+                                                 : rt_render_converged(half[0], half[1], until_psnr, check_every, spp, &err, &checks));
+        if (reached < 0) return die(adaptive ? "rt_render_adaptive(_filtered)" : "rt_render_converged(_filtered)");
         const int per_half = rt_current_sample(half[0]);
         // adaptive: what was rendered against what whole frames to that pass number would have been, and the sample map
         rt_stats st_half[2];
@@ -191,8 +198,9 @@ int main(int argc, char** argv) {
         const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (!out.empty() && !write_ppm(out, merged, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
         printf("{\"spheres\": %u, \"w\": %d, \"h\": %d, \"until_psnr\": %.3f, \"reached\": %s, \"passes_per_half\": %d, \"merged_passes\": %d, "
-               "\"checks\": %d, \"check_every\": %d, \"pair_psnr_db\": %.3f, \"differing\": %llu, \"max_abs\": %u, \"wall_ms\": %.4f}\n",
-               n, w, h, until_psnr, reached ? "true" : "false", per_half, rt_current_sample(frame), checks, check_every, rt_error_psnr(&err),
+               "\"checks\": %d, \"check_every\": %d, \"%s\": %.3f, \"differing\": %llu, \"max_abs\": %u, \"wall_ms\": %.4f}\n",
+               n, w, h, until_psnr, reached ? "true" : "false", per_half, rt_current_sample(frame), checks, check_every,
+               filtered ? "cross_filtered_pair_psnr_db" : "pair_psnr_db", rt_error_psnr(&err),
                (unsigned long long)err.differing, err.max_abs, wall_ms);
         if (adaptive)
             printf("{\"adaptive\": true, \"min_passes\": %d, \"checks\": %d, \"samples_rendered\": %llu, \"samples_of_whole_frames\": %llu, "
