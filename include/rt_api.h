@@ -589,6 +589,33 @@ RT_API int rt_denoise_planes(float *out, const float *merged, const float *a, co
  * refuses.  RT_ERR_STATE: pass numbers that differ, or zero.  A refused call changes nothing.                                                    */
 RT_API int rt_denoise_pair_async(rt_ctx *a, rt_ctx *b, const rt_denoise_params *p, void *hip_stream);
 
+/* rt_denoise_pair_async for the groups of the CURRENT SELECTION alone (adaptive sampling's groups of 32x8 pixels; rt_select_tiles): the float and the
+ * packed cross-filtered planes of the selected groups are formed again from the two colour planes as they are now, by rules 7-9 and the same packing,
+ * and every other pixel of the four planes keeps the words it held.  A pixel of a selected group receives exactly what rt_denoise_pair_async would
+ * write there now -- rt_denoise_pair_planes of the two current colour planes at that pixel.  What the call is for: after rt_render_tiles_async only the
+ * selected groups' colours have moved, and a group that was left out is never selected again (the front rule), so a check that only steers the next
+ * selection need not filter it again.  A RETIRED GROUP'S FILTERED VALUES ARE THEN THOSE OF ITS LAST CHECK, formed with its neighbours' colours of that
+ * time; they are not what rt_denoise_pair_async would write now.
+ * Three kernels on `hip_stream`, ordered as rt_denoise_pair_async's: one workgroup that compacts a's selection flags into the list of selected groups
+ * in ascending order (once per selection), rule 2's variance for the whole frame (it is bandwidth-bound and small beside the filter), and the pair
+ * kernel's body with ONE WORKGROUP PER SELECTED GROUP, its origin taken from the list: the grid is the selection, not the frame.  search_radius == 0
+ * copies and packs the halves of the selected groups.  `p` need not equal the parameters the planes were made with; a plane then holds both.
+ * THE KERNEL READS a's SELECTION FLAGS.  That b's selection is the same set of groups is the caller's responsibility, as in rt_render_adaptive (one map
+ * selects on both contexts); only the counts are compared.
+ * Accepted when every precondition of rt_denoise_pair_async holds, both contexts hold a selection with equal counts, and both contexts' cross-filtered
+ * planes are in the same one of two states:
+ *   (a) current, and made by one pair call: there is nothing to refresh; RT_OK, nothing is launched and nothing changes;
+ *   (b) ONE SELECTION BEHIND: they were current and made by one pair call (rt_denoise_pair_async or this one), and since then nothing has moved either
+ *       colour plane but rt_render_tiles_async of the selection still in hand, once or several times.
+ * Anything else leaves the planes stale for this call as for every other: a whole-frame launch, a reset, rt_seed_stream_async, a written or loaded
+ * state, a merge or rt_denoise_async into the context, a new rt_select_tiles, planes never made, or the two contexts behind different pair calls.
+ * Afterwards both planes are current under a new pair id that the two contexts share: rt_read_filtered and rt_compare_filtered* accept them.  Nothing
+ * else of either context changes.
+ * RT_ERR_ARG: as rt_denoise_pair_async.  RT_ERR_STATE: pass numbers that differ or are zero; no selection on either context; selections of different
+ * counts; planes in neither state (a) nor (b).  A refused call changes nothing.
+ * tools/live_check_probe.py times the call against rt_denoise_pair_async (profiles/r15_live_checks.jsonl); no time is promised.                      */
+RT_API int rt_denoise_pair_tiles_async(rt_ctx *a, rt_ctx *b, const rt_denoise_params *p, void *hip_stream);
+
 /* The same arithmetic on HOST planes of w x h pixels, as plain loops, FA into `out_a` and FB into `out_b`: what the device is tested against bit
  * for bit.  The outputs may not overlap the inputs or each other.  Needs no device.  Refusals are rt_denoise_planes'.                          */
 RT_API int rt_denoise_pair_planes(float *out_a, float *out_b, const float *a, const float *b, int w, int h, const rt_denoise_params *p);
@@ -616,6 +643,18 @@ RT_API int rt_render_converged_filtered(rt_ctx *a, rt_ctx *b, double target_psnr
  * tile_psnr_db; what is said above about a tile's figure being noisy, and about min_passes, holds as it stands.                               */
 RT_API int rt_render_adaptive_filtered(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
                                        const rt_denoise_params *p, rt_frame_error *last, int *checks);
+
+/* rt_render_adaptive_filtered with checks that filter only what is still rendering: the first check is the whole-frame rt_denoise_pair_async, every
+ * later one rt_denoise_pair_tiles_async of the selection that was just rendered; each is followed by the unchanged comparison of the whole packed planes
+ * and rt_select_tiles on both contexts.  Arguments and refusals are rt_render_adaptive_filtered's.
+ * THE SAME RENDER: the return value, *checks, rt_tile_passes, the colour planes, seeds and packed pixels of both contexts and rt_get_stats equal
+ * rt_render_adaptive_filtered's with the same arguments, bit for bit -- a live group's filtered values depend on the current colour planes alone, and a
+ * retired group's entry of the map is never read again.
+ * WHAT DIFFERS: *last, and the retired groups' part of the cross-filtered planes.  Both hold, for every group, the figures of THAT GROUP'S LAST CHECK: a
+ * retired group's filtered values were formed with its neighbours' colours of that time, and *last sums them as they stand.  As before, the figure is an
+ * estimate, not a bound.  The planes are current on return, as after rt_render_adaptive_filtered.                                                  */
+RT_API int rt_render_adaptive_filtered_tiles(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
+                                             const rt_denoise_params *p, rt_frame_error *last, int *checks);
 
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it

@@ -26,7 +26,7 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_tile_passes", "rt_select_tiles", "rt_render_tiles_async", "rt_render_adaptive",
            "rt_denoise_defaults", "rt_denoise_async", "rt_denoise_planes",
            "rt_denoise_pair_async", "rt_denoise_pair_planes", "rt_read_filtered", "rt_compare_filtered_async", "rt_compare_filtered",
-           "rt_render_converged_filtered", "rt_render_adaptive_filtered"]
+           "rt_render_converged_filtered", "rt_render_adaptive_filtered", "rt_denoise_pair_tiles_async", "rt_render_adaptive_filtered_tiles"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -159,6 +159,8 @@ def load_library(diag=False):
         "rt_compare_filtered": (i32, [vp, vp, C.POINTER(FrameError), vp]),
         "rt_render_converged_filtered": (i32, [vp, vp, C.c_double, i32, i32, C.POINTER(DenoiseParams), C.POINTER(FrameError), C.POINTER(i32)]),
         "rt_render_adaptive_filtered": (i32, [vp, vp, C.c_double, i32, i32, i32, C.POINTER(DenoiseParams), C.POINTER(FrameError), C.POINTER(i32)]),
+        "rt_denoise_pair_tiles_async": (i32, [vp, vp, C.POINTER(DenoiseParams), vp]),
+        "rt_render_adaptive_filtered_tiles": (i32, [vp, vp, C.c_double, i32, i32, i32, C.POINTER(DenoiseParams), C.POINTER(FrameError), C.POINTER(i32)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -526,6 +528,11 @@ class RtContext:
         context owns beside the colour plane (read_filtered, compare_filtered).  `params` as for denoise()."""
         self._check(self._lib.rt_denoise_pair_async(self._h, other._h if other is not None else None, _denoise_params(params), C.c_void_p(stream or 0)))
 
+    def denoise_pair_tiles(self, other, params=None, stream=None):
+        """rt_denoise_pair_tiles_async: denoise_pair() for the groups of the current selection alone -- the planes of the groups that
+        render_tiles_async has just rendered made current again, every other pixel kept."""
+        self._check(self._lib.rt_denoise_pair_tiles_async(self._h, other._h if other is not None else None, _denoise_params(params), C.c_void_p(stream or 0)))
+
     def read_filtered(self):
         """rt_read_filtered: the cross-filtered plane, float32 [3 * w * h] as read_colors() lays it out."""
         out = np.zeros(3 * self.w * self.h, np.float32)
@@ -563,6 +570,16 @@ class RtContext:
         err, checks = FrameError(), C.c_int()
         rc = self._lib.rt_render_adaptive_filtered(self._h, other._h if other is not None else None, tile_db, min_passes, passes_per_check,
                                                    max_passes, _denoise_params(params), C.byref(err), C.byref(checks))
+        if rc < 0:
+            self._check(rc)
+        return rc == 1, err.as_dict(), checks.value
+
+    def render_adaptive_filtered_tiles(self, other, tile_db, min_passes, passes_per_check, max_passes, params=None):
+        """rt_render_adaptive_filtered_tiles: render_adaptive_filtered() whose checks after the first filter only the groups that were just
+        rendered.  The same render bit for bit; the error dict sums every group's figure of its own last check."""
+        err, checks = FrameError(), C.c_int()
+        rc = self._lib.rt_render_adaptive_filtered_tiles(self._h, other._h if other is not None else None, tile_db, min_passes, passes_per_check,
+                                                         max_passes, _denoise_params(params), C.byref(err), C.byref(checks))
         if rc < 0:
             self._check(rc)
         return rc == 1, err.as_dict(), checks.value

@@ -312,6 +312,7 @@ RT_API void rt_destroy(rt_ctx *c) {
         (void)hipFree(c->tiles.d_passes);
         (void)hipFree(c->tiles.d_selected);
         (void)hipFree(c->tiles.d_list);
+        (void)hipFree(c->tiles.d_groups);
         (void)hipFree(c->order.d_tile_cost);
         (void)hipFree(c->order.d_order);
         (void)hipFree(c->d_timelog);

@@ -6,6 +6,7 @@
 //   rt_render_converged             two contexts rendered in step until the PSNR between them reaches a target
 //   rt_compare_filtered(_async)     the same metric and map over the packed cross-filtered planes of rt_denoise_pair_async (rt_denoise.hip)
 //   rt_render_converged_filtered    ... and the same loop (and rt_render_adaptive's, rt_tiles.hip's calls) with that figure as the check
+//   rt_render_adaptive_filtered_tiles   ... the adaptive one with every check after the first filtering only the groups that were just rendered
 // The difference between two independent N-pass renders of one scene is the standard estimate of an N-pass render's noise.  The reference
 // has one seed stream and compares nothing: this is the library's own extension and reproduces no reference frame.
 // The render kernels are not touched: the call reads the buffers their launches write (after the pack kernel, if the pixel store was off).
@@ -206,11 +207,14 @@ int check_filtered_pair(const rt_ctx *a, const rt_ctx *b, const char *call) {
 }
 
 // What a check of the two paired loops compares.  filter == null: the packed frames, as they are.  Else: rt_denoise_pair_async with these
-// (checked) parameters on `stream` first, then its packed planes -- the estimate of the FILTERED frame's error.
-int check_on(rt_ctx *a, rt_ctx *b, const rt_denoise_params *filter, rt_frame_error *result_dev, uint32_t *tiles_dev, hipStream_t stream) {
+// (checked) parameters on `stream` first, then its packed planes -- the estimate of the FILTERED frame's error.  `rendered_only`: not that call but
+// rt_denoise_pair_tiles_async -- the planes of the groups the selection in hand has just rendered, the other groups' as their last check left them.
+int check_on(rt_ctx *a, rt_ctx *b, const rt_denoise_params *filter, rt_frame_error *result_dev, uint32_t *tiles_dev, hipStream_t stream,
+             bool rendered_only = false) {
     if (!filter) return compare_on(a, b, result_dev, tiles_dev, stream);
-    int rc = denoise_pair_refuse(a, b, "rt_denoise_pair_async");
-    if (rc == RT_OK) rc = denoise_pair(a, b, *filter, stream);
+    const char *call = rendered_only ? "rt_denoise_pair_tiles_async" : "rt_denoise_pair_async";
+    int rc = denoise_pair_refuse(a, b, call);
+    if (rc == RT_OK) rc = rendered_only ? denoise_pair_tiles(a, b, *filter, stream, call) : denoise_pair(a, b, *filter, stream);
     if (rc == RT_OK) rc = compare_on(a, b, result_dev, tiles_dev, stream, Of::FilteredPlanes);
     return rc;
 }
@@ -321,9 +325,11 @@ static uint32_t tile_error_at(double db) {
     return v >= 4294967295.0 ? 0xffffffffu : (v > 0.0 ? (uint32_t)v : 0u);
 }
 
-// rt_render_adaptive and rt_render_adaptive_filtered: the loop, over what makes the map
-static int render_adaptive(rt_ctx *a, rt_ctx *b, const char *call, const rt_denoise_params *filter, double tile_psnr_db, int min_passes, int passes_per_check,
-                           int max_passes, rt_frame_error *last, int *checks) {
+// rt_render_adaptive, rt_render_adaptive_filtered and rt_render_adaptive_filtered_tiles: the loop, over what makes the map.  `live_checks`: every check
+// after the first filters the groups that were just rendered and no others (a retired group is never selected again, so its entry of the map is never
+// read again; a live group's planes depend on the colour planes alone)
+static int render_adaptive(rt_ctx *a, rt_ctx *b, const char *call, const rt_denoise_params *filter, bool live_checks, double tile_psnr_db, int min_passes,
+                           int passes_per_check, int max_passes, rt_frame_error *last, int *checks) {
     int rc = same_frame(a, b, call, "a", "b");
     if (rc == RT_OK) rc = tiles_refuse(a, call);
     if (rc == RT_OK) rc = tiles_refuse(b, call);
@@ -348,7 +354,7 @@ static int render_adaptive(rt_ctx *a, rt_ctx *b, const char *call, const rt_deno
     rt_frame_error *res = static_cast<rt_frame_error *>(a->d_compare);
     uint32_t *map = reinterpret_cast<uint32_t *>(res + 1);
     for (int done = 0;; ++done) {
-        rc = check_on(a, b, filter, res, map, a->stream);
+        rc = check_on(a, b, filter, res, map, a->stream, live_checks && done > 0);
         if (rc != RT_OK) return rc;
         HIP_TRY(hipMemcpyAsync(last, res, sizeof *res, hipMemcpyDeviceToHost, a->stream));
         uint32_t counts_a[2] = { 0, 0 }, counts_b[2] = { 0, 0 };
@@ -369,7 +375,7 @@ static int render_adaptive(rt_ctx *a, rt_ctx *b, const char *call, const rt_deno
 
 RT_API int rt_render_adaptive(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes, rt_frame_error *last,
                               int *checks) {
-    return render_adaptive(a, b, "rt_render_adaptive", nullptr, tile_psnr_db, min_passes, passes_per_check, max_passes, last, checks);
+    return render_adaptive(a, b, "rt_render_adaptive", nullptr, false, tile_psnr_db, min_passes, passes_per_check, max_passes, last, checks);
 }
 
 RT_API int rt_render_adaptive_filtered(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
@@ -377,7 +383,16 @@ RT_API int rt_render_adaptive_filtered(rt_ctx *a, rt_ctx *b, double tile_psnr_db
     rt_denoise_params q;
     const int rc = check_filtered_loop(a, b, "rt_render_adaptive_filtered", p, &q);
     if (rc != RT_OK) return rc;
-    return render_adaptive(a, b, "rt_render_adaptive_filtered", &q, tile_psnr_db, min_passes, passes_per_check, max_passes, last, checks);
+    return render_adaptive(a, b, "rt_render_adaptive_filtered", &q, false, tile_psnr_db, min_passes, passes_per_check, max_passes, last, checks);
+}
+
+RT_API int rt_render_adaptive_filtered_tiles(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
+                                             const rt_denoise_params *p, rt_frame_error *last, int *checks) {
+    rt_denoise_params q;
+    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;     // (ahead of the contexts: RT_ERR_ARG either way, and this one needs no context)
+    const int rc = check_filtered_loop(a, b, "rt_render_adaptive_filtered_tiles", p, &q);
+    if (rc != RT_OK) return rc;
+    return render_adaptive(a, b, "rt_render_adaptive_filtered_tiles", &q, true, tile_psnr_db, min_passes, passes_per_check, max_passes, last, checks);
 }
 
 }  // extern "C"

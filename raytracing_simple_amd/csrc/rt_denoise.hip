@@ -5,8 +5,10 @@
 // comments below name the rule a line implements.  The reference filters nothing: this is the library's own extension.
 // "The error of the filtered frame" of the same header lives here too --
 //   rt_denoise_pair_async    each half filtered with weights taken from the OTHER half, into planes of their own beside the colour planes
+//   rt_denoise_pair_tiles_async   ... of the groups in the current selection alone (adaptive sampling's groups: rt_tiles.hip), the rest kept
 //   rt_read_filtered         that plane of one context
-// and one kernel that forms both planes together (rt_denoise_pair_planes is its host statement).  rt_compare.hip compares the packed planes.
+// and one kernel body that forms both planes together, instantiated over the frame and over a list of groups (rt_denoise_pair_planes is its host
+// statement).  rt_compare.hip compares the packed planes.
 // The render kernels are not touched, and nothing here reads or writes anything but colour planes.
 // This unit is compiled with -ffp-contract=off: every multiply, add and IEEE division below is an operation of its own, in the written order.
 #include <hip/hip_runtime.h>
@@ -186,16 +188,19 @@ __device__ __forceinline__ bool dn_finite3(float a, float b, float c) { return f
 //   square and the division are per direction.
 // The index arithmetic and its bounds are that kernel's, line for line: every coordinate that indexes LDS or a plane is clamped to the image first,
 // and a clamped coordinate lies inside the staged window.  The packed words go to the pixel buffer's row (row 0 = bottom: plane row h - 1 - y).
-template <int P>
-__global__ void __launch_bounds__(kDnLanes) rt_denoise_pair_kernel(float *__restrict__ out_a, float *__restrict__ out_b, uint32_t *__restrict__ px_a,
-                                                                   uint32_t *__restrict__ px_b, const float *__restrict__ a, const float *__restrict__ b,
-                                                                   const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, int fast_a,
-                                                                   int fast_b) {
-    extern __shared__ float dn_lds[];
+// The body takes the workgroup's origin (x0, y0) in the plane from its kernel.  kAnyRow: y0 may be NEGATIVE, -7 at the least, and y0 + 7 >= 0 -- the
+// top group row of an image whose height is no multiple of 8 (rt_denoise_pair_tiles_kernel below).  The bounds hold as they stand: the 32x8 pixels
+// still hold an image pixel, so positions clamp into [max(0, y0 - P), min(h - 1, y0 + 7 + P)] and their partners within R of that, all inside the
+// window's rows [y0 - H, y0 + 7 + H] cut to the image; what is added is that a lane above the plane's row 0 is outside the image and stores nothing.
+template <int P, bool kAnyRow>
+__device__ __forceinline__ void dn_pair_body(float *dn_lds, const int x0, const int y0, float *__restrict__ out_a, float *__restrict__ out_b,
+                                             uint32_t *__restrict__ px_a, uint32_t *__restrict__ px_b, const float *__restrict__ a,
+                                             const float *__restrict__ b, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk,
+                                             int fast_a, int fast_b) {
     constexpr int EW = kDnTileW + 2 * P, EH = kDnTileH + 2 * P, EN = EW * EH;
     const int H = R + P, LW = kDnTileW + 2 * H, LH = kDnTileH + 2 * H, LN = LW * LH;
     float *const sA = dn_lds, *const sB = dn_lds + 3 * LN, *const sV = dn_lds + 6 * LN, *const sE = dn_lds + 9 * LN;
-    const int tid = (int)threadIdx.x, x0 = (int)blockIdx.x * kDnTileW, y0 = (int)blockIdx.y * kDnTileH;
+    const int tid = (int)threadIdx.x;
     const int wx0 = x0 - H, wy0 = y0 - H;
 
     for (int l = tid; l < LN; l += kDnLanes) {
@@ -230,7 +235,7 @@ __global__ void __launch_bounds__(kDnLanes) rt_denoise_pair_kernel(float *__rest
     }
 
     const int tx = tid & (kDnTileW - 1), ty = tid / kDnTileW, px = x0 + tx, py = y0 + ty;
-    const bool inside = px < w && py < h;
+    const bool inside = px < w && py < h && (!kAnyRow || py >= 0);
     const float inv = 1.0f / (float)(3 * (2 * P + 1) * (2 * P + 1));
     float na0 = 0.0f, na1 = 0.0f, na2 = 0.0f, da = 0.0f, nb0 = 0.0f, nb1 = 0.0f, nb2 = 0.0f, db = 0.0f;
     int buf = 0;
@@ -312,6 +317,62 @@ __global__ void __launch_bounds__(kDnLanes) rt_denoise_pair_kernel(float *__rest
     out_b[at + 2] = fb2;
     px_a[word] = dn_to_int(fa0, fast_a != 0) | (dn_to_int(fa1, fast_a != 0) << 8) | (dn_to_int(fa2, fast_a != 0) << 16);
     px_b[word] = dn_to_int(fb0, fast_b != 0) | (dn_to_int(fb1, fast_b != 0) << 8) | (dn_to_int(fb2, fast_b != 0) << 16);
+}
+
+// ... over the frame: the plane tiled from its row 0, a workgroup per 32x8 pixels
+template <int P>
+__global__ void __launch_bounds__(kDnLanes) rt_denoise_pair_kernel(float *__restrict__ out_a, float *__restrict__ out_b, uint32_t *__restrict__ px_a,
+                                                                   uint32_t *__restrict__ px_b, const float *__restrict__ a, const float *__restrict__ b,
+                                                                   const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, int fast_a,
+                                                                   int fast_b) {
+    extern __shared__ float dn_lds[];
+    dn_pair_body<P, false>(dn_lds, (int)blockIdx.x * kDnTileW, (int)blockIdx.y * kDnTileH, out_a, out_b, px_a, px_b, a, b, vs, w, h, R, alpha, kk, fast_a,
+                           fast_b);
+}
+
+// ... over the groups of a selection (rt_tiles.hip): workgroup i takes group list[i] -- g = gy * groups_x + gx in the PIXEL BUFFER's tile rows, row 0 at
+// the bottom -- and covers its pixel rows 8 gy .. 8 gy + 7, which are the plane's rows h - 8 (gy + 1) .. h - 1 - 8 gy: the origin is negative for the
+// top, partial, group row.  Every other pixel of the four output planes keeps its words.  A list entry that names no group is skipped by the whole
+// workgroup, ahead of the first barrier.
+template <int P>
+__global__ void __launch_bounds__(kDnLanes) rt_denoise_pair_tiles_kernel(float *__restrict__ out_a, float *__restrict__ out_b, uint32_t *__restrict__ px_a,
+                                                                         uint32_t *__restrict__ px_b, const float *__restrict__ a,
+                                                                         const float *__restrict__ b, const float *__restrict__ vs, int w, int h, int R,
+                                                                         float alpha, float kk, int fast_a, int fast_b, const uint32_t *__restrict__ list,
+                                                                         uint32_t groups_x, uint32_t n_groups) {
+    extern __shared__ float dn_lds[];
+    const uint32_t g = list[blockIdx.x];
+    if (g >= n_groups) return;
+    const uint32_t gy = g / groups_x, gx = g - gy * groups_x;
+    dn_pair_body<P, true>(dn_lds, (int)gx * kDnTileW, h - kDnTileH * ((int)gy + 1), out_a, out_b, px_a, px_b, a, b, vs, w, h, R, alpha, kk, fast_a, fast_b);
+}
+
+// The groups of a selection as a list: the indices g with selected[g] != 0 in ascending order -- a stable compaction by ONE workgroup, chunk by chunk,
+// as rt_tile_list_kernel builds the render's tile list (rt_tiles.hip): wave ballot + mbcnt inside the wavefront, the sixteen wave totals through LDS,
+// a running base.  Entries from the count up to `slots` get the sentinel n (no group).
+__global__ void __launch_bounds__(1024) rt_group_list_kernel(const uint32_t *__restrict__ selected, uint32_t n, uint32_t *__restrict__ list, uint32_t slots) {
+    __shared__ uint32_t s_wave[16];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    uint32_t base = 0;                                      // (the same in every lane)
+    for (uint32_t first = 0; first < n; first += 1024u) {
+        const uint32_t g = first + tid;
+        const bool keep = g < n && selected[g] != 0u;
+        const unsigned long long mask = __ballot(keep);
+        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if ((tid & 63u) == 0u) s_wave[wave] = (uint32_t)__popcll(mask);
+        __syncthreads();
+        uint32_t at = base, total = 0;
+#pragma unroll
+        for (uint32_t v = 0; v < 16u; ++v) {
+            const uint32_t c_ = s_wave[v];
+            at += v < wave ? c_ : 0u;
+            total += c_;
+        }
+        if (keep && at + before < slots) list[at + before] = g;
+        base += total;
+        __syncthreads();                                    // (s_wave is written again by the next chunk)
+    }
+    for (uint32_t k = base + tid; k < slots; k += 1024u) list[k] = n;
 }
 
 using namespace rt;
@@ -400,6 +461,55 @@ int denoise_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t s
     return RT_OK;
 }
 
+// The pair kernel over the groups `a` has selected.  Rule 2's plane is formed for the whole frame: it is bandwidth-bound and small beside the filter, and
+// the selected groups' halos reach into groups that are not selected.  The list of groups is built once per selection (FrameState::group_list_built).
+int denoise_pair_tiles(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream, const char *call) {
+    const FrameState &fa = a->frame, &fb = b->frame;
+    if (!fa.have_selection || !fb.have_selection) return fail(RT_ERR_STATE, "%s: no selection (rt_select_tiles on both contexts comes first)", call);
+    if (fa.counts[0] != fb.counts[0] || fa.counts[1] != fb.counts[1])
+        return fail(RT_ERR_STATE, "%s: the contexts hold selections of %u and %u groups", call, fa.counts[0], fb.counts[0]);
+    if (fa.filtered_with(fb)) return RT_OK;                 // nothing has moved a colour plane since the planes were made
+    if (!fa.filtered_behind_with(fb))
+        return fail(RT_ERR_STATE, "%s: the cross-filtered planes are not one selection behind -- they were never made, were made by different calls, or something "
+                                  "else than rt_render_tiles_async of the selection in hand has moved a colour plane since (rt_denoise_pair_async makes them whole)", call);
+    if (!a->d_filtered || !b->d_filtered || !a->d_filtered_px || !b->d_filtered_px || !a->d_denoise_var || !a->tiles.d_selected)
+        return fail(RT_ERR_STATE, "%s: a plane that the frame record calls made does not exist", call);
+    int rc = select_device(a);
+    if (rc != RT_OK) return rc;
+    const uint32_t n_groups = group_count(a), m = fa.counts[0];
+    if (m == 0 || m > n_groups) return fail(RT_ERR_STATE, "%s: a selection of %u of %u groups has been rendered", call, m, n_groups);
+    if (!a->tiles.d_groups) HIP_TRY(hipMalloc(&a->tiles.d_groups, (size_t)n_groups * sizeof(uint32_t)));
+    rc = chain(a, stream);
+    if (rc == RT_OK) rc = chain(b, stream);
+    if (rc != RT_OK) return rc;
+    if (fa.group_list_is_stale()) {
+        hipLaunchKernelGGL(rt_group_list_kernel, dim3(1), dim3(1024), 0, stream, a->tiles.d_selected, n_groups, a->tiles.d_groups, n_groups);
+        HIP_TRY(hipGetLastError());
+        a->frame.group_list_built();
+    }
+    hipLaunchKernelGGL(rt_denoise_variance_kernel, dim3((unsigned)((3 * (size_t)a->w + 255) / 256), (unsigned)std::min(a->h, 65535)), dim3(256), 0, stream,
+                       a->d_denoise_var, a->d_colors, b->d_colors, a->w, a->h);
+    HIP_TRY(hipGetLastError());
+    const size_t lds = denoise_pair_lds_bytes(q.search_radius, q.patch_radius);
+    const float kk = q.k * q.k;
+    const int fast_a = packs_fast(a), fast_b = packs_fast(b);
+#define RT_PAIR_TILES_LAUNCH(P)                                                                                                                               \
+    hipLaunchKernelGGL(rt_denoise_pair_tiles_kernel<P>, dim3(m), dim3(kDnLanes), lds, stream, a->d_filtered, b->d_filtered, a->d_filtered_px,                  \
+                       b->d_filtered_px, a->d_colors, b->d_colors, a->d_denoise_var, a->w, a->h, q.search_radius, q.alpha, kk, fast_a, fast_b,                  \
+                       a->tiles.d_groups, groups_per_row(a), n_groups)
+    switch (q.patch_radius) {
+    case 0: RT_PAIR_TILES_LAUNCH(0); break;
+    case 1: RT_PAIR_TILES_LAUNCH(1); break;
+    default: RT_PAIR_TILES_LAUNCH(2); break;
+    }
+#undef RT_PAIR_TILES_LAUNCH
+    HIP_TRY(hipGetLastError());
+    const uint64_t id = g_pair_calls.fetch_add(1) + 1;
+    a->frame.pair_tiles_refreshed(id);
+    b->frame.pair_tiles_refreshed(id);
+    return RT_OK;
+}
+
 }  // namespace rt
 
 extern "C" {
@@ -450,6 +560,14 @@ RT_API int rt_denoise_pair_async(rt_ctx *a, rt_ctx *b, const rt_denoise_params *
     rt_denoise_params q;
     if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
     return denoise_pair(a, b, q, (hipStream_t)hip_stream);
+}
+
+RT_API int rt_denoise_pair_tiles_async(rt_ctx *a, rt_ctx *b, const rt_denoise_params *p, void *hip_stream) {
+    int rc = denoise_pair_refuse(a, b, "rt_denoise_pair_tiles_async");
+    if (rc != RT_OK) return rc;
+    rt_denoise_params q;
+    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
+    return denoise_pair_tiles(a, b, q, (hipStream_t)hip_stream, "rt_denoise_pair_tiles_async");
 }
 
 RT_API int rt_read_filtered(rt_ctx *c, float *out_host) {

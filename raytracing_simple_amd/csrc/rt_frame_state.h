@@ -29,12 +29,22 @@ struct FrameState {
     // The error of the filtered frame (rt_denoise.hip rt_denoise_pair_async): the call that made this context's cross-filtered plane, numbered per
     // process from 1 and shared by the two contexts of that call; 0 while the plane is stale -- never made, or the colour plane has moved since
     uint64_t filtered_pair = 0;
+    // ... and, while the plane is stale for ONE reason only -- subset launches of the selection still in hand have moved the colour plane of the
+    // selected groups -- the call it was current under: what rt_denoise_pair_tiles_async refreshes from.  0 otherwise
+    uint64_t filtered_behind = 0;
+    // the compacted list of selected groups that call's kernel walks (TileSubset::d_groups): the selection it was built from, 0 = none
+    uint64_t group_list_serial = 0;
 
     // at pass 0 the next launch would read the default stream (nothing but a custom stream or a written state puts another one there)
     bool on_default_stream() const { return seeds_default || !seeds_custom; }
     bool list_is_stale(bool by_order, uint32_t tiles) const { return !list_valid || list_serial != selection_serial || list_tiles != tiles || list_by_order != by_order; }
     // the cross-filtered planes of this context and of `other` are current and were made by one rt_denoise_pair_async call
     bool filtered_with(const FrameState &other) const { return filtered_pair != 0 && filtered_pair == other.filtered_pair; }
+    // ... were so, and nothing but subset launches of the selections both still hold has moved either colour plane since
+    bool filtered_behind_with(const FrameState &other) const {
+        return filtered_behind != 0 && filtered_behind == other.filtered_behind && have_selection && other.have_selection;
+    }
+    bool group_list_is_stale() const { return group_list_serial == 0 || group_list_serial != selection_serial; }
 
     // ---- resets and written states: a whole frame at one pass number again ----
     // rt_reset: the restore kernel copies the default stream into d_seeds and clears the pixels
@@ -47,9 +57,11 @@ struct FrameState {
     void debug_reset_by_copy() { current_sample = 0; seeds_default = seeds_custom = false; }    // the round-1 reset (rt_debug.hip): seeds and pass, nothing else
 
     // ---- launches ----
-    void launched(int n_samples, bool pixel_store) { advance(n_samples); pixels_current = pixel_store; }    // a whole-frame launch
+    void launched(int n_samples, bool pixel_store) { advance(n_samples); pixels_current = pixel_store; filtered_behind = 0; }    // a whole-frame launch
     void launched_subset(int n_samples, bool pixel_store, bool all_groups) {    // (the tiles left out keep the packed pixels they had)
+        const uint64_t was = filtered_pair != 0 ? filtered_pair : filtered_behind;      // current, or behind by launches of this same selection already
         advance(n_samples);
+        filtered_behind = was;          // the cross-filtered plane is one selection behind: the groups left out hold what it held
         pixels_current = pixel_store && (all_groups || pixels_current);
         ragged = !all_groups;           // every group selected means every group at the front: the frame stays (or is again) whole
     }
@@ -59,24 +71,28 @@ struct FrameState {
 
     // ---- selection and tile list ----
     void order_resorted() { list_valid = false; }               // a subset launch's list follows the heavy-first order
-    void selection_started() { have_selection = false; list_valid = false; }    // the flags are being rewritten: no selection until the counts are back
+    // the flags are being rewritten: no selection until the counts are back, and a plane that was behind the old selection cannot be refreshed by the new one
+    void selection_started() { have_selection = false; list_valid = false; filtered_behind = 0; }
     void selection_landed(uint32_t groups, uint32_t tiles) { counts[0] = groups; counts[1] = tiles; selection_serial += 1; have_selection = true; }
     void list_built(bool by_order, uint32_t tiles, uint32_t slots) {
         list_valid = true; list_by_order = by_order; list_serial = selection_serial; list_tiles = tiles; list_slots = slots;
     }
+    void group_list_built() { group_list_serial = selection_serial; }          // rt_denoise_pair_tiles_async: once per selection
 
     // ---- the colour plane written by something else than a launch: rt_read_pixels packs it ----
-    void merged(int total) { current_sample = total; have_selection = false; pixels_current = false; filtered_pair = 0; }     // (a selection was made at another pass number)
+    void merged(int total) { current_sample = total; have_selection = false; pixels_current = false; filtered_pair = filtered_behind = 0; }     // (a selection was made at another pass number)
     void merged_by_tile(int total) { merged(total); ragged = true; list_valid = false; }                    // every tile by its own weights: dst's front has moved
-    void colours_replaced() { pixels_current = false; filtered_pair = 0; }     // rt_denoise_async
+    void colours_replaced() { pixels_current = false; filtered_pair = filtered_behind = 0; }     // rt_denoise_async
     void pixels_packed() { pixels_current = true; }             // refresh_pixels
     // rt_denoise_pair_async: the cross-filtered plane beside the colour plane is current, until anything moves the colour plane (a launch, a reset,
     // a written state, a merge or a filter into it); nothing else of the frame changes
-    void pair_filtered(uint64_t call) { filtered_pair = call; }
+    void pair_filtered(uint64_t call) { filtered_pair = call; filtered_behind = 0; }
+    // rt_denoise_pair_tiles_async: the selected groups' part of a plane that was one selection behind has been formed again -- current, under a new id
+    void pair_tiles_refreshed(uint64_t call) { pair_filtered(call); }
 
 private:
     // every tile holds `pass` passes; a selection does not outlive that, and the launch count starts again
-    void restart(int pass) { current_sample = pass; launches = 0; last_ms = 0.0; ragged = have_selection = list_valid = false; filtered_pair = 0; }
+    void restart(int pass) { current_sample = pass; launches = 0; last_ms = 0.0; ragged = have_selection = list_valid = false; filtered_pair = filtered_behind = 0; }
     // a launch has written every seed pair it renders: the default stream is no longer read in place
     void advance(int n_samples) { current_sample += n_samples; launches += 1; seeds_default = false; filtered_pair = 0; }
 };

@@ -71,6 +71,8 @@ struct TileSubset {
                                         // means something only while the frame is ragged: otherwise every tile holds current_sample passes and nothing is stored
     uint32_t *d_selected = nullptr;     // one flag per group (rt_select_tiles), then two words: selected groups, the 8x8 tiles they cover
     uint32_t *d_list = nullptr;         // the subset launch's tile list: the launch tiles of the selected groups, padded with the sentinel to whole grid rows
+    uint32_t *d_groups = nullptr;       // rt_denoise_pair_tiles_async (rt_denoise.hip): the selected groups' indices in ascending order, then the sentinel; one
+                                        // word per group, allocated on that call's first use
 };
 
 }  // namespace rt
@@ -253,6 +255,9 @@ int render_shard(rt_ctx *c, int n_samples, bool may_block);      // rt_launch.hi
 // ---- rt_denoise.hip: the cross-filtered halves, for the paired loops of rt_compare.hip ----
 int denoise_pair_refuse(const rt_ctx *a, const rt_ctx *b, const char *call);     // the contexts rt_denoise_pair_async does not take, and pass numbers that differ or are zero
 int denoise_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream);    // a checked pair, checked parameters: the planes made on `stream`, both marked current
+// ... the same pair and parameters: the planes of the groups in the current selection made again, if the planes are one selection behind (FrameState::filtered_behind);
+// RT_OK and nothing launched if they are current; RT_ERR_STATE for anything else, `call` named in the message
+int denoise_pair_tiles(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream, const char *call);
 
 // ---- rt_tiles.hip: the subset launch's device side ----
 int tiles_refuse(const rt_ctx *c, const char *call);                  // RT_ERR_ARG for the contexts the adaptive calls do not take (null, multi-device, sharded)

@@ -5,7 +5,7 @@
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
 //            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]
-//             [--denoise [--denoise-radius R]] [--filtered]]
+//             [--denoise [--denoise-radius R]] [--filtered [--live-checks]]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -26,6 +26,9 @@
 //   --filtered          with --until-psnr: DB is the target for the FILTERED merge.  The check is the PSNR between the two cross-filtered halves
 //                       (rt_render_converged_filtered; with --adaptive per tile, rt_render_adaptive_filtered) -- an estimate of the filtered
 //                       frame's quality, not a bound -- and the halves are then merged and filtered as by --denoise, with the same parameters
+//   --live-checks       with --until-psnr DB --filtered --adaptive: every check after the first cross-filters only the groups that were just
+//                       rendered (rt_render_adaptive_filtered_tiles): the same render bit for bit; the printed PSNR sums every group's
+//                       figure of its own last check
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
@@ -77,6 +80,7 @@ int main(int argc, char** argv) {
     int min_passes = 16;
     bool denoise = false;       // --until-psnr: merge into a third context and filter it (rt_denoise_async)
     bool filtered = false;      // --until-psnr judged on the cross-filtered halves: the *_filtered loops, then merge and filter
+    bool live_checks = false;   // --filtered --adaptive: rt_render_adaptive_filtered_tiles instead of rt_render_adaptive_filtered
     rt_denoise_params dn;
     rt_denoise_defaults(&dn);
     std::vector<const char*> pos;
@@ -105,6 +109,7 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-radius") dn.search_radius = atoi(next());
         else if (a == "--filtered") filtered = denoise = true;
+        else if (a == "--live-checks") live_checks = true;
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -118,6 +123,10 @@ int main(int argc, char** argv) {
     if (pos.size() >= 4) scene_path = pos[3];
     if (denoise && !until) {
         fprintf(stderr, "--denoise filters the merge of two halves: it needs --until-psnr\n");
+        return 1;
+    }
+    if (live_checks && !(until && filtered && adaptive)) {
+        fprintf(stderr, "--live-checks is a form of the filtered adaptive loop: it needs --until-psnr DB --filtered --adaptive\n");
         return 1;
     }
 
@@ -162,7 +171,7 @@ int main(int argc, char** argv) {
         rt_frame_error err{};
         int checks = 0;
         const auto t0 = std::chrono::steady_clock::now();
-        const int reached = filtered ? (adaptive ? rt_render_adaptive_filtered(half[0], half[1], until_psnr, min_passes, check_every, spp, &dn, &err, &checks)
+        const int reached = filtered ? (adaptive ? (live_checks ? rt_render_adaptive_filtered_tiles : rt_render_adaptive_filtered)(half[0], half[1], until_psnr, min_passes, check_every, spp, &dn, &err, &checks)
                                                  : rt_render_converged_filtered(half[0], half[1], until_psnr, check_every, spp, &dn, &err, &checks))
                                      : (adaptive ? rt_render_adaptive(half[0], half[1], until_psnr, min_passes, check_every, spp, &err, &checks)
                                                  : rt_render_converged(half[0], half[1], until_psnr, check_every, spp, &err, &checks));
