@@ -195,11 +195,17 @@ int check_paired_render(const rt_ctx *a, const rt_ctx *b, const char *call, cons
     return RT_OK;
 }
 
-// the pair rt_compare_filtered* takes: one frame on one device, neither sharded, both planes current and made by one rt_denoise_pair_async call
-int check_filtered_pair(const rt_ctx *a, const rt_ctx *b, const char *call) {
+// what the filter and the subset launches ask of a pair: one frame on one device, neither context sharded
+int one_unsharded_frame(const rt_ctx *a, const rt_ctx *b, const char *call) {
     int rc = same_frame(a, b, call, "a", "b");
     if (rc == RT_OK) rc = tiles_refuse(a, call);
     if (rc == RT_OK) rc = tiles_refuse(b, call);
+    return rc;
+}
+
+// the pair rt_compare_filtered* takes: that, both planes current and made by one rt_denoise_pair_async call
+int check_filtered_pair(const rt_ctx *a, const rt_ctx *b, const char *call) {
+    const int rc = one_unsharded_frame(a, b, call);
     if (rc != RT_OK) return rc;
     if (!a->frame.filtered_with(b->frame))
         return fail(RT_ERR_STATE, "%s: the cross-filtered planes are not current, or were not made by one rt_denoise_pair_async call (whatever moves a colour plane ends its plane)", call);
@@ -221,9 +227,7 @@ int check_on(rt_ctx *a, rt_ctx *b, const rt_denoise_params *filter, rt_frame_err
 
 // the filtered loops' own refusals, ahead of the shared ones: contexts the filter does not take, parameters it does not take (`q`: the checked copy)
 int check_filtered_loop(const rt_ctx *a, const rt_ctx *b, const char *call, const rt_denoise_params *p, rt_denoise_params *q) {
-    int rc = same_frame(a, b, call, "a", "b");
-    if (rc == RT_OK) rc = tiles_refuse(a, call);
-    if (rc == RT_OK) rc = tiles_refuse(b, call);
+    int rc = one_unsharded_frame(a, b, call);
     if (rc == RT_OK && rt_host_denoise_params(p, q) != RT_OK) rc = RT_ERR_ARG;
     return rc;
 }
@@ -330,9 +334,7 @@ static uint32_t tile_error_at(double db) {
 // read again; a live group's planes depend on the colour planes alone)
 static int render_adaptive(rt_ctx *a, rt_ctx *b, const char *call, const rt_denoise_params *filter, bool live_checks, double tile_psnr_db, int min_passes,
                            int passes_per_check, int max_passes, rt_frame_error *last, int *checks) {
-    int rc = same_frame(a, b, call, "a", "b");
-    if (rc == RT_OK) rc = tiles_refuse(a, call);
-    if (rc == RT_OK) rc = tiles_refuse(b, call);
+    int rc = one_unsharded_frame(a, b, call);
     if (rc != RT_OK) return rc;
     if (min_passes < 0) return fail(RT_ERR_ARG, "min_passes %d", min_passes);      // (every refusal ahead of the pass counts' is RT_ERR_ARG: their order does not show)
     rc = check_paired_render(a, b, call, last, passes_per_check, tile_psnr_db, max_passes);
@@ -389,9 +391,7 @@ RT_API int rt_render_adaptive_filtered(rt_ctx *a, rt_ctx *b, double tile_psnr_db
 RT_API int rt_render_adaptive_filtered_tiles(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
                                              const rt_denoise_params *p, rt_frame_error *last, int *checks) {
     rt_denoise_params q;
-    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;     // (ahead of the contexts: RT_ERR_ARG either way, and this one needs no context)
-    const int rc = check_filtered_loop(a, b, "rt_render_adaptive_filtered_tiles", p, &q);
-    if (rc != RT_OK) return rc;
+    if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;     // (ahead of the contexts, which render_adaptive checks first: RT_ERR_ARG either way)
     return render_adaptive(a, b, "rt_render_adaptive_filtered_tiles", &q, true, tile_psnr_db, min_passes, passes_per_check, max_passes, last, checks);
 }
 

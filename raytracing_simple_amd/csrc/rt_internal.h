@@ -72,7 +72,7 @@ struct TileSubset {
     uint32_t *d_selected = nullptr;     // one flag per group (rt_select_tiles), then two words: selected groups, the 8x8 tiles they cover
     uint32_t *d_list = nullptr;         // the subset launch's tile list: the launch tiles of the selected groups, padded with the sentinel to whole grid rows
     uint32_t *d_groups = nullptr;       // rt_denoise_pair_tiles_async (rt_denoise.hip): the selected groups' indices in ascending order, then the sentinel; one
-                                        // word per group, allocated on that call's first use
+                                        // word per group, allocated on that call's first use (tiles_build_group_list)
 };
 
 }  // namespace rt
@@ -264,6 +264,7 @@ int tiles_refuse(const rt_ctx *c, const char *call);                  // RT_ERR_
 int tiles_ensure(rt_ctx *c);                                          // the three device arrays of rt_ctx::tiles, on first use
 int merge_by_tile(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, int total, hipStream_t stream);   // rt_merge_async with a ragged context among them (checked by the caller)
 int tiles_build_list(rt_ctx *c, int waves, bool by_order, uint32_t n_launch, uint32_t slots, hipStream_t stream);   // d_list for an instance of `waves` wavefronts
+int tiles_build_group_list(rt_ctx *c, hipStream_t stream);            // d_groups (allocated on first use): the selected groups in ascending order, by the same kernel
 int tiles_advance(rt_ctx *c, int n_samples, hipStream_t stream);      // + n_samples on every tile of every selected group (the array made explicit first)
 int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream);       // rt_launch.hip: n_samples passes on the selected groups
 

@@ -180,6 +180,19 @@ int tiles_build_list(rt_ctx *c, int waves, bool by_order, uint32_t n_launch, uin
     return RT_OK;
 }
 
+// The selected groups themselves as a list (TileSubset::d_groups: what rt_denoise_pair_tiles_async's kernel walks): the same compaction with a group as
+// its own launch tile -- no order, n = slots = sentinel = the group count, groups_x tiles per row, one per group, so that id = i and the flag read is
+// selected[id].  The render's list and its key (FrameState::list_built) are not touched.
+int tiles_build_group_list(rt_ctx *c, hipStream_t stream) {
+    rt::TileSubset &s = c->tiles;
+    const uint32_t n_groups = group_count(c), groups_x = groups_per_row(c);
+    if (!s.d_groups) HIP_TRY(hipMalloc(&s.d_groups, (size_t)n_groups * sizeof(uint32_t)));
+    hipLaunchKernelGGL(rt_tile_list_kernel, dim3(1), dim3(1024), 0, stream, nullptr, n_groups, groups_x, 1u, groups_x, s.d_selected, s.d_groups, n_groups, n_groups);
+    HIP_TRY(hipGetLastError());
+    c->frame.group_list_built();
+    return RT_OK;
+}
+
 int tiles_advance(rt_ctx *c, int n_samples, hipStream_t stream) {
     const uint32_t n = tile_count(c);
     hipLaunchKernelGGL(rt_tile_advance_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, c->tiles.d_passes, c->frame.ragged ? 1 : 0,

@@ -118,6 +118,34 @@ def test_a_fast_context_packs_its_refreshed_groups_with_fast_modes_to_int():
         assert got == ref and np.array_equal(got_tiles, ref_tiles)
 
 
+def test_a_list_of_groups_longer_than_a_chunk_names_the_groups_either_side_of_the_boundary():
+    """523x521: 17 x 66 = 1122 groups, two chunks of the one-workgroup compaction.  Groups (60, 3) and (60, 4) are indices 1023 and 1024 -- the last
+    entry of the first chunk and the first of the second, so the second's place in the list is the running base the first chunk leaves -- beside
+    (0, 0) and the top-right group (65, 16), which is one pixel high (its origin in the plane is negative) and eleven wide."""
+    w, h = 523, 521
+    params = PARAMS[2]
+    assert params == {"search_radius": 1, "patch_radius": 0}
+    ty, _, gx = T.shape(w, h)
+    assert (ty, gx) == (66, 17) and 60 * gx + 3 == 1023
+    mask = np.zeros((ty, gx), bool)
+    mask[60, 3] = mask[60, 4] = mask[0, 0] = mask[65, 16] = True
+    a, b = rendered_pair(w, h, 3)
+    with a, b:
+        a.denoise_pair(b, params)
+        before = a.read_filtered().copy(), b.read_filtered().copy()
+        assert select(a, mask) == select(b, mask) == (4, int(T.tiles_of(mask, w, h).sum()))
+        a.render_tiles_async(2, a.stream)
+        b.render_tiles_async(2, b.stream)
+        a.denoise_pair_tiles(b, params)
+        want, m = expected_planes(a, b, params, before, mask)
+        for g, x, old in zip((a.read_filtered(), b.read_filtered()), want, before):
+            assert_same_bits(g, x)
+            assert np.array_equal(bits(g).reshape(h, w, 3)[~m], bits(old).reshape(h, w, 3)[~m])      # every other word is the one from before
+        err, tiles = a.compare_filtered(b, tiles=True)
+        want_err, want_tiles = metric_of(want[0], want[1], w, h)
+        assert err == want_err and np.array_equal(tiles, want_tiles)
+
+
 # ---- 2. every group selected equals rt_denoise_pair_async -------------------------------------------------------------------------------
 @pytest.mark.parametrize("w,h", [(41, 23), (96, 64)])
 def test_with_every_group_selected_the_refresh_is_the_whole_frame_call(w, h):
