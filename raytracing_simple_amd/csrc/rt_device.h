@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/rt_api.h"
+#include "rt_bvh_layout.h"     // kBvhLeaf, kBvhLeafRef, the offsets into the hierarchy's blob
 
 namespace rt {
 
@@ -34,7 +35,7 @@ struct SceneTables {
     uint32_t n_lights;
 };
 
-// Bounding-volume hierarchy over the small spheres of a large scene (built by rt_bvh.hip, walked by rt_walk.inc.h).
+// Bounding-volume hierarchy over the small spheres of a large scene (built by rt_bvh.hip and rt_bvh_host.cpp, walked by rt_walk.inc.h).
 // It only decides WHICH spheres a ray is tested against: every test that is made is the reference's arithmetic, and
 // the selection rule (smallest distance, lowest scene index among equals; lowest blocking index for shadow rays) is
 // the reference's loop order restated, so frames and counters do not change.  One blob in HBM:
@@ -46,16 +47,11 @@ struct SceneTables {
 //            twice; ref = kBvhLeafRef | leaf number, or the number of the child's own pair.  The walk takes the nearer
 //            child first and keeps the other on a per-lane stack.  Inner node m - 1 is the one that splits its range
 //            of leaves in front of leaf m, wherever that split lies: the device build halves every range (root = pair
-//            n_leaves / 2 - 1), the host build of a full scene upload cuts by surface area (rt_bvh.hip); BvhTables::root says
+//            n_leaves / 2 - 1), the host build of a full scene upload cuts by surface area (rt_bvh_host.cpp); BvhTables::root says
 //            which pair the walk starts at -- it travels in the header (hdr[1].w), because a tree shaped on the device has it where the host cannot see it (a tree of one leaf has no pairs: kBvhLeafRef).
 //   emis[j], colr[j] = the material records of slot j ({ emission, bits(refl) }, { colour, radius }: SceneTables' records in SLOT
 //            order): a closest hit reads its material by the slot the walk ended on -- one round trip to L2 instead of two
 //            (scene index first, then the record by index)
-#ifndef RT_BVH_LEAF
-#define RT_BVH_LEAF 8                   /* spheres per leaf (4 measured in round 4: tools/leaf_size_ab.sh) */
-#endif
-constexpr int kBvhLeaf = RT_BVH_LEAF;
-constexpr uint32_t kBvhLeafRef = 0x8000u;
 struct BvhTables {
     const float4 *blob;     // hdr | slots | index | pairs | emis by slot | colr by slot
     uint32_t n_always, n_leaves, n_slots;
@@ -71,13 +67,6 @@ struct BvhTables {
 };
 constexpr uint32_t kBvhLowShift = 2;        // (262 144 scene indices in 16 bits: a lower bound of the lowest index below a child prunes as safely as the index itself)
 constexpr uint32_t kBvhTopPairs = 255;      // eight full levels: 16 KiB of LDS beside the stacks, five workgroups per CU still fit
-// offsets into the blob, in float4 units
-__host__ __device__ inline uint32_t bvh_slots_at() { return 2u; }
-__host__ __device__ inline uint32_t bvh_index_at(uint32_t n_slots) { return 2u + n_slots; }
-__host__ __device__ inline uint32_t bvh_pairs_at(uint32_t n_slots) { return 2u + n_slots + (n_slots + 3u) / 4u; }
-__host__ __device__ inline uint32_t bvh_emis_at(uint32_t n_leaves, uint32_t n_slots) { return bvh_pairs_at(n_slots) + 4u * (n_leaves ? n_leaves - 1u : 0u); }
-__host__ __device__ inline uint32_t bvh_colr_at(uint32_t n_leaves, uint32_t n_slots) { return bvh_emis_at(n_leaves, n_slots) + n_slots; }
-inline size_t bvh_blob_float4s(uint32_t n_leaves, uint32_t n_slots) { return (size_t)bvh_colr_at(n_leaves, n_slots) + (size_t)n_slots; }
 // LDS of the instance that walks the pairs: hdr | pairs | slots | per-lane stacks (u16) for `threads` lanes
 inline size_t lds_bytes_pairs(uint32_t n_spheres, uint32_t n_lights, bool mat_in_lds, int n_samples, uint32_t n_leaves,
                               uint32_t n_slots, uint32_t stack_depth, int threads) {

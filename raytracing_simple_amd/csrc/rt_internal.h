@@ -120,7 +120,7 @@ struct rt_ctx {
     float4 *d_bvh = nullptr;            // blob, sized for scene_cap
     rt::BvhTables bvh{};
     bool bvh_ok = false;                // the blob describes the current scene
-    float4 *h_bvh_stage = nullptr;      // page-locked buffer of the host-side build (trees beyond the one-workgroup device build)
+    float4 *h_bvh_stage = nullptr;      // page-locked buffer a host-shaped tree is written into (rt_bvh.hip upload_host_tree)
     size_t bvh_stage_cap = 0;           // float4
     hipEvent_t bvh_stage_ev = nullptr;
     bool bvh_stage_used = false;
@@ -133,7 +133,7 @@ struct rt_ctx {
     int bvh_sah = 1;                    // the hierarchy's shape is chosen by surface area (rt_bvh.hip): 1 = uploads below kAlwaysWalkFrom tree spheres on the host,
                                         // larger uploads and every device-resident update on the device; 2 = the device for uploads too; 0 = the fixed (halved) shape
     uint32_t bvh_n_tree = 0;            // spheres inside the tree (the slots are padded to whole leaves)
-    // surface-area sums of a host-built tree (rt_bvh.hip): what a random line through the root box is expected to visit --
+    // surface-area sums of a host-built tree (rt_bvh_host.cpp bvh_estimate, set by rt_bvh.hip upload_host_tree): what a random line through the root box is expected to visit --
     // pair steps (inner nodes, the root counted once) and leaves; the estimate that settles hierarchy against sweep without a launch
     double bvh_est_pairs = 0.0, bvh_est_leaves = 0.0;
     bool bvh_est_valid = false;

@@ -2,6 +2,7 @@
 which spheres a ray is tested against, so everything must stay BIT-EXACT: frames, colour plane, seeds and the work
 counters against the oracle, with the hierarchy forced on small and adversarial scenes too."""
 import ctypes as C
+import json
 import os
 import sys
 
@@ -13,6 +14,7 @@ from raytracing_simple_amd import api, host, scenes
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import bvh_check  # noqa: E402
+from bvh_scenes import _adversarial, _many_spheres, _two_size_classes, _with_repeats  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -96,6 +98,21 @@ def test_device_built_tables_are_a_valid_hierarchy_in_the_product_layout(maker):
                 assert b["root"] < b["n_leaves"] - 1, (by_area, b["root"], b["n_leaves"])
 
 
+_TABLES_RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bvh_tables.json")
+
+
+@pytest.mark.parametrize("case", list(bvh_check.DIGEST_CASES))
+def test_every_builder_writes_the_recorded_bits(case):
+    """tests/golden/bvh_tables.json (tools/bvh_check.py digests): the tables of the four builders -- device and host, halved and by surface
+    area -- on the smallest scenes at which each of their paths can go wrong, recorded before the builders were made of one set of steps.
+    Counts, every section of the blob and the surface-area estimate of an upload are still those bits; a failure names what moved."""
+    with open(_TABLES_RECORD) as f:
+        want = json.load(f)["cases"][case]
+    got = bvh_check.digest_case(case)
+    assert got["builder"] == got["meant"] == want["meant"], (got["n_tree"], got["builder"])
+    assert bvh_check.digest_differences(got, want) == []
+
+
 def _breadth_first(b):
     """Pair numbers in breadth-first order from the header's root, side 0 before side 1 (rt_bvh.hip rt_bvh_promote_kernel's order)."""
     order, queue = [], [b["root"]]
@@ -175,33 +192,6 @@ def test_walk_and_plain_sweep_agree_ray_by_ray():
         assert r["closest_differ"] == 0 and r["shadow_differ"] == 0, r
 
 
-def _adversarial(seed):
-    """Duplicated spheres (the reference's loader doubles them: exact ties), zero and negative radii, concentric and
-    heavily overlapping spheres, a camera inside a glass sphere, non-finite records, a far-away cluster."""
-    rng = np.random.default_rng(seed)
-    n = int(rng.choice([40, 70, 130]))
-    sph = np.zeros(n, api.SPHERE_DT)
-    sph["rad"] = rng.uniform(0.5, 6.0, n).astype(np.float32)
-    sph["p"] = rng.uniform(-30, 30, (n, 3)).astype(np.float32)
-    sph["c"] = rng.uniform(0.1, 0.95, (n, 3)).astype(np.float32)
-    sph["refl"] = rng.integers(0, 3, n)
-    sph["rad"][0], sph["p"][0], sph["refl"][0] = 1000.0, (0, -1030, 0), 0          # ground
-    sph["rad"][1], sph["p"][1], sph["e"][1] = 8.0, (0, 45, 0), (10, 10, 10)         # light
-    half = n // 2
-    dup = rng.integers(2, half, 8)
-    sph[half:half + 8] = sph[dup]                                                   # exact duplicates, higher index
-    sph["rad"][half + 8] = 0.0
-    sph["rad"][half + 9] = -3.0                                                      # rad*rad is what the test uses
-    sph["p"][half + 10] = sph["p"][half + 11]                                        # concentric
-    sph["rad"][half + 12] = np.float32("nan")
-    sph["p"][half + 13, 1] = np.float32("inf")
-    sph["p"][half + 14] = (4000.0, 10.0, -3000.0)                                    # far-away member of the tree
-    orig = (float(sph["p"][3, 0]), float(sph["p"][3, 1]), float(sph["p"][3, 2]) + 0.5) if seed % 2 else (10.0, 30.0, 70.0)
-    if seed % 2:
-        sph["refl"][3], sph["rad"][3] = 2, 5.0                                       # the camera sits inside glass
-    return sph, orig, (0.0, 5.0, 0.0)
-
-
 @pytest.mark.parametrize("seed", range(6))
 def test_adversarial_scenes_equal_the_oracle_with_the_hierarchy_forced(seed):
     sph, orig, target = _adversarial(seed)
@@ -214,36 +204,6 @@ def test_adversarial_scenes_equal_the_oracle_with_the_hierarchy_forced(seed):
         _same(_render(sph, cam, w, h, spp, inst=inst), want)
     r = bvh_check.agreement(sph, cam, w, h, 60000)
     assert r["closest_differ"] == 0 and r["shadow_differ"] == 0, r
-
-
-def _with_repeats(seed):
-    """A scene in which later records repeat earlier ones bit for bit in centre and radius^2 but NOT in material (a repeated diffuse sphere that
-    is glass, black, a light), a repeated light, a repeated ground (always-list), a record with the negated radius (same radius^2) and the
-    reference loader's own pattern: a block of zero-radius records at the origin in FRONT of everything (Utility.cpp:120,154)."""
-    rng = np.random.default_rng(100 + seed)
-    n_real, n_ph = 90, 40
-    real = np.zeros(n_real, api.SPHERE_DT)
-    real["rad"] = rng.uniform(0.8, 5.0, n_real).astype(np.float32)
-    real["p"] = rng.uniform(-30, 30, (n_real, 3)).astype(np.float32)
-    real["p"][:, 1] = np.abs(real["p"][:, 1])
-    real["c"] = rng.uniform(0.1, 0.95, (n_real, 3)).astype(np.float32)
-    real["refl"] = rng.integers(0, 3, n_real)
-    real["rad"][0], real["p"][0], real["refl"][0] = 1000.0, (0, -1000, 0), 0         # ground
-    real["rad"][1], real["p"][1], real["e"][1], real["refl"][1] = 8.0, (0, 45, 0), (10, 10, 10), 0          # light
-    for k, src in enumerate(rng.integers(2, 40, 12)):                                # repeats with OTHER materials, at higher indices
-        dst = 60 + k
-        real[dst] = real[src]
-        real["refl"][dst] = (int(real["refl"][src]) + 1 + k % 2) % 3
-        real["c"][dst] = (0.05, 0.9, 0.05)
-        if k % 4 == 0:
-            real["e"][dst] = (3, 3, 3)                                               # a repeat that is a light (it is sampled as one; never hit)
-        if k % 3 == 0:
-            real["rad"][dst] = -real["rad"][dst]                                     # same radius^2
-    real[75] = real[1]                                                               # the light, repeated
-    real[76] = real[0]                                                               # the ground, repeated (always-list)
-    real["c"][76] = (0.9, 0.1, 0.1)
-    phantoms = np.zeros(n_ph, api.SPHERE_DT)
-    return np.concatenate([phantoms, real]), (20.0, 40.0, 90.0), (0.0, 8.0, 0.0)
 
 
 @pytest.mark.parametrize("seed", range(3))
@@ -575,19 +535,6 @@ def test_walk_equals_sweep_for_adversarial_rays(maker):
     assert (out[1::2, 0] < len(sph)).sum() > 1000               # ... and of blocked shadow rays
 
 
-def _many_spheres(n, seed=7):
-    """n small spheres in a slab above a ground sphere, one light: beyond what LDS holds for n > ~9000."""
-    rng = np.random.default_rng(seed)
-    sph = np.zeros(n, api.SPHERE_DT)
-    sph["rad"] = rng.uniform(0.3, 1.2, n).astype(np.float32)
-    sph["p"] = np.stack([rng.uniform(-90, 90, n), rng.uniform(0.5, 9, n), rng.uniform(-90, 90, n)], 1).astype(np.float32)
-    sph["c"] = rng.uniform(0.1, 0.9, (n, 3)).astype(np.float32)
-    sph["refl"] = rng.choice([api.DIFF, api.DIFF, api.SPEC, api.REFR], n)
-    sph["rad"][0], sph["p"][0], sph["refl"][0], sph["c"][0] = 1000.0, (0, -1000, 0), api.DIFF, (.75, .75, .75)
-    sph["rad"][1], sph["p"][1], sph["e"][1], sph["refl"][1] = 9.0, (0, 70, 0), (14, 14, 14), api.DIFF
-    return sph, host.DEMO_ORIG, host.DEMO_TARGET
-
-
 @pytest.mark.parametrize("n", [2000, 5000, 9500, 30000])
 def test_scenes_beyond_lds(n):
     """More spheres than the LDS budget holds (the hierarchy's whole tables stop at ~1100 spheres, the sweep's at ~2500: four workgroups per CU): while the PAIRS
@@ -678,13 +625,6 @@ def test_many_scattered_updates_then_one_launch():
             got = {"pixels": ctx.read_pixels(), "colors": ctx.read_colors(), "seeds": ctx.read_seeds(), "stats": ctx.stats()}
             _same(got, O.render(sph, cam, w, h, spp, threads=16))
         assert bvh_check.check_structure(api.as_spheres(sph), bvh_check.read_bvh(ctx)) == []
-
-
-def _two_size_classes(n_small, n_large, seed=3):
-    """Dust among objects fifty times its size, a ground sphere and a light (tools/always_list_probe.py)."""
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import always_list_probe
-    return always_list_probe.two_classes(n_small, n_large, seed)
 
 
 @pytest.mark.parametrize("n_small,n_large,by_area", [(700, 300, 1), (3000, 600, 1), (3000, 600, 2), (9000, 1500, 1), (300, 700, 1)])

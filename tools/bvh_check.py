@@ -9,11 +9,16 @@
               rays of the scene itself here; tests/test_gpu_bvh.py adds the adversarial ones
   parity      the shipped instance against the oracle, and timing with the hierarchy on / off
   census      what the walk executes (instance rt_trace_parity_pairs_census): pair steps, leaf steps, lanes taking part
+  digests     every builder's tables as SHA-256 per section, for the cases of DIGEST_CASES (tests/golden/bvh_tables.json is such a
+              record; tests/test_gpu_bvh.py holds every later library to it)
 
     python tools/bvh_check.py [--quick] [--census] [--timing-only]
+    python tools/bvh_check.py digests [--out FILE] [--against FILE]
 """
 import argparse
 import ctypes as C
+import functools
+import hashlib
 import json
 import os
 import sys
@@ -91,6 +96,131 @@ def check_packed(b, pk, low_shift=2):
         if np.any(bound > low) or np.any((low - bound >= (1 << low_shift)) & (lq != 0xffff)):
             bad.append("side %d: the packed lowest scene index is not a tight lower bound" % side)
     return bad
+
+
+SECTIONS = ("hdr", "slots", "index", "pairs", "emis", "colr")
+# The thresholds of rt_bvh.hip build_bvh_tables: which builder a tree of n_tree spheres reaches.
+SAH_MIN_TREE, SAH_HOST_MAX_TREE, DEVICE_MAX_TREE = 128, 1499, 8192
+
+
+def builder_reached(n_tree, shape, upload):
+    """The builder build_bvh_tables takes: shape = rt_debug_set_tree_shape's argument, upload = rt_set_scene (not a device-resident update)."""
+    if upload and n_tree < SAH_MIN_TREE:
+        return "host_halved"
+    if upload and shape == 1 and n_tree <= SAH_HOST_MAX_TREE:
+        return "host_by_area"
+    if shape in (1, 2) and SAH_MIN_TREE <= n_tree <= DEVICE_MAX_TREE:
+        return "device_by_area"
+    return "device_halved" if n_tree <= DEVICE_MAX_TREE else "host_halved"
+
+
+def _digest_cases():
+    """name -> (scene, rt_debug_set_tree_shape, followed by a whole-scene update, the builder the case is meant to reach): the smallest
+    scenes at which each path of each builder can still go wrong."""
+    cases = {}
+
+    def add(scene, shape, update, builder):
+        cases["%s-shape%d%s" % (scene, shape, "-update" if update else "")] = (scene, shape, update, builder)
+
+    add("demo", 1, False, "host_halved")                        # a tree of one leaf, no pairs
+    add("random_97", 1, False, "host_halved")
+    add("random_97", 1, True, "device_halved")
+    for scene in ("random_300", "random_1024"):
+        for shape, builder in ((0, "device_halved"), (1, "host_by_area"), (2, "device_by_area")):
+            add(scene, shape, False, builder)
+    add("random_300", 1, True, "device_by_area")
+    add("slab_5000", 0, False, "device_halved")                 # the split into the two lists over several chunks of 1024 records
+    add("slab_5000", 1, False, "device_by_area")                # more than 512 leaves: the unions towards both ends in two passes
+    add("slab_9500", 1, False, "host_halved")                   # beyond what one workgroup sorts
+    for scene in ("adversarial_0", "adversarial_1", "repeats_0"):    # always list, repeats, NaN and infinite records
+        for shape in (0, 1, 2):
+            add(scene, shape, False, "host_halved")                  # (fewer than 128 tree spheres each)
+    add("adversarial_0", 1, True, "device_halved")              # ... and the same records through the device's split (d_dup)
+    add("repeats_0", 1, True, "device_halved")
+    add("two_classes_700_300", 1, False, "host_by_area")        # the extent term of the cut
+    return cases
+
+
+DIGEST_CASES = _digest_cases()
+
+
+@functools.lru_cache(maxsize=None)
+def _digest_scene(name):
+    import bvh_scenes
+    kind, _, arg = name.partition("_")
+    if kind == "demo":
+        return api.as_spheres(host.demo_scene())
+    if kind == "random":
+        return api.as_spheres(scenes.random_spheres(int(arg))[0])
+    if kind == "slab":
+        return api.as_spheres(bvh_scenes._many_spheres(int(arg))[0])
+    if kind == "adversarial":
+        return api.as_spheres(bvh_scenes._adversarial(int(arg))[0])
+    if kind == "repeats":
+        return api.as_spheres(bvh_scenes._with_repeats(int(arg))[0])
+    n_small, n_large = arg.split("_")[1:]
+    return api.as_spheres(bvh_scenes._two_size_classes(int(n_small), int(n_large))[0])
+
+
+def digest_case(name):
+    """One case of DIGEST_CASES: the tables built and read back (nothing is rendered) -- the four counts of rt_debug_read_bvh, the tree's
+    sphere count, the builder reached, a SHA-256 per section of read_bvh over its uint32 view, and for an upload the surface-area estimate."""
+    scene, shape, update, meant = DIGEST_CASES[name]
+    sph = _digest_scene(scene)
+    with api.RtContext(64, 64, diag=True) as ctx:
+        ctx._check(ctx._lib.rt_debug_set_tree_shape(ctx._h, shape))
+        ctx._check(ctx._lib.rt_debug_set_bvh(ctx._h, 1, 0))
+        ctx.set_scene(sph)
+        if update:
+            ctx.update_spheres(0, sph)
+        counts = (C.c_uint32 * 4)()
+        ctx._check(ctx._lib.rt_debug_read_bvh(ctx._h, None, 0, counts))
+        b = read_bvh(ctx)
+        est = (C.c_double * 4)()
+        has_est = ctx._lib.rt_debug_tree_estimate(ctx._h, est)
+    n_tree = int((b["index"][b["n_always"]:] != 0xffffffff).sum())
+    rec = {"counts": list(counts), "n_tree": n_tree, "meant": meant, "builder": builder_reached(n_tree, shape, not update),
+           "sha256": {k: hashlib.sha256(np.ascontiguousarray(b[k]).view(np.uint32).tobytes()).hexdigest() for k in SECTIONS}}
+    if not update:
+        rec["estimate"] = {"returned": int(has_est), "bits": ["%016x" % v for v in np.array(est[:2], np.float64).view(np.uint64)]}
+    return rec
+
+
+def digest_differences(got, want):
+    """What of a case's record differs from another recording of it, by name (empty = the same bits)."""
+    bad = [k for k in ("counts", "n_tree", "builder", "estimate") if got.get(k) != want.get(k)]
+    return bad + ["section " + k for k in SECTIONS if got["sha256"][k] != want["sha256"].get(k)]
+
+
+def digest_complaints(cases):
+    """A recording that does not test what it claims: a case that reaches another builder than it is meant to, or two cases meant for
+    different builders of different shapes (halved / by area) that wrote the same pairs."""
+    bad = ["%s: reaches %s, meant %s" % (n, r["builder"], r["meant"]) for n, r in cases.items() if r["builder"] != r["meant"]]
+    names = sorted(cases)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            ra, rb = cases[a], cases[b]
+            if ra["meant"] != rb["meant"] and ra["meant"].split("_", 1)[1] != rb["meant"].split("_", 1)[1] and ra["counts"][1] > 1 \
+                    and ra["sha256"]["pairs"] == rb["sha256"]["pairs"]:
+                bad.append("%s and %s: different builders, the same pairs" % (a, b))
+    return bad
+
+
+def digests(out=None, against=None):
+    record = {"build_id": api.build_id(diag=True), "cases": {name: digest_case(name) for name in DIGEST_CASES}}
+    bad = digest_complaints(record["cases"])
+    if against:
+        want = json.load(open(against))["cases"]
+        bad += ["%s: %s differs" % (n, d) for n in DIGEST_CASES for d in digest_differences(record["cases"][n], want[n])]
+    for line in bad:
+        print("digests:", line, flush=True)
+    if bad:
+        return 1
+    text = json.dumps(record, indent=1, sort_keys=True) + "\n"
+    if out:
+        open(out, "w").write(text)
+    print("digests: %d cases, library %s%s" % (len(record["cases"]), record["build_id"], ", equal to " + against if against else ""), flush=True)
+    return 0
 
 
 def sum_of_box_areas(b):
@@ -324,12 +454,17 @@ def timed(sph, cam, w, h, spp, bvh_min, reps=3, mode=api.RT_MODE_PARITY, walk=(0
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("what", nargs="?", choices=["digests"], help="digests: record every builder's tables (DIGEST_CASES)")
+    ap.add_argument("--out", help="digests: the file to write")
+    ap.add_argument("--against", help="digests: an earlier record these must equal")
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--boxes", action="store_true", help="timing on enclosed all-specular scenes instead of the open ones")
     ap.add_argument("--timing-only", action="store_true")
     ap.add_argument("--census", action="store_true", help="only the step census of the walk (c3 and c5 at quarter size)")
     args = ap.parse_args()
     report = {}
+    if args.what == "digests":
+        return digests(args.out, args.against)
     if args.census:
         for name, mk, (w, h, spp) in [("c3", lambda: scenes.random_spheres(1024), (480, 270, 16)),
                                       ("mirror_box_256", lambda: scenes.mirror_box(256), (480, 270, 16))]:

@@ -1,7 +1,8 @@
 #!/bin/bash
 # AddressSanitizer + UndefinedBehaviorSanitizer over the CPU-side code (GPU sanitizers are not
-# available on this pool): the oracle's renderer and the product's host helpers (scene reader with
-# good, truncated and missing files, seed stream, camera basis).  Run from the repository root.
+# available on this pool): the oracle's renderer, the product's host helpers (scene reader with
+# good, truncated and missing files, seed stream, camera basis) and the hierarchy's host builders.
+# Run from the repository root.
 set -eu
 R=$(cd "$(dirname "$0")/../.." && pwd)
 T=/tmp/rt_san; mkdir -p $T
@@ -18,6 +19,10 @@ gcc -std=c11 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -mfma -
 $T/oracle_san
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -ffp-contract=off -I$R/include \
     $R/tools/sanitize/host_main.cpp $R/raytracing_simple_amd/csrc/rt_host.cpp -o $T/host_san
+# the hierarchy's host builders (rt_bvh_host.cpp alone: plain C++), both shapes, on generated record sets
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off -I$R/include \
+    $R/tools/sanitize/bvh_main.cpp $R/raytracing_simple_amd/csrc/rt_bvh_host.cpp -o $T/bvh_san
+$T/bvh_san
 $T/host_san
 # the .scn reader on 1000 mutated files (deletions, junk tokens, non-finite numbers, truncation)
 mkdir -p $T/fz

@@ -5,9 +5,9 @@
 
   set_scene_ms   wall time of rt_set_scene + one 64x64 pass (upload, tables, hierarchy, the pass behind them), with the tree's shape
                  0 = halved on the device, 1 = the library's choice (the host by surface area below 1500 tree spheres, the device by
-                 surface area up to 4096, halved beyond), 2 = the device by surface area wherever it can
+                 surface area up to 8192, halved beyond), 2 = the device by surface area wherever it can
   host_ms        host time of the rt_set_scene call alone (what the caller is held for)
-  update_ms      rt_update_spheres_async of the whole scene + the pass, default shape (the device by surface area up to 4096)
+  update_ms      rt_update_spheres_async of the whole scene + the pass, default shape (the device by surface area up to 8192)
   update_host_ms host time of the update call alone"""
 import json
 import os
