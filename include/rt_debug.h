@@ -74,6 +74,8 @@ RT_API int rt_debug_bvh_pick(rt_ctx *ctx);   /* 0 = not decided yet, 1 = the hie
 RT_API int rt_debug_read_bvh(rt_ctx *ctx, float *blob_out, uint32_t cap_float4, uint32_t *counts4);
 RT_API int rt_debug_read_packed_pairs(rt_ctx *ctx, void *out, uint32_t cap_bytes, uint32_t *n_pairs);   /* the packed pair table of the walk that reads its tables from HBM / L2 (csrc/rt_device.h BvhTables::packed_at): 32 bytes of frame { r0.xyz, - }, { scale.xyz, - }, then 32 bytes per pair in the pairs' order; *n_pairs = 0 when the scene's hierarchy has none */
 RT_API int rt_debug_set_wg_waves(rt_ctx *ctx, int waves);          /* 0 = automatic, 1 or 4 wavefronts per workgroup */
+RT_API int rt_debug_set_direct_camera(rt_ctx *ctx, int max_candidates);   /* camera rays are resolved lane by lane against their tile's candidate spheres while the tile has no more of them than this (default 3; -1 = never: every camera ray goes through the wave-wide sweep; at most 4) */
+RT_API int rt_debug_tile_candidates(const float *cam15, int w, int h, const rt_sphere *spheres, uint32_t n, int rank, int nranks, int tile_rows, unsigned long long *out_masks);   /* host only: the candidate mask (bit i = sphere i, n <= 64) of every 8x8 tile of a rank's rows, ceil(w / 8) masks per tile row */
 RT_API int rt_debug_set_tile_order(rt_ctx *ctx, int on);           /* 0 = natural tile order; 1 = heavy first (the default) */
 RT_API int rt_debug_read_tile_order(rt_ctx *ctx, uint32_t *order_out, uint32_t *cost_out, uint32_t cap, uint32_t *n_tiles, int *valid);
 RT_API int rt_debug_read_tile_list(rt_ctx *ctx, uint32_t *list_out, uint32_t cap, uint32_t *n_slots, uint32_t *n_launch, int *by_order);   /* the tile list the last rt_render_tiles_async walked: grid.x * grid.y entries, the sentinel (= *n_launch) at the end; *by_order = 1 if it follows the heavy-first order */

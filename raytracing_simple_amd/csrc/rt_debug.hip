@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "rt_candidates.h"
 #include "rt_internal.h"
 
 #ifndef RT_DIAGNOSTICS
@@ -192,6 +193,7 @@ static int dbg_set_persist(rt_ctx *c, int v) { c->persist = v ? 1 : 0; return RT
 static int dbg_set_ncus(rt_ctx *c, int v) { c->n_cus = v; return RT_OK; }
 static int dbg_set_coop(rt_ctx *c, int v) { c->coop_min = v & 0xffffff; c->coop_kmax = v >> 24; c->choice.coop_probe = 0; rearm_probe(c); return RT_OK; }     // (a threshold set by hand decides alone: no measurement)
 static int dbg_set_wg(rt_ctx *c, int v) { c->wg_waves = v; return RT_OK; }
+static int dbg_set_direct(rt_ctx *c, int v) { c->direct_max = v; return RT_OK; }
 static int dbg_set_order(rt_ctx *c, int v) { c->order.enable(v != 0); return RT_OK; }
 static int dbg_apply(rt_ctx *c, int (*fn)(rt_ctx *, int), int v) { return c->multi ? rt::multi_debug_each(c, fn, v) : fn(c, v); }
 
@@ -215,6 +217,45 @@ RT_API int rt_debug_set_ncus(rt_ctx *c, int n) {      // shrink the persistent g
 RT_API int rt_debug_set_wg_waves(rt_ctx *c, int waves) {    // 0 = automatic, 1 = single-wavefront workgroups, 4 = four wavefronts
     if (!c || (waves != 0 && waves != 1 && waves != 4)) return fail(RT_ERR_ARG, "waves %d", waves);
     return dbg_apply(c, dbg_set_wg, waves);
+}
+// RT_OPT_DIRECT_CAMERA's fallback threshold: camera rays of a tile with more candidate spheres than this go through the wave-wide sweep
+// (default 3; -1: every camera ray does, the loop's old behaviour on the new form).  At most 4: the indices a wavefront keeps (rt_candidates.h kCandPacked).
+RT_API int rt_debug_set_direct_camera(rt_ctx *c, int max_candidates) {
+    if (!c || max_candidates < -1 || max_candidates > (int)rt::kCandPacked) return fail(RT_ERR_ARG, "max_candidates %d", max_candidates);
+    return dbg_apply(c, dbg_set_direct, max_candidates);
+}
+// The certificate on the CPU (rt_candidates.h, the text the kernels' prologue runs): the candidate mask of every 8x8 tile of a rank's rows, tile
+// (tx, ty) of local rows [8 ty, 8 ty + 7] at out_masks[ty * ceil(w / 8) + tx].  cam15 as rt_compute_camera leaves it.  Needs no device.
+RT_API int rt_debug_tile_candidates(const float *cam15, int w, int h, const rt_sphere *spheres, uint32_t n, int rank, int nranks, int tile_rows,
+                                    unsigned long long *out_masks) {
+    if (!cam15 || !spheres || !out_masks || w <= 0 || h <= 0 || n > rt::kCandMaxSpheres || nranks < 1 || rank < 0 || rank >= nranks || tile_rows < 1)
+        return fail(RT_ERR_ARG, "rt_debug_tile_candidates: %d x %d, %u spheres, rank %d of %d, %d tile rows", w, h, n, rank, nranks, tile_rows);
+    rt::CandCamera cc;
+    for (int k = 0; k < 3; ++k) {
+        cc.o[k] = cam15[k];
+        cc.d[k] = cam15[6 + k];
+        cc.x[k] = cam15[9 + k];
+        cc.y[k] = cam15[12 + k];
+    }
+    cc.inv_w = 1.f / (float)w;
+    cc.inv_h = 1.f / (float)h;
+    // this rank's local rows: the rows of its row tiles that lie inside the image
+    int local_rows = 0;
+    for (int y = 0; y < h; ++y)
+        if ((y / tile_rows) % nranks == rank) local_rows += 1;
+    const int tiles_x = (w + 7) / 8, tiles_y = (local_rows + 7) / 8;
+    for (int ty = 0; ty < tiles_y; ++ty) {
+        const int y0 = rt::cand_image_row(8 * ty, rank, nranks, tile_rows), y1 = rt::cand_image_row(8 * ty + 7, rank, nranks, tile_rows);
+        for (int tx = 0; tx < tiles_x; ++tx) {
+            unsigned long long m = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                const rt_sphere &s = spheres[i];
+                if (rt::tile_sphere_candidate(cc, 8 * tx, 8 * tx + 7, y0, y1, s.p.x, s.p.y, s.p.z, s.rad * s.rad)) m |= 1ull << i;
+            }
+            out_masks[(size_t)ty * tiles_x + tx] = m;
+        }
+    }
+    return RT_OK;
 }
 RT_API int rt_debug_set_tile_order(rt_ctx *c, int on) {      // 0: tiles in their natural order (the round-1 behaviour); 1: heavy first
     if (!c || on < 0 || on > 1) return fail(RT_ERR_ARG, "ctx is null / order %d", on);

@@ -109,6 +109,9 @@ struct LaunchParams {
     // offsets, and with them their scalar loads and SGPR allocation, are what they were without it
     int walk_round;         // rt_walk.inc.h: pair steps in a row before the leaf step of the lanes that hold a leaf
     BvhTables bvh;
+    // RT_OPT_DIRECT_CAMERA (behind everything, for the same reason): a wavefront runs the rotated loop, its lanes resolving their camera rays
+    // themselves, while its tile has no more candidate spheres than this (rt_candidates.h); with more, and with -1 always, it runs the old loop
+    int direct_max;
 };
 
 // LDS bytes the kernels need for a scene

@@ -161,6 +161,7 @@ struct rt_ctx {
                                         // (profiles/r06_g_threshold.jsonl): at 48 KB (3 per CU) rt_trace_*_g takes 0.62 / 0.92 x the staged sweep's time (NaN records / a closed
                                         // box of mirrors), at 64 KB (2) 0.41 / 0.63, at 96 KB and more (1) 0.19; at 32 KB (4) 0.80 / 1.12, below that 0.9 ... 1.3
     int coop_kmax = 0;                  // cooperative any-hit only while no more than this many shadow rays are pending in the wavefront (0 = no limit)
+    int direct_max = 3;                 // RT_OPT_DIRECT_CAMERA: candidate spheres per tile up to which camera rays are resolved lane by lane (-1 = never; rt_debug_set_direct_camera)
     int coop_min = 12;                  // scenes with at least this many spheres use the cooperative any-hit instance (0 = never)
     int persist = 0;                    // diagnostics: persistent-wavefront instances
     int n_cus = 256;

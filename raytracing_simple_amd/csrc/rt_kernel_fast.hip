@@ -31,6 +31,7 @@
 #define RT_NS fast_w1
 #define RT_KERNEL_NAME rt_trace_fast_w1
 #define RT_OPT_WG_WAVES 1
+#define RT_OPT_DIRECT_CAMERA 1       /* the plain sweep only: the cooperative instances sit at 80 registers and spill with it */
 #include "rt_trace.inc.h"
 #include "rt_opts_reset.h"
 

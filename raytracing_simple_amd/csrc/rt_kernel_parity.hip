@@ -43,6 +43,7 @@
 #define RT_NS parity_w1              /* single-wavefront workgroups (8x8 tiles): scenes with small tables */
 #define RT_KERNEL_NAME rt_trace_parity_w1
 #define RT_OPT_WG_WAVES 1
+#define RT_OPT_DIRECT_CAMERA 1       /* the plain sweep only: the cooperative instances sit at 80 registers and spill with it */
 #define RT_OPT_MINWAVES 6
 #include "rt_trace.inc.h"
 #include "rt_opts_reset.h"
@@ -197,6 +198,13 @@
 #include "rt_trace.inc.h"
 #include "rt_opts_reset.h"
 
+#define RT_NS parity_w1_sweptcam     /* A/B: the headline instance with the loop it had before RT_OPT_DIRECT_CAMERA (every camera ray through the sweep) */
+#define RT_KERNEL_NAME rt_trace_parity_w1_sweptcam
+#define RT_OPT_WG_WAVES 1
+#define RT_OPT_MINWAVES 6
+#include "rt_trace.inc.h"
+#include "rt_opts_reset.h"
+
 #define RT_NS parity_tl              /* the shipped shape + device wall-clock logging (P.timelog / P.wavelog) */
 #define RT_KERNEL_NAME rt_trace_parity_tl
 #define RT_OPT_TIMELOG 1
@@ -238,6 +246,7 @@ static const Instance kParityInstances[] = {
     { parity_persist_coop::rt_trace_parity_persist_coop, "rt_trace_parity_persist_coop", 4, kTabSweepLds, kRolePersistCoop,
       kInstPersistent | kInstNoTileCost | kInstStaticCoop },
     { parity_tl::rt_trace_parity_tl, "rt_trace_parity_tl", 4, kTabSweepLds, kRoleTimelog, 0 },
+    { parity_w1_sweptcam::rt_trace_parity_w1_sweptcam, "rt_trace_parity_w1_sweptcam", 1, kTabSweepLds, kRoleNone, 0 },
 #endif
 };
 

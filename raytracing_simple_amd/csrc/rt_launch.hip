@@ -77,6 +77,7 @@ rt::LaunchParams make_params(rt_ctx *c, int n_samples) {
     p.inv_h = 1.f / (float)c->h;
     p.regen_gate = c->regen_gate > 0 ? c->regen_gate : (c->scene.n_spheres <= 512 ? 8 : 1);
     p.coop_kmax = c->coop_kmax;
+    p.direct_max = c->direct_max;
     p.tiles_x = (int)tiles_per_row(c);
     p.n_tiles = (int)tile_count(c);
     return p;

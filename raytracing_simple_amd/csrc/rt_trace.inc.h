@@ -22,6 +22,7 @@
 // consumes its own RNG stream in the reference order, so results do not depend on this.
 #include <hip/hip_runtime.h>
 
+#include "rt_candidates.h"
 #include "rt_detmath.h"
 #include "rt_device.h"
 
@@ -46,6 +47,10 @@
 //                         (rt_walk.inc.h, its own kernel body); 2: the same with a census of its steps (diagnostics)
 //   RT_OPT_GLOBAL_TABLES  tables beyond the LDS budget are read where they lie in HBM / L2 (the plain sweep: through the scalar cache)
 //   RT_OPT_MINWAVES       launch bound: wavefronts per SIMD the register allocation must allow
+//   RT_OPT_DIRECT_CAMERA  1: a wavefront whose tile can reach only a few spheres (rt_candidates.h, one ballot in the prologue) runs the loop
+//                         ROTATED -- a regenerating lane resolves its camera ray itself against those 0..4 spheres, and the wave-wide sweep
+//                         carries bounce rays only; every other wavefront keeps the old order of a trip (the staged sweep instances; tables in
+//                         HBM / L2, the walk and the diagnostics arms have the old loop only)
 // Diagnostics build only:
 //   RT_OPT_PERSIST        persistent wavefronts: the grid only fills the machine, each wavefront pulls 8x8 pixel tiles
 //                         from a global queue and hands their pixels to its lanes one by one as lanes finish
@@ -68,6 +73,12 @@
 #endif
 #ifndef RT_OPT_PERSIST
 #define RT_OPT_PERSIST 0
+#endif
+#ifndef RT_OPT_DIRECT_CAMERA
+#define RT_OPT_DIRECT_CAMERA 0
+#endif
+#if RT_OPT_DIRECT_CAMERA && (RT_OPT_GLOBAL_TABLES || RT_OPT_WALK || RT_OPT_PERSIST || RT_OPT_STAMPS)
+#error "RT_OPT_DIRECT_CAMERA is for the staged sweep instances only"
 #endif
 // Fused mode, diagnostics build only (the experiment VERDICT r4 item 1c asked for, profiles/r05_fast_gate.jsonl): every DECISION of
 // a path -- the sphere test's discriminant, root and epsilon compares (.cl:173-201), which side of a light and of the surface a
@@ -703,8 +714,49 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
     if (tid < 12) s_census[tid] = 0;
     __syncthreads();
 #endif
+#if RT_OPT_DIRECT_CAMERA
+    // The tile's candidate spheres (rt_candidates.h): lane i classifies sphere i, one ballot.  What the loop keeps of it is ONE scalar
+    // register (the loop fills the scalar file: the 64-bit mask cost the cooperative instances two spilled registers): the count in bits
+    // 24.., the first kCandPacked indices, ascending, in 6 bits each below.  A count of 127 says "not rotated": beyond 64 spheres (no
+    // certificate) and on a tile with more candidates than P.direct_max (<= kCandPacked by the host's check; silhouette tiles of
+    // many-sphere scenes, every tile of a closed box -- the camera is inside a wall) the wavefront runs the trips in their old order,
+    // [regenerate] -> [sweep] -> [shade], camera rays through the sweep: a subset of the lanes resolving near-full candidate lists one by
+    // one would repeat the sweep at partial lanes.
+    uint32_t cand_pack = 127u << 24;
+    if (n <= kCandMaxSpheres) {
+        const CandCamera cc = { { P.cam.orig.x, P.cam.orig.y, P.cam.orig.z }, { P.cam.dir.x, P.cam.dir.y, P.cam.dir.z },
+                                { P.cam.x.x, P.cam.x.y, P.cam.x.z }, { P.cam.y.x, P.cam.y.y, P.cam.y.z }, P.inv_w, P.inv_h };
+        const int cx0 = tile_bx * kTileW + wave * 8, clr0 = tile_by * kTileH;
+        const int cy0 = cand_image_row(clr0, P.rank, P.nranks, P.tile_rows), cy1 = cand_image_row(clr0 + 7, P.rank, P.nranks, P.tile_rows);
+        bool is_cand = false;
+        if ((uint32_t)lane < n) {
+            const float4 g = s_geom[lane];
+            is_cand = tile_sphere_candidate(cc, cx0, cx0 + 7, cy0, cy1, g.x, g.y, g.z, g.w);
+        }
+        unsigned long long m = __builtin_amdgcn_ballot_w64(is_cand);
+        if ((int)__popcll(m) <= P.direct_max) {
+            cand_pack = (uint32_t)__popcll(m) << 24;
+            for (uint32_t k = 0; m != 0ull; ++k, m &= m - 1ull) cand_pack |= (uint32_t)(__ffsll((long long)m) - 1) << (6u * k);
+        }
+    }
+    // The rotated loop: [fold a finished path, regenerate, resolve the camera ray against the candidates] -> [shade] -> [sweep the rays
+    // shading produced].  (t, id) is the lane's hit record across the back edge: written by the regeneration step or by the sweep at the
+    // end of the last trip, read by shading; t = 1e20 on a lane that is not waiting for a new path says its path has ended (a miss, an
+    // emitter, the depth limit) and its sample is folded at the top of the next trip, where the lane regenerates in the same trip.
+    // `rotated` is wave-uniform and fixed for the launch (formed from cand_pack where it is used: no register of its own).
+#define RT_ROTATED ((cand_pack >> 24) != 127u)
+    float t = 1e20f;
+    uint32_t id = 0;
+#endif
     for (;;) {
         RT_STAMP(8);
+#if RT_OPT_DIRECT_CAMERA
+        if (RT_ROTATED && !need_ray && !(t < 1e20f)) {
+            acc = fold_sample(acc, rad, s, P.first_sample, s_k2, k2_in_lds);
+            s += 1;
+            need_ray = true;
+        }
+#endif
         // The wave-level decisions below (ballots) are only meaningful if ALL lanes that are
         // still in the loop execute them together.  A `continue` for the waiting lanes gives the
         // loop a second back edge, and the compiler is then free to spin the waiting lanes
@@ -822,9 +874,34 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
             depth = 0;
             after_specular = true;
             need_ray = false;
+#if RT_OPT_DIRECT_CAMERA
+            // ---- the camera ray's closest hit, .cl:215-232, over the tile's candidates in scene order: the sweep's own test on the
+            // sweep's own operands; a sphere left out has a negative discriminant for every ray of the tile and changes neither t nor id
+            if (RT_ROTATED) {
+                t = 1e20f;
+                id = 0;
+                c_closest += 1;
+                for (uint32_t left = cand_pack >> 24, pk = cand_pack; left != 0u; --left, pk >>= 6) {
+                    const uint32_t i = pk & 63u;
+                    const HitPre p0 = hit_pre(s_geom[i], o, d);
+                    if (wave_any_nonneg(p0.det)) {
+                        const HitRoots h0 = hit_roots(p0);
+                        if (h0.hit && h0.t < t) { t = h0.t; id = i; }
+                    }
+                }
+            }
+#endif
         }
 
         // ---- closest hit, .cl:215-232: wave-uniform sweep, LDS broadcast reads ----
+#if RT_OPT_DIRECT_CAMERA
+        if (!RT_ROTATED) {          // (the old order of a trip: every ray, camera rays included, is swept here)
+            t = 1e20f;
+            id = 0;
+            sweep_closest(s_geom, n, o, d, t, id, st_roots_c);
+            c_closest += 1;
+        }
+#else
         float t = 1e20f;
         uint32_t id = 0;
         RT_STAMP(1);
@@ -832,6 +909,7 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
         sweep_closest(s_geom, n, o, d, t, id, st_roots_c);
         RT_STAMP_ROOTS(10, st_roots_c);
         c_closest += 1;
+#endif
 
         bool path_done = false;
         bool is_diff = false, is_gloss = false;   // what the hit asks for next
@@ -1035,12 +1113,31 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
             if (depth >= kMaxDepth) path_done = true;                      // .cl:320
         }
 
+#if RT_OPT_DIRECT_CAMERA
+        // ---- rotated: closest hit of the rays shading produced, .cl:215-232: wave-uniform sweep, LDS broadcast reads; skipped when no
+        // lane of the wavefront has a ray.  A path that ended keeps t = 1e20 for the fold at the top of the next trip.
+        if (RT_ROTATED) {
+            t = 1e20f;
+            id = 0;
+            if (__builtin_amdgcn_ballot_w64(!path_done) != 0ull) {
+                if (!path_done) {
+                    sweep_closest(s_geom, n, o, d, t, id, st_roots_c);
+                    c_closest += 1;
+                }
+            }
+        } else if (path_done) {
+            acc = fold_sample(acc, rad, s, P.first_sample, s_k2, k2_in_lds);
+            s += 1;
+            need_ray = true;
+        }
+#else
         if (path_done) {
             RT_STAMP(9);
             acc = fold_sample(acc, rad, s, P.first_sample, s_k2, k2_in_lds);
             s += 1;
             need_ray = true;
         }
+#endif
         }   // if (!idle)
     }
 
@@ -1133,6 +1230,7 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
     }
 #endif
 }
+#undef RT_ROTATED
 #endif   // !RT_OPT_WALK
 
 #if !defined(RT_VARIANT_KERNEL)
