@@ -656,6 +656,99 @@ RT_API int rt_render_adaptive_filtered(rt_ctx *a, rt_ctx *b, double tile_psnr_db
 RT_API int rt_render_adaptive_filtered_tiles(rt_ctx *a, rt_ctx *b, double tile_psnr_db, int min_passes, int passes_per_check, int max_passes,
                                              const rt_denoise_params *p, rt_frame_error *last, int *checks);
 
+/* ---- feature planes from camera rays, and NL-means guided by them -----------------------------------
+ * Every filter above sees colour only.  At 4 to 16 passes per half the variance estimate of two halves is itself noisy, and colour-only NL-means then
+ * blurs across object and wall boundaries.  Rousselle, Manzi and Zwicker (2013) add noise-free geometry features -- albedo, normal, depth --
+ * that can only RESTRICT a weight.  THIS LIBRARY'S OWN EXTENSION: it reproduces no reference frame and touches no render kernel, and no call above
+ * changes behaviour while no guide is set.  The planes are useful on their own: what lies under every pixel.
+ *
+ * THE FEATURE PLANE is F[h][w][8], 32 bytes per pixel, in the colour plane's row order (row h - 1 - y for image row y, .cl:579): words 0-2 the albedo,
+ * 3-5 the normal, 6 the distance, 7 the bits of the scene index as uint32.  Rules 10-12 are binary32, uncontracted, IEEE division and square root, in
+ * the written order -- ALWAYS parity's arithmetic, whatever rt_set_mode says.
+ *  10. the ray: GenerateCameraRay (.cl:494-549) with both random numbers 0.5, r1 = r2 = 0.0f: kcx = ((float)x + 0.0f) * (1.f / w) - 0.5f, kcy alike;
+ *      rdir = (cam.x * kcx + cam.y * kcy) + cam.dir per component; o = 0.1f * rdir + cam.orig; d = rdir * (1.f / sqrt(rdir . rdir)).
+ *  11. the hit: Intersect (.cl:215-232) over every record in scene order with SphereIntersect (.cl:173-201): t = 1e20f; a record replaces it when
+ *      dist != 0.f && dist < t, so equal distances keep the lowest index.  A hit is t < 1e20f.
+ *  12. the values.  On a hit P = o + d * t, n = vnorm(P - p_id) (.cl:346-347, NOT turned towards the ray), albedo = c_id + e_id per channel,
+ *      word 6 = t, word 7 = id.  On a miss seven 0.0f and 0xFFFFFFFF.  Non-finite records behave as in the reference: a NaN discriminant never
+ *      hits; a zero-radius hit gives a NaN normal, which is stored as it is.
+ * The kernel is a plain sweep, pixels x records tests, made ONCE per scene and camera: one lane per pixel over 8x8 tiles, the geometry table staged
+ * in LDS in chunks of 1024 records with a barrier between chunks, so any count up to RT_MAX_SPHERES works.  THE HIERARCHY IS DELIBERATELY NOT USED:
+ * the plane is formed once where a frame takes hundreds of passes, and the sweep's answer is the reference's by construction.
+ *
+ * THE GUIDE.  Rules 13-14 extend rules 1-9; the symbols are those of the denoising sections.
+ *  13. the feature distance of a pixel p and q = p + o inside the image.  ia = 1.0f / (k_albedo * k_albedo), in and id alike.
+ *      PHIa = ((a0 * a0 + a1 * a1) + a2 * a2) * ia with a_c = F[p][c] - F[q][c];  PHIn the same over words 3-5, times in;
+ *      r = (t_p - t_q) / ((t_p + t_q) + 1e-10f), PHId = (r * r) * id.  PHI = 0.0f; then for PHIa, PHIn, PHId in that order: if (term > PHI) PHI = term
+ *      (a NaN term constrains nothing).  wf = 1.0f / (1.0f + PHI * (1.0f + PHI * 0.5f)).
+ *  14. in rule 5, for an offset other than (0, 0) that is not skipped, wgt = wf < wgt ? wf : wgt.  Nothing else of rules 1-9 changes: the skips, the
+ *      centre weight, the offset order, the double clamp.  In the pair filter one wf, formed once, serves both directions.
+ * So: with R = 0 the output is the input; with every k = 1e18f and finite features, or with a constant feature plane, wf is exactly 1 and the guided
+ * result equals the unguided one bit for bit.
+ * MEASURED, in numpy on a CPU before any kernel existed (the prototype), with frames of this project's oracle alone: halves on seed streams 1 and 2,
+ * truth 2048 passes of the default stream, PSNR over 8-bit channels packed by clip ** (1 / 2.2) * 255 + .5, the filter's defaults, the guide's
+ * defaults {0.15, 0.2, 0.05}; "k 0.6" is the same guide with the filter's k raised to 0.6.  96x64, dB:
+ *     scene           passes per half    merged    NL-means unguided    guided    guided, k 0.6
+ *     Demo                  4            20.41         27.62            27.83        27.97
+ *     Demo                 16            26.43         31.46            31.57        31.30
+ *     cornell.scn           4            17.14         25.05            25.67        26.01
+ *     cornell.scn          16            21.16         28.50            29.11        29.22
+ *     simple.scn            4            24.83         29.67            30.94        30.73
+ *     simple.scn           16            31.69         34.18            34.90        34.20
+ * AND BY rt_denoise_guided_planes ITSELF (tests/test_guided_cpu.py asserts half of each gain): the scenes of tests/golden at 96x96, 4 passes per half,
+ * truth 1024 oracle passes, the same pack, dB:
+ *     scene                          unguided    guided     gain      (the prototype's gain at 96x64)
+ *     cornell (18 records)            24.76       25.30     +0.54           +0.6
+ *     simple (10 records)             29.04       30.29     +1.24           +1.3
+ *     Demo                            27.56       28.15     +0.59           +0.2
+ * The gain is largest on scenes of diffuse surfaces and smallest on the Demo scene, which is mostly glass.
+ * ON THE DEVICE: a guided workgroup stages words 0-6 of its tile and an R-halo beside the colour planes, 28 (32 + 2R)(8 + 2R) bytes more LDS -- about
+ * 58 KiB for the pair kernel at the defaults, 92 KiB at R 8, P 2 (the dynamic-LDS limit is raised for it).
+ * MEASURED on an MI355X by tools/guided_probe.py (profiles/r21_guided.jsonl; device time between two events, medians; NO TIME IS PROMISED):
+ *   rt_features_async, 800x600 / 1920x1080, beside ONE pass of the same scene:  Demo 0.010 / 0.022 ms (a pass 0.042 / 0.10);  1024 spheres 0.26 / 0.92
+ *   (0.22 / 0.58);  8192 spheres 1.96 / 6.04 (0.42 / 1.02);  262 144 spheres 60 / 193 (2.0 / 4.9).  The plain sweep costs one pass at a thousand records
+ *   and forty at RT_MAX_SPHERES -- once per scene and camera, where a frame takes hundreds of passes.
+ *   the filters at 1920x1080, unguided / guided:  rt_denoise_async 0.94 / 1.42 ms;  rt_denoise_pair_async 1.58 / 2.79;  rt_denoise_pair_tiles_async with
+ *   half of the groups selected 0.85 / 1.45.  The unguided kernels are the machine code they were before the guide existed.
+ *   the table above from rendered contexts, filtered on the device: unguided / guided 27.62 / 27.83 and 31.46 / 31.57 (Demo, 4 and 16 passes),
+ *   25.05 / 25.67 and 28.50 / 29.11 (cornell), 29.67 / 30.94 and 34.18 / 34.90 (simple): the prototype's figures to the last digit.              */
+typedef struct { float k_albedo, k_normal, k_depth; uint32_t reserved; } rt_guide_params;   /* 16 bytes; each k finite and > 0, reserved 0 */
+
+/* {0.15f, 0.2f, 0.05f, 0}.  Needs no device.                                                                                   */
+RT_API void rt_guide_defaults(rt_guide_params *g);
+
+/* Form the feature plane of ctx's scene and camera on `hip_stream`, without a host wait, into plane memory that ctx owns (allocated on first use, freed
+ * by rt_destroy).  Ordered behind everything the context has queued: a table rebuild that rt_update_spheres_async left pending runs first.
+ * The plane is CURRENT from this call until rt_set_scene, rt_update_spheres_async or rt_set_camera on the context -- whatever they set.  Launches,
+ * resets, merges and filters do not touch it: it depends on scene and camera alone.  Nothing else of the context changes.
+ * RT_ERR_STATE without scene or camera; RT_ERR_ARG for a null, multi-device or sharded context.                                               */
+RT_API int rt_features_async(rt_ctx *ctx, void *hip_stream);
+
+/* The context's feature plane, 8 words per pixel, into HOST memory.  Blocking.  RT_ERR_STATE when the plane is not current; RT_ERR_ARG for a null,
+ * multi-device or sharded context or a null buffer.                                                                                            */
+RT_API int rt_read_features(rt_ctx *ctx, float *out_host);
+
+/* Rules 10-12 as plain host loops over `count` records: what the device is tested against bit for bit.  Needs no device.  RT_ERR_ARG: a null
+ * argument (spheres may be null when count is 0), w or h < 1.                                                                                 */
+RT_API int rt_features_planes(float *out, const rt_sphere *spheres, uint32_t count, const rt_camera *cam, int w, int h);
+
+/* The guide, a per-context setting like rt_set_mode.  NULL = off, the default.  While it is off on both halves every filter call and loop above is
+ * what it was, bit for bit.  Six calls consult it: rt_denoise_async, rt_denoise_pair_async, rt_denoise_pair_tiles_async, rt_render_converged_filtered,
+ * rt_render_adaptive_filtered and rt_render_adaptive_filtered_tiles.  The setting of the two HALVES a and b counts (dst's is ignored): both off, or
+ * both on with the same 16 bytes -- otherwise RT_ERR_STATE.  When on, the feature plane is READ FROM a, and the planes of a and b must both be current
+ * (RT_ERR_STATE otherwise); that they describe one scene and camera is the caller's responsibility, as the selections are in
+ * rt_denoise_pair_tiles_async.  Exchanging a and b keeps exchanging FA and FB.  A refused call changes nothing.  As with differing rt_denoise_params,
+ * changing the guide does not by itself make cross-filtered planes stale.
+ * RT_ERR_ARG: a null, multi-device or sharded context; a k that is not finite or <= 0; reserved != 0.                                            */
+RT_API int rt_set_denoise_guide(rt_ctx *ctx, const rt_guide_params *g);
+
+/* rt_denoise_planes and rt_denoise_pair_planes under a guide: `feat` is a feature plane of w x h pixels, 8 words each.  With g == NULL they ARE those
+ * functions (feat is not read).  Need no device.  Refusals are theirs, and a null feat or parameters rt_set_denoise_guide refuses.              */
+RT_API int rt_denoise_guided_planes(float *out, const float *merged, const float *a, const float *b, const float *feat, int w, int h,
+                                    const rt_denoise_params *p, const rt_guide_params *g);
+RT_API int rt_denoise_pair_guided_planes(float *out_a, float *out_b, const float *a, const float *b, const float *feat, int w, int h,
+                                         const rt_denoise_params *p, const rt_guide_params *g);
+
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it
  * from the scene -- "rt_trace_parity_w1" (few spheres: one wavefront per workgroup), "..._coop_w1" / "..._coop"

@@ -26,7 +26,9 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_tile_passes", "rt_select_tiles", "rt_render_tiles_async", "rt_render_adaptive",
            "rt_denoise_defaults", "rt_denoise_async", "rt_denoise_planes",
            "rt_denoise_pair_async", "rt_denoise_pair_planes", "rt_read_filtered", "rt_compare_filtered_async", "rt_compare_filtered",
-           "rt_render_converged_filtered", "rt_render_adaptive_filtered", "rt_denoise_pair_tiles_async", "rt_render_adaptive_filtered_tiles"]
+           "rt_render_converged_filtered", "rt_render_adaptive_filtered", "rt_denoise_pair_tiles_async", "rt_render_adaptive_filtered_tiles",
+           "rt_guide_defaults", "rt_features_async", "rt_read_features", "rt_features_planes", "rt_set_denoise_guide",
+           "rt_denoise_guided_planes", "rt_denoise_pair_guided_planes"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -70,6 +72,14 @@ class DenoiseParams(C.Structure):
 
     def as_dict(self):
         return {"search_radius": int(self.search_radius), "patch_radius": int(self.patch_radius), "alpha": float(self.alpha), "k": float(self.k)}
+
+
+class GuideParams(C.Structure):
+    """include/rt_api.h rt_guide_params (16 bytes): k_albedo, k_normal, k_depth, reserved (0)."""
+    _fields_ = [("k_albedo", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"k_albedo": float(self.k_albedo), "k_normal": float(self.k_normal), "k_depth": float(self.k_depth), "reserved": int(self.reserved)}
 
 
 class _Scene(C.Structure):
@@ -161,6 +171,13 @@ def load_library(diag=False):
         "rt_render_adaptive_filtered": (i32, [vp, vp, C.c_double, i32, i32, i32, C.POINTER(DenoiseParams), C.POINTER(FrameError), C.POINTER(i32)]),
         "rt_denoise_pair_tiles_async": (i32, [vp, vp, C.POINTER(DenoiseParams), vp]),
         "rt_render_adaptive_filtered_tiles": (i32, [vp, vp, C.c_double, i32, i32, i32, C.POINTER(DenoiseParams), C.POINTER(FrameError), C.POINTER(i32)]),
+        "rt_guide_defaults": (None, [C.POINTER(GuideParams)]),
+        "rt_features_async": (i32, [vp, vp]),
+        "rt_read_features": (i32, [vp, vp]),
+        "rt_features_planes": (i32, [vp, vp, u32, vp, i32, i32]),
+        "rt_set_denoise_guide": (i32, [vp, C.POINTER(GuideParams)]),
+        "rt_denoise_guided_planes": (i32, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(DenoiseParams), C.POINTER(GuideParams)]),
+        "rt_denoise_pair_guided_planes": (i32, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(DenoiseParams), C.POINTER(GuideParams)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -535,6 +552,22 @@ class RtContext:
         render_tiles_async has just rendered made current again, every other pixel kept."""
         self._check(self._lib.rt_denoise_pair_tiles_async(self._h, other._h if other is not None else None, _denoise_params(params), C.c_void_p(stream or 0)))
 
+    # --- feature planes and the guide (rt_features.hip) --------------------------------------------
+    def features_async(self, stream=None):
+        """rt_features_async: the feature plane of this context's scene and camera, formed on the device (read_features)."""
+        self._check(self._lib.rt_features_async(self._h, C.c_void_p(stream or 0)))
+
+    def read_features(self):
+        """rt_read_features: the feature plane, float32 [h][w][8] in the colour plane's row order: albedo, normal, distance and -- word 7, view it as
+        uint32 -- the scene index (0xFFFFFFFF: the sky)."""
+        out = np.zeros((self.h, self.w, 8), np.float32)
+        self._check(self._lib.rt_read_features(self._h, _ptr(out)))
+        return out
+
+    def set_denoise_guide(self, guide=None):
+        """rt_set_denoise_guide: None switches the guide off; a GuideParams or a dict of fields laid over guide_defaults() switches it on."""
+        self._check(self._lib.rt_set_denoise_guide(self._h, _guide_params(guide)))
+
     def read_filtered(self):
         """rt_read_filtered: the cross-filtered plane, float32 [3 * w * h] as read_colors() lays it out."""
         out = np.zeros(3 * self.w * self.h, np.float32)
@@ -697,6 +730,69 @@ def denoise_pair_planes(a, b, w, h, params=None):
             raise ValueError("expected %d floats, got %d" % (3 * w * h, x.size))
     out_a, out_b = np.zeros(3 * w * h, np.float32), np.zeros(3 * w * h, np.float32)
     _check(load_library().rt_denoise_pair_planes(_ptr(out_a), _ptr(out_b), _ptr(planes[0]), _ptr(planes[1]), w, h, _denoise_params(params)))
+    return out_a, out_b
+
+
+def guide_defaults():
+    """rt_guide_defaults: GuideParams {0.15, 0.2, 0.05, 0}.  Needs no device."""
+    g = GuideParams()
+    load_library().rt_guide_defaults(C.byref(g))
+    return g
+
+
+def _guide_params(guide):
+    """None (no guide), a GuideParams, or a dict of fields laid over the defaults -> what the C call takes."""
+    if guide is None or isinstance(guide, GuideParams):
+        return C.byref(guide) if guide is not None else None
+    g = guide_defaults()
+    for name, value in dict(guide).items():
+        if name not in ("k_albedo", "k_normal", "k_depth", "reserved"):
+            raise ValueError("rt_guide_params has no field %r" % name)
+        setattr(g, name, value)
+    return C.byref(g)
+
+
+def features_planes(spheres, cam, w, h):
+    """rt_features_planes: the feature plane of HOST records and a camera, float32 [h][w][8] (RtContext.read_features).  Needs no device."""
+    sph = as_spheres(spheres)
+    camera = as_camera(cam)
+    out = np.zeros((h, w, 8), np.float32)
+    _check(load_library().rt_features_planes(_ptr(out), _ptr(sph) if len(sph) else None, len(sph), _ptr(camera), w, h))
+    return out
+
+
+def _feature_plane(feat, w, h, guide):
+    if guide is None:
+        return None
+    f = np.ascontiguousarray(feat, dtype=np.float32).reshape(-1)
+    if f.size != 8 * w * h:
+        raise ValueError("expected %d floats, got %d" % (8 * w * h, f.size))
+    return f
+
+
+def denoise_guided_planes(merged, a, b, feat, w, h, params=None, guide=None):
+    """rt_denoise_guided_planes: denoise_planes under a guide (None: exactly denoise_planes; `feat` is then not read).  Needs no device."""
+    planes = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (merged, a, b)]
+    for x in planes:
+        if x.size != 3 * w * h:
+            raise ValueError("expected %d floats, got %d" % (3 * w * h, x.size))
+    f = _feature_plane(feat, w, h, guide)
+    out = np.zeros(3 * w * h, np.float32)
+    _check(load_library().rt_denoise_guided_planes(_ptr(out), _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), _ptr(f) if f is not None else None, w, h,
+                                                   _denoise_params(params), _guide_params(guide)))
+    return out
+
+
+def denoise_pair_guided_planes(a, b, feat, w, h, params=None, guide=None):
+    """rt_denoise_pair_guided_planes: denoise_pair_planes under a guide (None: exactly denoise_pair_planes).  Needs no device."""
+    planes = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (a, b)]
+    for x in planes:
+        if x.size != 3 * w * h:
+            raise ValueError("expected %d floats, got %d" % (3 * w * h, x.size))
+    f = _feature_plane(feat, w, h, guide)
+    out_a, out_b = np.zeros(3 * w * h, np.float32), np.zeros(3 * w * h, np.float32)
+    _check(load_library().rt_denoise_pair_guided_planes(_ptr(out_a), _ptr(out_b), _ptr(planes[0]), _ptr(planes[1]), _ptr(f) if f is not None else None, w, h,
+                                                        _denoise_params(params), _guide_params(guide)))
     return out_a, out_b
 
 

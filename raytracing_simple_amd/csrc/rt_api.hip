@@ -309,6 +309,7 @@ RT_API void rt_destroy(rt_ctx *c) {
         (void)hipFree(c->d_denoise_var);
         (void)hipFree(c->d_filtered);
         (void)hipFree(c->d_filtered_px);
+        (void)hipFree(c->d_features);
         (void)hipFree(c->tiles.d_passes);
         (void)hipFree(c->tiles.d_selected);
         (void)hipFree(c->tiles.d_list);
@@ -358,6 +359,7 @@ RT_API int rt_set_scene(rt_ctx *c, const rt_sphere *spheres, uint32_t count) {
     if (count > 0 && !spheres) return fail(RT_ERR_ARG, "spheres is null");
     if (count > RT_MAX_SPHERES) return fail(RT_ERR_ARG, "%u spheres > RT_MAX_SPHERES (%u)", count, RT_MAX_SPHERES);
     if (c->multi) return rt::multi_set_scene(c, spheres, count);
+    c->features_current = false;        // (whatever is set: the feature plane is current UNTIL this call)
     // the very scene the context already holds (a host that sets it before every frame): nothing to do
     if (c->have_scene && count == c->scene.n_spheres && c->h_spheres.size() == count &&
         (count == 0 || memcmp(c->h_spheres.data(), spheres, (size_t)count * sizeof(rt_sphere)) == 0))
@@ -386,6 +388,7 @@ RT_API int rt_update_spheres_async(rt_ctx *c, uint32_t first, uint32_t count, co
     if (c->multi) return rt::multi_update_spheres(c, first, count, spheres);
     const uint32_t n = c->scene.n_spheres;
     if (first > n || count > n - first) return fail(RT_ERR_ARG, "spheres [%u, %u) of a scene of %u", first, first + count, n);
+    c->features_current = false;
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     if (count) memcpy(c->h_spheres.data() + first, spheres, (size_t)count * sizeof(rt_sphere));
@@ -400,6 +403,7 @@ RT_API int rt_set_camera(rt_ctx *c, const rt_camera *cam) {
     if (c->multi) return rt::multi_set_camera(c, cam);
     if (!c->have_cam || memcmp(&c->cam, cam, sizeof *cam) != 0) c->order.scene_or_camera_moved();
     c->cam = *cam;                      // a kernel argument: nothing to upload
+    c->features_current = false;
     c->have_cam = true;
     return RT_OK;
 }

@@ -237,6 +237,7 @@ int render_converged(rt_ctx *a, rt_ctx *b, const char *call, const rt_denoise_pa
                      rt_frame_error *last, int *checks) {
     int rc = same_frame(a, b, call, "a", "b");
     if (rc == RT_OK) rc = check_paired_render(a, b, call, last, passes_per_check, target_psnr_db, max_passes);
+    if (rc == RT_OK && filter) rc = guide_refuse(a, b, call);      // (ahead of the first pass: a refused call changes nothing)
     if (rc == RT_OK) rc = select_device(a);
     if (rc == RT_OK) rc = ensure_scratch(a);
     if (rc != RT_OK) return rc;
@@ -338,6 +339,7 @@ static int render_adaptive(rt_ctx *a, rt_ctx *b, const char *call, const rt_deno
     if (rc != RT_OK) return rc;
     if (min_passes < 0) return fail(RT_ERR_ARG, "min_passes %d", min_passes);      // (every refusal ahead of the pass counts' is RT_ERR_ARG: their order does not show)
     rc = check_paired_render(a, b, call, last, passes_per_check, tile_psnr_db, max_passes);
+    if (rc == RT_OK && filter) rc = guide_refuse(a, b, call);      // (ahead of the first pass: a refused call changes nothing)
     if (rc != RT_OK) return rc;
     if (checks) *checks = 0;
     rc = select_device(a);

@@ -20,8 +20,8 @@
 #include <cmath>
 
 #include <atomic>
-#include <type_traits>
 
+#include "rt_denoise.inc.h"
 #include "rt_detmath.h"
 #include "rt_internal.h"
 
@@ -29,33 +29,6 @@ using rt::fail;
 
 extern "C" int rt_host_denoise_params(const rt_denoise_params *p, rt_denoise_params *out);     // rt_host.cpp: the parameter rules (null = defaults)
 
-namespace {
-
-constexpr int kDnTileW = 32, kDnTileH = 8, kDnLanes = kDnTileW * kDnTileH;      // a workgroup's output pixels: four wavefronts, a row of 32 per half-wave
-
-__device__ __forceinline__ int dn_clamp(int v, int n) { return min(max(v, 0), n - 1); }
-
-// .cl:34, the pack kernel's toInt (rt_trace.inc.h to_int): parity's restated powf, or fast mode's exp2 / log2 with the fused multiply-add that
-// unit's contraction makes of g * 255 + .5 (this unit contracts nothing, so it is written out)
-__device__ __forceinline__ uint32_t dn_to_int(float v, bool fast) {
-    const float c = fminf(fmaxf(v, 0.f), 1.f);
-    if (fast) return (uint32_t)(int)__builtin_fmaf(rt::fm_powf(c, 1.f / 2.2f), 255.f, .5f);
-    return (uint32_t)(int)(rt::dm_powf(c, 1.f / 2.2f) * 255.f + .5f);
-}
-
-__device__ __forceinline__ bool dn_finite3(float a, float b, float c) { return fabsf(a) <= FLT_MAX && fabsf(b) <= FLT_MAX && fabsf(c) <= FLT_MAX; }
-
-// What a filter kernel reads and writes per image: the plane, the filtered plane, and -- the halves only -- the filtered plane packed by the toInt
-// of that context's mode
-template <int N>
-struct DnPlanes {
-    const float *img[N];
-    float *out[N];
-    uint32_t *px[N];
-    int fast[N];
-};
-
-}  // namespace
 
 // Rules 1 and 2: one thread per float of a plane row (blockIdx.y walks the rows, so that no index is divided in 64 bits).  V = ((A - B) * 0.5)^2 is
 // formed nine times per float rather than stored: the planes of a frame sit in L2, and a pass of its own over V would cost a plane's traffic more.
@@ -75,161 +48,6 @@ __global__ void __launch_bounds__(256) rt_denoise_variance_kernel(float *__restr
                 sum = (j == -1 && k == -1) ? v : sum + v;
             }
         vs[3 * ((size_t)y * (size_t)w + (size_t)x) + (size_t)c] = sum * (1.0f / 9.0f);
-    }
-}
-
-// Rules 3 to 6 for N images at once: image i takes its weights from guide N - 1 - i -- itself (N = 1: rt_denoise_planes) or the other half (N = 2:
-// rt_denoise_pair_planes, the header's three substitutions).  A workgroup owns the 32x8 output pixels at (x0, y0) of the plane; H = R + P.
-//   LDS: 3 N image planes and three variance planes (Vs; N = 2: Vh = Vs + Vs, the variance of one half) of LW x LH = (32 + 2H) x (8 + 2H) floats,
-//   entry (ly, lx) = the plane at cl(y0 - H + ly, x0 - H + lx) -- one float per lane and read, consecutive lanes on consecutive banks -- then 2 N
-//   buffers of EW x EH = (32 + 2P) x (8 + 2P) floats: e(., o) of every guide, twice.  48 (N + 1)(R + P + 16)(R + P + 4) + 32 N (P + 16)(P + 4) bytes,
-//   59 328 for N = 2 at R 8, P 2: below 64 KiB, no attribute call.
-//   Per offset o: every lane forms e(x, o) for its one or two positions x of the tile and its P-halo (x = the CLAMPED position, its partner cl(x + o):
-//   rule 4's double clamp; x's own planes stay in registers for all offsets; rule 3's alpha * (V[x] + m) and 1e-10f + kk * (V[x] + V[q']) serve every
-//   guide, t, the square and the division are per guide), one barrier, then every pixel sums its (2P + 1)^2 patch from the buffers.  Two sets of
-//   buffers make one barrier per offset enough: offset n + 1 writes the other set while slower lanes still read this one, and the barrier of offset
-//   n + 1 lies between those reads and the writes of offset n + 2.
-//   Bounds: every coordinate that indexes LDS or a plane is clamped to the image first, and a clamped coordinate lies inside the staged window: the
-//   32x8 pixels hold at least one image pixel, so positions clamp into [max(0, x0 - P), min(w - 1, x0 + 31 + P)] (rows alike) and their partners within
-//   R of that, all inside the window [x0 - H, x0 + 31 + H] cut to the image.  kAnyRow: y0 may be NEGATIVE, -7 at the least, with y0 + 7 >= 0 -- the
-//   top group row of an image whose height is no multiple of 8 (rt_denoise_pair_tiles_kernel).  The argument holds as it stands; what is added is that
-//   a lane above the plane's row 0 is outside the image and stores nothing.
-// N = 2 also packs: the words go to the pixel buffer's row (row 0 = bottom: plane row h - 1 - y).
-template <int P, int N, bool kAnyRow>
-__device__ __forceinline__ void dn_body(float *dn_lds, const int x0, const int y0, const DnPlanes<N> &k, const float *__restrict__ vs, int w, int h, int R,
-                                        float alpha, float kk) {
-    constexpr int EW = kDnTileW + 2 * P, EH = kDnTileH + 2 * P, EN = EW * EH;      // 256 / 340 / 432 positions: at most two per lane
-    const int H = R + P, LW = kDnTileW + 2 * H, LH = kDnTileH + 2 * H, LN = LW * LH;
-    float *const sI = dn_lds, *const sV = dn_lds + 3 * N * LN, *const sE = dn_lds + 3 * (N + 1) * LN;     // image i, channel c: sI + (3 i + c) LN
-    const int tid = (int)threadIdx.x;
-    const int wx0 = x0 - H, wy0 = y0 - H;                   // the window's origin in the plane
-
-    for (int l = tid; l < LN; l += kDnLanes) {
-        const int ly = l / LW, lx = l - ly * LW;
-        const size_t at = 3 * ((size_t)dn_clamp(wy0 + ly, h) * (size_t)w + (size_t)dn_clamp(wx0 + lx, w));
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = vs[at + c];
-#pragma unroll
-            for (int i = 0; i < N; ++i) sI[(3 * i + c) * LN + l] = k.img[i][at + c];
-            sV[c * LN + l] = N == 2 ? v + v : v;
-        }
-    }
-    __syncthreads();
-
-    // this lane's positions of the tile and its P-halo: plane coordinates (clamped), and what rule 3 reads of the position itself
-    int ex[2], ey[2];
-    float pi[2][N][3], pv[2][3];
-    bool have[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        have[s] = tid + s * kDnLanes < EN;
-        const int idx = have[s] ? tid + s * kDnLanes : 0, iy = idx / EW, ix = idx - iy * EW;
-        ex[s] = dn_clamp(x0 - P + ix, w);
-        ey[s] = dn_clamp(y0 - P + iy, h);
-        const int l = (ey[s] - wy0) * LW + (ex[s] - wx0);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-#pragma unroll
-            for (int i = 0; i < N; ++i) pi[s][i][c] = sI[(3 * i + c) * LN + l];
-            pv[s][c] = sV[c * LN + l];
-        }
-    }
-
-    const int tx = tid & (kDnTileW - 1), ty = tid / kDnTileW, px = x0 + tx, py = y0 + ty;
-    const bool inside = px < w && py < h && (!kAnyRow || py >= 0);
-    const float inv = 1.0f / (float)(3 * (2 * P + 1) * (2 * P + 1));
-    float num[N][3], den[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) num[i][0] = num[i][1] = num[i][2] = den[i] = 0.0f;
-    int buf = 0;
-    for (int oy = -R; oy <= R; ++oy)
-        for (int ox = -R; ox <= R; ++ox) {
-            const bool centre = oy == 0 && ox == 0;
-            float *const e = sE + (N * buf) * EN;           // e(., o) of guide g: e + g * EN
-            if (!centre) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    if (!have[s]) continue;
-                    const int l = (dn_clamp(ey[s] + oy, h) - wy0) * LW + (dn_clamp(ex[s] + ox, w) - wx0);    // q' = cl(x + o)
-                    float d[N][3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {           // rule 3, for every guide
-                        const float qv = sV[c * LN + l];
-                        const float m = qv < pv[s][c] ? qv : pv[s][c];
-                        const float off = alpha * (pv[s][c] + m), dnm = 1e-10f + kk * (pv[s][c] + qv);
-#pragma unroll
-                        for (int g = 0; g < N; ++g) {
-                            const float t = pi[s][g][c] - sI[(3 * g + c) * LN + l];
-                            d[g][c] = (t * t - off) / dnm;
-                        }
-                    }
-#pragma unroll
-                    for (int g = 0; g < N; ++g) e[g * EN + tid + s * kDnLanes] = (d[g][0] + d[g][1]) + d[g][2];
-                }
-            }
-            __syncthreads();
-            buf ^= 1;
-            const int qx = px + ox, qy = py + oy;
-            if (inside && qx >= 0 && qx < w && qy >= 0 && qy < h) {   // rule 5: p + o outside the image is skipped
-                const int l = (qy - wy0) * LW + (qx - wx0);
-                float q[N][3], wgt[N];
-                bool take[N];
-#pragma unroll
-                for (int i = 0; i < N; ++i) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) q[i][c] = sI[(3 * i + c) * LN + l];
-                    wgt[i] = 1.0f;
-                    take[i] = true;
-                }
-                if (!centre) {
-                    float S[N];                             // rule 4: the entries of the tile's P-halo ARE the clamped positions
-#pragma unroll
-                    for (int g = 0; g < N; ++g) S[g] = 0.f;
-#pragma unroll
-                    for (int dy = 0; dy <= 2 * P; ++dy)
-#pragma unroll
-                        for (int dx = 0; dx <= 2 * P; ++dx)
-#pragma unroll
-                            for (int g = 0; g < N; ++g) {
-                                const float v = e[g * EN + (ty + dy) * EW + tx + dx];
-                                S[g] = (dy == 0 && dx == 0) ? v : S[g] + v;
-                            }
-#pragma unroll
-                    for (int i = 0; i < N; ++i) {
-                        const float T = S[N - 1 - i] * inv;
-                        take[i] = T == T && dn_finite3(q[i][0], q[i][1], q[i][2]);
-                        const float g = T > 0.f ? T : 0.f;
-                        wgt[i] = 1.0f / (1.0f + g * (1.0f + g * 0.5f));
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < N; ++i)
-                    if (take[i]) {                          // rule 6
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) num[i][c] = num[i][c] + wgt[i] * q[i][c];
-                        den[i] = den[i] + wgt[i];
-                    }
-            }
-        }
-    if (!inside) return;
-    const size_t at = 3 * ((size_t)py * (size_t)w + (size_t)px);
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        float f0 = num[i][0] / den[i], f1 = num[i][1] / den[i], f2 = num[i][2] / den[i];
-        if constexpr (N == 2) {
-            if (R == 0) {                                   // the window is the pixel itself: the halves, bit for bit
-                const int l = (py - wy0) * LW + (px - wx0);
-                f0 = sI[(3 * i) * LN + l], f1 = sI[(3 * i + 1) * LN + l], f2 = sI[(3 * i + 2) * LN + l];
-            }
-        }
-        k.out[i][at] = f0;
-        k.out[i][at + 1] = f1;
-        k.out[i][at + 2] = f2;
-        if constexpr (N == 2) {
-            const bool fast = k.fast[i] != 0;
-            k.px[i][(size_t)(h - 1 - py) * (size_t)w + (size_t)px] = dn_to_int(f0, fast) | (dn_to_int(f1, fast) << 8) | (dn_to_int(f2, fast) << 16);
-        }
     }
 }
 
@@ -273,11 +91,6 @@ namespace {
 
 std::atomic<uint64_t> g_pair_calls{0};                     // numbers the calls that make cross-filtered planes (FrameState::filtered_pair)
 
-size_t lds_bytes(int N, int R, int P) {                    // dn_body's layout
-    const int H = R + P;
-    return ((size_t)3 * (N + 1) * (kDnTileW + 2 * H) * (kDnTileH + 2 * H) + (size_t)2 * N * (kDnTileW + 2 * P) * (kDnTileH + 2 * P)) * sizeof(float);
-}
-
 bool packs_fast(const rt_ctx *c) { return c->mode == RT_MODE_FAST || c->mode >= 200; }     // which pack kernel refresh_pixels launches (rt_api.hip)
 
 dim3 frame_grid(const rt_ctx *c) { return dim3((unsigned)((c->w + kDnTileW - 1) / kDnTileW), (unsigned)((c->h + kDnTileH - 1) / kDnTileH)); }
@@ -286,16 +99,6 @@ int launch_variance(float *var, const float *a, const float *b, int w, int h, hi
     hipLaunchKernelGGL(rt_denoise_variance_kernel, dim3((unsigned)((3 * (size_t)w + 255) / 256), (unsigned)std::min(h, 65535)), dim3(256), 0, stream, var, a, b, w, h);
     HIP_TRY(hipGetLastError());
     return RT_OK;
-}
-
-// f(std::integral_constant<int, P>) for the instantiated patch radius (rt_host_denoise_params allows 0, 1, 2)
-template <class F>
-void with_patch_radius(int patch_radius, F &&f) {
-    switch (patch_radius) {
-    case 0: f(std::integral_constant<int, 0>{}); break;
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    default: f(std::integral_constant<int, 2>{}); break;
-    }
 }
 
 // two halves hold the same number of passes, and at least one
@@ -335,9 +138,13 @@ int filter_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t st
     if (rc == RT_OK) rc = launch_variance(a->d_denoise_var, a->d_colors, b->d_colors, a->w, a->h, stream);
     if (rc != RT_OK) return rc;
     const DnPlanes<2> k{ { a->d_colors, b->d_colors }, { a->d_filtered, b->d_filtered }, { a->d_filtered_px, b->d_filtered_px }, { packs_fast(a), packs_fast(b) } };
-    const size_t lds = lds_bytes(2, q.search_radius, q.patch_radius);
+    const size_t lds = dn_lds_bytes(2, q.search_radius, q.patch_radius);
     const float kk = q.k * q.k;
-    with_patch_radius(q.patch_radius, [&](auto P) {
+    if (a->have_guide) {                                    // (guide_refuse has passed: b holds the same, both feature planes are current)
+        const GuidedFilter f{ { a->d_colors, b->d_colors }, { a->d_filtered, b->d_filtered }, { a->d_filtered_px, b->d_filtered_px }, { packs_fast(a), packs_fast(b) },
+                              a->d_denoise_var, tiles ? a->tiles.d_groups : nullptr, tiles ? a->frame.counts[0] : 0u };
+        rc = launch_guided_filter(2, f, a, q, stream);
+    } else with_patch_radius(q.patch_radius, [&](auto P) {
         if (tiles)
             hipLaunchKernelGGL(rt_denoise_pair_tiles_kernel<decltype(P)::value>, dim3(a->frame.counts[0]), dim3(kDnLanes), lds, stream, k, a->d_denoise_var, a->w,
                                a->h, q.search_radius, q.alpha, kk, a->tiles.d_groups, groups_per_row(a), group_count(a));
@@ -345,6 +152,7 @@ int filter_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t st
             hipLaunchKernelGGL(rt_denoise_pair_kernel<decltype(P)::value>, frame_grid(a), dim3(kDnLanes), lds, stream, k, a->d_denoise_var, a->w, a->h,
                                q.search_radius, q.alpha, kk);
     });
+    if (rc != RT_OK) return rc;
     HIP_TRY(hipGetLastError());
     const uint64_t call = g_pair_calls.fetch_add(1) + 1;
     for (rt_ctx *c : { a, b }) tiles ? c->frame.pair_tiles_refreshed(call) : c->frame.pair_filtered(call);
@@ -361,6 +169,7 @@ int denoise_pair_refuse(const rt_ctx *a, const rt_ctx *b, const char *call) {
     if (rc == RT_OK) rc = tiles_refuse(b, call);
     if (rc == RT_OK) rc = same_frame(a, b, call, "the first half", "the second half", false);
     if (rc == RT_OK) rc = halves_refuse(a, b, call);
+    if (rc == RT_OK) rc = guide_refuse(a, b, call);
     return rc;
 }
 
@@ -401,6 +210,9 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
     if ((long long)dst->frame.current_sample != 2ll * a->frame.current_sample)
         return fail(RT_ERR_STATE, "rt_denoise_async: the destination holds %d passes, the halves %d each: it is not their merge", dst->frame.current_sample,
                     a->frame.current_sample);
+    bool guided = false;
+    rc = guide_refuse(a, b, "rt_denoise_async", &guided);
+    if (rc != RT_OK) return rc;
     if (q.search_radius == 0) return RT_OK;                 // the window is the pixel itself: the image, bit for bit
     rc = select_device(dst);
     if (rc != RT_OK) return rc;
@@ -415,10 +227,14 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
     if (rc == RT_OK) rc = launch_variance(dst->d_denoise_var, a->d_colors, b->d_colors, dst->w, dst->h, stream);
     if (rc != RT_OK) return rc;
     const DnPlanes<1> k{ { dst->d_colors }, { dst->d_denoise }, { nullptr }, { 0 } };       // (nothing is packed: rt_read_pixels packs the colour plane)
-    with_patch_radius(q.patch_radius, [&](auto P) {
-        hipLaunchKernelGGL(rt_denoise_kernel<decltype(P)::value>, frame_grid(dst), dim3(kDnLanes), lds_bytes(1, q.search_radius, q.patch_radius), stream, k,
+    if (guided) {                                           // (the feature plane is a's)
+        const GuidedFilter f{ { dst->d_colors, nullptr }, { dst->d_denoise, nullptr }, { nullptr, nullptr }, { 0, 0 }, dst->d_denoise_var, nullptr, 0u };
+        rc = launch_guided_filter(1, f, a, q, stream);
+    } else with_patch_radius(q.patch_radius, [&](auto P) {
+        hipLaunchKernelGGL(rt_denoise_kernel<decltype(P)::value>, frame_grid(dst), dim3(kDnLanes), dn_lds_bytes(1, q.search_radius, q.patch_radius), stream, k,
                            dst->d_denoise_var, dst->w, dst->h, q.search_radius, q.alpha, q.k * q.k);
     });
+    if (rc != RT_OK) return rc;
     HIP_TRY(hipGetLastError());
     std::swap(dst->d_colors, dst->d_denoise);               // the filtered plane IS the colour plane now; the old one is the next call's scratch
     dst->frame.colours_replaced();                          // rt_read_pixels packs the filtered plane

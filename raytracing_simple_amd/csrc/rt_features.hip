@@ -1,0 +1,154 @@
+// rt_features.hip -- feature planes from camera rays (include/rt_api.h, "feature planes"): what lies under every pixel --
+//   rt_features_async        albedo, normal, distance and scene index of the pixel-centre ray's first hit, into a plane the context owns
+//   rt_read_features         that plane
+//   rt_set_denoise_guide     the per-context setting that lets the filters of rt_denoise.hip restrict their weights by it
+// and the kernel behind the first.  rt_features_planes (rt_host.cpp) is the same arithmetic as plain loops; the header states it as rules 10-12, and
+// the comments below name the rule a line implements.  The reference hands out no such plane: this is the library's own extension.
+// This unit is compiled with parity's flags (-ffp-contract=off, correctly rounded division and square root): every multiply, add, division and square
+// root below is an operation of its own, in the written order -- whatever rt_set_mode says.
+// A PLAIN SWEEP, pixels x records tests: the plane is formed once per scene and camera, where a frame takes hundreds of passes over the same scene, and
+// the sweep's answer is the reference's Intersect by construction.  The hierarchy is deliberately not used.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "rt_internal.h"
+
+using rt::fail;
+
+extern "C" int rt_host_guide_params(const rt_guide_params *g);     // rt_host.cpp: the guide's parameter rules
+
+namespace {
+
+constexpr int kFtTileW = 32, kFtTileH = 8, kFtLanes = kFtTileW * kFtTileH;     // a workgroup's pixels: four wavefronts, an 8x8 tile each, as the render kernels'
+constexpr uint32_t kFtChunk = 1024;                                             // records staged at a time: 16 KiB of LDS
+
+struct FtCamera {
+    float ox, oy, oz, dx, dy, dz, xx, xy, xz, yx, yy, yz;
+};
+
+}  // namespace
+
+// One lane per pixel.  The geometry table {centre, radius^2} (rt_scene.hip: the reference's own rad * rad) goes through LDS in chunks of kFtChunk
+// records, a barrier either side of a chunk's tests, and is read back at wave-uniform addresses.  EVERY lane stays in the chunk loop until its last
+// barrier -- a lane outside the image traces the ray of a pixel that does not exist and stores nothing.
+// Bounds: a chunk stages records [base, min(base + kFtChunk, n)) of a table of n and tests exactly those; the hit's records are read at id < n; the
+// store is guarded by x < w && y < h.
+__global__ void __launch_bounds__(kFtLanes) rt_features_kernel(float4 *__restrict__ out, const float4 *__restrict__ geom, const float4 *__restrict__ emis,
+                                                               const float4 *__restrict__ colr, uint32_t n, FtCamera cam, int w, int h) {
+    __shared__ float4 s_geom[kFtChunk];
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x = (int)blockIdx.x * kFtTileW + wave * 8 + (lane & 7), y = (int)blockIdx.y * kFtTileH + (lane >> 3);
+
+    // rule 10: the ray through the pixel's centre
+    const float kcx = ((float)x + 0.0f) * (1.f / (float)w) - 0.5f, kcy = ((float)y + 0.0f) * (1.f / (float)h) - 0.5f;
+    const float rx = cam.xx * kcx + cam.yx * kcy + cam.dx;
+    const float ry = cam.xy * kcx + cam.yy * kcy + cam.dy;
+    const float rz = cam.xz * kcx + cam.yz * kcy + cam.dz;
+    const float ox = 0.1f * rx + cam.ox, oy = 0.1f * ry + cam.oy, oz = 0.1f * rz + cam.oz;
+    const float f = 1.f / sqrtf(rx * rx + ry * ry + rz * rz);
+    const float dx = rx * f, dy = ry * f, dz = rz * f;
+
+    // rule 11: the nearest record in scene order
+    float t = 1e20f;
+    uint32_t id = 0xFFFFFFFFu;
+    for (uint32_t base = 0; base < n; base += kFtChunk) {
+        const uint32_t m = min(kFtChunk, n - base);
+        for (uint32_t i = (uint32_t)tid; i < m; i += (uint32_t)kFtLanes) s_geom[i] = geom[base + i];
+        __syncthreads();
+        for (uint32_t i = 0; i < m; ++i) {
+            const float4 g = s_geom[i];
+            const float px = g.x - ox, py = g.y - oy, pz = g.z - oz;
+            const float b = px * dx + py * dy + pz * dz;
+            float det = b * b - (px * px + py * py + pz * pz) + g.w;
+            float dist = 0.f;
+            if (!(det < 0.f)) {
+                det = sqrtf(det);
+                const float t1 = b - det, t2 = b + det;
+                dist = t1 > 0.01f ? t1 : (t2 > 0.01f ? t2 : 0.f);
+            }
+            if (dist != 0.f && dist < t) {
+                t = dist;
+                id = base + i;
+            }
+        }
+        __syncthreads();
+    }
+    if (x >= w || y >= h) return;
+
+    // rule 12: the values
+    float4 lo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+    if (t < 1e20f) {
+        const float4 g = geom[id], e = emis[id], c = colr[id];
+        const float nx = (ox + dx * t) - g.x, ny = (oy + dy * t) - g.y, nz = (oz + dz * t) - g.z;
+        const float nf = 1.f / sqrtf(nx * nx + ny * ny + nz * nz);
+        lo = make_float4(c.x + e.x, c.y + e.y, c.z + e.z, nx * nf);
+        hi = make_float4(ny * nf, nz * nf, t, __uint_as_float(id));
+    }
+    const size_t at = (size_t)(h - 1 - y) * (size_t)w + (size_t)x;
+    out[2 * at] = lo;
+    out[2 * at + 1] = hi;
+}
+
+namespace rt {
+
+int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guided) {
+    if (guided) *guided = false;
+    if (a->have_guide != b->have_guide || (a->have_guide && memcmp(&a->guide, &b->guide, sizeof a->guide) != 0))
+        return fail(RT_ERR_STATE, "%s: the halves differ in their guide (rt_set_denoise_guide: both off, or both on with the same parameters)", call);
+    if (!a->have_guide) return RT_OK;
+    if (!a->features_current || !b->features_current || !a->d_features)
+        return fail(RT_ERR_STATE, "%s: a guide is set and the feature plane of %s is not current (rt_features_async forms it; rt_set_scene, "
+                                  "rt_update_spheres_async and rt_set_camera end it)", call, !a->features_current || !a->d_features ? "the first half" : "the second half");
+    if (guided) *guided = true;
+    return RT_OK;
+}
+
+}  // namespace rt
+
+using namespace rt;
+
+extern "C" {
+
+RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
+    int rc = tiles_refuse(c, "rt_features_async");
+    if (rc != RT_OK) return rc;
+    if (!c->have_scene || !c->have_cam) return fail(RT_ERR_STATE, "rt_features_async: rt_set_scene and rt_set_camera come first");
+    rc = select_device(c);
+    if (rc != RT_OK) return rc;
+    if (!c->d_features) HIP_TRY(hipMalloc(&c->d_features, 8 * image_pixels(c) * sizeof(float)));
+    // behind everything the context has queued; the tables from the records as they are now
+    hipStream_t stream = (hipStream_t)hip_stream;
+    rc = chain(c, stream);
+    if (rc == RT_OK) rc = refresh_tables(c, stream);
+    if (rc != RT_OK) return rc;
+    const rt_camera &m = c->cam;
+    const FtCamera cam{ m.orig.x, m.orig.y, m.orig.z, m.dir.x, m.dir.y, m.dir.z, m.x.x, m.x.y, m.x.z, m.y.x, m.y.y, m.y.z };
+    const dim3 grid((unsigned)((c->w + kFtTileW - 1) / kFtTileW), (unsigned)((c->h + kFtTileH - 1) / kFtTileH));
+    hipLaunchKernelGGL(rt_features_kernel, grid, dim3(kFtLanes), 0, stream, reinterpret_cast<float4 *>(c->d_features), c->scene.geom, c->scene.emis, c->scene.colr,
+                       c->scene.n_spheres, cam, c->w, c->h);
+    HIP_TRY(hipGetLastError());
+    c->features_current = true;
+    return RT_OK;
+}
+
+RT_API int rt_read_features(rt_ctx *c, float *out_host) {
+    int rc = tiles_refuse(c, "rt_read_features");
+    if (rc != RT_OK) return rc;
+    if (!out_host) return fail(RT_ERR_ARG, "rt_read_features: out_host is null");
+    if (!c->features_current || !c->d_features)
+        return fail(RT_ERR_STATE, "rt_read_features: the context holds no current feature plane (rt_features_async forms one; rt_set_scene, rt_update_spheres_async "
+                                  "and rt_set_camera end it)");
+    return read_back(c, out_host, c->d_features, 8 * image_pixels(c) * sizeof(float));
+}
+
+RT_API int rt_set_denoise_guide(rt_ctx *c, const rt_guide_params *g) {
+    int rc = tiles_refuse(c, "rt_set_denoise_guide");
+    if (rc != RT_OK) return rc;
+    if (g && rt_host_guide_params(g) != RT_OK) return RT_ERR_ARG;
+    c->have_guide = g != nullptr;
+    c->guide = g ? *g : rt_guide_params{};
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -226,11 +226,45 @@ int rt_host_denoise_params(const rt_denoise_params *p, rt_denoise_params *out) {
     return RT_OK;
 }
 
+void rt_guide_defaults(rt_guide_params *g) {
+    if (!g) return;
+    g->k_albedo = 0.15f;
+    g->k_normal = 0.2f;
+    g->k_depth = 0.05f;
+    g->reserved = 0;
+}
+
+// the guide's parameter rules (every entry point that takes or holds one); hidden, like rt_host_denoise_params
+int rt_host_guide_params(const rt_guide_params *g) {
+    if (!g) return host_fail("rt_guide_params: null");
+    const float k[3] = { g->k_albedo, g->k_normal, g->k_depth };
+    static const char *const name[3] = { "k_albedo", "k_normal", "k_depth" };
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(k[i]) || k[i] <= 0.f) return host_fail("rt_guide_params: %s %g (finite, > 0)", name[i], (double)k[i]);
+    if (g->reserved != 0) return host_fail("rt_guide_params: reserved %u (0)", g->reserved);
+    return RT_OK;
+}
+
 }  // extern "C"
 
 namespace {
 
 inline int dn_cl(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
+
+// rule 13: the feature weight of two pixels from their records of the feature plane (8 words each; word 7 is not read)
+inline float guide_weight(const float *fp, const float *fq, float ia, float in, float id) {
+    const float a0 = fp[0] - fq[0], a1 = fp[1] - fq[1], a2 = fp[2] - fq[2];
+    const float n0 = fp[3] - fq[3], n1 = fp[4] - fq[4], n2 = fp[5] - fq[5];
+    const float pa = ((a0 * a0 + a1 * a1) + a2 * a2) * ia;
+    const float pn = ((n0 * n0 + n1 * n1) + n2 * n2) * in;
+    const float r = (fp[6] - fq[6]) / ((fp[6] + fq[6]) + 1e-10f);
+    const float pd = (r * r) * id;
+    float phi = 0.0f;
+    if (pa > phi) phi = pa;                                  // (a NaN term constrains nothing)
+    if (pn > phi) phi = pn;
+    if (pd > phi) phi = pd;
+    return 1.0f / (1.0f + phi * (1.0f + phi * 0.5f));
+}
 
 // rules 1 and 2: the variance of the mean of the two halves, smoothed over 3x3, clamped
 std::vector<float> smoothed_variance(const float *a, const float *b, int w, int h) {
@@ -257,9 +291,11 @@ std::vector<float> smoothed_variance(const float *a, const float *b, int w, int 
 
 // rules 3 to 6 with the image and the guide apart: the weights come from `guide` (rule 3's t) and the variance plane `var`, the values that are
 // tested (rule 5) and averaged (rule 6) from `img`.  rt_denoise_planes: img == guide == the merged frame, var = Vs.  rt_denoise_pair_planes: img
-// one half, guide the other, var = Vh
-void nlm_planes(float *out, const float *img, const float *guide, const std::vector<float> &var, int w, int h, const rt_denoise_params &q) {
+// one half, guide the other, var = Vh.  `gd` non-null (the guided functions): rule 14, the weight never above rule 13's of the feature plane `feat`
+void nlm_planes(float *out, const float *img, const float *guide, const std::vector<float> &var, int w, int h, const rt_denoise_params &q,
+                const float *feat, const rt_guide_params *gd) {
     const int R = q.search_radius, P = q.patch_radius;
+    const float ia = gd ? 1.0f / (gd->k_albedo * gd->k_albedo) : 0.f, in = gd ? 1.0f / (gd->k_normal * gd->k_normal) : 0.f, id = gd ? 1.0f / (gd->k_depth * gd->k_depth) : 0.f;
     const float alpha = q.alpha, kk = q.k * q.k, inv = 1.0f / (float)(3 * (2 * P + 1) * (2 * P + 1));
     const auto at = [w](int y, int x) { return 3 * ((size_t)y * (size_t)w + (size_t)x); };
     const size_t px = (size_t)w * (size_t)h;
@@ -300,8 +336,12 @@ void nlm_planes(float *out, const float *img, const float *guide, const std::vec
                     const float *dq = img + at(qy, qx);
                     if (std::isnan(T) || !std::isfinite(dq[0]) || !std::isfinite(dq[1]) || !std::isfinite(dq[2])) continue;
                     const float g = T > 0.f ? T : 0.f;
-                    const float wgt = 1.0f / (1.0f + g * (1.0f + g * 0.5f));
+                    float wgt = 1.0f / (1.0f + g * (1.0f + g * 0.5f));
                     const size_t i = (size_t)y * w + x;
+                    if (gd) {                                                 // 14.
+                        const float wf = guide_weight(feat + 8 * i, feat + 8 * ((size_t)qy * w + qx), ia, in, id);
+                        wgt = wf < wgt ? wf : wgt;
+                    }
                     for (int c = 0; c < 3; ++c) num[3 * i + c] = num[3 * i + c] + wgt * dq[c];
                     den[i] = den[i] + wgt;
                 }
@@ -314,22 +354,37 @@ void nlm_planes(float *out, const float *img, const float *guide, const std::vec
 
 extern "C" {
 
-int rt_denoise_planes(float *out, const float *merged, const float *a, const float *b, int w, int h, const rt_denoise_params *p) {
+// `g` == null: the filter without a guide; else its parameters checked and the feature plane there
+static int guide_args(const char *call, const float *feat, const rt_guide_params *g) {
+    if (!g) return RT_OK;
+    if (!feat) return host_fail("%s: null feature plane", call);
+    return rt_host_guide_params(g);
+}
+
+int rt_denoise_guided_planes(float *out, const float *merged, const float *a, const float *b, const float *feat, int w, int h, const rt_denoise_params *p,
+                             const rt_guide_params *g) {
     if (!out || !merged || !a || !b) return host_fail("rt_denoise_planes: null plane");
     if (w < 1 || h < 1) return host_fail("rt_denoise_planes: %dx%d", w, h);
     rt_denoise_params q;
     if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
-    nlm_planes(out, merged, merged, smoothed_variance(a, b, w, h), w, h, q);
+    if (guide_args("rt_denoise_guided_planes", feat, g) != RT_OK) return RT_ERR_ARG;
+    nlm_planes(out, merged, merged, smoothed_variance(a, b, w, h), w, h, q, feat, g);
     return RT_OK;
+}
+
+int rt_denoise_planes(float *out, const float *merged, const float *a, const float *b, int w, int h, const rt_denoise_params *p) {
+    return rt_denoise_guided_planes(out, merged, a, b, nullptr, w, h, p, nullptr);
 }
 
 // ---- rt_denoise_pair_planes: the cross-filtered halves of include/rt_api.h ("the error of the filtered frame"), as plain loops ----
 // rt_denoise_pair_async runs the same arithmetic on the device (rt_denoise.hip) and is tested against this function bit for bit.
-int rt_denoise_pair_planes(float *out_a, float *out_b, const float *a, const float *b, int w, int h, const rt_denoise_params *p) {
+int rt_denoise_pair_guided_planes(float *out_a, float *out_b, const float *a, const float *b, const float *feat, int w, int h, const rt_denoise_params *p,
+                                  const rt_guide_params *g) {
     if (!out_a || !out_b || !a || !b) return host_fail("rt_denoise_pair_planes: null plane");
     if (w < 1 || h < 1) return host_fail("rt_denoise_pair_planes: %dx%d", w, h);
     rt_denoise_params q;
     if (rt_host_denoise_params(p, &q) != RT_OK) return RT_ERR_ARG;
+    if (guide_args("rt_denoise_pair_guided_planes", feat, g) != RT_OK) return RT_ERR_ARG;
     const size_t n = 3 * (size_t)w * (size_t)h;
     if (q.search_radius == 0) {                              // the window is the pixel itself: the halves, bit for bit
         memcpy(out_a, a, n * sizeof(float));
@@ -338,8 +393,65 @@ int rt_denoise_pair_planes(float *out_a, float *out_b, const float *a, const flo
     }
     std::vector<float> Vh = smoothed_variance(a, b, w, h);
     for (size_t i = 0; i < n; ++i) Vh[i] = Vh[i] + Vh[i];    // the variance of ONE half: twice that of the mean
-    nlm_planes(out_a, a, b, Vh, w, h, q);                    // FA: A's values, weights from B
-    nlm_planes(out_b, b, a, Vh, w, h, q);                    // FB: B's values, weights from A
+    nlm_planes(out_a, a, b, Vh, w, h, q, feat, g);           // FA: A's values, weights from B
+    nlm_planes(out_b, b, a, Vh, w, h, q, feat, g);           // FB: B's values, weights from A
+    return RT_OK;
+}
+
+int rt_denoise_pair_planes(float *out_a, float *out_b, const float *a, const float *b, int w, int h, const rt_denoise_params *p) {
+    return rt_denoise_pair_guided_planes(out_a, out_b, a, b, nullptr, w, h, p, nullptr);
+}
+
+// ---- rt_features_planes: the feature plane of include/rt_api.h ("feature planes"), rules 10-12, as plain loops ----
+// rt_features_async forms the same words on the device (rt_features.hip) and is tested against this function bit for bit.
+int rt_features_planes(float *out, const rt_sphere *spheres, uint32_t count, const rt_camera *cam, int w, int h) {
+    if (!out || !cam || (count > 0 && !spheres)) return host_fail("rt_features_planes: null argument");
+    if (w < 1 || h < 1) return host_fail("rt_features_planes: %dx%d", w, h);
+    const float inv_w = 1.f / (float)w, inv_h = 1.f / (float)h;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            // 10. the ray through the pixel's centre (.cl:494-549 with both random numbers 0.5)
+            const float kcx = ((float)x + 0.0f) * inv_w - 0.5f, kcy = ((float)y + 0.0f) * inv_h - 0.5f;
+            const float rx = cam->x.x * kcx + cam->y.x * kcy + cam->dir.x;
+            const float ry = cam->x.y * kcx + cam->y.y * kcy + cam->dir.y;
+            const float rz = cam->x.z * kcx + cam->y.z * kcy + cam->dir.z;
+            const float ox = 0.1f * rx + cam->orig.x, oy = 0.1f * ry + cam->orig.y, oz = 0.1f * rz + cam->orig.z;
+            const float f = 1.f / std::sqrt(rx * rx + ry * ry + rz * rz);
+            const float dx = rx * f, dy = ry * f, dz = rz * f;
+            // 11. the nearest record in scene order (.cl:215-232 over .cl:173-201)
+            float t = 1e20f;
+            uint32_t id = 0xFFFFFFFFu;
+            for (uint32_t i = 0; i < count; ++i) {
+                const rt_sphere &s = spheres[i];
+                const float px = s.p.x - ox, py = s.p.y - oy, pz = s.p.z - oz;
+                const float b = px * dx + py * dy + pz * dz;
+                float det = b * b - (px * px + py * py + pz * pz) + s.rad * s.rad;
+                float dist = 0.f;
+                if (!(det < 0.f)) {
+                    det = std::sqrt(det);
+                    const float t1 = b - det, t2 = b + det;
+                    dist = t1 > 0.01f ? t1 : (t2 > 0.01f ? t2 : 0.f);
+                }
+                if (dist != 0.f && dist < t) {
+                    t = dist;
+                    id = i;
+                }
+            }
+            // 12. the values (.cl:338-347; the normal is not turned towards the ray)
+            float *o = out + 8 * ((size_t)(h - 1 - y) * (size_t)w + (size_t)x);
+            if (t < 1e20f) {
+                const rt_sphere &s = spheres[id];
+                const float nx = (ox + dx * t) - s.p.x, ny = (oy + dy * t) - s.p.y, nz = (oz + dz * t) - s.p.z;
+                const float nf = 1.f / std::sqrt(nx * nx + ny * ny + nz * nz);
+                o[0] = s.c.x + s.e.x, o[1] = s.c.y + s.e.y, o[2] = s.c.z + s.e.z;
+                o[3] = nx * nf, o[4] = ny * nf, o[5] = nz * nf;
+                o[6] = t;
+            } else {
+                for (int k = 0; k < 7; ++k) o[k] = 0.0f;
+                id = 0xFFFFFFFFu;
+            }
+            memcpy(o + 7, &id, sizeof id);
+        }
     return RT_OK;
 }
 

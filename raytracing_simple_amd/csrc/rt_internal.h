@@ -113,6 +113,12 @@ struct rt_ctx {
     rt::SceneTables scene{};
     rt_camera cam{};
     bool have_scene = false, have_cam = false;
+    // feature planes (rt_features.hip; include/rt_api.h "feature planes"): what lies under every pixel, from scene and camera alone -- so it is kept here,
+    // beside them, not in the frame's state
+    float *d_features = nullptr;        // [h][w][8]: albedo, normal, distance, scene index; allocated on first use
+    bool features_current = false;      // formed by rt_features_async since the last rt_set_scene / rt_update_spheres_async / rt_set_camera
+    rt_guide_params guide{};            // rt_set_denoise_guide: what the filters of a pair of halves add to their weights ...
+    bool have_guide = false;            // ... when it is on
     bool tables_stale = false;          // rt_update_spheres_async has changed records since the tables and the hierarchy were built: refresh_tables() builds them
                                         // ONCE, on the stream of whatever reads them next, however many updates went by (200 moved spheres by 200 calls cost 200
                                         // rebuilds before: 353 ms a frame at 8192 spheres against 4.9 in one call -- profiles/r06_update_calls.jsonl)
@@ -259,6 +265,20 @@ int denoise_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t s
 // ... the same pair and parameters: the planes of the groups in the current selection made again, if the planes are one selection behind (FrameState::filtered_behind);
 // RT_OK and nothing launched if they are current; RT_ERR_STATE for anything else, `call` named in the message
 int denoise_pair_tiles(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream, const char *call);
+
+// the guide of a pair of halves (rt_set_denoise_guide): RT_ERR_STATE when the two settings differ, or -- on -- a feature plane is not current.  *guided: on
+int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guided = nullptr);
+// ---- rt_denoise_guided.hip: the filter kernels under a guide, launched for rt_denoise.hip ----
+struct GuidedFilter {
+    const float *img[2];                // the frame, or the two halves
+    float *out[2];
+    uint32_t *px[2];                    // the halves: the packed planes
+    int fast[2];                        // ... and which toInt packs them
+    const float *var;                   // rule 2's plane
+    const uint32_t *groups;             // non-null: the halves over this list of selected groups ...
+    uint32_t n_selected;                // ... of this many entries
+};
+int launch_guided_filter(int n_images, const GuidedFilter &f, const rt_ctx *a, const rt_denoise_params &q, hipStream_t stream);
 
 // ---- rt_tiles.hip: the subset launch's device side ----
 int tiles_refuse(const rt_ctx *c, const char *call);                  // RT_ERR_ARG for the contexts the adaptive calls do not take (null, multi-device, sharded)

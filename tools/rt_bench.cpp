@@ -5,7 +5,7 @@
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
 //            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]
-//             [--denoise [--denoise-radius R]] [--filtered [--live-checks]]]
+//             [--denoise [--denoise-radius R]] [--filtered [--live-checks]] [--guided]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -26,6 +26,9 @@
 //   --filtered          with --until-psnr: DB is the target for the FILTERED merge.  The check is the PSNR between the two cross-filtered halves
 //                       (rt_render_converged_filtered; with --adaptive per tile, rt_render_adaptive_filtered) -- an estimate of the filtered
 //                       frame's quality, not a bound -- and the halves are then merged and filtered as by --denoise, with the same parameters
+//   --guided            with --denoise or --filtered: the feature planes of both halves are formed (rt_features_async) and the guide's defaults
+//                       set on them (rt_set_denoise_guide), so that every filter of the run -- the checks and the final one -- restricts its
+//                       weights by albedo, normal and depth
 //   --live-checks       with --until-psnr DB --filtered --adaptive: every check after the first cross-filters only the groups that were just
 //                       rendered (rt_render_adaptive_filtered_tiles): the same render bit for bit; the printed PSNR sums every group's
 //                       figure of its own last check
@@ -80,6 +83,7 @@ int main(int argc, char** argv) {
     int min_passes = 16;
     bool denoise = false;       // --until-psnr: merge into a third context and filter it (rt_denoise_async)
     bool filtered = false;      // --until-psnr judged on the cross-filtered halves: the *_filtered loops, then merge and filter
+    bool guided = false;        // --denoise / --filtered under the guide's defaults: feature planes formed, rt_set_denoise_guide on both halves
     bool live_checks = false;   // --filtered --adaptive: rt_render_adaptive_filtered_tiles instead of rt_render_adaptive_filtered
     rt_denoise_params dn;
     rt_denoise_defaults(&dn);
@@ -109,6 +113,7 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-radius") dn.search_radius = atoi(next());
         else if (a == "--filtered") filtered = denoise = true;
+        else if (a == "--guided") guided = true;
         else if (a == "--live-checks") live_checks = true;
         else pos.push_back(argv[i]);
     }
@@ -123,6 +128,10 @@ int main(int argc, char** argv) {
     if (pos.size() >= 4) scene_path = pos[3];
     if (denoise && !until) {
         fprintf(stderr, "--denoise filters the merge of two halves: it needs --until-psnr\n");
+        return 1;
+    }
+    if (guided && !denoise) {
+        fprintf(stderr, "--guided guides a filter: it needs --denoise or --filtered\n");
         return 1;
     }
     if (live_checks && !(until && filtered && adaptive)) {
@@ -167,6 +176,12 @@ int main(int argc, char** argv) {
             if (rt_set_camera(half[k], &cam) != RT_OK) return die("rt_set_camera");
             if (rt_set_mode(half[k], mode) != RT_OK) return die("rt_set_mode");
             if (rt_seed_stream_async(half[k], 1 + (unsigned)k, rt_stream(half[k])) != RT_OK) return die("rt_seed_stream_async");
+            if (guided) {
+                rt_guide_params guide;
+                rt_guide_defaults(&guide);
+                if (rt_set_denoise_guide(half[k], &guide) != RT_OK) return die("rt_set_denoise_guide");
+                if (rt_features_async(half[k], rt_stream(half[k])) != RT_OK) return die("rt_features_async");
+            }
         }
         rt_frame_error err{};
         int checks = 0;
@@ -217,8 +232,8 @@ int main(int argc, char** argv) {
                    min_passes, checks, (unsigned long long)(st_half[0].samples + st_half[1].samples), 2ull * (unsigned long long)w * h * per_half,
                    tile_passes.front(), tile_passes[tile_passes.size() / 2], tile_passes.back());
         if (denoise) {
-            printf("{\"denoise\": true, \"search_radius\": %d, \"patch_radius\": %d, \"alpha\": %.3f, \"k\": %.3f, \"denoise_wall_ms\": %.4f}\n",
-                   dn.search_radius, dn.patch_radius, (double)dn.alpha, (double)dn.k, denoise_ms);
+            printf("{\"denoise\": true, \"guided\": %s, \"search_radius\": %d, \"patch_radius\": %d, \"alpha\": %.3f, \"k\": %.3f, \"denoise_wall_ms\": %.4f}\n",
+                   guided ? "true" : "false", dn.search_radius, dn.patch_radius, (double)dn.alpha, (double)dn.k, denoise_ms);
             rt_destroy(frame);
         }
         rt_destroy(half[0]);
