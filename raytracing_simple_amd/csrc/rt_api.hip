@@ -53,6 +53,17 @@ int fail(int code, const char *fmt, ...) {
 
 using rt::fail;
 
+// the one place a handle of a record (rt_owned.h) goes back to the runtime
+void rt::owned_free(rt::Owned::Kind kind, void *handle) {
+    switch (kind) {
+    case rt::Owned::Kind::Device: (void)hipFree(handle); break;
+    case rt::Owned::Kind::Pinned: (void)hipHostFree(handle); break;
+    case rt::Owned::Kind::Registered: (void)hipHostUnregister(handle); break;
+    case rt::Owned::Kind::Event: (void)hipEventDestroy(static_cast<hipEvent_t>(handle)); break;
+    case rt::Owned::Kind::Stream: (void)hipStreamDestroy(static_cast<hipStream_t>(handle)); break;
+    }
+}
+
 // rt_reset_async zeroes the work counters with a kernel on the caller's stream and restores NO seeds:
 // the next launch reads the pristine default stream directly (LaunchParams::seeds_in).
 __global__ void rt_zero_counters_kernel(unsigned long long *counters, unsigned long long *stats) {
@@ -227,24 +238,25 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
     auto alloc_all = [&]() -> int {
         double t = now_ms();
         auto lap = [&](int k) { const double n_ = now_ms(); g_create_ms[k] = n_ - t; t = n_; };
-        HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+        rt::Owned &own = c->owned;
+        RT_TRY(own_stream(own, &c->stream));        // the record's first entry: the last to go
         c->last_stream = c->stream;
-        HIP_TRY(hipEventCreate(&c->ev0));
-        HIP_TRY(hipEventCreate(&c->ev1));
-        for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreate(&c->probe.ev[k]));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_dep, hipEventDisableTiming));
-        for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreateWithFlags(&c->stage_ev[k], hipEventDisableTiming));
+        RT_TRY(own_event(own, &c->ev0));
+        RT_TRY(own_event(own, &c->ev1));
+        for (int k = 0; k < 4; ++k) RT_TRY(own_event(own, &c->probe.ev[k]));
+        RT_TRY(own_event(own, &c->ev_dep, hipEventDisableTiming));
+        for (int k = 0; k < 4; ++k) RT_TRY(own_event(own, &c->stage_ev[k], hipEventDisableTiming));
         lap(1);
-        HIP_TRY(hipMalloc(&c->d_seeds, 2 * px * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->d_seeds0, 2 * px * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->d_colors, 3 * px * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->d_pixels, (local_pixels(c) + 4) * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->d_counters, 32 * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&c->d_stats, rt::kStatReplicas * 8 * sizeof(unsigned long long)));
+        RT_TRY(own_device(own, &c->d_seeds, 2 * px));
+        RT_TRY(own_device(own, &c->d_seeds0, 2 * px));
+        RT_TRY(own_device(own, &c->d_colors, 3 * px));
+        RT_TRY(own_device(own, &c->d_pixels, local_pixels(c) + 4));
+        RT_TRY(own_device(own, &c->d_counters, 32));
+        RT_TRY(own_device(own, &c->d_stats, (size_t)rt::kStatReplicas * 8));
         c->order.n_tiles = tile_count(c);           // the finest tile shape (8x8)
         if (c->order.n_tiles) {
-            HIP_TRY(hipMalloc(&c->order.d_tile_cost, (size_t)c->order.n_tiles * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc(&c->order.d_order, (size_t)c->order.n_tiles * sizeof(uint32_t)));
+            RT_TRY(own_device(own, &c->order.d_tile_cost, c->order.n_tiles));
+            RT_TRY(own_device(own, &c->order.d_order, c->order.n_tiles));
         }
         lap(2);
         // function attributes (dynamic-LDS limit) are per device, not per context
@@ -286,58 +298,18 @@ RT_API void rt_destroy(rt_ctx *c) {
         delete c;
         return;
     }
-    if (c->abandon_streams) {
-        // a shard of a multi-device context whose gather failed AND whose streams had not drained two seconds later (rt_multi.hip
-        // multi_destroy polls them): a stream may hold a transfer that never completes, and hipFree / hipHostFree / hipStreamDestroy
-        // synchronise with the device's work -- so nothing on the device is waited for or freed; the shard's device memory and stream
-        // are leaked, the call returns
+    // A shard of a multi-device context whose gather failed AND whose streams had not drained two seconds later (rt_multi.hip multi_destroy
+    // polls them) abandons its streams: one may hold a transfer that never completes, and hipFree / hipHostFree / hipStreamDestroy synchronise
+    // with the device's work -- so nothing on the device is waited for or given back; what the record holds is leaked, the call returns.
+    // (A device that cannot be selected: likewise.)
+    if (c->abandon_streams || hipSetDevice(c->device) != hipSuccess) {
+        c->owned.forget();
         delete c;
         return;
     }
-    if (hipSetDevice(c->device) == hipSuccess) {
-        if (c->last_stream && c->last_stream != c->stream) (void)hipStreamSynchronize(c->last_stream);
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-        if (c->pinned_out) (void)hipHostUnregister(c->pinned_out);
-        (void)hipFree(c->d_seeds);
-        (void)hipFree(c->d_seeds0);
-        (void)hipFree(c->d_colors);
-        (void)hipFree(c->d_pixels);
-        (void)hipFree(c->d_counters);
-        (void)hipFree(c->d_stats);
-        (void)hipFree(c->d_compare);
-        (void)hipFree(c->d_denoise);
-        (void)hipFree(c->d_denoise_var);
-        (void)hipFree(c->d_filtered);
-        (void)hipFree(c->d_filtered_px);
-        (void)hipFree(c->d_features);
-        (void)hipFree(c->tiles.d_passes);
-        (void)hipFree(c->tiles.d_selected);
-        (void)hipFree(c->tiles.d_list);
-        (void)hipFree(c->tiles.d_groups);
-        (void)hipFree(c->order.d_tile_cost);
-        (void)hipFree(c->order.d_order);
-        (void)hipFree(c->d_timelog);
-        (void)hipFree(c->d_wavelog);
-        (void)hipFree(c->d_blocklog);
-        (void)hipFree(c->d_stalelog);
-        free_scene(c);
-        if (c->h_stage) (void)hipHostFree(c->h_stage);
-        if (c->ev0) (void)hipEventDestroy(c->ev0);
-        if (c->ev1) (void)hipEventDestroy(c->ev1);
-        for (int k = 0; k < 4; ++k)
-            if (c->probe.ev[k]) (void)hipEventDestroy(c->probe.ev[k]);
-        if (c->bvh_stage_ev) (void)hipEventDestroy(c->bvh_stage_ev);
-        if (c->dup_ev) (void)hipEventDestroy(c->dup_ev);
-        if (c->h_bvh_stage) (void)hipHostFree(c->h_bvh_stage);
-        if (c->ev_dep) (void)hipEventDestroy(c->ev_dep);
-        for (int k = 0; k < 4; ++k)
-            if (c->stage_ev[k]) (void)hipEventDestroy(c->stage_ev[k]);
-        for (auto &f : c->flight) {
-            if (f.start) (void)hipEventDestroy(f.start);
-            if (f.stop) (void)hipEventDestroy(f.stop);
-        }
-        if (c->stream) (void)hipStreamDestroy(c->stream);
-    }
+    if (c->last_stream && c->last_stream != c->stream) (void)hipStreamSynchronize(c->last_stream);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    c->owned.release();                 // everything the context acquired, wherever (rt_owned.h), the last first; its stream at the end
     delete c;
 }
 
@@ -495,9 +467,9 @@ RT_API int rt_throttle(rt_ctx *c, int max_in_flight, double *ms_per_pass) {
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     if (!c->throttle_on) {
-        for (auto &f : c->flight) {
-            HIP_TRY(hipEventCreate(&f.start));
-            HIP_TRY(hipEventCreate(&f.stop));
+        for (auto &f : c->flight) {         // (a call that failed half-way left the events it made in place: they are not made again)
+            if (!f.start) RT_TRY(own_event(c->owned, &f.start));
+            if (!f.stop) RT_TRY(own_event(c->owned, &f.stop));
         }
         c->throttle_on = true;
         if (max_in_flight == 0) return wait_all(c);
@@ -593,12 +565,12 @@ RT_API int rt_pin_output(rt_ctx *c, uint32_t *out_host, size_t count) {
     if (c->pinned_out) {
         rc = wait_all(c);
         if (rc != RT_OK) return rc;
-        (void)hipHostUnregister(c->pinned_out);
+        c->owned.drop(c->pinned_out);
         c->pinned_out = nullptr;
     }
     if (!out_host || local_pixels(c) == 0) return RT_OK;    // nothing to pin (a rank without rows)
     if (count < local_pixels(c)) return fail(RT_ERR_ARG, "output buffer of %zu < %zu elements", count, local_pixels(c));
-    HIP_TRY(hipHostRegister(out_host, count * sizeof(uint32_t), hipHostRegisterDefault));
+    RT_TRY(own_registered(c->owned, out_host, count * sizeof(uint32_t)));
     c->pinned_out = out_host;
     return RT_OK;
 }
@@ -682,7 +654,7 @@ namespace {
 struct CacheEntry {
     int w = 0, h = 0;
     rt_ctx *ctx = nullptr;
-    uint32_t *h_pix = nullptr;          // page-locked, w*h
+    uint32_t *h_pix = nullptr;          // page-locked, w*h; this and the events are entered in ctx's record: they go with it
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
     unsigned long long stamp = 0;
 };
@@ -696,9 +668,6 @@ void cache_drop(CacheEntry &e) {
         (void)hipSetDevice(e.ctx->device);
         rt_destroy(e.ctx);
     }
-    if (e.h_pix) (void)hipHostFree(e.h_pix);
-    for (auto &v : e.ev)
-        if (v) (void)hipEventDestroy(v);
     e = CacheEntry{};
 }
 
@@ -717,8 +686,8 @@ int cache_get(int w, int h, CacheEntry **out) {
     if (rc != RT_OK) return rc;
     e.w = w;
     e.h = h;
-    hipError_t he = hipHostMalloc(reinterpret_cast<void **>(&e.h_pix), (size_t)w * h * sizeof(uint32_t), hipHostMallocDefault);
-    for (int k = 0; k < 4 && he == hipSuccess; ++k) he = hipEventCreateWithFlags(&e.ev[k], hipEventDisableTiming);
+    hipError_t he = take_pinned(e.ctx->owned, &e.h_pix, (size_t)w * h);
+    for (int k = 0; k < 4 && he == hipSuccess; ++k) he = take_event(e.ctx->owned, &e.ev[k], hipEventDisableTiming);
     if (he != hipSuccess) {
         cache_drop(e);
         return fail(RT_ERR_ALLOC, "rt_render staging: %s", hipGetErrorString(he));

@@ -653,17 +653,17 @@ int upload_host_tree(rt_ctx *c, const rt::BvhHostTree &tree, hipStream_t stream)
     const size_t total4 = rt::bvh_blob_float4s(tree.n_leaves(), tree.n_slots());
     if (c->bvh_stage_cap < total4) {
         if (c->bvh_stage_used) HIP_TRY(hipEventSynchronize(c->bvh_stage_ev));
-        if (c->h_bvh_stage) (void)hipHostFree(c->h_bvh_stage);
-        c->h_bvh_stage = nullptr;
-        c->bvh_stage_cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_bvh_stage), total4 * sizeof(float4), hipHostMallocDefault));
+        float4 *grown = nullptr;
+        RT_TRY(own_pinned(c->owned, &grown, total4));
+        c->owned.drop(c->h_bvh_stage);
+        c->h_bvh_stage = grown;
         c->bvh_stage_cap = total4;
     } else if (c->bvh_stage_used) {
         HIP_TRY(hipEventSynchronize(c->bvh_stage_ev));       // the last build's copy still reads the buffer
     }
     rt::bvh_emit(tree, c->h_spheres.data(), reinterpret_cast<rt::Float4 *>(c->h_bvh_stage));
     HIP_TRY(hipMemcpyAsync(c->d_bvh, c->h_bvh_stage, total4 * sizeof(float4), hipMemcpyHostToDevice, stream));
-    if (!c->bvh_stage_ev) HIP_TRY(hipEventCreate(&c->bvh_stage_ev));
+    if (!c->bvh_stage_ev) RT_TRY(own_event(c->owned, &c->bvh_stage_ev));
     HIP_TRY(hipEventRecord(c->bvh_stage_ev, stream));
     c->bvh_stage_used = true;
     c->bvh_est_valid = rt::bvh_estimate(tree, &c->bvh_est_pairs, &c->bvh_est_leaves);
@@ -743,11 +743,11 @@ static int mark_duplicates(rt_ctx *c, uint32_t n_total, hipStream_t stream) {
     static thread_local std::vector<uint8_t> flags;
     const uint32_t found = bvh_mark_repeats(c->h_spheres.data(), n_total, flags);
     if (found == 0 && !had) return RT_OK;       // (nothing to say, and the device holds no flags of an earlier scene)
-    if (!c->h_dup_stage) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_dup_stage), (size_t)c->scene_cap, hipHostMallocDefault));
+    if (!c->h_dup_stage) RT_TRY(own_pinned(c->owned, &c->h_dup_stage, c->scene_cap));
     if (c->dup_stage_used) HIP_TRY(hipEventSynchronize(c->dup_ev));
     memcpy(c->h_dup_stage, flags.data(), n_total);
     HIP_TRY(hipMemcpyAsync(c->d_dup, c->h_dup_stage, n_total, hipMemcpyHostToDevice, stream));
-    if (!c->dup_ev) HIP_TRY(hipEventCreate(&c->dup_ev));
+    if (!c->dup_ev) RT_TRY(own_event(c->owned, &c->dup_ev));
     HIP_TRY(hipEventRecord(c->dup_ev, stream));
     c->dup_stage_used = true;
     c->have_dups = found != 0;

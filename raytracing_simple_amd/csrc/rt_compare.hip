@@ -157,9 +157,7 @@ int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles
 
 // the blocking calls' scratch on a's device: one rt_frame_error, then the tile map
 int ensure_scratch(rt_ctx *a) {
-    if (a->d_compare) return RT_OK;
-    HIP_TRY(hipMalloc(&a->d_compare, sizeof(rt_frame_error) + std::max<size_t>(tile_count(a), 1) * sizeof(uint32_t)));
-    return RT_OK;
+    return ensure_device(a->owned, reinterpret_cast<unsigned char **>(&a->d_compare), sizeof(rt_frame_error) + std::max<size_t>(tile_count(a), 1) * sizeof(uint32_t));
 }
 
 // rt_compare: on a's own stream through a's scratch, then the wait

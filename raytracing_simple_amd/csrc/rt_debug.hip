@@ -381,16 +381,15 @@ RT_API int rt_debug_walk_rays(rt_ctx *c, const float *rays8, uint32_t n_rays, ui
     p.bvh = c->bvh;
     const size_t lds = rt::lds_bytes_pairs(0, 0, false, 0, c->bvh.n_leaves, c->bvh.n_slots, c->bvh.stack_depth, 256);
     if (lds > 152 * 1024) return fail(RT_ERR_ARG, "tables need %zu B of LDS", lds);
+    rt::Owned scratch;                  // (given back when the call returns, however)
     float4 *d_rays = nullptr;
     uint4 *d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_rays, (size_t)n_rays * 32 + 32));
-    hipError_t e = hipMalloc(&d_out, (size_t)n_rays * 16 + 16);
+    RT_TRY(own_device(scratch, &d_rays, (size_t)n_rays * 2 + 2));
+    hipError_t e = take_device(scratch, &d_out, (size_t)n_rays + 1);
     if (e == hipSuccess) e = hipMemcpy(d_rays, rays8, (size_t)n_rays * 32, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = rt::launch_walk_rays(p, d_rays, n_rays, d_out, lds, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(out4, d_out, (size_t)n_rays * 16, hipMemcpyDeviceToHost);
-    (void)hipFree(d_rays);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_debug_walk_rays: %s", hipGetErrorString(e));
     return RT_OK;
 }
@@ -539,15 +538,15 @@ RT_API int rt_debug_timelog_enable(rt_ctx *c, uint32_t entries, uint32_t wave_en
     if (rc != RT_OK) return rc;
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
-    (void)hipFree(c->d_timelog);
-    (void)hipFree(c->d_wavelog);
-    (void)hipFree(c->d_blocklog);
-    (void)hipFree(c->d_stalelog);
+    c->owned.drop(c->d_timelog);
+    c->owned.drop(c->d_wavelog);
+    c->owned.drop(c->d_blocklog);
+    c->owned.drop(c->d_stalelog);
     c->d_timelog = c->d_wavelog = c->d_blocklog = nullptr;
     c->d_stalelog = nullptr;
     c->timelog_cap = c->timelog_used = c->wavelog_cap = 0;
     if (entries) {
-        HIP_TRY(hipMalloc(&c->d_blocklog, (size_t)entries * 1024 * sizeof(unsigned long long)));
+        RT_TRY(own_device(c->owned, &c->d_blocklog, (size_t)entries * 1024));
         HIP_TRY(hipMemset(c->d_blocklog, 0, (size_t)entries * 1024 * sizeof(unsigned long long)));
         if (wave_entries == 0xC0FFEEu) {
             // provenance experiment (tools/gather_stress.py RT_LOG_PATTERN=1): the zeros above were written by the
@@ -561,16 +560,16 @@ RT_API int rt_debug_timelog_enable(rt_ctx *c, uint32_t entries, uint32_t wave_en
             HIP_TRY(hipDeviceSynchronize());
             wave_entries = 0;
         }
-        HIP_TRY(hipMalloc(&c->d_stalelog, (size_t)entries * 64 * sizeof(uint32_t)));
+        RT_TRY(own_device(c->owned, &c->d_stalelog, (size_t)entries * 64));
         HIP_TRY(hipMemset(c->d_stalelog, 0, (size_t)entries * 64 * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->d_timelog, (size_t)entries * 8 * sizeof(unsigned long long)));
+        RT_TRY(own_device(c->owned, &c->d_timelog, (size_t)entries * 8));
         std::vector<unsigned long long> init((size_t)entries * 8, 0ull);
         for (uint32_t i = 0; i < entries; ++i) init[8 * (size_t)i] = ~0ull;
         HIP_TRY(hipMemcpy(c->d_timelog, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
         c->timelog_cap = entries;
     }
     if (wave_entries) {
-        HIP_TRY(hipMalloc(&c->d_wavelog, (size_t)wave_entries * 3 * sizeof(unsigned long long)));
+        RT_TRY(own_device(c->owned, &c->d_wavelog, (size_t)wave_entries * 3));
         HIP_TRY(hipMemset(c->d_wavelog, 0, (size_t)wave_entries * 3 * sizeof(unsigned long long)));
         c->wavelog_cap = wave_entries;
     }
@@ -623,12 +622,12 @@ RT_API int rt_debug_wavelog_read(rt_ctx *c, unsigned long long *out, uint32_t wa
 static long long sqrt_check(int which) {
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device");
+    rt::Owned scratch;
     unsigned long long *d = nullptr, h = 0;
-    if (hipSetDevice(0) != hipSuccess || hipMalloc(&d, 8) != hipSuccess) return fail(RT_ERR_HIP, "alloc");
+    if (hipSetDevice(0) != hipSuccess || take_device(scratch, &d, 1) != hipSuccess) return fail(RT_ERR_HIP, "alloc");
     hipError_t e = hipMemset(d, 0, 8);
     if (e == hipSuccess) e = rt::launch_sqrt_check(d, nullptr, which);
     if (e == hipSuccess) e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "sqrt check %d: %s", which, hipGetErrorString(e));
     return (long long)h;
 }
@@ -641,12 +640,12 @@ RT_API int rt_debug_rcp_probe(unsigned long long *out1024) {
     if (!out1024) return fail(RT_ERR_ARG, "null argument");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device");
+    rt::Owned scratch;
     unsigned long long *d = nullptr;
-    if (hipSetDevice(0) != hipSuccess || hipMalloc(&d, 8192) != hipSuccess) return fail(RT_ERR_HIP, "alloc");
+    if (hipSetDevice(0) != hipSuccess || take_device(scratch, &d, 1024) != hipSuccess) return fail(RT_ERR_HIP, "alloc");
     hipError_t e = hipMemset(d, 0, 8192);
     if (e == hipSuccess) e = rt::launch_rcp_probe(d, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out1024, d, 8192, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_debug_rcp_probe: %s", hipGetErrorString(e));
     return RT_OK;
 }
@@ -659,13 +658,12 @@ RT_API int rt_debug_eval(int op, const float *in_host, float *out_host, size_t n
     if (n == 0) return RT_OK;
     float *d_in = nullptr, *d_out = nullptr;
     HIP_TRY(hipSetDevice(0));
-    HIP_TRY(hipMalloc(&d_in, n * sizeof(float)));
-    hipError_t e = hipMalloc(&d_out, n * sizeof(float));
+    rt::Owned scratch;
+    RT_TRY(own_device(scratch, &d_in, n));
+    hipError_t e = take_device(scratch, &d_out, n);
     if (e == hipSuccess) e = hipMemcpy(d_in, in_host, n * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = rt::launch_eval_parity(op, d_in, d_out, n, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out_host, d_out, n * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_debug_eval: %s", hipGetErrorString(e));
     return RT_OK;
 }

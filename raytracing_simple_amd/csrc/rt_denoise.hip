@@ -127,10 +127,10 @@ int check_three(const rt_ctx *dst, const rt_ctx *a, const rt_ctx *b) {
 int filter_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream, bool tiles) {
     const size_t n_floats = color_floats(a), n_words = image_pixels(a);
     for (rt_ctx *c : { a, b }) {
-        if (!c->d_filtered) HIP_TRY(hipMalloc(&c->d_filtered, n_floats * sizeof(float)));
-        if (!c->d_filtered_px) HIP_TRY(hipMalloc(&c->d_filtered_px, n_words * sizeof(uint32_t)));
+        RT_TRY(ensure_device(c->owned, &c->d_filtered, n_floats));
+        RT_TRY(ensure_device(c->owned, &c->d_filtered_px, n_words));
     }
-    if (!a->d_denoise_var) HIP_TRY(hipMalloc(&a->d_denoise_var, n_floats * sizeof(float)));
+    RT_TRY(ensure_device(a->owned, &a->d_denoise_var, n_floats));
     // behind everything the two contexts have queued; their later work behind the filter
     int rc = chain(a, stream);
     if (rc == RT_OK) rc = chain(b, stream);
@@ -217,8 +217,8 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
     rc = select_device(dst);
     if (rc != RT_OK) return rc;
     const size_t n_floats = color_floats(dst);
-    if (!dst->d_denoise) HIP_TRY(hipMalloc(&dst->d_denoise, n_floats * sizeof(float)));
-    if (!dst->d_denoise_var) HIP_TRY(hipMalloc(&dst->d_denoise_var, n_floats * sizeof(float)));
+    RT_TRY(ensure_device(dst->owned, &dst->d_denoise, n_floats));
+    RT_TRY(ensure_device(dst->owned, &dst->d_denoise_var, n_floats));
     // behind everything the three contexts have queued; their later work behind the filter
     hipStream_t stream = (hipStream_t)hip_stream;
     rc = chain(dst, stream);

@@ -116,7 +116,7 @@ RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
     if (!c->have_scene || !c->have_cam) return fail(RT_ERR_STATE, "rt_features_async: rt_set_scene and rt_set_camera come first");
     rc = select_device(c);
     if (rc != RT_OK) return rc;
-    if (!c->d_features) HIP_TRY(hipMalloc(&c->d_features, 8 * image_pixels(c) * sizeof(float)));
+    RT_TRY(ensure_device(c->owned, &c->d_features, 8 * image_pixels(c)));
     // behind everything the context has queued; the tables from the records as they are now
     hipStream_t stream = (hipStream_t)hip_stream;
     rc = chain(c, stream);

@@ -1,6 +1,6 @@
 // rt_internal.h -- what the translation units of the library share behind the C ABI: the context record and the records embedded in it
-// (Choice, Probe, TileOrder, FrameState), the frame's geometry said once, error reporting, the checks and the blocking read several units
-// share, and the hooks of the multi-device context (rt_multi.hip).
+// (Choice, Probe, TileOrder, FrameState, Owned), the frame's geometry said once, error reporting, acquisition of device resources into the
+// context's record, the checks and the blocking read several units share, and the hooks of the multi-device context (rt_multi.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 
 #include "rt_device.h"
 #include "rt_frame_state.h"
+#include "rt_owned.h"
 #include "rt_tile_order.h"
 
 struct rt_multi;                    // rt_multi.hip
@@ -67,17 +68,19 @@ constexpr int kMergeMax = 16;           // rt_merge_async: dst + 15 sources
 // Adaptive sampling (rt_tiles.hip; include/rt_api.h "adaptive sampling"): the device arrays.  What they currently mean -- ragged, the selection, what
 // the list was built from -- is host state of the frame: rt_frame_state.h.
 struct TileSubset {
-    uint32_t *d_passes = nullptr;       // one word per 8x8 tile of the local pixel buffer (rt_compare_tiles' indexing); allocated on first use.  Its content
+    uint32_t *d_passes = nullptr;       // one word per 8x8 tile of the local pixel buffer (rt_compare_tiles' indexing); acquired on first use (tiles_ensure).  Its content
                                         // means something only while the frame is ragged: otherwise every tile holds current_sample passes and nothing is stored
     uint32_t *d_selected = nullptr;     // one flag per group (rt_select_tiles), then two words: selected groups, the 8x8 tiles they cover
     uint32_t *d_list = nullptr;         // the subset launch's tile list: the launch tiles of the selected groups, padded with the sentinel to whole grid rows
     uint32_t *d_groups = nullptr;       // rt_denoise_pair_tiles_async (rt_denoise.hip): the selected groups' indices in ascending order, then the sentinel; one
-                                        // word per group, allocated on that call's first use (tiles_build_group_list)
+                                        // word per group, acquired on that call's first use (tiles_build_group_list)
 };
 
 }  // namespace rt
 
 struct rt_ctx {
+    rt::Owned owned;                    // every device block, page-locked block, registered range, event and stream below (rt_owned.h): entered by the own_* /
+                                        // ensure_device helpers where it is acquired, given back by rt_destroy -- no member is freed by name
     int device = 0;
     int w = 0, h = 0;
     int rank = 0, nranks = 1, tile_rows = 8, local_rows = 0;
@@ -91,12 +94,13 @@ struct rt_ctx {
     int pixel_write = 1;                // rt_set_pixel_write
     rt::FrameState frame;               // what the progressive frame currently is: pass number, seed stream, packed pixels, launch count, tile bookkeeping
     rt::TileSubset tiles;               // adaptive sampling (rt_tiles.hip): a pass count per 8x8 tile, the selected groups, the launch list of a subset launch
-    float *d_denoise = nullptr;         // rt_denoise_async (rt_denoise.hip): the plane the filter writes, EXCHANGED with d_colors after every call; allocated on first use
+    float *d_denoise = nullptr;         // rt_denoise_async (rt_denoise.hip): the plane the filter writes, EXCHANGED with d_colors after every call (the record
+                                        // frees by value: whichever block a member holds at teardown goes once); acquired on first use
     float *d_denoise_var = nullptr;     // ... and the smoothed variance plane it is steered by (rt_denoise_pair_async: the first context's, for both halves)
-    float *d_filtered = nullptr;        // rt_denoise_pair_async: this half filtered with the other half's weights, a plane like d_colors; allocated on first use.
+    float *d_filtered = nullptr;        // rt_denoise_pair_async: this half filtered with the other half's weights, a plane like d_colors; acquired on first use.
                                         // Whether it is current is frame.filtered_pair
     uint32_t *d_filtered_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom): what rt_compare_filtered reads
-    void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; allocated on first use)
+    void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; acquired on first use)
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters
     // scene: raw records + the tables the device-side build kernel derives from them, one allocation
@@ -115,7 +119,7 @@ struct rt_ctx {
     bool have_scene = false, have_cam = false;
     // feature planes (rt_features.hip; include/rt_api.h "feature planes"): what lies under every pixel, from scene and camera alone -- so it is kept here,
     // beside them, not in the frame's state
-    float *d_features = nullptr;        // [h][w][8]: albedo, normal, distance, scene index; allocated on first use
+    float *d_features = nullptr;        // [h][w][8]: albedo, normal, distance, scene index; acquired on first use
     bool features_current = false;      // formed by rt_features_async since the last rt_set_scene / rt_update_spheres_async / rt_set_camera
     rt_guide_params guide{};            // rt_set_denoise_guide: what the filters of a pair of halves add to their weights ...
     bool have_guide = false;            // ... when it is on
@@ -222,6 +226,65 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
             return rt::fail(RT_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
                             __FILE__, __LINE__);                                               \
     } while (0)
+// ... and a call that has said so itself (fail): its code is passed on
+#define RT_TRY(call)                    \
+    do {                                \
+        const int rc_ = (call);         \
+        if (rc_ != RT_OK) return rc_;   \
+    } while (0)
+
+// ---- acquisition into a record (rt_owned.h): the handle is entered where it is made, so whatever fails later, teardown finds it ----
+// (the take_* forms return the runtime's answer for callers that report it in words of their own; a failed call enters nothing and leaves null)
+template <class T> inline hipError_t take_device(Owned &owned, T **p, size_t count) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
+    if (e == hipSuccess) owned.adopt(Owned::Kind::Device, *p);
+    else *p = nullptr;
+    return e;
+}
+template <class T> inline hipError_t take_pinned(Owned &owned, T **p, size_t count) {
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(p), count * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess) owned.adopt(Owned::Kind::Pinned, *p);
+    else *p = nullptr;
+    return e;
+}
+inline hipError_t take_event(Owned &owned, hipEvent_t *ev, unsigned flags) {
+    const hipError_t e = hipEventCreateWithFlags(ev, flags);
+    if (e == hipSuccess) owned.adopt(Owned::Kind::Event, *ev);
+    else *ev = nullptr;
+    return e;
+}
+inline int own_failed(const char *what, hipError_t e, const char *file, int line) {
+    return fail(RT_ERR_HIP, "%s failed: %s (%s:%d)", what, hipGetErrorString(e), file, line);
+}
+// `count` elements of *p's type; RT_ERR_HIP with the caller's file and line, as HIP_TRY says it
+template <class T> inline int own_device(Owned &owned, T **p, size_t count, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    const hipError_t e = take_device(owned, p, count);
+    return e == hipSuccess ? RT_OK : own_failed("hipMalloc", e, file, line);
+}
+template <class T> inline int own_pinned(Owned &owned, T **p, size_t count, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    const hipError_t e = take_pinned(owned, p, count);
+    return e == hipSuccess ? RT_OK : own_failed("hipHostMalloc", e, file, line);
+}
+inline int own_event(Owned &owned, hipEvent_t *ev, unsigned flags = hipEventDefault, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    const hipError_t e = take_event(owned, ev, flags);
+    return e == hipSuccess ? RT_OK : own_failed("hipEventCreateWithFlags", e, file, line);
+}
+inline int own_stream(Owned &owned, hipStream_t *s, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {      // non-blocking, like every stream of the library
+    const hipError_t e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+    if (e != hipSuccess) return own_failed("hipStreamCreateWithFlags", e, file, line);
+    owned.adopt(Owned::Kind::Stream, *s);
+    return RT_OK;
+}
+inline int own_registered(Owned &owned, void *host, size_t bytes, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {   // a caller's buffer, page-locked in place
+    const hipError_t e = hipHostRegister(host, bytes, hipHostRegisterDefault);
+    if (e != hipSuccess) return own_failed("hipHostRegister", e, file, line);
+    owned.adopt(Owned::Kind::Registered, host);
+    return RT_OK;
+}
+// "acquired on first use": nothing when *p is there already
+template <class T> inline int ensure_device(Owned &owned, T **p, size_t count, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    return *p ? RT_OK : own_device(owned, p, count, file, line);
+}
 
 // ---- rt_api.hip: the context's device and the order of its work ----
 int select_device(const rt_ctx *c);
@@ -249,7 +312,6 @@ double estimate_ratio(const rt_ctx *c);             // predicted walk / sweep ti
 int launch(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block = false);
 
 // ---- rt_scene.hip: records, tables, staging ----
-void free_scene(rt_ctx *c);
 int ensure_scene_capacity(rt_ctx *c, uint32_t count);
 int upload_spheres(rt_ctx *c, uint32_t first, uint32_t count, const rt_sphere *spheres, uint32_t n_total, hipStream_t stream, bool full_upload);
 
@@ -285,7 +347,7 @@ int tiles_refuse(const rt_ctx *c, const char *call);                  // RT_ERR_
 int tiles_ensure(rt_ctx *c);                                          // the three device arrays of rt_ctx::tiles, on first use
 int merge_by_tile(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, int total, hipStream_t stream);   // rt_merge_async with a ragged context among them (checked by the caller)
 int tiles_build_list(rt_ctx *c, int waves, bool by_order, uint32_t n_launch, uint32_t slots, hipStream_t stream);   // d_list for an instance of `waves` wavefronts
-int tiles_build_group_list(rt_ctx *c, hipStream_t stream);            // d_groups (allocated on first use): the selected groups in ascending order, by the same kernel
+int tiles_build_group_list(rt_ctx *c, hipStream_t stream);            // d_groups (acquired on first use): the selected groups in ascending order, by the same kernel
 int tiles_advance(rt_ctx *c, int n_samples, hipStream_t stream);      // + n_samples on every tile of every selected group (the array made explicit first)
 int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream);       // rt_launch.hip: n_samples passes on the selected groups
 

@@ -102,6 +102,7 @@ int load_rccl() {
 struct rt_multi {
     int n = 0;
     int w = 0, h = 0, tile_rows = 8, pad_rows = 0;
+    rt::Owned owned;                    // the root device's blocks, events, gather stream and the registered output buffer below (rt_owned.h); the shards keep their own
     bool emulated = false;              // a device is listed twice: D2D copies stand in for ncclSend/ncclRecv
     std::vector<int> devices;
     std::vector<rt_ctx *> shard;        // shard[r] = rt_create_sharded(w, h, devices[r], r, n, tile_rows)
@@ -308,19 +309,19 @@ RT_API int rt_create_multi_on(rt_ctx **out, int w, int h, const int *devices, in
             m->shard.push_back(s);
         }
         HIP_TRY(hipSetDevice(devices[0]));
-        HIP_TRY(hipMalloc(&m->d_full, ((size_t)w * h + 4) * sizeof(uint32_t)));
+        RT_TRY(own_device(m->owned, &m->d_full, (size_t)w * h + 4));
         HIP_TRY(hipMemset(m->d_full, 0, (size_t)w * h * sizeof(uint32_t)));
         if (ngpus == 1)                                 // the one shard's rows are the frame: no slots, no gather, no de-interleave
             return rt_set_pixel_buffer(m->shard[0], m->d_full, (size_t)w * h);
         for (int k = 0; k < 2; ++k) {
-            HIP_TRY(hipMalloc(&m->d_gathered[k], ((size_t)ngpus * m->pad_rows * w + 4) * sizeof(uint32_t)));
+            RT_TRY(own_device(m->owned, &m->d_gathered[k], (size_t)ngpus * m->pad_rows * w + 4));
             HIP_TRY(hipMemset(m->d_gathered[k], 0, (size_t)ngpus * m->pad_rows * w * sizeof(uint32_t)));
-            HIP_TRY(hipEventCreateWithFlags(&m->ev_gathered[k], hipEventDisableTiming));
+            RT_TRY(own_event(m->owned, &m->ev_gathered[k], hipEventDisableTiming));
         }
-        HIP_TRY(hipStreamCreateWithFlags(&m->gather_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_rendered, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_ready, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&m->ev_copied, hipEventDisableTiming));
+        RT_TRY(own_stream(m->owned, &m->gather_stream));
+        RT_TRY(own_event(m->owned, &m->ev_rendered, hipEventDisableTiming));
+        RT_TRY(own_event(m->owned, &m->ev_ready, hipEventDisableTiming));
+        RT_TRY(own_event(m->owned, &m->ev_copied, hipEventDisableTiming));
         // the root renders its own rows straight into the receive slot of the frame (begin_frame sets it per frame)
         return rt_set_pixel_buffer(m->shard[0], m->d_gathered[0], (size_t)m->pad_rows * w);
     };
@@ -388,18 +389,10 @@ void multi_destroy(rt_ctx *front) {
     if (m->gather_stream && !m->broken && !m->devices.empty() && hipSetDevice(m->devices[0]) == hipSuccess)
         (void)hipStreamSynchronize(m->gather_stream);   // (it reads the shards' buffers: before they go)
     for (rt_ctx *s : m->shard) rt_destroy(s);           // waits for each shard's stream (a stuck context's shards: neither wait nor free, rt_api.hip)
-    if (!stuck && !m->devices.empty() && hipSetDevice(m->devices[0]) == hipSuccess) {
-        if (m->pinned_out) (void)hipHostUnregister(m->pinned_out);
-        (void)hipFree(m->d_gathered[0]);
-        (void)hipFree(m->d_gathered[1]);
-        (void)hipFree(m->d_full);
-        if (m->ev_ready) (void)hipEventDestroy(m->ev_ready);
-        if (m->ev_copied) (void)hipEventDestroy(m->ev_copied);
-        if (m->ev_rendered) (void)hipEventDestroy(m->ev_rendered);
-        for (hipEvent_t e : m->ev_gathered)
-            if (e) (void)hipEventDestroy(e);
-        if (m->gather_stream) (void)hipStreamDestroy(m->gather_stream);
-    }
+    if (!stuck && !m->devices.empty() && hipSetDevice(m->devices[0]) == hipSuccess)
+        m->owned.release();
+    else
+        m->owned.forget();
     // (mark_broken has aborted and cleared the communicators where the library has ncclCommAbort; where it has not, a
     // communicator that sits in a failed group is not handed to ncclCommDestroy, which may wait for that group: leaked)
     for (rcclComm c : m->comm)
@@ -619,12 +612,12 @@ int multi_pin_output(rt_ctx *front, uint32_t *out_host, size_t count) {
     HIP_TRY(hipSetDevice(m->devices[0]));
     if (m->pinned_out) {
         HIP_TRY(hipStreamSynchronize(frame_stream(m)));
-        (void)hipHostUnregister(m->pinned_out);
+        m->owned.drop(m->pinned_out);
         m->pinned_out = nullptr;
     }
     if (!out_host) return RT_OK;
     if (count < (size_t)m->w * (size_t)m->h) return fail(RT_ERR_ARG, "output buffer of %zu < %zu elements", count, (size_t)m->w * (size_t)m->h);
-    HIP_TRY(hipHostRegister(out_host, count * sizeof(uint32_t), hipHostRegisterDefault));
+    RT_TRY(own_registered(m->owned, out_host, count * sizeof(uint32_t)));
     m->pinned_out = out_host;
     return RT_OK;
 }

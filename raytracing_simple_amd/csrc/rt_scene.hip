@@ -66,12 +66,13 @@ namespace rt {
 
 static bool light_test(const rt_sphere &s) { return !((s.e.x == 0.f) && (s.e.z == 0.f)); }   // .cl:135-138,266
 
-void free_scene(rt_ctx *c) {
-    (void)hipFree(c->d_spheres);
-    (void)hipFree(c->d_tables);
-    (void)hipFree(c->d_bvh);
-    (void)hipFree(c->d_dup);
-    if (c->h_dup_stage) (void)hipHostFree(c->h_dup_stage);
+// the blocks sized by scene_cap given back (the staging of uploads and of host-built trees have capacities of their own and stay)
+static void free_scene(rt_ctx *c) {
+    c->owned.drop(c->d_spheres);
+    c->owned.drop(c->d_tables);
+    c->owned.drop(c->d_bvh);
+    c->owned.drop(c->d_dup);
+    c->owned.drop(c->h_dup_stage);
     c->d_dup = nullptr;
     c->h_dup_stage = nullptr;
     c->dup_stage_used = false;
@@ -89,20 +90,21 @@ int ensure_scene_capacity(rt_ctx *c, uint32_t count) {
     while (cap < count) cap *= 2;
     int rc = wait_all(c);               // nothing may still read the tables that are about to go
     if (rc != RT_OK) return rc;
+    // the new blocks first, the old ones after (free_scene): a failure leaves the scene the context holds as it was
+    rt::Owned &own = c->owned;
     rt_sphere *ns = nullptr;
-    float4 *nt = nullptr;
-    HIP_TRY(hipMalloc(&ns, (size_t)cap * sizeof(rt_sphere)));
-    float4 *nb = nullptr;
-    hipError_t e = hipMalloc(&nt, ((size_t)cap * 5 + 1) * sizeof(float4));
+    float4 *nt = nullptr, *nb = nullptr;
+    uint8_t *nd = nullptr;
+    RT_TRY(own_device(own, &ns, cap));
+    hipError_t e = take_device(own, &nt, (size_t)cap * 5 + 1);
     // blob: hdr 2 + slots (< cap + 8; up to twice that with the partial leaves of the shaped tree) + index (a quarter of the
     // slots) + pairs (< cap / 2 + 4) + two material records per slot, in float4
-    if (e == hipSuccess) e = hipMalloc(&nb, ((size_t)cap * 6 + 64) * sizeof(float4));
-    uint8_t *nd = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&nd, (size_t)cap);
+    if (e == hipSuccess) e = take_device(own, &nb, (size_t)cap * 6 + 64);
+    if (e == hipSuccess) e = take_device(own, &nd, cap);
     if (e != hipSuccess) {
-        (void)hipFree(ns);
-        (void)hipFree(nt);
-        (void)hipFree(nb);
+        own.drop(ns);
+        own.drop(nt);
+        own.drop(nb);
         return fail(RT_ERR_ALLOC, "scene tables for %u spheres: %s", cap, hipGetErrorString(e));
     }
     free_scene(c);
@@ -123,10 +125,10 @@ static int ensure_stage_capacity(rt_ctx *c, uint32_t count) {
             HIP_TRY(hipEventSynchronize(c->stage_ev[k]));
             c->stage_used[k] = false;
         }
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr;
-    c->stage_cap = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_stage), (size_t)cap * 4 * sizeof(rt_sphere), hipHostMallocDefault));
+    rt_sphere *grown = nullptr;
+    RT_TRY(own_pinned(c->owned, &grown, (size_t)cap * 4));
+    c->owned.drop(c->h_stage);
+    c->h_stage = grown;
     c->stage_cap = cap;
     return RT_OK;
 }

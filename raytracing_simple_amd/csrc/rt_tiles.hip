@@ -152,13 +152,13 @@ using namespace rt;
 
 namespace rt {
 
-// the three device arrays, on first use (rt_destroy frees them)
+// the three device arrays, on first use
 int tiles_ensure(rt_ctx *c) {
     rt::TileSubset &s = c->tiles;
     const size_t tiles = std::max<size_t>(tile_count(c), 1), tiles_x = tiles_per_row(c);
-    if (!s.d_passes) HIP_TRY(hipMalloc(&s.d_passes, tiles * sizeof(uint32_t)));
-    if (!s.d_selected) HIP_TRY(hipMalloc(&s.d_selected, ((size_t)group_count(c) + 2) * sizeof(uint32_t)));
-    if (!s.d_list) HIP_TRY(hipMalloc(&s.d_list, (tiles + tiles_x) * sizeof(uint32_t)));      // every tile, and the padding of the last grid row
+    RT_TRY(ensure_device(c->owned, &s.d_passes, tiles));
+    RT_TRY(ensure_device(c->owned, &s.d_selected, (size_t)group_count(c) + 2));
+    RT_TRY(ensure_device(c->owned, &s.d_list, tiles + tiles_x));      // every tile, and the padding of the last grid row
     return RT_OK;
 }
 
@@ -186,7 +186,7 @@ int tiles_build_list(rt_ctx *c, int waves, bool by_order, uint32_t n_launch, uin
 int tiles_build_group_list(rt_ctx *c, hipStream_t stream) {
     rt::TileSubset &s = c->tiles;
     const uint32_t n_groups = group_count(c), groups_x = groups_per_row(c);
-    if (!s.d_groups) HIP_TRY(hipMalloc(&s.d_groups, (size_t)n_groups * sizeof(uint32_t)));
+    RT_TRY(ensure_device(c->owned, &s.d_groups, n_groups));
     hipLaunchKernelGGL(rt_tile_list_kernel, dim3(1), dim3(1024), 0, stream, nullptr, n_groups, groups_x, 1u, groups_x, s.d_selected, s.d_groups, n_groups, n_groups);
     HIP_TRY(hipGetLastError());
     c->frame.group_list_built();

@@ -322,3 +322,101 @@ def test_a_checkpoint_file_resumes_the_render_and_bad_files_are_refused(tmp_path
             s2 = snapshot(other)
             assert "image size" in _refused(other, RT_ERR_ARG, other.load_state, path)
             assert_unchanged(other, s2)
+
+
+# ---- what a context acquires, its teardown gives back (csrc/rt_owned.h) -------------------------------------------------------------------
+def _every_resource_once(w, h):
+    """Two halves and a destination of w x h on device 0, driven through every call that acquires something on first use; returns what must stay
+    alive until they are closed: the contexts, and the buffers the first one has had registered."""
+    cam = host.compute_camera(host.DEMO_ORIG, host.DEMO_TARGET, w, h)
+    many = scenes.random_spheres(200)[0].copy()
+    many[199] = many[198]                                   # one record repeats another bit for bit: the duplicate flags and their staging exist
+    a, b, dst = (api.RtContext(w, h) for _ in range(3))
+    for k, c in enumerate((a, b, dst)):
+        c.set_scene(host.demo_scene())                      # tables and staging ring for 64 records ...
+        c.set_camera(cam)
+        c.set_scene(many)                                   # ... grown to 256; the hierarchy, the host's tree and its staging
+        c.update_spheres(3, many[3:9])
+        if k < 2:
+            c.seed_stream(k + 1)
+            c.render_async(2)
+    dst.merge([a, b])
+    a.compare(b, tiles=True)
+    for c in (a, b):
+        c.set_denoise_guide(api.guide_defaults())
+        c.features_async()
+    dst.denoise(a, b)
+    a.denoise_pair(b)
+    assert a.select_tiles(None, 0, a.stream) == b.select_tiles(None, 0, b.stream)
+    a.render_tiles_async(1, a.stream)
+    b.render_tiles_async(1, b.stream)
+    a.denoise_pair_tiles(b)
+    outs = [np.zeros(w * h, np.uint32) for _ in range(2)]
+    for c in (a, b, dst):
+        c.throttle(4)
+        c.throttle(0)
+    for out in outs:
+        a.pin_output(out)                                   # the second call gives the first registration back
+    return [a, b, dst], outs
+
+
+def test_contexts_give_back_every_resource_they_acquired():
+    """Free device memory after two halves and a destination that have acquired everything a context can -- regrown scene tables and staging, the
+    hierarchy's blob and staging, duplicate flags, the tile arrays, compare scratch, feature, filter and variance planes, throttle events, a registered
+    output buffer -- and were closed is what it was before them, within the megabyte tests/test_gpu_features.py allows a broken multi-device
+    context; and again after a second such cycle against the SAME baseline, so that one plane lost per cycle shows even where the first loss fits
+    the margin.  While they are held, at least the bytes the planes acquired on first use ask for are gone (the sum below, from w and h alone)."""
+    import torch
+    w, h = 512, 256
+    px = w * h
+    on_first_use = (2 * 8 * px * 4          # feature planes of the two halves
+                    + 2 * 3 * px * 4        # their cross-filtered planes ...
+                    + 2 * px * 4            # ... packed
+                    + 2 * 3 * px * 4        # variance planes: the first half's, the destination's
+                    + 3 * px * 4)           # the plane the destination's filter writes
+    ctxs, outs = _every_resource_once(w, h)                 # (a first cycle pays the process-wide allocations: not part of the baseline)
+    for c in ctxs:
+        c.close()
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info(0)[0]
+    for cycle in range(2):
+        ctxs, outs = _every_resource_once(w, h)
+        torch.cuda.synchronize()
+        held = free_before - torch.cuda.mem_get_info(0)[0]
+        print("cycle %d: %d bytes held, %d acquired on first use" % (cycle, held, on_first_use))
+        assert held >= on_first_use, (cycle, held, on_first_use)
+        for c in ctxs:
+            c.close()
+        torch.cuda.synchronize()
+        free_after = torch.cuda.mem_get_info(0)[0]
+        print("cycle %d: free %d before, %d after" % (cycle, free_before, free_after))
+        assert free_after >= free_before - (1 << 20), (cycle, free_before, free_after)
+        del outs
+
+
+def test_a_multi_device_context_gives_back_what_it_acquired():
+    """The same bound for rt_multi's own record (the assembled frame, the two receive slots, events, the gather stream) and its shards: one device
+    listed twice, created, rendered, closed."""
+    import torch
+    w, h = 96, 64
+    sph, orig, target = scene("plus")
+    cam = host.compute_camera(orig, target, w, h)
+
+    def cycle():
+        ctx = api.RtContext(w, h, devices=[0, 0])
+        ctx.set_scene(sph)
+        ctx.set_camera(cam)
+        ctx.render_pass(1)
+        return ctx
+
+    cycle().close()                                         # (process-wide allocations)
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info(0)[0]
+    for _ in range(2):
+        ctx = cycle()
+        assert torch.cuda.mem_get_info(0)[0] < free_before  # (the context holds device memory now)
+        ctx.close()
+        torch.cuda.synchronize()
+        free_after = torch.cuda.mem_get_info(0)[0]
+        print("multi: free %d before, %d after" % (free_before, free_after))
+        assert free_after >= free_before - (1 << 20), (free_before, free_after)

@@ -1,7 +1,8 @@
 #!/bin/bash
 # AddressSanitizer + UndefinedBehaviorSanitizer over the CPU-side code (GPU sanitizers are not
 # available on this pool): the oracle's renderer, the product's host helpers (scene reader with
-# good, truncated and missing files, seed stream, camera basis) and the hierarchy's host builders.
+# good, truncated and missing files, seed stream, camera basis), the hierarchy's host builders and
+# the record of a context's resources (rt_owned.h, with a recorder in owned_free's place).
 # Run from the repository root.
 set -eu
 R=$(cd "$(dirname "$0")/../.." && pwd)
@@ -24,6 +25,8 @@ g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-
     $R/tools/sanitize/bvh_main.cpp $R/raytracing_simple_amd/csrc/rt_bvh_host.cpp -o $T/bvh_san
 $T/bvh_san
 $T/host_san
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/owned_main.cpp -o $T/owned_san
+$T/owned_san
 # the .scn reader on 1000 mutated files (deletions, junk tokens, non-finite numbers, truncation)
 mkdir -p $T/fz
 python3 - <<PY
