@@ -243,7 +243,7 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
         c->last_stream = c->stream;
         RT_TRY(own_event(own, &c->ev0));
         RT_TRY(own_event(own, &c->ev1));
-        for (int k = 0; k < 4; ++k) RT_TRY(own_event(own, &c->probe.ev[k]));
+        for (int k = 0; k < 4; ++k) RT_TRY(own_event(own, &c->probe_ev[k]));
         RT_TRY(own_event(own, &c->ev_dep, hipEventDisableTiming));
         for (int k = 0; k < 4; ++k) RT_TRY(own_event(own, &c->stage_ev[k], hipEventDisableTiming));
         lap(1);
@@ -343,7 +343,7 @@ RT_API int rt_set_scene(rt_ctx *c, const rt_sphere *spheres, uint32_t count) {
     c->is_light.assign(c->scene_cap, 0);
     c->h_spheres.assign(spheres, spheres + count);
     c->order.forget();
-    rearm_probe(c);                     // a new scene: hierarchy or plain sweep is measured again
+    c->choice.new_scene();              // hierarchy or plain sweep, cooperative any-hit or not: undecided again
     rc = upload_spheres(c, 0, count, spheres, count, c->stream, true);
     if (rc != RT_OK) {
         c->have_scene = false;          // the tables are in an unknown state

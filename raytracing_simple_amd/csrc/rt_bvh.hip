@@ -640,7 +640,7 @@ __global__ void __launch_bounds__(256) rt_bvh_pack_pairs_kernel(const float4 *bl
 #endif   // RT_DIAGNOSTICS
 
 constexpr uint32_t kDeviceBuildMax = 8192;      // beyond: more than one workgroup sorts in LDS, the host builds (rt_bvh_host.cpp bvh_shape_halved)
-constexpr uint32_t kSahMaxTree = rt::kAlwaysWalkFrom - 1;   // the host shapes the trees whose surface areas the choice of form is estimated from (1.2 ms at 1024
+constexpr uint32_t kSahMaxTree = rt::Choice::kAlwaysWalkFrom - 1;   // the host shapes the trees whose surface areas the choice of form is estimated from (1.2 ms at 1024
                                                 // spheres); from kAlwaysWalkFrom on nothing is estimated and the device shapes the tree (rt_bvh_build_sah_kernel)
 constexpr uint32_t kSahMinTree = 128;           // below 16 leaves the halved shape is as good (64 spheres: 6.95 against 7.03 ms) and one level shallower
 
@@ -666,7 +666,9 @@ int upload_host_tree(rt_ctx *c, const rt::BvhHostTree &tree, hipStream_t stream)
     if (!c->bvh_stage_ev) RT_TRY(own_event(c->owned, &c->bvh_stage_ev));
     HIP_TRY(hipEventRecord(c->bvh_stage_ev, stream));
     c->bvh_stage_used = true;
-    c->bvh_est_valid = rt::bvh_estimate(tree, &c->bvh_est_pairs, &c->bvh_est_leaves);
+    double pairs = 0.0, leaves = 0.0;
+    const bool valid = rt::bvh_estimate(tree, &pairs, &leaves);
+    c->choice.tree_uploaded(valid, pairs, leaves);
     return RT_OK;
 }
 
@@ -777,7 +779,7 @@ static int build_bvh_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, boo
     c->bvh_ok = false;
     c->bvh = {};
     c->bvh_n_tree = 0;
-    if (full_upload) c->bvh_est_valid = false;          // (a device-resident update keeps the upload's estimate: the probe logic decides when it is stale)
+    if (full_upload) c->choice.uploading_without_estimate();     // (a device-resident update keeps the upload's estimate: Choice::tables_rebuilt decides when it is stale)
     if (c->bvh_min <= 0 || n_total < (uint32_t)c->bvh_min || !c->d_bvh) return RT_OK;
     {
         const int rc = mark_duplicates(c, n_total, stream);

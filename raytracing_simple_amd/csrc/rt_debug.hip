@@ -191,7 +191,7 @@ static int dbg_set_gate(rt_ctx *c, int v) { c->regen_gate = v; return RT_OK; }
 static int dbg_set_matlds(rt_ctx *c, int v) { c->mat_lds_limit = v; return RT_OK; }
 static int dbg_set_persist(rt_ctx *c, int v) { c->persist = v ? 1 : 0; return RT_OK; }
 static int dbg_set_ncus(rt_ctx *c, int v) { c->n_cus = v; return RT_OK; }
-static int dbg_set_coop(rt_ctx *c, int v) { c->coop_min = v & 0xffffff; c->coop_kmax = v >> 24; c->choice.coop_probe = 0; rearm_probe(c); return RT_OK; }     // (a threshold set by hand decides alone: no measurement)
+static int dbg_set_coop(rt_ctx *c, int v) { c->coop_min = v & 0xffffff; c->coop_kmax = v >> 24; c->choice.coop_threshold_set_by_hand(); return RT_OK; }     // (a threshold set by hand decides alone: no measurement)
 static int dbg_set_wg(rt_ctx *c, int v) { c->wg_waves = v; return RT_OK; }
 static int dbg_set_direct(rt_ctx *c, int v) { c->direct_max = v; return RT_OK; }
 static int dbg_set_order(rt_ctx *c, int v) { c->order.enable(v != 0); return RT_OK; }
@@ -297,7 +297,7 @@ RT_API int rt_debug_read_tile_list(rt_ctx *c, uint32_t *list_out, uint32_t cap, 
 static int dbg_set_bvh_lds(rt_ctx *c, int v) { if (v > 0) c->bvh_lds_limit = v; return RT_OK; }
 static int dbg_set_bvh_min(rt_ctx *c, int v) {
     c->bvh_min = v;
-    rearm_probe(c);
+    c->choice.knob_set();
     if (!c->have_scene) return RT_OK;
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
@@ -308,7 +308,7 @@ static int dbg_set_bvh_min(rt_ctx *c, int v) {
 }
 static int dbg_set_tree_shape(rt_ctx *c, int v) {
     c->bvh_sah = v < 0 ? 0 : (v > 2 ? 2 : v);
-    return dbg_set_bvh_min(c, c->bvh_min);          // (rebuilds the current scene's tables, re-arms the probe)
+    return dbg_set_bvh_min(c, c->bvh_min);          // (rebuilds the current scene's tables, undecided again)
 }
 // rt_set_mode of an A/B instance that reads a table the product's layout lacks -- ..._gt / _gtp the promoted top, _gq the packed pair table --
 // asks for it as rt_debug_set_bvh_layout would (kept for the context's later scenes) and rebuilds the current scene's tables at once.  Any
@@ -351,7 +351,7 @@ RT_API int rt_debug_set_walk_round(rt_ctx *c, int steps) {
     return dbg_apply(c, dbg_set_walk_round, steps);
 }
 
-static int dbg_set_walk_forced(rt_ctx *c, int v) { c->walk_forced = v ? 1 : 0; rearm_probe(c); return RT_OK; }
+static int dbg_set_walk_forced(rt_ctx *c, int v) { c->walk_forced = v ? 1 : 0; c->choice.knob_set(); return RT_OK; }
 // rt_walk.inc.h: pair steps per lane per loop trip, ready lanes that make a wavefront shade (0 = keep either), and
 // forced: 0 = hierarchy or plain sweep by measurement (the library's behaviour), 1 = the hierarchy whenever the scene has one
 RT_API int rt_debug_set_walk(rt_ctx *c, int steps, int gate, int forced) {
@@ -400,13 +400,14 @@ RT_API int rt_debug_walk_rays(rt_ctx *c, const float *rays8, uint32_t n_rays, ui
 RT_API int rt_debug_tree_estimate(rt_ctx *c, double *out4) {
     if (!c || c->multi || !out4) return fail(RT_ERR_ARG, "null / multi-device context");
     if (c->tables_stale && select_device(c) == RT_OK) (void)fresh_tables(c);
-    out4[0] = c->bvh_est_pairs;
-    out4[1] = c->bvh_est_leaves;
-    out4[2] = c->bvh_est_valid && c->bvh_ok ? estimate_ratio(c) : 0.0;
+    const bool have = c->choice.est_valid && c->bvh_ok;
+    out4[0] = c->choice.est_pairs;
+    out4[1] = c->choice.est_leaves;
+    out4[2] = have ? c->choice.estimate_ratio(c->bvh.n_always, c->scene.n_spheres) : 0.0;
     out4[3] = c->choice.pick_estimated ? 1.0 : 0.0;
-    return c->bvh_est_valid && c->bvh_ok ? 1 : 0;
+    return have ? 1 : 0;
 }
-static int dbg_set_estimate(rt_ctx *c, int v) { c->choice.use_estimate = v ? 1 : 0; rearm_probe(c); return RT_OK; }
+static int dbg_set_estimate(rt_ctx *c, int v) { c->choice.estimate_switched(v != 0); return RT_OK; }
 RT_API int rt_debug_set_choice_estimate(rt_ctx *c, int on) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     return dbg_apply(c, dbg_set_estimate, on);

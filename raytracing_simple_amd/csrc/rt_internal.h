@@ -1,5 +1,5 @@
 // rt_internal.h -- what the translation units of the library share behind the C ABI: the context record and the records embedded in it
-// (Choice, Probe, TileOrder, FrameState, Owned), the frame's geometry said once, error reporting, acquisition of device resources into the
+// (Choice, TileOrder, FrameState, Owned), the frame's geometry said once, error reporting, acquisition of device resources into the
 // context's record, the checks and the blocking read several units share, and the hooks of the multi-device context (rt_multi.hip).
 #pragma once
 
@@ -7,6 +7,7 @@
 
 #include <vector>
 
+#include "rt_choice.h"
 #include "rt_device.h"
 #include "rt_frame_state.h"
 #include "rt_owned.h"
@@ -16,52 +17,6 @@ struct rt_multi;                    // rt_multi.hip
 struct rt_ctx;
 
 namespace rt {
-
-// What a launch renders with: asked of launch_form() (rt_launch.hip), kept as a scene's verdicts, recorded of the last launch.
-//   Auto        the context's own choice from its thresholds.  As a verdict: not decided yet; as the last launch: nothing launched yet
-//   Walk        the hierarchy (if the scene has one)
-//   Sweep       the plain sweep; cooperative any-hit or not as the sphere count says
-//   SweepCoop   the sweep WITH cooperative any-hit whatever the sphere count says (the small-scene measurement); SweepPlain: WITHOUT
-enum class Form : uint8_t { Auto, Walk, Sweep, SweepCoop, SweepPlain };
-inline bool sweeps(Form f) { return f >= Form::Sweep; }
-// the C ABI's number for a hierarchy verdict (rt_scene_choice, rt_debug_bvh_pick): 0 = not decided yet, 1 = hierarchy, 2 = plain sweep
-inline int verdict_number(Form f) { return f == Form::Auto ? 0 : (f == Form::Walk ? 1 : 2); }
-
-// Which form renders this scene, and what the decision rests on (rt_launch.hip launch(), launch_small()).
-struct Choice {
-    // hierarchy or plain sweep?  Decided per scene by measurement (rt_launch.hip launch()): each form once warm and once
-    // timed between events, in the same tile order; whichever took less time per pass renders the rest
-    Form bvh_pick = Form::Auto;         // Auto = not decided yet, Walk, Sweep
-    bool pick_estimated = false;        // ... and it came from the surface-area estimate, not from a measurement
-    int use_estimate = 1;               // diagnostics knob: 0 = every undecided scene is measured
-    double est_ratio = 0.0;             // the estimate's predicted walk / sweep time (0 = none made)
-    uint32_t probe_tree = 0, probe_always = 0;   // the tree the verdict was measured on
-    int probe_updates = 0;              // device-resident updates since the verdict (it is measured again after 256)
-    double probe_ms[2] = { 0.0, 0.0 };  // measured time per pass: hierarchy, plain sweep (0 = not measured)
-    // ... and for a scene WITHOUT a hierarchy and fewer spheres than coop_min: cooperative any-hit or not, timed on the host's own launches (rt_launch.hip launch_small).
-    // Below 12 spheres the threshold alone picks wrongly either way -- the Demo scene is 2 % faster without the sharing, the reference's simple.scn,
-    // caustic.scn and caustic3.scn (6 and 10 records) 7-11 % faster with it (profiles/r06_reference_scenes.jsonl) -- so it is measured.
-    Form coop_pick = Form::Auto;        // Auto = not decided yet, SweepCoop, SweepPlain
-    int coop_probe = 1;                 // diagnostics knob: 0 = the threshold alone decides (round 5's behaviour)
-    uint32_t scene_frames = 0;          // resets since rt_set_scene that followed at least one launch OF THAT SCENE: frames of it already rendered
-    uint64_t scene_launches = 0;        // launches since rt_set_scene
-    rt_ctx *leader = nullptr;           // a shard of a multi-device context: the shard whose verdict it follows (null: its own)
-    Form last = Form::Auto;             // what the last launch was: Walk, SweepCoop (a cooperative any-hit instance) or SweepPlain (any other sweep) --
-                                        // what a multi-device context's other shards follow
-    // rt_reset / rt_reset_async: a frame of the current scene has been rendered, if anything of it was launched (rt_launch.hip launch_small)
-    void frame_ended() { if (scene_launches > 0) scene_frames += 1; }
-};
-
-// The measurement in flight, if any.  Both are four steps on the context's launches -- arm 0 warm, arm 0 timed, arm 1 warm, arm 1 timed; a timed
-// step lies between ev[2 * arm] and ev[2 * arm + 1] -- and differ in what the arms are and in how many passes a step takes (rt_launch.hip).
-struct Probe {
-    enum Which : uint8_t { None, WalkVsSweep, CoopVsPlain };
-    Which which = None;
-    int state = 0;                      // steps finished (0..4)
-    int acc = 0;                        // passes launched so far inside the timed step that is open
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    int samples[2] = { 0, 0 };          // passes between the events of arm 0, arm 1
-};
 
 constexpr int kMergeMax = 16;           // rt_merge_async: dst + 15 sources
 
@@ -143,10 +98,6 @@ struct rt_ctx {
     int bvh_sah = 1;                    // the hierarchy's shape is chosen by surface area (rt_bvh.hip): 1 = uploads below kAlwaysWalkFrom tree spheres on the host,
                                         // larger uploads and every device-resident update on the device; 2 = the device for uploads too; 0 = the fixed (halved) shape
     uint32_t bvh_n_tree = 0;            // spheres inside the tree (the slots are padded to whole leaves)
-    // surface-area sums of a host-built tree (rt_bvh_host.cpp bvh_estimate, set by rt_bvh.hip upload_host_tree): what a random line through the root box is expected to visit --
-    // pair steps (inner nodes, the root counted once) and leaves; the estimate that settles hierarchy against sweep without a launch
-    double bvh_est_pairs = 0.0, bvh_est_leaves = 0.0;
-    bool bvh_est_valid = false;
     int bvh_min = 56;                   // scenes with at least this many spheres inside the tree use it (0 = never)
     int bvh_lds_limit = 31 * 1024;      // its tables are staged in LDS while five workgroups of that size fit a CU (2048 spheres: 6.2 ms from L2 with
                                         // 4-5 waves per SIMD against 9.5 ms from LDS with two workgroups per CU); larger ones are read from HBM / L2
@@ -158,8 +109,8 @@ struct rt_ctx {
                                         // (round 4, this kernel: 2 / 3 / 4 / 6 in a row = 5.42 / 5.37 / 5.22 / 5.45 ms on C3, profiles/r04k_walk_sweep.jsonl)
     int walk_tail = 0;                  // lanes that may be left walking when a trip's walk phase ends (0 = none: every walk runs to its end within the trip)
     int walk_forced = 0;                // 0 = measured choice (`choice` below); diagnostics: 1 = the hierarchy whenever the scene has one
-    rt::Choice choice;                  // hierarchy or sweep, cooperative any-hit or not: the verdicts for this scene
-    rt::Probe probe;                    // ... and the measurement behind them, while one runs
+    rt::Choice choice;                  // hierarchy or sweep, cooperative any-hit or not: the verdicts for this scene, the measurement behind them, the estimate (rt_choice.h)
+    hipEvent_t probe_ev[4] = { nullptr, nullptr, nullptr, nullptr };       // ... and the measurement's events: arm a's timed step lies between probe_ev[2 * a] and probe_ev[2 * a + 1]
     rt::TileOrder order;                // heavy-first tile schedule (rt_tile_order.h; rt_trace.inc.h reads and writes its arrays)
     // what a launch is made of besides (rt_launch.hip choose_instance): arithmetic mode, thresholds, diagnostics knobs
     int wg_waves = 0;                   // diagnostics knob: 0 = automatic, 1 / 4 = force the workgroup shape
@@ -299,16 +250,12 @@ int read_back(rt_ctx *c, void *host, const void *dev, size_t bytes, bool wait = 
 int same_frame(const rt_ctx *a, const rt_ctx *b, const char *call, const char *a_name, const char *b_name, bool sharding = true);
 
 // ---- rt_launch.hip: one launch of the render kernel ----
-constexpr uint32_t kAlwaysWalkFrom = 1500;          // tree spheres from which the hierarchy is walked without estimate or measurement (rt_launch.hip)
 constexpr size_t kLdsMax = 152 * 1024;              // what the kernels' dynamic-LDS attribute allows
 LaunchParams make_params(rt_ctx *c, int n_samples);
 const Instance *instances(bool fast, int *count);
 bool tables_fit_lds(const rt_ctx *c, int n_samples);
-void probe_poll(rt_ctx *c, bool wait);              // hierarchy against sweep: the measurement's verdict, if its events have completed
-void rearm_probe(rt_ctx *c);                        // a new scene: undecided again
-void rearm_probe_if_changed(rt_ctx *c);             // after a device-resident update rebuilt the hierarchy
+void probe_poll(rt_ctx *c, bool wait);              // the verdict of the measurement in flight, if its events have completed (Choice::times_arrived)
 int refresh_tables(rt_ctx *c, hipStream_t stream);     // rt_scene.hip: tables and hierarchy from the records as they are now, if updates made them stale
-double estimate_ratio(const rt_ctx *c);             // predicted walk / sweep time per ray from the uploaded tree's surface areas
 int launch(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block = false);
 
 // ---- rt_scene.hip: records, tables, staging ----

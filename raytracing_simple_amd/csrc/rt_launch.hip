@@ -1,7 +1,7 @@
 // rt_launch.hip -- what one launch of the render kernel is made of: which kernel instance (rt_device.h Instance: arithmetic mode x
 // role x workgroup shape), its tables and LDS, the scheduling data it runs with (heavy-first tile order) and, for scenes
 // that have a hierarchy, whether it is walked or the plain sweep runs -- settled by a
-// surface-area estimate at rt_set_scene, by measurement inside the estimate's band.
+// surface-area estimate at rt_set_scene, by measurement inside the estimate's band (rt_choice.h holds the rules; launch() carries them out).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -252,12 +252,16 @@ static int prepare_launch(rt_ctx *c, int n_samples, Form form, bool from_list, P
 
 // The launch is queued: the frame has its passes, and the form choice knows what rendered them
 static void after_launch(rt_ctx *c, const rt::Instance &inst, int n_samples, const bool *all_groups) {
-    if (all_groups) c->frame.launched_subset(n_samples, c->pixel_write != 0, *all_groups);
-    else c->frame.launched(n_samples, c->pixel_write != 0);
-    c->choice.scene_launches += 1;
     c->last_kernel = inst.name;
     const bool coop = inst.role == rt::kRoleCoop || inst.role == rt::kRolePersistCoop;
-    c->choice.last = rt::walks_hierarchy(inst.tables) ? Form::Walk : (coop ? Form::SweepCoop : Form::SweepPlain);
+    const Form what = rt::walks_hierarchy(inst.tables) ? Form::Walk : (coop ? Form::SweepCoop : Form::SweepPlain);
+    if (all_groups) {
+        c->frame.launched_subset(n_samples, c->pixel_write != 0, *all_groups);
+        c->choice.subset_launch_queued(what);
+    } else {
+        c->frame.launched(n_samples, c->pixel_write != 0);
+        c->choice.launch_queued(what);
+    }
 }
 
 // persistent instances: just enough workgroups to fill the machine; the tile queue (counters[30]) does the rest
@@ -372,10 +376,7 @@ int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream) {
         rc = tiles_advance(c, n_samples, stream);           // (reads current_sample as it was: the count the selected groups come from)
         if (rc != RT_OK) return rc;
     }
-    // (a timed step of the cooperative-or-plain measurement that is open lies between an event and the full launches still to come: this launch
-    // would be timed with them, so the step starts again with the next full launch -- nothing of the measurement is started, advanced or timed here)
-    if ((c->probe.state & 1) != 0 && c->probe.acc > 0) c->probe.acc = 0;
-    after_launch(c, *inst, n_samples, &all);
+    after_launch(c, *inst, n_samples, &all);        // (an open timed step of the small-scene measurement starts again: Choice::subset_launch_queued)
     return RT_OK;
 }
 
@@ -396,174 +397,40 @@ static int launch_priced(rt_ctx *c, int n_samples, hipStream_t stream, Form form
     return rc;
 }
 
-// ---- the two measurements ----
-// Both run as four steps on the context's launches (rt_internal.h Probe): arm 0 warm, arm 0 timed, arm 1 warm, arm 1 timed.
-constexpr int kProbeSteps = 4;
-
-// what arm 0 / arm 1 of the measurement in flight renders with
-static Form probe_arm(const rt::Probe &pr, int arm) {
-    if (pr.which == rt::Probe::CoopVsPlain) return arm == 0 ? Form::SweepCoop : Form::SweepPlain;
-    return arm == 0 ? Form::Walk : Form::Sweep;
-}
-
-// Before a launch of the step that is open: `stream` joins the context's work, and a timed step that holds no passes yet gets its opening event.
-// `skip_warm`: this launch is long enough to warm itself -- an open warm step counts as done.  Yields the arm the launch belongs to.
-static int probe_begin_step(rt_ctx *c, hipStream_t stream, bool skip_warm, int *arm) {
-    rt::Probe &pr = c->probe;
-    if (skip_warm && (pr.state & 1) == 0) pr.state += 1;
-    const int rc = chain(c, stream);
-    if (rc != RT_OK) return rc;
-    *arm = pr.state >> 1;
-    if ((pr.state & 1) != 0 && pr.acc == 0) HIP_TRY(hipEventRecord(pr.ev[2 * *arm], stream));
-    return RT_OK;
-}
-
-// After that launch: a warm step ends with it; a timed step ends, with its closing event, once it holds `passes_needed` passes.
-static int probe_end_step(rt_ctx *c, hipStream_t stream, int n_samples, int passes_needed) {
-    rt::Probe &pr = c->probe;
-    const int arm = pr.state >> 1;
-    if ((pr.state & 1) != 0) {
-        pr.acc += n_samples;
-        if (pr.acc < passes_needed) return RT_OK;
-        HIP_TRY(hipEventRecord(pr.ev[2 * arm + 1], stream));
-        pr.samples[arm] = pr.acc;
-        pr.acc = 0;
-    }
-    pr.state += 1;
-    return RT_OK;
-}
-
-// hierarchy or sweep is settled, by the estimate or by measurement: the tree the verdict is about (rearm_probe_if_changed)
-static void verdict_is_of_this_tree(rt_ctx *c, bool estimated) {
-    c->choice.pick_estimated = estimated;
-    c->choice.probe_tree = c->bvh_n_tree;
-    c->choice.probe_always = c->bvh.n_always;
-    c->choice.probe_updates = 0;
-}
+// ---- which form renders the scene: rt_choice.h decides, this carries it out ----
 
 // the verdict of the measurement in flight, if all four steps are queued and the last event has completed (wait: block for it)
 void probe_poll(rt_ctx *c, bool wait) {
-    rt::Probe &pr = c->probe;
-    const bool coop = pr.which == rt::Probe::CoopVsPlain;
-    if ((coop ? c->choice.coop_pick : c->choice.bvh_pick) != Form::Auto || pr.state < kProbeSteps) return;
+    if (!c->choice.awaiting_times()) return;
+    hipEvent_t *ev = c->probe_ev;
     if (wait) {
-        if (hipEventSynchronize(pr.ev[3]) != hipSuccess) return;
-    } else if (hipEventQuery(pr.ev[3]) != hipSuccess) {
+        if (hipEventSynchronize(ev[3]) != hipSuccess) return;
+    } else if (hipEventQuery(ev[3]) != hipSuccess) {
         (void)hipGetLastError();
         return;
     }
     float a = 0.f, b = 0.f;
-    if (hipEventElapsedTime(&a, pr.ev[0], pr.ev[1]) != hipSuccess || hipEventElapsedTime(&b, pr.ev[2], pr.ev[3]) != hipSuccess) {
+    if (hipEventElapsedTime(&a, ev[0], ev[1]) != hipSuccess || hipEventElapsedTime(&b, ev[2], ev[3]) != hipSuccess) {
         (void)hipGetLastError();
         return;
     }
-    const double ta = (double)a / pr.samples[0], tb = (double)b / pr.samples[1];
-    if (coop) {
-        // arm 0 = cooperative any-hit, arm 1 = plain.  The plain instance -- what the threshold says -- keeps anything inside 4 %: the scenes the
-        // sharing is for gain 7-14 %, the Demo scene loses 2-10 %, and a timed probe of a 1/8 shard of a 1080p frame lasts 65 microseconds (two of the
-        // eight shards of profiles/r06_shard_prediction.jsonl's first run picked the slower form on a 2 % dead band)
-        c->choice.coop_pick = ta < 0.96 * tb ? Form::SweepCoop : Form::SweepPlain;
-        return;
-    }
-    c->choice.probe_ms[0] = ta;
-    c->choice.probe_ms[1] = tb;
-    c->choice.bvh_pick = ta <= 1.05 * tb ? Form::Walk : Form::Sweep;      // (a dead band of 5 % towards the usual winner: no flipping on a tie)
-    verdict_is_of_this_tree(c, false);
+    c->choice.times_arrived(a, b, c->bvh_n_tree, c->bvh.n_always);
 }
 
-void rearm_probe(rt_ctx *c) {
-    c->choice.scene_frames = 0;
-    c->choice.scene_launches = 0;
-    c->choice.coop_pick = c->choice.bvh_pick = Form::Auto;
-    c->choice.pick_estimated = false;
-    c->choice.probe_ms[0] = c->choice.probe_ms[1] = 0.0;
-    c->choice.probe_updates = 0;
-    c->probe.which = rt::Probe::None;
-    c->probe.state = c->probe.acc = 0;
-}
-
-// after a device-resident update rebuilt the hierarchy: is the verdict still about this tree?
-void rearm_probe_if_changed(rt_ctx *c) {
-    if (c->probe.which == rt::Probe::CoopVsPlain) return;       // (coop against plain on a scene without a hierarchy: an update cannot change the sphere count -- the verdict stays)
-    if (c->choice.bvh_pick == Form::Auto && c->probe.state == 0) return;
-    if (!c->bvh_ok) {
-        rearm_probe(c);
-        return;
-    }
-    const uint32_t tree = c->bvh_n_tree, always = c->bvh.n_always;        // spheres, not padded slots: the shaped tree of an upload has partial leaves
-    auto moved = [](uint32_t now, uint32_t then) { return 4u * (now > then ? now - then : then - now) > then + 8u; };
-    if (moved(tree, c->choice.probe_tree) || moved(always, c->choice.probe_always) || ++c->choice.probe_updates >= 256) {
-        rearm_probe(c);
-        c->bvh_est_valid = false;               // (the areas were the uploaded tree's: the changed scene is measured)
-    }
-}
-
-// Hierarchy or plain sweep for this scene?  The walk wins by 5x on a thousand spheres scattered over a plane and
-// loses on a box packed with overlapping glass -- so it is measured, once per scene: four launches in the same
-// (natural) tile order -- the hierarchy warm, the hierarchy timed, the sweep warm, the sweep timed, each timed one
-// between two events -- and when both timings have arrived (asked without blocking) the form that took less time per
-// pass renders the rest.  A blocking call with enough passes splits off 1 + 2 + 1 + 2 passes for the probes and waits
-// for the verdict before it queues the rest (progressive passes equal one launch bit for bit).  The verdict is kept
-// for the scene; device-resident updates keep it until the tree has changed size by a quarter or 256 updates have
-// gone by (rearm_probe_if_changed).  In a multi-device context only the first shard measures; the others follow it.
-static int launch_probe(rt_ctx *c, int n_samples, hipStream_t stream) {
-    if (c->probe.which == rt::Probe::None) c->probe.which = rt::Probe::WalkVsSweep;
-    int arm = 0;
-    int rc = probe_begin_step(c, stream, false, &arm);
-    if (rc != RT_OK) return rc;
-    rc = launch_form(c, n_samples, stream, probe_arm(c->probe, arm), true);
-    if (rc != RT_OK) return rc;
-    return probe_end_step(c, stream, n_samples, 1);             // (any launch is a whole step)
-}
-
-// The same question answered WITHOUT a launch, from the surface areas of the tree the host built at rt_set_scene (rt_bvh.hip):
-// a random line through the root box is expected to visit  P = sum of area(inner node) / area(root)  pairs (and leaves in
-// proportion), each ray sweeps the always-list besides, and the plain sweep tests all n spheres.  Predicted time per ray of
-// the walk over that of the sweep, in units of one sphere test of the sweep:
-//     ratio = (kEstPair * P + kEstAlways * n_always) / (n + kEstSweepFixed)
-// The three weights are a least-squares fit (log ratio) to the probe's own timings of both forms on 32 scenes of four
-// families -- spheres scattered on a plane, a closed box packed with mirror / glass spheres, a cloud in the air, the Demo
-// scene plus scattered spheres; 64 to 1400 spheres -- tools/choice_calibration.py, profiles/r04k_choice_calibration.jsonl
-// (this round's walk kernel): rms error 11 %, 9 % at worst between 0.55 and 1.8.  (A term for the expected leaf visits fitted to zero: they go with P.)
-// Outside a band around 1 the estimate decides and nothing is measured -- a new scene's first frame then costs what a frame
-// costs; inside it the four probe launches run as before.
-constexpr double kEstPair = 18.7, kEstAlways = 8.9, kEstSweepFixed = 17.9;
-constexpr double kEstBandLo = 0.75, kEstBandHi = 1.33;
-double estimate_ratio(const rt_ctx *c) {
-    return (kEstPair * c->bvh_est_pairs + kEstAlways * (double)c->bvh.n_always) / ((double)c->scene.n_spheres + kEstSweepFixed);
-}
-
-// Cooperative any-hit or not for a scene of fewer than coop_min spheres (rt_internal.h Choice::coop_pick): MEASURED, on the host's own launches as they
-// come -- never split, never reordered, scheduled like any other (heavy tiles first): the sharing's worth depends on the order the tiles run in, so
-// it is timed under the order the frames will run in.  Four steps: coop warm, coop timed, plain warm, plain timed; a step takes whole launches and
-// ends once it holds enough passes -- a warm step one launch, a timed step 16 passes between its two events; a launch of 16 passes or more needs no
-// warm step (it warms itself), so a host that renders whole frames spends its second frame on the cooperative instance, its third on the plain
-// one, and has the verdict for the fourth; a host that queues a pass per call has it after 34 passes.  A scene's FIRST long blocking frame is not
-// part of it (a new scene's first frame prices its tiles and runs partly in image order: it measures neither form's steady state), so a host that
-// renders one frame per scene never runs the form the threshold would not have picked.  (The first version of this round split a long call into
-// four short probe launches in natural tile order, as the hierarchy's probe does: +6 ... +8 % on that frame, and on shards of a frame, 65
-// microseconds per timed probe, it picked the slower form on two shards of eight -- profiles/r06_coop_probe_first_frame.jsonl.)
-constexpr uint32_t kCoopProbeFrom = 4;          // (below four spheres a shadow sweep has nothing to share out)
-constexpr int kCoopTimedPasses = 16;
-static int launch_small(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block) {
-    if (c->choice.leader)                       // a shard of a multi-device context: the form the first shard just launched
-        return launch_priced(c, n_samples, stream, c->choice.leader->choice.last == Form::SweepCoop ? Form::SweepCoop : Form::SweepPlain);
-    const uint32_t n = c->scene.n_spheres;
-    const bool open = c->choice.coop_probe != 0 && c->coop_min > 0 && n >= kCoopProbeFrom && n < (uint32_t)c->coop_min && c->wg_waves == 0 && c->persist == 0 &&
-                      tables_fit_lds(c, n_samples);
-    if (!open) return launch_priced(c, n_samples, stream, Form::Sweep);
-    c->probe.which = rt::Probe::CoopVsPlain;
-    probe_poll(c, false);
-    if (c->choice.coop_pick != Form::Auto) return launch_priced(c, n_samples, stream, c->choice.coop_pick);
-    if (c->probe.state == kProbeSteps) return launch_priced(c, n_samples, stream, Form::SweepPlain);   // both timings queued, not back yet: what the threshold says meanwhile
-    const bool whole_frame = may_block && n_samples >= kCoopTimedPasses;        // (a long launch warms itself)
-    if (whole_frame && c->choice.scene_frames == 0 && c->probe.state == 0) return launch_priced(c, n_samples, stream, Form::Sweep);
-    int arm = 0;
-    int rc = probe_begin_step(c, stream, whole_frame, &arm);
-    if (rc != RT_OK) return rc;
-    rc = launch_priced(c, n_samples, stream, probe_arm(c->probe, arm));
-    if (rc != RT_OK) return rc;
-    return probe_end_step(c, stream, n_samples, kCoopTimedPasses);
+// what Choice::next_launch is told of the context and its scene for a call of n_samples passes
+static rt::Choice::Facts choice_facts(const rt_ctx *c, int n_samples) {
+    rt::Choice::Facts f;
+    f.diagnostics = c->walk_forced != 0 || c->mode >= 100;
+    f.nothing_to_render = n_samples <= 0 || c->local_rows == 0 || !c->have_scene || !c->have_cam;     // (or the error: launch_form says which)
+    f.hierarchy = bvh_usable(c);
+    f.tables_fit = tables_fit_lds(c, n_samples);
+    f.n_tree = c->bvh_n_tree;
+    f.n_always = c->bvh.n_always;
+    f.n_spheres = c->scene.n_spheres;
+    f.coop_min = c->coop_min;
+    f.wg_waves = c->wg_waves;
+    f.persist = c->persist;
+    return f;
 }
 
 int launch(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block) {
@@ -571,38 +438,25 @@ int launch(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block) {
         const int rc = refresh_tables(c, stream);
         if (rc != RT_OK) return rc;
     }
-    if (c->walk_forced != 0 || c->mode >= 100) return launch_form(c, n_samples, stream, Form::Auto);      // diagnostics: nothing is measured
-    if (n_samples <= 0 || c->local_rows == 0 || !c->have_scene || !c->have_cam) return launch_priced(c, n_samples, stream, Form::Sweep);   // (nothing to render, or the error)
-    if (!bvh_usable(c)) return launch_small(c, n_samples, stream, may_block);
-    // no probe where the answer is known and asking is dear: from 1500 spheres in the tree on the hierarchy won on every
-    // scene measured, open or packed, and one pass of the sweep at 1080p costs 2.6 ms at 1024 spheres,
-    // 28 ms at 4096, 138 ms at 8192 from staged tables (through the scalar cache, round 6: a fifth of that at 8192 -- still tens of milliseconds a pass)
-    if (c->bvh_n_tree >= kAlwaysWalkFrom || !tables_fit_lds(c, n_samples)) return launch_priced(c, n_samples, stream, Form::Walk);
-    if (c->choice.leader)                       // a shard of a multi-device context: the form the first shard just launched
-        return launch_priced(c, n_samples, stream, sweeps(c->choice.leader->choice.last) ? Form::Sweep : Form::Walk);
-    probe_poll(c, false);
-    if (c->choice.bvh_pick == Form::Auto && c->probe.state == 0 && c->choice.use_estimate && c->bvh_est_valid) {
-        const double r = estimate_ratio(c);
-        c->choice.est_ratio = r;
-        if (r < kEstBandLo || r > kEstBandHi) {
-            c->choice.bvh_pick = r < 1.0 ? Form::Walk : Form::Sweep;
-            verdict_is_of_this_tree(c, true);
+    using Next = rt::Choice::Next;
+    const rt::Choice::Facts facts = choice_facts(c, n_samples);
+    Next nx, prev;
+    for (bool first = true;; first = false, prev = nx) {
+        nx = c->choice.next_launch(facts, n_samples, may_block, first ? nullptr : &prev);
+        if (nx.ask != Next::Launch) {
+            probe_poll(c, nx.ask == Next::TimesBlocking);
+            continue;
         }
-    }
-    if (c->choice.bvh_pick != Form::Auto) return launch_priced(c, n_samples, stream, c->choice.bvh_pick);
-    if (c->probe.state == kProbeSteps) return launch_form(c, n_samples, stream, Form::Walk);    // probes in flight: the usual winner meanwhile
-    if (may_block && n_samples >= 16) {
-        int done = 0;
-        while (c->probe.state < kProbeSteps) {
-            const int k = (c->probe.state & 1) ? 2 : 1;
-            const int rc = launch_probe(c, k, stream);
-            if (rc != RT_OK) return rc;
-            done += k;
+        if (nx.record_before >= 0) {    // a timed step opens: `stream` joins the context's work first
+            RT_TRY(chain(c, stream));
+            HIP_TRY(hipEventRecord(c->probe_ev[nx.record_before], stream));
         }
-        probe_poll(c, true);
-        return launch_priced(c, n_samples - done, stream, c->choice.bvh_pick != Form::Auto ? c->choice.bvh_pick : Form::Walk);
+        RT_TRY(nx.priced ? launch_priced(c, nx.passes, stream, nx.form) : launch_form(c, nx.passes, stream, nx.form, nx.natural_order));
+        if (nx.record_after >= 0) HIP_TRY(hipEventRecord(c->probe_ev[nx.record_after], stream));
+        if (nx.step) c->choice.step_queued(nx);
+        if (!nx.more) return RT_OK;
+        n_samples -= nx.passes;
     }
-    return launch_probe(c, n_samples, stream);
 }
 
 // a shard's launch on its own stream, for the multi-device context (rt_multi.hip)

@@ -305,7 +305,7 @@ RT_API int rt_create_multi_on(rt_ctx **out, int w, int h, const int *devices, in
             int rc = rt_create_sharded(&s, w, h, devices[r], r, ngpus, tile_rows);
             if (rc != RT_OK) return rc;
             // ONE decision per context between the hierarchy and the plain sweep: the first shard measures, the others follow
-            if (r > 0) s->choice.leader = m->shard[0];
+            if (r > 0) s->choice.follow(&m->shard[0]->choice);
             m->shard.push_back(s);
         }
         HIP_TRY(hipSetDevice(devices[0]));

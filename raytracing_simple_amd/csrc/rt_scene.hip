@@ -185,7 +185,7 @@ int refresh_tables(rt_ctx *c, hipStream_t stream) {
     int rc = chain(c, stream);          // (behind the copies of the records, whatever streams the updates were given)
     if (rc != RT_OK) return rc;
     rc = build_tables(c, c->scene.n_spheres, stream, false);
-    if (rc == RT_OK) rearm_probe_if_changed(c);
+    if (rc == RT_OK) c->choice.tables_rebuilt(c->bvh_ok, c->bvh_n_tree, c->bvh.n_always);
     return rc;
 }
 

@@ -337,6 +337,29 @@ def test_small_scenes_measure_cooperative_any_hit_against_plain_on_their_own_lau
                 assert ctx.last_kernel == "rt_trace_parity_w1"
 
 
+def test_a_subset_launch_inside_a_timed_step_starts_the_step_again():
+    """The small-scene measurement a pass per call, with a subset launch after the warm launch and 5 timed passes of the cooperative arm
+    (rt_choice.h Choice::subset_launch_queued; tools/sanitize/choice_main.cpp has the same sequence without a device): the subset launch would be
+    timed with the step's full launches, so the step starts again -- 16 further full passes of the cooperative instance before the plain arm opens,
+    22 launches in all, then the plain arm's 17.  Every group selected, so the frame stays whole and is the oracle's at 40 passes."""
+    w, h = 64, 48
+    sph = host.demo_scene()
+    cam = host.compute_camera(host.DEMO_ORIG, host.DEMO_TARGET, w, h)
+    with api.RtContext(w, h) as ctx:
+        ctx.set_scene(sph); ctx.set_camera(cam)
+        names = []
+        for _ in range(6):
+            ctx.render_async(1)
+            names.append(ctx.last_kernel)
+        ctx.select_tiles(None, 0)
+        ctx.render_tiles_async(1)
+        for _ in range(33):
+            ctx.render_async(1)
+            names.append(ctx.last_kernel)
+        assert names == ["rt_trace_parity_coop_w1"] * 22 + ["rt_trace_parity_w1"] * 17, names
+        assert np.array_equal(ctx.read_pixels(), O.render(sph, cam, w, h, 40)["pixels"])
+
+
 def test_short_launches_build_their_own_tile_order_from_a_window_of_costs():
     """The reference's regime is a pass per call: launches too short to price tiles one by one.  While the order is missing, short launches ADD their
     per-tile costs up (the kernel's epilogue adds instead of stores) and the launch that finds 16 passes' worth sorts from them; from then on short

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What measuring cooperative any-hit against plain INSIDE a small scene's first long frame would cost (rt_launch.hip launch_small defers it to the
+"""What measuring cooperative any-hit against plain INSIDE a small scene's first long frame would cost (rt_choice.h Choice::next_small defers it to the
 second frame): the Demo scene and the reference's simple.scn, first frame of 64 passes on a fresh context --
   as the library does it   the first frame whole (pricing launch + the rest), the second frame split for the four probe launches, the third decided
   probes in frame 1        emulated with the library's own pieces: the passes of the four probe launches as separate short calls first (they ARE the

@@ -1,8 +1,9 @@
 #!/bin/bash
 # AddressSanitizer + UndefinedBehaviorSanitizer over the CPU-side code (GPU sanitizers are not
 # available on this pool): the oracle's renderer, the product's host helpers (scene reader with
-# good, truncated and missing files, seed stream, camera basis), the hierarchy's host builders and
-# the record of a context's resources (rt_owned.h, with a recorder in owned_free's place).
+# good, truncated and missing files, seed stream, camera basis), the hierarchy's host builders,
+# the record of a context's resources (rt_owned.h, with a recorder in owned_free's place) and the
+# record of which form renders a scene (rt_choice.h, with a log in the launches' place).
 # Run from the repository root.
 set -eu
 R=$(cd "$(dirname "$0")/../.." && pwd)
@@ -27,6 +28,9 @@ $T/bvh_san
 $T/host_san
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/owned_main.cpp -o $T/owned_san
 $T/owned_san
+# which form renders a scene (rt_choice.h alone), driven as rt_launch.hip drives it
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/choice_main.cpp -o $T/choice_san
+$T/choice_san
 # the .scn reader on 1000 mutated files (deletions, junk tokens, non-finite numbers, truncation)
 mkdir -p $T/fz
 python3 - <<PY

@@ -30,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 TILE_ROWS = 8
-WARM = 4                              # untimed frames per context: a scene of 4-11 spheres has its instance measured on frames 2 and 3 (rt_launch.hip launch_small)
+WARM = 4                              # untimed frames per context: a scene of 4-11 spheres has its instance measured on frames 2 and 3 (rt_choice.h Choice::next_small)
 XGMI_LINK_GBS = 153.0                 # MI355X_MICROARCH.md: 7 links x ~153 GB/s per GPU, point to point
 
 
