@@ -224,13 +224,7 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
     c->rank = rank;
     c->nranks = nranks;
     c->tile_rows = tile_rows;
-    const int n_tiles = (h + tile_rows - 1) / tile_rows;
-    int rows = 0;
-    for (int t = rank; t < n_tiles; t += nranks) {
-        const int r0 = t * tile_rows;
-        rows += (r0 + tile_rows <= h) ? tile_rows : (h - r0);
-    }
-    c->local_rows = rows;
+    c->local_rows = rt::rows_of_rank(h, rank, nranks, tile_rows);
 
     int rc = select_device(c);
     const size_t px = image_pixels(c);
@@ -245,7 +239,7 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
         RT_TRY(own_event(own, &c->ev1));
         for (int k = 0; k < 4; ++k) RT_TRY(own_event(own, &c->probe_ev[k]));
         RT_TRY(own_event(own, &c->ev_dep, hipEventDisableTiming));
-        for (int k = 0; k < 4; ++k) RT_TRY(own_event(own, &c->stage_ev[k], hipEventDisableTiming));
+        RT_TRY(c->scene.ring.ensure_events(own, hipEventDisableTiming));        // (made here: the first upload costs what every upload costs)
         lap(1);
         RT_TRY(own_device(own, &c->d_seeds, 2 * px));
         RT_TRY(own_device(own, &c->d_seeds0, 2 * px));
@@ -331,39 +325,39 @@ RT_API int rt_set_scene(rt_ctx *c, const rt_sphere *spheres, uint32_t count) {
     if (count > 0 && !spheres) return fail(RT_ERR_ARG, "spheres is null");
     if (count > RT_MAX_SPHERES) return fail(RT_ERR_ARG, "%u spheres > RT_MAX_SPHERES (%u)", count, RT_MAX_SPHERES);
     if (c->multi) return rt::multi_set_scene(c, spheres, count);
-    c->features_current = false;        // (whatever is set: the feature plane is current UNTIL this call)
+    rt::SceneState &st = c->scene.state;
     // the very scene the context already holds (a host that sets it before every frame): nothing to do
-    if (c->have_scene && count == c->scene.n_spheres && c->h_spheres.size() == count &&
-        (count == 0 || memcmp(c->h_spheres.data(), spheres, (size_t)count * sizeof(rt_sphere)) == 0))
+    if (st.have_scene && count == c->scene.tables.n_spheres && c->scene.h_spheres.size() == count &&
+        (count == 0 || memcmp(c->scene.h_spheres.data(), spheres, (size_t)count * sizeof(rt_sphere)) == 0)) {
+        st.same_records_set();
         return RT_OK;
+    }
+    st.records_replaced();
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     rc = ensure_scene_capacity(c, count);
     if (rc != RT_OK) return rc;
-    c->is_light.assign(c->scene_cap, 0);
-    c->h_spheres.assign(spheres, spheres + count);
+    c->scene.is_light.assign(c->scene.cap, 0);
+    c->scene.h_spheres.assign(spheres, spheres + count);
     c->order.forget();
     c->choice.new_scene();              // hierarchy or plain sweep, cooperative any-hit or not: undecided again
     rc = upload_spheres(c, 0, count, spheres, count, c->stream, true);
-    if (rc != RT_OK) {
-        c->have_scene = false;          // the tables are in an unknown state
-        return rc;
-    }
-    c->have_scene = true;
-    return RT_OK;
+    if (rc != RT_OK) st.upload_failed();
+    else st.uploaded();
+    return rc;
 }
 
 RT_API int rt_update_spheres_async(rt_ctx *c, uint32_t first, uint32_t count, const rt_sphere *spheres, void *hip_stream) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
-    if (!c->have_scene && !c->multi) return fail(RT_ERR_STATE, "rt_set_scene must precede rt_update_spheres_async");
+    if (!c->scene.state.have_scene && !c->multi) return fail(RT_ERR_STATE, "rt_set_scene must precede rt_update_spheres_async");
     if (count > 0 && !spheres) return fail(RT_ERR_ARG, "spheres is null");
     if (c->multi) return rt::multi_update_spheres(c, first, count, spheres);
-    const uint32_t n = c->scene.n_spheres;
+    const uint32_t n = c->scene.tables.n_spheres;
     if (first > n || count > n - first) return fail(RT_ERR_ARG, "spheres [%u, %u) of a scene of %u", first, first + count, n);
-    c->features_current = false;
+    c->scene.state.records_updated();
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
-    if (count) memcpy(c->h_spheres.data() + first, spheres, (size_t)count * sizeof(rt_sphere));
+    if (count) memcpy(c->scene.h_spheres.data() + first, spheres, (size_t)count * sizeof(rt_sphere));
     // the last frame's costs still predict this one (moving spheres): the order stays in use and the next long launch sorts it again from them
     c->order.scene_or_camera_moved();
     // (the records go now; tables and hierarchy are rebuilt once, by the next launch -- rt_scene.hip refresh_tables -- however many updates precede it)
@@ -373,10 +367,9 @@ RT_API int rt_update_spheres_async(rt_ctx *c, uint32_t first, uint32_t count, co
 RT_API int rt_set_camera(rt_ctx *c, const rt_camera *cam) {
     if (!c || !cam) return fail(RT_ERR_ARG, "null argument");
     if (c->multi) return rt::multi_set_camera(c, cam);
-    if (!c->have_cam || memcmp(&c->cam, cam, sizeof *cam) != 0) c->order.scene_or_camera_moved();
+    if (!c->scene.state.have_cam || memcmp(&c->cam, cam, sizeof *cam) != 0) c->order.scene_or_camera_moved();
     c->cam = *cam;                      // a kernel argument: nothing to upload
-    c->features_current = false;
-    c->have_cam = true;
+    c->scene.state.camera_set();
     return RT_OK;
 }
 
@@ -729,7 +722,6 @@ RT_API int rt_render(const rt_scene *scene, const rt_camera *cam, uint32_t *out,
         }
         // read-back in four row blocks through page-locked staging: block k+1 crosses the bus while block k is
         // copied into the caller's (pageable) buffer
-        const size_t total = (size_t)w * h;
         size_t off[5];
         for (int k = 0; k <= 4; ++k) off[k] = ((size_t)h * k / 4) * (size_t)w;
         for (int k = 0; k < 4; ++k) {
@@ -742,7 +734,6 @@ RT_API int rt_render(const rt_scene *scene, const rt_camera *cam, uint32_t *out,
             HIP_TRY(hipEventSynchronize(e->ev[k]));
             if (off[k + 1] > off[k]) memcpy(out + off[k], e->h_pix + off[k], (off[k + 1] - off[k]) * sizeof(uint32_t));
         }
-        (void)total;
         return RT_OK;
     };
     rc = run();

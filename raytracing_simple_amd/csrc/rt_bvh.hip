@@ -651,21 +651,11 @@ static_assert(sizeof(rt::Float4) == sizeof(float4) && alignof(rt::Float4) <= ali
 // estimated from them (rt_launch.hip).
 int upload_host_tree(rt_ctx *c, const rt::BvhHostTree &tree, hipStream_t stream) {
     const size_t total4 = rt::bvh_blob_float4s(tree.n_leaves(), tree.n_slots());
-    if (c->bvh_stage_cap < total4) {
-        if (c->bvh_stage_used) HIP_TRY(hipEventSynchronize(c->bvh_stage_ev));
-        float4 *grown = nullptr;
-        RT_TRY(own_pinned(c->owned, &grown, total4));
-        c->owned.drop(c->h_bvh_stage);
-        c->h_bvh_stage = grown;
-        c->bvh_stage_cap = total4;
-    } else if (c->bvh_stage_used) {
-        HIP_TRY(hipEventSynchronize(c->bvh_stage_ev));       // the last build's copy still reads the buffer
-    }
-    rt::bvh_emit(tree, c->h_spheres.data(), reinterpret_cast<rt::Float4 *>(c->h_bvh_stage));
-    HIP_TRY(hipMemcpyAsync(c->d_bvh, c->h_bvh_stage, total4 * sizeof(float4), hipMemcpyHostToDevice, stream));
-    if (!c->bvh_stage_ev) RT_TRY(own_event(c->owned, &c->bvh_stage_ev));
-    HIP_TRY(hipEventRecord(c->bvh_stage_ev, stream));
-    c->bvh_stage_used = true;
+    float4 *stage = nullptr;
+    RT_TRY(c->scene.tree_stage.acquire(c->owned, total4, &stage));      // (waits while the last build's copy still reads the buffer)
+    rt::bvh_emit(tree, c->scene.h_spheres.data(), reinterpret_cast<rt::Float4 *>(stage));
+    HIP_TRY(hipMemcpyAsync(c->scene.d_bvh, stage, total4 * sizeof(float4), hipMemcpyHostToDevice, stream));
+    RT_TRY(c->scene.tree_stage.sent(c->owned, stream));
     double pairs = 0.0, leaves = 0.0;
     const bool valid = rt::bvh_estimate(tree, &pairs, &leaves);
     c->choice.tree_uploaded(valid, pairs, leaves);
@@ -688,22 +678,22 @@ hipError_t prepare_bvh_build() {        // (the largest trees the device builds)
 // table, for the A/B walks that stage it (rt_trace_*_pairs_gt, _gtp).  Costs one small launch per build (20-60 us).  By default every tree keeps
 // the builders' numbering -- the layout the product library walks.
 static int promote_top(rt_ctx *c, hipStream_t stream) {
-    c->bvh.n_top = 0;
+    c->scene.bvh.n_top = 0;
 #if !RT_DIAGNOSTICS
     (void)stream;
     return RT_OK;           // (the arm that stages the promoted top lost its A/B: the product library promotes nothing)
 #else
-    if (!c->bvh_ok || c->bvh.n_leaves < 2 || c->bvh_top_pairs <= 0) return RT_OK;
-    const uint32_t n_pairs = c->bvh.n_leaves - 1u;
-    const size_t used = rt::bvh_blob_float4s(c->bvh.n_leaves, c->bvh.n_slots);
+    if (!c->scene.state.has_hierarchy() || c->scene.bvh.n_leaves < 2 || c->bvh_top_pairs <= 0) return RT_OK;
+    const uint32_t n_pairs = c->scene.bvh.n_leaves - 1u;
+    const size_t used = rt::bvh_blob_float4s(c->scene.bvh.n_leaves, c->scene.bvh.n_slots);
     const size_t scratch4 = 4 * (size_t)n_pairs + ((size_t)n_pairs * 2 + 15) / 16 + 1;
-    if (used + scratch4 > (size_t)c->scene_cap * 6 + 64) return RT_OK;                   // (no room behind the blob: the tree stays as it is, nothing is staged)
+    if (used + scratch4 > rt::bvh_blob_capacity(c->scene.cap)) return RT_OK;                   // (no room behind the blob: the tree stays as it is, nothing is staged)
     uint32_t top = std::min<uint32_t>((uint32_t)c->bvh_top_pairs, rt::kBvhTopPairs);
     if (const char *e = getenv("RT_TOP_PAIRS")) top = std::min<uint32_t>((uint32_t)atoi(e), 256u);       // (experiments: how much of the top is worth staging)
     if (top == 0u) return RT_OK;
-    hipLaunchKernelGGL(rt_bvh_promote_kernel, dim3(1), dim3(1024), 0, stream, c->d_bvh, c->bvh.n_slots, c->bvh.n_leaves, top, c->d_bvh + used);
+    hipLaunchKernelGGL(rt_bvh_promote_kernel, dim3(1), dim3(1024), 0, stream, c->scene.d_bvh, c->scene.bvh.n_slots, c->scene.bvh.n_leaves, top, c->scene.d_bvh + used);
     HIP_TRY(hipGetLastError());
-    c->bvh.n_top = std::min(top, n_pairs);
+    c->scene.bvh.n_top = std::min(top, n_pairs);
     return RT_OK;
 #endif
 }
@@ -711,19 +701,19 @@ static int promote_top(rt_ctx *c, hipStream_t stream) {
 // ... and the packed pair table behind the blob (where the promotion's scratch was: it is dead by then -- same stream), for the A/B walks that
 // read it (rt_trace_*_pairs_gq, _gtp), likewise only when asked for
 static int pack_pairs(rt_ctx *c, hipStream_t stream) {
-    c->bvh.packed_at = 0;
+    c->scene.bvh.packed_at = 0;
 #if !RT_DIAGNOSTICS
     (void)stream;
     return RT_OK;           // (likewise: no product kernel reads a packed table)
 #else
-    if (!c->bvh_ok || c->bvh.n_leaves < 2 || c->bvh_packed == 0) return RT_OK;
-    const uint32_t n_pairs = c->bvh.n_leaves - 1u;
-    const size_t used = rt::bvh_blob_float4s(c->bvh.n_leaves, c->bvh.n_slots);
-    if (used + 2 + 2 * (size_t)n_pairs > (size_t)c->scene_cap * 6 + 64) return RT_OK;
+    if (!c->scene.state.has_hierarchy() || c->scene.bvh.n_leaves < 2 || c->bvh_packed == 0) return RT_OK;
+    const uint32_t n_pairs = c->scene.bvh.n_leaves - 1u;
+    const size_t used = rt::bvh_blob_float4s(c->scene.bvh.n_leaves, c->scene.bvh.n_slots);
+    if (used + 2 + 2 * (size_t)n_pairs > rt::bvh_blob_capacity(c->scene.cap)) return RT_OK;
     const unsigned blocks = (unsigned)std::min<size_t>((n_pairs + 255) / 256, 1024);
-    hipLaunchKernelGGL(rt_bvh_pack_pairs_kernel, dim3(blocks), dim3(256), 0, stream, c->d_bvh, c->bvh.n_slots, c->bvh.n_leaves, c->d_bvh + used);
+    hipLaunchKernelGGL(rt_bvh_pack_pairs_kernel, dim3(blocks), dim3(256), 0, stream, c->scene.d_bvh, c->scene.bvh.n_slots, c->scene.bvh.n_leaves, c->scene.d_bvh + used);
     HIP_TRY(hipGetLastError());
-    c->bvh.packed_at = (uint32_t)used;
+    c->scene.bvh.packed_at = (uint32_t)used;
     return RT_OK;
 #endif
 }
@@ -738,22 +728,18 @@ static int pack_pairs(rt_ctx *c, hipStream_t stream) {
 // such records.  Materials play no part: a repeated record's material is never read.
 // (rt_bvh_host.cpp bvh_mark_repeats finds them; here: the flags to the device)
 static int mark_duplicates(rt_ctx *c, uint32_t n_total, hipStream_t stream) {
-    const bool had = c->have_dups;
-    c->have_dups = false;
-    c->n_dups = 0;
-    if (n_total < 2 || !c->d_dup) return RT_OK;
+    const bool had = c->scene.state.flags_on_device();
+    c->scene.state.duplicates_marked(0);        // (until the flags are on their way)
+    if (n_total < 2 || !c->scene.d_dup) return RT_OK;
     static thread_local std::vector<uint8_t> flags;
-    const uint32_t found = bvh_mark_repeats(c->h_spheres.data(), n_total, flags);
+    const uint32_t found = bvh_mark_repeats(c->scene.h_spheres.data(), n_total, flags);
     if (found == 0 && !had) return RT_OK;       // (nothing to say, and the device holds no flags of an earlier scene)
-    if (!c->h_dup_stage) RT_TRY(own_pinned(c->owned, &c->h_dup_stage, c->scene_cap));
-    if (c->dup_stage_used) HIP_TRY(hipEventSynchronize(c->dup_ev));
-    memcpy(c->h_dup_stage, flags.data(), n_total);
-    HIP_TRY(hipMemcpyAsync(c->d_dup, c->h_dup_stage, n_total, hipMemcpyHostToDevice, stream));
-    if (!c->dup_ev) RT_TRY(own_event(c->owned, &c->dup_ev));
-    HIP_TRY(hipEventRecord(c->dup_ev, stream));
-    c->dup_stage_used = true;
-    c->have_dups = found != 0;
-    c->n_dups = found;
+    uint8_t *stage = nullptr;
+    RT_TRY(c->scene.dup_stage.acquire(c->owned, c->scene.cap, &stage));     // (sized like d_dup; given back with it)
+    memcpy(stage, flags.data(), n_total);
+    HIP_TRY(hipMemcpyAsync(c->scene.d_dup, stage, n_total, hipMemcpyHostToDevice, stream));
+    RT_TRY(c->scene.dup_stage.sent(c->owned, stream));
+    c->scene.state.duplicates_marked(found);
     return RT_OK;
 }
 
@@ -765,10 +751,10 @@ int build_bvh(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload)
 }
 
 // the blob on the device describes the current scene
-static int adopt(rt_ctx *c, uint32_t n_always, uint32_t n_leaves, uint32_t stack_depth) {
+static int adopt(rt_ctx *c, uint32_t n_tree, uint32_t n_always, uint32_t n_leaves, uint32_t stack_depth) {
     const uint32_t n_slots = n_always + rt::kBvhLeaf * n_leaves;
-    c->bvh = rt::BvhTables{ c->d_bvh, n_always, n_leaves, n_slots, stack_depth, rt::bvh_emis_at(n_leaves, n_slots) };
-    c->bvh_ok = true;
+    c->scene.bvh = rt::BvhTables{ c->scene.d_bvh, n_always, n_leaves, n_slots, stack_depth, rt::bvh_emis_at(n_leaves, n_slots) };
+    c->scene.state.hierarchy_adopted(n_tree);
     return RT_OK;
 }
 
@@ -776,29 +762,29 @@ static int adopt(rt_ctx *c, uint32_t n_always, uint32_t n_leaves, uint32_t stack
 // and the always list and the counts -- decided here, from the host mirror, with the test the device applies to the same bits
 // (rt_bvh_host.cpp bvh_plan) --, then one of the four builders, then the tables are the context's.
 static int build_bvh_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload) {
-    c->bvh_ok = false;
-    c->bvh = {};
-    c->bvh_n_tree = 0;
+    c->scene.state.hierarchy_voided();
+    c->scene.bvh = {};
     if (full_upload) c->choice.uploading_without_estimate();     // (a device-resident update keeps the upload's estimate: Choice::tables_rebuilt decides when it is stale)
-    if (c->bvh_min <= 0 || n_total < (uint32_t)c->bvh_min || !c->d_bvh) return RT_OK;
+    if (c->bvh_min <= 0 || n_total < (uint32_t)c->bvh_min || !c->scene.d_bvh) return RT_OK;
     {
         const int rc = mark_duplicates(c, n_total, stream);
         if (rc != RT_OK) return rc;
     }
-    const uint8_t *d_dup = c->have_dups ? c->d_dup : nullptr, *h_dup = c->have_dups ? c->h_dup_stage : nullptr;
-    const rt_sphere *sph = c->h_spheres.data();
+    // (the host goes on reading the flags it staged while their copy is pending: only the next marking waits for it)
+    const bool dups = c->scene.state.flags_on_device();
+    const uint8_t *d_dup = dups ? c->scene.d_dup : nullptr, *h_dup = dups ? c->scene.dup_stage.host() : nullptr;
+    const rt_sphere *sph = c->scene.h_spheres.data();
     BvhPlan plan;
-    if (!bvh_plan(sph, n_total, h_dup, c->n_dups, &plan) || plan.n_tree < (uint32_t)c->bvh_min) return RT_OK;
+    if (!bvh_plan(sph, n_total, h_dup, c->scene.state.n_dups, &plan) || plan.n_tree < (uint32_t)c->bvh_min) return RT_OK;
     const uint32_t n_tree = plan.n_tree, n_always = plan.n_always, n_leaves = (n_tree + rt::kBvhLeaf - 1) / rt::kBvhLeaf;
-    c->bvh_n_tree = n_tree;
     // a full upload (rt_set_scene: the call blocks and the host has every record): the shape by surface area, on the host -- unless
     // the result does not fit the tables' allocation (ensure_scene_capacity) or the stack budget: then the shapes below
     if (full_upload && c->bvh_sah == 1 && n_tree >= kSahMinTree && n_tree <= kSahMaxTree) {
         BvhHostTree tree;
         if (!bvh_shape_by_area(sph, n_total, h_dup, plan, &tree)) return rt::fail(RT_ERR_STATE, "hierarchy: the split changed under the build");
-        if (!tree.too_deep && tree.n_leaves() < rt::kBvhLeafRef && rt::bvh_blob_float4s(tree.n_leaves(), tree.n_slots()) <= (size_t)c->scene_cap * 6 + 64) {
+        if (!tree.too_deep && tree.n_leaves() < rt::kBvhLeafRef && rt::bvh_blob_float4s(tree.n_leaves(), tree.n_slots()) <= rt::bvh_blob_capacity(c->scene.cap)) {
             const int rc = upload_host_tree(c, tree, stream);
-            return rc != RT_OK ? rc : adopt(c, n_always, tree.n_leaves(), tree.depth);
+            return rc != RT_OK ? rc : adopt(c, n_tree, n_always, tree.n_leaves(), tree.depth);
         }
     }
     // device-resident updates, and uploads too large for the host to shape in passing: the shape by surface area, on the device
@@ -811,17 +797,17 @@ static int build_bvh_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, boo
         if (const char *e = getenv("RT_SAH_DEPTH_MARGIN")) margin = (uint32_t)atoi(e);
 #endif
         depth_cap += margin;
-        hipLaunchKernelGGL(rt_bvh_build_sah_kernel, dim3(1), dim3(1024), bvh_build_sah_lds_bytes(n_pad, n_leaves), stream, c->d_spheres, d_dup, n_total, plan.r_cut, plan.r_floor,
-                           n_always, n_tree, n_pad, depth_cap, c->d_bvh);
+        hipLaunchKernelGGL(rt_bvh_build_sah_kernel, dim3(1), dim3(1024), bvh_build_sah_lds_bytes(n_pad, n_leaves), stream, c->scene.d_spheres, d_dup, n_total, plan.r_cut, plan.r_floor,
+                           n_always, n_tree, n_pad, depth_cap, c->scene.d_bvh);
         HIP_TRY(hipGetLastError());
-        return adopt(c, n_always, n_leaves, depth_cap + 1);
+        return adopt(c, n_tree, n_always, n_leaves, depth_cap + 1);
     }
     // the halved shape.  On the host for a full upload of a small tree (the same tree the device builds: same splits, same boxes),
     // because the host then knows the surface areas the choice between hierarchy and sweep is estimated from; and beyond the device's reach
     if (n_tree <= kDeviceBuildMax && !(full_upload && n_tree < kSahMinTree)) {
         const uint32_t n_pad = bvh_sort_pad(n_tree);
-        hipLaunchKernelGGL(rt_bvh_build_kernel, dim3(1), dim3(1024), bvh_build_lds_bytes(n_pad, n_leaves), stream, c->d_spheres, d_dup, n_total, plan.r_cut, plan.r_floor,
-                           n_always, n_tree, n_pad, c->d_bvh);
+        hipLaunchKernelGGL(rt_bvh_build_kernel, dim3(1), dim3(1024), bvh_build_lds_bytes(n_pad, n_leaves), stream, c->scene.d_spheres, d_dup, n_total, plan.r_cut, plan.r_floor,
+                           n_always, n_tree, n_pad, c->scene.d_bvh);
         HIP_TRY(hipGetLastError());
     } else {
         BvhHostTree tree;
@@ -831,7 +817,7 @@ static int build_bvh_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, boo
     }
     uint32_t depth = 1;
     while ((1u << depth) < n_leaves) depth += 1;
-    return adopt(c, n_always, n_leaves, depth + 1);
+    return adopt(c, n_tree, n_always, n_leaves, depth + 1);
 }
 
 }  // namespace rt

@@ -27,6 +27,10 @@ RT_HD inline uint32_t bvh_pairs_at(uint32_t n_slots) { return 2u + n_slots + (n_
 RT_HD inline uint32_t bvh_emis_at(uint32_t n_leaves, uint32_t n_slots) { return bvh_pairs_at(n_slots) + 4u * (n_leaves ? n_leaves - 1u : 0u); }
 RT_HD inline uint32_t bvh_colr_at(uint32_t n_leaves, uint32_t n_slots) { return bvh_emis_at(n_leaves, n_slots) + n_slots; }
 inline size_t bvh_blob_float4s(uint32_t n_leaves, uint32_t n_slots) { return (size_t)bvh_colr_at(n_leaves, n_slots) + (size_t)n_slots; }
+// ... and what a context allocates for a scene capacity of `scene_cap` records: hdr 2 + slots (< cap + 8; up to twice that with the partial leaves of the
+// shaped tree) + index (a quarter of the slots) + pairs (< cap / 2 + 4) + two material records per slot.  A tree that needs more is not uploaded, and
+// the diagnostics' tables behind the blob are made only where they fit: every such check asks here
+inline size_t bvh_blob_capacity(uint32_t scene_cap) { return (size_t)scene_cap * 6 + 64; }
 
 // A sphere stays outside the tree ("always" list, scene order kept) unless its radius and centre are finite and |rad| <= r_cut.
 // Host and device agree on the counts because they apply the same test to the same bits.

@@ -138,23 +138,23 @@ RT_API const char *rt_debug_shard_kernel(rt_ctx *c, int shard) {
     return rt::multi_shard(c, shard)->last_kernel;
 }
 // (readers of the tables and the hierarchy: device-resident updates leave them stale until something asks -- rt_scene.hip refresh_tables)
-static int fresh_tables(rt_ctx *c) { return c->tables_stale ? rt::refresh_tables(c, c->stream) : RT_OK; }
+static int fresh_tables(rt_ctx *c) { return c->scene.state.tables_stale ? rt::refresh_tables(c, c->stream) : RT_OK; }
 
 // The render kernels' table staging alone (rt_stage_probe_kernel), `repeats` launches of the grid and workgroup shape the library
 // would use for `n_samples` passes of the current scene: for a profiler run that isolates the L2 behaviour of those reads.
 RT_API int rt_debug_stage_tables(rt_ctx *c, int n_samples, int repeats) {
-    if (!c || c->multi || !c->have_scene) return fail(RT_ERR_ARG, "null / multi-device context, or no scene");
+    if (!c || c->multi || !c->scene.state.have_scene) return fail(RT_ERR_ARG, "null / multi-device context, or no scene");
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     rc = fresh_tables(c);
     if (rc != RT_OK) return rc;
     rc = chain(c, c->stream);
     if (rc != RT_OK) return rc;
-    const size_t lds_all = rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, true, n_samples);
+    const size_t lds_all = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, true, n_samples);
     const int mat = lds_all <= (size_t)c->mat_lds_limit ? 1 : 0;
-    const size_t lds = rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, mat != 0, n_samples);
+    const size_t lds = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, mat != 0, n_samples);
     if (lds > kLdsMax) return fail(RT_ERR_ARG, "tables of %zu B do not fit LDS", lds);
-    const bool coop = c->coop_min > 0 && c->scene.n_spheres >= (uint32_t)c->coop_min;
+    const bool coop = c->coop_min > 0 && c->scene.tables.n_spheres >= (uint32_t)c->coop_min;
     const bool w1 = lds + (coop ? 1536u : 256u) <= 6 * 1024;
     const int tile_w = w1 ? 8 : 32;
     const dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), tile_row_count(c));
@@ -163,7 +163,7 @@ RT_API int rt_debug_stage_tables(rt_ctx *c, int n_samples, int repeats) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rt_stage_probe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "rt_debug_stage_tables: %s", hipGetErrorString(e));
     for (int k = 0; k < repeats; ++k) {
-        hipLaunchKernelGGL(rt_stage_probe_kernel, grid, dim3(w1 ? 64 : 256), lds, c->stream, c->scene, mat, sink);
+        hipLaunchKernelGGL(rt_stage_probe_kernel, grid, dim3(w1 ? 64 : 256), lds, c->stream, c->scene.tables, mat, sink);
         HIP_TRY(hipGetLastError());
     }
     c->order.forget();                                                      // (the probe scribbled over the tile costs)
@@ -298,13 +298,13 @@ static int dbg_set_bvh_lds(rt_ctx *c, int v) { if (v > 0) c->bvh_lds_limit = v; 
 static int dbg_set_bvh_min(rt_ctx *c, int v) {
     c->bvh_min = v;
     c->choice.knob_set();
-    if (!c->have_scene) return RT_OK;
+    if (!c->scene.state.have_scene) return RT_OK;
     int rc = select_device(c);
     if (rc != RT_OK) return rc;
     rc = fresh_tables(c);
     if (rc != RT_OK) return rc;
     rc = chain(c, c->stream);
-    return rc != RT_OK ? rc : rt::build_bvh(c, c->scene.n_spheres, c->stream, true);
+    return rc != RT_OK ? rc : rt::build_bvh(c, c->scene.tables.n_spheres, c->stream, true);
 }
 static int dbg_set_tree_shape(rt_ctx *c, int v) {
     c->bvh_sah = v < 0 ? 0 : (v > 2 ? 2 : v);
@@ -373,13 +373,13 @@ RT_API int rt_debug_walk_rays(rt_ctx *c, const float *rays8, uint32_t n_rays, ui
     if (rc != RT_OK) return rc;
     rc = fresh_tables(c);
     if (rc != RT_OK) return rc;
-    if (!c->bvh_ok) return fail(RT_ERR_STATE, "the scene has no hierarchy (rt_debug_set_bvh)");
+    if (!c->scene.state.has_hierarchy()) return fail(RT_ERR_STATE, "the scene has no hierarchy (rt_debug_set_bvh)");
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
-    if (!c->have_cam) c->cam = rt_camera{};
+    if (!c->scene.state.have_cam) c->cam = rt_camera{};
     rt::LaunchParams p = make_params(c, 1);
-    p.bvh = c->bvh;
-    const size_t lds = rt::lds_bytes_pairs(0, 0, false, 0, c->bvh.n_leaves, c->bvh.n_slots, c->bvh.stack_depth, 256);
+    p.bvh = c->scene.bvh;
+    const size_t lds = rt::lds_bytes_pairs(0, 0, false, 0, c->scene.bvh.n_leaves, c->scene.bvh.n_slots, c->scene.bvh.stack_depth, 256);
     if (lds > 152 * 1024) return fail(RT_ERR_ARG, "tables need %zu B of LDS", lds);
     rt::Owned scratch;                  // (given back when the call returns, however)
     float4 *d_rays = nullptr;
@@ -399,11 +399,11 @@ RT_API int rt_debug_walk_rays(rt_ctx *c, const float *rays8, uint32_t n_rays, ui
 // scene is then measured (the calibration's way of getting both timings).
 RT_API int rt_debug_tree_estimate(rt_ctx *c, double *out4) {
     if (!c || c->multi || !out4) return fail(RT_ERR_ARG, "null / multi-device context");
-    if (c->tables_stale && select_device(c) == RT_OK) (void)fresh_tables(c);
-    const bool have = c->choice.est_valid && c->bvh_ok;
+    if (c->scene.state.tables_stale && select_device(c) == RT_OK) (void)fresh_tables(c);
+    const bool have = c->choice.est_valid && c->scene.state.has_hierarchy();
     out4[0] = c->choice.est_pairs;
     out4[1] = c->choice.est_leaves;
-    out4[2] = have ? c->choice.estimate_ratio(c->bvh.n_always, c->scene.n_spheres) : 0.0;
+    out4[2] = have ? c->choice.estimate_ratio(c->scene.bvh.n_always, c->scene.tables.n_spheres) : 0.0;
     out4[3] = c->choice.pick_estimated ? 1.0 : 0.0;
     return have ? 1 : 0;
 }
@@ -432,12 +432,12 @@ RT_API int rt_debug_read_packed_pairs(rt_ctx *c, void *out, uint32_t cap_bytes, 
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
     *n_pairs = 0;
-    if (!c->bvh_ok || c->bvh.packed_at == 0 || c->bvh.n_leaves < 2) return RT_OK;
-    const size_t need = 32 + 32 * (size_t)(c->bvh.n_leaves - 1);
-    *n_pairs = c->bvh.n_leaves - 1;
+    if (!c->scene.state.has_hierarchy() || c->scene.bvh.packed_at == 0 || c->scene.bvh.n_leaves < 2) return RT_OK;
+    const size_t need = 32 + 32 * (size_t)(c->scene.bvh.n_leaves - 1);
+    *n_pairs = c->scene.bvh.n_leaves - 1;
     if (out) {
         if (cap_bytes < need) return fail(RT_ERR_ARG, "the packed table takes %zu bytes", need);
-        HIP_TRY(hipMemcpy(out, c->d_bvh + c->bvh.packed_at, need, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, c->scene.d_bvh + c->scene.bvh.packed_at, need, hipMemcpyDeviceToHost));
     }
     return RT_OK;
 }
@@ -453,16 +453,16 @@ RT_API int rt_debug_read_bvh(rt_ctx *c, float *blob_out, uint32_t cap_float4, ui
     rc = wait_all(c);
     if (rc != RT_OK) return rc;
     counts4[0] = counts4[1] = counts4[2] = counts4[3] = 0;
-    if (!c->bvh_ok) return RT_OK;
+    if (!c->scene.state.has_hierarchy()) return RT_OK;
     float4 hdr[2];                          // (the root pair travels in the header: a tree shaped on the device has it where only the device knows)
-    HIP_TRY(hipMemcpy(hdr, c->d_bvh, sizeof hdr, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hdr, c->scene.d_bvh, sizeof hdr, hipMemcpyDeviceToHost));
     uint32_t last;
     memcpy(&last, &hdr[1].w, 4);
-    counts4[0] = c->bvh.n_always; counts4[1] = c->bvh.n_leaves; counts4[2] = c->bvh.stack_depth; counts4[3] = last & 0xffffu;
-    const size_t need = rt::bvh_blob_float4s(c->bvh.n_leaves, c->bvh.n_slots);
+    counts4[0] = c->scene.bvh.n_always; counts4[1] = c->scene.bvh.n_leaves; counts4[2] = c->scene.bvh.stack_depth; counts4[3] = last & 0xffffu;
+    const size_t need = rt::bvh_blob_float4s(c->scene.bvh.n_leaves, c->scene.bvh.n_slots);
     if (blob_out) {
         if (cap_float4 < need) return fail(RT_ERR_ARG, "blob needs %zu float4", need);
-        HIP_TRY(hipMemcpy(blob_out, c->d_bvh, need * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(blob_out, c->scene.d_bvh, need * sizeof(float4), hipMemcpyDeviceToHost));
     }
     return RT_OK;
 }

@@ -97,9 +97,9 @@ int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guide
     if (a->have_guide != b->have_guide || (a->have_guide && memcmp(&a->guide, &b->guide, sizeof a->guide) != 0))
         return fail(RT_ERR_STATE, "%s: the halves differ in their guide (rt_set_denoise_guide: both off, or both on with the same parameters)", call);
     if (!a->have_guide) return RT_OK;
-    if (!a->features_current || !b->features_current || !a->d_features)
+    if (!a->scene.state.features_current || !b->scene.state.features_current || !a->scene.d_features)
         return fail(RT_ERR_STATE, "%s: a guide is set and the feature plane of %s is not current (rt_features_async forms it; rt_set_scene, "
-                                  "rt_update_spheres_async and rt_set_camera end it)", call, !a->features_current || !a->d_features ? "the first half" : "the second half");
+                                  "rt_update_spheres_async and rt_set_camera end it)", call, !a->scene.state.features_current || !a->scene.d_features ? "the first half" : "the second half");
     if (guided) *guided = true;
     return RT_OK;
 }
@@ -113,10 +113,10 @@ extern "C" {
 RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
     int rc = tiles_refuse(c, "rt_features_async");
     if (rc != RT_OK) return rc;
-    if (!c->have_scene || !c->have_cam) return fail(RT_ERR_STATE, "rt_features_async: rt_set_scene and rt_set_camera come first");
+    if (!c->scene.state.renderable()) return fail(RT_ERR_STATE, "rt_features_async: rt_set_scene and rt_set_camera come first");
     rc = select_device(c);
     if (rc != RT_OK) return rc;
-    RT_TRY(ensure_device(c->owned, &c->d_features, 8 * image_pixels(c)));
+    RT_TRY(ensure_device(c->owned, &c->scene.d_features, 8 * image_pixels(c)));
     // behind everything the context has queued; the tables from the records as they are now
     hipStream_t stream = (hipStream_t)hip_stream;
     rc = chain(c, stream);
@@ -125,10 +125,10 @@ RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
     const rt_camera &m = c->cam;
     const FtCamera cam{ m.orig.x, m.orig.y, m.orig.z, m.dir.x, m.dir.y, m.dir.z, m.x.x, m.x.y, m.x.z, m.y.x, m.y.y, m.y.z };
     const dim3 grid((unsigned)((c->w + kFtTileW - 1) / kFtTileW), (unsigned)((c->h + kFtTileH - 1) / kFtTileH));
-    hipLaunchKernelGGL(rt_features_kernel, grid, dim3(kFtLanes), 0, stream, reinterpret_cast<float4 *>(c->d_features), c->scene.geom, c->scene.emis, c->scene.colr,
-                       c->scene.n_spheres, cam, c->w, c->h);
+    hipLaunchKernelGGL(rt_features_kernel, grid, dim3(kFtLanes), 0, stream, reinterpret_cast<float4 *>(c->scene.d_features), c->scene.tables.geom, c->scene.tables.emis, c->scene.tables.colr,
+                       c->scene.tables.n_spheres, cam, c->w, c->h);
     HIP_TRY(hipGetLastError());
-    c->features_current = true;
+    c->scene.state.features_formed();
     return RT_OK;
 }
 
@@ -136,10 +136,10 @@ RT_API int rt_read_features(rt_ctx *c, float *out_host) {
     int rc = tiles_refuse(c, "rt_read_features");
     if (rc != RT_OK) return rc;
     if (!out_host) return fail(RT_ERR_ARG, "rt_read_features: out_host is null");
-    if (!c->features_current || !c->d_features)
+    if (!c->scene.state.features_current || !c->scene.d_features)
         return fail(RT_ERR_STATE, "rt_read_features: the context holds no current feature plane (rt_features_async forms one; rt_set_scene, rt_update_spheres_async "
                                   "and rt_set_camera end it)");
-    return read_back(c, out_host, c->d_features, 8 * image_pixels(c) * sizeof(float));
+    return read_back(c, out_host, c->scene.d_features, 8 * image_pixels(c) * sizeof(float));
 }
 
 RT_API int rt_set_denoise_guide(rt_ctx *c, const rt_guide_params *g) {

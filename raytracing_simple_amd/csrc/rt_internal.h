@@ -1,6 +1,7 @@
 // rt_internal.h -- what the translation units of the library share behind the C ABI: the context record and the records embedded in it
-// (Choice, TileOrder, FrameState, Owned), the frame's geometry said once, error reporting, acquisition of device resources into the
-// context's record, the checks and the blocking read several units share, and the hooks of the multi-device context (rt_multi.hip).
+// (Choice, TileOrder, FrameState, Owned, Scene), error reporting, acquisition of device resources into the context's record, page-locked
+// staging (Staged), the frame's geometry said once, the checks and the blocking read several units share, and the hooks of the multi-device
+// context (rt_multi.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include "rt_device.h"
 #include "rt_frame_state.h"
 #include "rt_owned.h"
+#include "rt_scene_state.h"
 #include "rt_tile_order.h"
 
 struct rt_multi;                    // rt_multi.hip
@@ -30,143 +32,6 @@ struct TileSubset {
     uint32_t *d_groups = nullptr;       // rt_denoise_pair_tiles_async (rt_denoise.hip): the selected groups' indices in ascending order, then the sentinel; one
                                         // word per group, acquired on that call's first use (tiles_build_group_list)
 };
-
-}  // namespace rt
-
-struct rt_ctx {
-    rt::Owned owned;                    // every device block, page-locked block, registered range, event and stream below (rt_owned.h): entered by the own_* /
-                                        // ensure_device helpers where it is acquired, given back by rt_destroy -- no member is freed by name
-    int device = 0;
-    int w = 0, h = 0;
-    int rank = 0, nranks = 1, tile_rows = 8, local_rows = 0;
-    rt_multi *multi = nullptr;          // non-null: this record is the front of a multi-device context
-    uint32_t *d_seeds = nullptr;
-    uint32_t *d_seeds0 = nullptr;       // pristine default stream, for device-side resets
-    float *d_colors = nullptr;
-    uint32_t *d_pixels = nullptr;
-    uint32_t *d_pixels_ext = nullptr;   // caller-owned target of rt_set_pixel_buffer, or null
-    void *pinned_out = nullptr;         // host buffer page-locked by rt_pin_output, or null
-    int pixel_write = 1;                // rt_set_pixel_write
-    rt::FrameState frame;               // what the progressive frame currently is: pass number, seed stream, packed pixels, launch count, tile bookkeeping
-    rt::TileSubset tiles;               // adaptive sampling (rt_tiles.hip): a pass count per 8x8 tile, the selected groups, the launch list of a subset launch
-    float *d_denoise = nullptr;         // rt_denoise_async (rt_denoise.hip): the plane the filter writes, EXCHANGED with d_colors after every call (the record
-                                        // frees by value: whichever block a member holds at teardown goes once); acquired on first use
-    float *d_denoise_var = nullptr;     // ... and the smoothed variance plane it is steered by (rt_denoise_pair_async: the first context's, for both halves)
-    float *d_filtered = nullptr;        // rt_denoise_pair_async: this half filtered with the other half's weights, a plane like d_colors; acquired on first use.
-                                        // Whether it is current is frame.filtered_pair
-    uint32_t *d_filtered_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom): what rt_compare_filtered reads
-    void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; acquired on first use)
-    unsigned long long *d_counters = nullptr;
-    unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters
-    // scene: raw records + the tables the device-side build kernel derives from them, one allocation
-    rt_sphere *d_spheres = nullptr;
-    float4 *d_tables = nullptr;         // geom | emis | colr | lightA | lightB, each `scene_cap` entries
-    uint32_t scene_cap = 0;
-    std::vector<unsigned char> is_light;   // host mirror of the light test per sphere (sizes the light list)
-    std::vector<rt_sphere> h_spheres;      // host mirror of the records (an identical rt_set_scene uploads nothing)
-    rt_sphere *h_stage = nullptr;       // page-locked staging ring for sphere uploads
-    uint32_t stage_cap = 0;             // records per slot
-    int stage_next = 0;
-    hipEvent_t stage_ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    bool stage_used[4] = { false, false, false, false };
-    rt::SceneTables scene{};
-    rt_camera cam{};
-    bool have_scene = false, have_cam = false;
-    // feature planes (rt_features.hip; include/rt_api.h "feature planes"): what lies under every pixel, from scene and camera alone -- so it is kept here,
-    // beside them, not in the frame's state
-    float *d_features = nullptr;        // [h][w][8]: albedo, normal, distance, scene index; acquired on first use
-    bool features_current = false;      // formed by rt_features_async since the last rt_set_scene / rt_update_spheres_async / rt_set_camera
-    rt_guide_params guide{};            // rt_set_denoise_guide: what the filters of a pair of halves add to their weights ...
-    bool have_guide = false;            // ... when it is on
-    bool tables_stale = false;          // rt_update_spheres_async has changed records since the tables and the hierarchy were built: refresh_tables() builds them
-                                        // ONCE, on the stream of whatever reads them next, however many updates went by (200 moved spheres by 200 calls cost 200
-                                        // rebuilds before: 353 ms a frame at 8192 spheres against 4.9 in one call -- profiles/r06_update_calls.jsonl)
-    // hierarchy over the small spheres of a large scene (rt_device.h BvhTables), rebuilt with the tables
-    float4 *d_bvh = nullptr;            // blob, sized for scene_cap
-    rt::BvhTables bvh{};
-    bool bvh_ok = false;                // the blob describes the current scene
-    float4 *h_bvh_stage = nullptr;      // page-locked buffer a host-shaped tree is written into (rt_bvh.hip upload_host_tree)
-    size_t bvh_stage_cap = 0;           // float4
-    hipEvent_t bvh_stage_ev = nullptr;
-    bool bvh_stage_used = false;
-    // records that repeat an EARLIER record bit for bit in what a ray test reads ({centre, radius^2}) stay out of the hierarchy (rt_bvh.hip mark_duplicates):
-    // one byte per record on the device, uploaded only while the scene has such records
-    uint8_t *d_dup = nullptr, *h_dup_stage = nullptr;       // [scene_cap] each; the second page-locked
-    hipEvent_t dup_ev = nullptr;
-    bool dup_stage_used = false, have_dups = false;
-    uint32_t n_dups = 0;
-    int bvh_sah = 1;                    // the hierarchy's shape is chosen by surface area (rt_bvh.hip): 1 = uploads below kAlwaysWalkFrom tree spheres on the host,
-                                        // larger uploads and every device-resident update on the device; 2 = the device for uploads too; 0 = the fixed (halved) shape
-    uint32_t bvh_n_tree = 0;            // spheres inside the tree (the slots are padded to whole leaves)
-    int bvh_min = 56;                   // scenes with at least this many spheres inside the tree use it (0 = never)
-    int bvh_lds_limit = 31 * 1024;      // its tables are staged in LDS while five workgroups of that size fit a CU (2048 spheres: 6.2 ms from L2 with
-                                        // 4-5 waves per SIMD against 9.5 ms from LDS with two workgroups per CU); larger ones are read from HBM / L2
-    int bvh_top_pairs = 0;              // pairs promoted to the front of the table for the A/B walks that stage the top (rt_bvh.hip promote_top; diagnostics only,
-                                        // rt_debug_set_bvh_layout: 0 = none -- the product's layout, which keeps the builders' numbering)
-    int bvh_packed = 0;                 // the packed pair table behind the blob for the A/B walk that reads it (rt_bvh.hip pack_pairs; diagnostics only, 0 = none)
-    int bvh_mixed = 1;                  // tables beyond that limit whose PAIRS fit it: pairs staged, slots from HBM / L2 (rt_trace_*_pairs_m); diagnostics knob: 0 = everything from L2
-    int walk_gate = 16, walk_round = 4; // rt_walk.inc.h: ready lanes that make the wavefront shade; pair steps in a row before a leaf step
-                                        // (round 4, this kernel: 2 / 3 / 4 / 6 in a row = 5.42 / 5.37 / 5.22 / 5.45 ms on C3, profiles/r04k_walk_sweep.jsonl)
-    int walk_tail = 0;                  // lanes that may be left walking when a trip's walk phase ends (0 = none: every walk runs to its end within the trip)
-    int walk_forced = 0;                // 0 = measured choice (`choice` below); diagnostics: 1 = the hierarchy whenever the scene has one
-    rt::Choice choice;                  // hierarchy or sweep, cooperative any-hit or not: the verdicts for this scene, the measurement behind them, the estimate (rt_choice.h)
-    hipEvent_t probe_ev[4] = { nullptr, nullptr, nullptr, nullptr };       // ... and the measurement's events: arm a's timed step lies between probe_ev[2 * a] and probe_ev[2 * a + 1]
-    rt::TileOrder order;                // heavy-first tile schedule (rt_tile_order.h; rt_trace.inc.h reads and writes its arrays)
-    // what a launch is made of besides (rt_launch.hip choose_instance): arithmetic mode, thresholds, diagnostics knobs
-    int wg_waves = 0;                   // diagnostics knob: 0 = automatic, 1 / 4 = force the workgroup shape
-    int mode = RT_MODE_PARITY;
-    int regen_gate = 0;                 // 0 = choose from the scene size
-    int mat_lds_limit = 24 * 1024;
-    int sweep_lds_limit = 40 * 1024;    // the plain / cooperative sweep stages its tables while four workgroups of that size fit a CU; beyond, the table is read through the
-                                        // scalar cache at six wavefronts per SIMD whatever its size (rt_trace_*_g).  Measured at 1080p on scenes without a hierarchy
-                                        // (profiles/r06_g_threshold.jsonl): at 48 KB (3 per CU) rt_trace_*_g takes 0.62 / 0.92 x the staged sweep's time (NaN records / a closed
-                                        // box of mirrors), at 64 KB (2) 0.41 / 0.63, at 96 KB and more (1) 0.19; at 32 KB (4) 0.80 / 1.12, below that 0.9 ... 1.3
-    int coop_kmax = 0;                  // cooperative any-hit only while no more than this many shadow rays are pending in the wavefront (0 = no limit)
-    int direct_max = 3;                 // RT_OPT_DIRECT_CAMERA: candidate spheres per tile up to which camera rays are resolved lane by lane (-1 = never; rt_debug_set_direct_camera)
-    int coop_min = 12;                  // scenes with at least this many spheres use the cooperative any-hit instance (0 = never)
-    int persist = 0;                    // diagnostics: persistent-wavefront instances
-    int n_cus = 256;
-    const char *last_kernel = "";       // symbol of the instance the last launch used
-    unsigned long long debug_counters[24] = {};   // diagnostic instances only
-    hipStream_t stream = nullptr;       // the context's own (non-blocking) stream
-    hipStream_t last_stream = nullptr;  // stream of the most recent launch / update (what readers wait for)
-    bool used_foreign_stream = false;   // some launch went to a caller's stream
-    bool abandon_streams = false;       // a shard of a multi-device context whose gather failed: its stream may hold a transfer that never
-                                        // completes, so rt_destroy does not wait for it
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_dep = nullptr;
-    // rt_throttle: the rt_render_async launches in flight, each between two events (a ring, oldest at flight_next)
-    struct Flight {
-        hipEvent_t start = nullptr, stop = nullptr;
-        int n_samples = 0;
-        bool pending = false;
-    };
-    static constexpr int kFlights = 8;
-    Flight flight[kFlights];
-    int flight_next = 0;
-    bool throttle_on = false;
-    double flight_ms_per_pass = 0.0;    // device time per pass of the most recent finished launch
-    // diagnostics build: device wall-clock logs
-    unsigned long long *d_timelog = nullptr, *d_wavelog = nullptr, *d_blocklog = nullptr;
-    uint32_t *d_stalelog = nullptr;
-    uint32_t timelog_cap = 0, timelog_used = 0, wavelog_cap = 0;
-    unsigned long long timelog_tag = 0;
-};
-
-namespace rt {
-
-// ---- the frame's geometry on the host (the kernels keep their own arithmetic) ----
-inline uint32_t tiles_per_row(const rt_ctx *c) { return (uint32_t)((c->w + 7) / 8); }                  // 8x8 tiles
-inline uint32_t tile_row_count(const rt_ctx *c) { return (uint32_t)((c->local_rows + 7) / 8); }        // ... of the local pixel buffer
-inline uint32_t tile_count(const rt_ctx *c) { return tiles_per_row(c) * tile_row_count(c); }
-inline uint32_t groups_per_row(const rt_ctx *c) { return (tiles_per_row(c) + 3) / 4; }                 // groups of four tiles (rt_tiles.hip)
-inline uint32_t group_count(const rt_ctx *c) { return groups_per_row(c) * tile_row_count(c); }
-inline size_t image_pixels(const rt_ctx *c) { return (size_t)c->w * (size_t)c->h; }                    // the full image, whatever rows the context renders
-inline size_t local_pixels(const rt_ctx *c) { return (size_t)c->local_rows * (size_t)c->w; }
-inline size_t color_floats(const rt_ctx *c) { return 3 * image_pixels(c); }
-inline uint32_t *frame_pixels(const rt_ctx *c) { return c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels; }     // the buffer launches write
-
-// a reset or a written state ends a frame of the current scene for the form choice too (Choice::frame_ended): end_frame(c).reset_in_place()
-inline FrameState &end_frame(rt_ctx *c) { c->choice.frame_ended(); return c->frame; }
 
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
@@ -237,6 +102,197 @@ template <class T> inline int ensure_device(Owned &owned, T **p, size_t count, c
     return *p ? RT_OK : own_device(owned, p, count, file, line);
 }
 
+// ---- page-locked staging: N slots of one block, an event behind the copy that reads each slot.  A slot is written only after the copy that last read it has
+// completed; the HOST may go on reading it while its copy is pending (host()).  kRing: slots of a power of two, at least 64, elements; otherwise exactly what is asked ----
+template <class T, int N, bool kRing = false> struct Staged {
+    T *block = nullptr;
+    size_t cap = 0;                     // elements per slot
+    int next = 0, cur = 0;              // the slot the next acquire takes; the one last handed out
+    hipEvent_t ev[N] = {};
+    bool pending[N] = {};               // a copy recorded by ev[k] reads slot k
+
+    T *host() const { return block + (size_t)cur * cap; }
+    int ensure_events(Owned &owned, unsigned flags, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {     // ... made now, not by the first sent()
+        for (int k = 0; k < N; ++k)
+            if (!ev[k]) RT_TRY(own_event(owned, &ev[k], flags, file, line));
+        return RT_OK;
+    }
+    int settle(int k) {
+        if (pending[k]) HIP_TRY(hipEventSynchronize(ev[k]));
+        pending[k] = false;
+        return RT_OK;
+    }
+    // the next slot, round robin, with room for `count` elements and nothing reading it.  A larger block is acquired BEFORE the old one goes (behind every pending
+    // copy): a failure leaves the staging as it was
+    int acquire(Owned &owned, size_t count, T **out, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+        if (count > cap) {
+            size_t grown_cap = kRing ? 64 : count;
+            while (grown_cap < count) grown_cap *= 2;
+            for (int k = 0; k < N; ++k) RT_TRY(settle(k));
+            T *grown = nullptr;
+            RT_TRY(own_pinned(owned, &grown, grown_cap * N, file, line));
+            owned.drop(block);
+            block = grown;
+            cap = grown_cap;
+        }
+        cur = next;
+        next = (next + 1) % N;
+        RT_TRY(settle(cur));
+        *out = host();
+        return RT_OK;
+    }
+    // a copy out of the slot last handed out has been queued on `stream`
+    int sent(Owned &owned, hipStream_t stream, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+        if (!ev[cur]) RT_TRY(own_event(owned, &ev[cur], hipEventDisableTiming, file, line));
+        HIP_TRY(hipEventRecord(ev[cur], stream));
+        pending[cur] = true;
+        return RT_OK;
+    }
+    void give_back(Owned &owned) {      // the block dropped (the caller knows that nothing reads it), the events kept
+        owned.drop(block);
+        block = nullptr;
+        cap = 0;
+        for (int k = 0; k < N; ++k) pending[k] = false;
+    }
+};
+
+// What a context holds of its scene: the state (rt_scene_state.h) and the blocks it speaks of.  Raw pointers, freed by value through Owned
+struct Scene {
+    SceneState state;
+    // raw records + the tables the device-side build kernel derives from them, one allocation
+    rt_sphere *d_spheres = nullptr;
+    float4 *d_tables = nullptr;         // geom | emis | colr | lightA | lightB, each `cap` entries
+    uint32_t cap = 0;                   // records the blocks below are sized for (rt_scene.hip ensure_scene_capacity)
+    SceneTables tables{};               // ... as the kernels' argument
+    std::vector<unsigned char> is_light;   // host mirror of the light test per sphere (sizes the light list)
+    std::vector<rt_sphere> h_spheres;      // host mirror of the records (an identical rt_set_scene uploads nothing)
+    Staged<rt_sphere, 4, true> ring;    // sphere uploads go through it
+    // hierarchy over the small spheres of a large scene (rt_device.h BvhTables), rebuilt with the tables; current while state.bvh_ok
+    float4 *d_bvh = nullptr;            // blob of bvh_blob_capacity(cap) float4
+    BvhTables bvh{};
+    Staged<float4, 1> tree_stage;       // a host-shaped tree is written into it (rt_bvh.hip upload_host_tree)
+    // records that repeat an EARLIER record bit for bit in what a ray test reads ({centre, radius^2}) stay out of the hierarchy (rt_bvh.hip mark_duplicates):
+    // one byte per record on the device, uploaded only while the scene has such records (state.have_dups)
+    uint8_t *d_dup = nullptr;           // [cap]
+    Staged<uint8_t, 1> dup_stage;       // [cap] too: given back with the blocks above
+    // feature planes (rt_features.hip; include/rt_api.h "feature planes"): what lies under every pixel, from scene and camera alone -- so it is kept here,
+    // not in the frame's state; current while state.features_current
+    float *d_features = nullptr;        // [h][w][8]: albedo, normal, distance, scene index; acquired on first use
+};
+
+// the rows of an image of `h` that rank `rank` of `nranks` renders, the image dealt out in tiles of `tile_rows` (api.local_rows_of says the same in Python)
+inline int rows_of_rank(int h, int rank, int nranks, int tile_rows) {
+    const int n_tiles = (h + tile_rows - 1) / tile_rows;
+    int rows = 0;
+    for (int t = rank; t < n_tiles; t += nranks) rows += (t * tile_rows + tile_rows <= h) ? tile_rows : (h - t * tile_rows);
+    return rows;
+}
+
+}  // namespace rt
+
+struct rt_ctx {
+    rt::Owned owned;                    // every device block, page-locked block, registered range, event and stream below (rt_owned.h): entered by the own_* /
+                                        // ensure_device helpers where it is acquired, given back by rt_destroy -- no member is freed by name
+    int device = 0;
+    int w = 0, h = 0;
+    int rank = 0, nranks = 1, tile_rows = 8, local_rows = 0;
+    rt_multi *multi = nullptr;          // non-null: this record is the front of a multi-device context
+    uint32_t *d_seeds = nullptr;
+    uint32_t *d_seeds0 = nullptr;       // pristine default stream, for device-side resets
+    float *d_colors = nullptr;
+    uint32_t *d_pixels = nullptr;
+    uint32_t *d_pixels_ext = nullptr;   // caller-owned target of rt_set_pixel_buffer, or null
+    void *pinned_out = nullptr;         // host buffer page-locked by rt_pin_output, or null
+    int pixel_write = 1;                // rt_set_pixel_write
+    rt::FrameState frame;               // what the progressive frame currently is: pass number, seed stream, packed pixels, launch count, tile bookkeeping
+    rt::TileSubset tiles;               // adaptive sampling (rt_tiles.hip): a pass count per 8x8 tile, the selected groups, the launch list of a subset launch
+    float *d_denoise = nullptr;         // rt_denoise_async (rt_denoise.hip): the plane the filter writes, EXCHANGED with d_colors after every call (the record
+                                        // frees by value: whichever block a member holds at teardown goes once); acquired on first use
+    float *d_denoise_var = nullptr;     // ... and the smoothed variance plane it is steered by (rt_denoise_pair_async: the first context's, for both halves)
+    float *d_filtered = nullptr;        // rt_denoise_pair_async: this half filtered with the other half's weights, a plane like d_colors; acquired on first use.
+                                        // Whether it is current is frame.filtered_pair
+    uint32_t *d_filtered_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom): what rt_compare_filtered reads
+    void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; acquired on first use)
+    unsigned long long *d_counters = nullptr;
+    unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters
+    rt::Scene scene;                    // what the context holds of its scene: records, tables, hierarchy, duplicate flags, feature plane, their staging -- and what of
+                                        // that is currently true (rt_scene_state.h)
+    rt_camera cam{};                    // a kernel argument (scene.state.have_cam)
+    rt_guide_params guide{};            // rt_set_denoise_guide: what the filters of a pair of halves add to their weights ...
+    bool have_guide = false;            // ... when it is on
+    // the hierarchy's knobs
+    int bvh_sah = 1;                    // the hierarchy's shape is chosen by surface area (rt_bvh.hip): 1 = uploads below kAlwaysWalkFrom tree spheres on the host,
+                                        // larger uploads and every device-resident update on the device; 2 = the device for uploads too; 0 = the fixed (halved) shape
+    int bvh_min = 56;                   // scenes with at least this many spheres inside the tree use it (0 = never)
+    int bvh_lds_limit = 31 * 1024;      // its tables are staged in LDS while five workgroups of that size fit a CU (2048 spheres: 6.2 ms from L2 with
+                                        // 4-5 waves per SIMD against 9.5 ms from LDS with two workgroups per CU); larger ones are read from HBM / L2
+    int bvh_top_pairs = 0;              // pairs promoted to the front of the table for the A/B walks that stage the top (rt_bvh.hip promote_top; diagnostics only,
+                                        // rt_debug_set_bvh_layout: 0 = none -- the product's layout, which keeps the builders' numbering)
+    int bvh_packed = 0;                 // the packed pair table behind the blob for the A/B walk that reads it (rt_bvh.hip pack_pairs; diagnostics only, 0 = none)
+    int bvh_mixed = 1;                  // tables beyond that limit whose PAIRS fit it: pairs staged, slots from HBM / L2 (rt_trace_*_pairs_m); diagnostics knob: 0 = everything from L2
+    int walk_gate = 16, walk_round = 4; // rt_walk.inc.h: ready lanes that make the wavefront shade; pair steps in a row before a leaf step
+                                        // (round 4, this kernel: 2 / 3 / 4 / 6 in a row = 5.42 / 5.37 / 5.22 / 5.45 ms on C3, profiles/r04k_walk_sweep.jsonl)
+    int walk_tail = 0;                  // lanes that may be left walking when a trip's walk phase ends (0 = none: every walk runs to its end within the trip)
+    int walk_forced = 0;                // 0 = measured choice (`choice` below); diagnostics: 1 = the hierarchy whenever the scene has one
+    rt::Choice choice;                  // hierarchy or sweep, cooperative any-hit or not: the verdicts for this scene, the measurement behind them, the estimate (rt_choice.h)
+    hipEvent_t probe_ev[4] = { nullptr, nullptr, nullptr, nullptr };       // ... and the measurement's events: arm a's timed step lies between probe_ev[2 * a] and probe_ev[2 * a + 1]
+    rt::TileOrder order;                // heavy-first tile schedule (rt_tile_order.h; rt_trace.inc.h reads and writes its arrays)
+    // what a launch is made of besides (rt_launch.hip choose_instance): arithmetic mode, thresholds, diagnostics knobs
+    int wg_waves = 0;                   // diagnostics knob: 0 = automatic, 1 / 4 = force the workgroup shape
+    int mode = RT_MODE_PARITY;
+    int regen_gate = 0;                 // 0 = choose from the scene size
+    int mat_lds_limit = 24 * 1024;
+    int sweep_lds_limit = 40 * 1024;    // the plain / cooperative sweep stages its tables while four workgroups of that size fit a CU; beyond, the table is read through the
+                                        // scalar cache at six wavefronts per SIMD whatever its size (rt_trace_*_g).  Measured at 1080p on scenes without a hierarchy
+                                        // (profiles/r06_g_threshold.jsonl): at 48 KB (3 per CU) rt_trace_*_g takes 0.62 / 0.92 x the staged sweep's time (NaN records / a closed
+                                        // box of mirrors), at 64 KB (2) 0.41 / 0.63, at 96 KB and more (1) 0.19; at 32 KB (4) 0.80 / 1.12, below that 0.9 ... 1.3
+    int coop_kmax = 0;                  // cooperative any-hit only while no more than this many shadow rays are pending in the wavefront (0 = no limit)
+    int direct_max = 3;                 // RT_OPT_DIRECT_CAMERA: candidate spheres per tile up to which camera rays are resolved lane by lane (-1 = never; rt_debug_set_direct_camera)
+    int coop_min = 12;                  // scenes with at least this many spheres use the cooperative any-hit instance (0 = never)
+    int persist = 0;                    // diagnostics: persistent-wavefront instances
+    int n_cus = 256;
+    const char *last_kernel = "";       // symbol of the instance the last launch used
+    unsigned long long debug_counters[24] = {};   // diagnostic instances only
+    hipStream_t stream = nullptr;       // the context's own (non-blocking) stream
+    hipStream_t last_stream = nullptr;  // stream of the most recent launch / update (what readers wait for)
+    bool used_foreign_stream = false;   // some launch went to a caller's stream
+    bool abandon_streams = false;       // a shard of a multi-device context whose gather failed: its stream may hold a transfer that never
+                                        // completes, so rt_destroy does not wait for it
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_dep = nullptr;
+    // rt_throttle: the rt_render_async launches in flight, each between two events (a ring, oldest at flight_next)
+    struct Flight {
+        hipEvent_t start = nullptr, stop = nullptr;
+        int n_samples = 0;
+        bool pending = false;
+    };
+    static constexpr int kFlights = 8;
+    Flight flight[kFlights];
+    int flight_next = 0;
+    bool throttle_on = false;
+    double flight_ms_per_pass = 0.0;    // device time per pass of the most recent finished launch
+    // diagnostics build: device wall-clock logs
+    unsigned long long *d_timelog = nullptr, *d_wavelog = nullptr, *d_blocklog = nullptr;
+    uint32_t *d_stalelog = nullptr;
+    uint32_t timelog_cap = 0, timelog_used = 0, wavelog_cap = 0;
+    unsigned long long timelog_tag = 0;
+};
+
+namespace rt {
+
+// ---- the frame's geometry on the host (the kernels keep their own arithmetic) ----
+inline uint32_t tiles_per_row(const rt_ctx *c) { return (uint32_t)((c->w + 7) / 8); }                  // 8x8 tiles
+inline uint32_t tile_row_count(const rt_ctx *c) { return (uint32_t)((c->local_rows + 7) / 8); }        // ... of the local pixel buffer
+inline uint32_t tile_count(const rt_ctx *c) { return tiles_per_row(c) * tile_row_count(c); }
+inline uint32_t groups_per_row(const rt_ctx *c) { return (tiles_per_row(c) + 3) / 4; }                 // groups of four tiles (rt_tiles.hip)
+inline uint32_t group_count(const rt_ctx *c) { return groups_per_row(c) * tile_row_count(c); }
+inline size_t image_pixels(const rt_ctx *c) { return (size_t)c->w * (size_t)c->h; }                    // the full image, whatever rows the context renders
+inline size_t local_pixels(const rt_ctx *c) { return (size_t)c->local_rows * (size_t)c->w; }
+inline size_t color_floats(const rt_ctx *c) { return 3 * image_pixels(c); }
+inline uint32_t *frame_pixels(const rt_ctx *c) { return c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels; }     // the buffer launches write
+
+// a reset or a written state ends a frame of the current scene for the form choice too (Choice::frame_ended): end_frame(c).reset_in_place()
+inline FrameState &end_frame(rt_ctx *c) { c->choice.frame_ended(); return c->frame; }
+
 // ---- rt_api.hip: the context's device and the order of its work ----
 int select_device(const rt_ctx *c);
 int chain(rt_ctx *c, hipStream_t stream);          // `stream` waits for whatever the context queued last elsewhere (ALL its work runs in issue order)
@@ -263,7 +319,7 @@ int ensure_scene_capacity(rt_ctx *c, uint32_t count);
 int upload_spheres(rt_ctx *c, uint32_t first, uint32_t count, const rt_sphere *spheres, uint32_t n_total, hipStream_t stream, bool full_upload);
 
 // the hierarchy of large scenes (rt_bvh.hip): per-device set-up of the build kernel; build on `stream` for the scene the
-// context's host mirror holds (sets c->bvh / c->bvh_ok; nothing is read back)
+// context's host mirror holds (sets c->scene.bvh, reports to c->scene.state; nothing is read back)
 hipError_t prepare_bvh_build();
 int build_bvh(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload = false);
 int render_shard(rt_ctx *c, int n_samples, bool may_block);      // rt_launch.hip: one shard's launch on its own stream

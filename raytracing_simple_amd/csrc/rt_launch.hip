@@ -56,7 +56,7 @@ namespace rt {
 
 rt::LaunchParams make_params(rt_ctx *c, int n_samples) {
     rt::LaunchParams p{};
-    p.scene = c->scene;
+    p.scene = c->scene.tables;
     p.cam = c->cam;
     p.seeds = c->d_seeds;
     p.seeds_in = c->frame.seeds_default ? c->d_seeds0 : c->d_seeds;
@@ -75,7 +75,7 @@ rt::LaunchParams make_params(rt_ctx *c, int n_samples) {
     p.skip_pixels = c->pixel_write ? 0 : 1;
     p.inv_w = 1.f / (float)c->w;          // correctly rounded on the host as on the device (-ffp-contract=off, IEEE division)
     p.inv_h = 1.f / (float)c->h;
-    p.regen_gate = c->regen_gate > 0 ? c->regen_gate : (c->scene.n_spheres <= 512 ? 8 : 1);
+    p.regen_gate = c->regen_gate > 0 ? c->regen_gate : (c->scene.tables.n_spheres <= 512 ? 8 : 1);
     p.coop_kmax = c->coop_kmax;
     p.direct_max = c->direct_max;
     p.tiles_x = (int)tiles_per_row(c);
@@ -99,29 +99,29 @@ static const rt::Instance *find_role(bool fast, int role, int waves) {
 
 // LDS the hierarchy's staged tables take for this scene
 static size_t pairs_lds(const rt_ctx *c, bool mat, int n_samples, int waves = 4) {
-    return rt::lds_bytes_pairs(c->scene.n_spheres, c->scene.n_lights, mat, n_samples, c->bvh.n_leaves, c->bvh.n_slots, c->bvh.stack_depth, 64 * waves);
+    return rt::lds_bytes_pairs(c->scene.tables.n_spheres, c->scene.tables.n_lights, mat, n_samples, c->scene.bvh.n_leaves, c->scene.bvh.n_slots, c->scene.bvh.stack_depth, 64 * waves);
 }
 
 // the plain sweep's tables (geometry and lights) fit LDS for this launch
 bool tables_fit_lds(const rt_ctx *c, int n_samples) {
-    return rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, false, n_samples) <= kLdsMax;
+    return rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, false, n_samples) <= kLdsMax;
 }
 // ... and are staged there: while at least four workgroups of that size fit a CU.  Larger tables go through the scalar cache (rt_trace_*_g), which
 // keeps six wavefronts per SIMD at any size: a sweep over 96 KB of staged tables runs ONE workgroup per CU and takes five times as long (rt_internal.h)
 static bool sweep_stages_tables(const rt_ctx *c, int n_samples) {
-    return rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, false, n_samples) <= (size_t)(c->sweep_lds_limit < (int)kLdsMax ? c->sweep_lds_limit : (int)kLdsMax);
+    return rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, false, n_samples) <= (size_t)(c->sweep_lds_limit < (int)kLdsMax ? c->sweep_lds_limit : (int)kLdsMax);
 }
 
 // the hierarchy's tables fit the LDS budget given to them; otherwise the walk reads them from HBM / L2
 static bool bvh_fits_lds(const rt_ctx *c, int n_samples) { return pairs_lds(c, false, n_samples) <= (size_t)c->bvh_lds_limit; }
 // ... or at least its PAIRS do (header | pairs | stacks): the chain of dependent fetches a walk consists of then stays in LDS
 static size_t pairs_only_lds(const rt_ctx *c, int n_samples, int waves = 4) {
-    return rt::lds_bytes_pairs(0, 0, false, n_samples, c->bvh.n_leaves, 0, c->bvh.stack_depth, 64 * waves);
+    return rt::lds_bytes_pairs(0, 0, false, n_samples, c->scene.bvh.n_leaves, 0, c->scene.bvh.stack_depth, 64 * waves);
 }
 static bool bvh_pairs_fit_lds(const rt_ctx *c, int n_samples) { return c->bvh_mixed != 0 && pairs_only_lds(c, n_samples) <= (size_t)c->bvh_lds_limit; }
 
 // the scene has a hierarchy and the context may use it
-static bool bvh_usable(const rt_ctx *c) { return c->bvh_ok && c->wg_waves != 1 && c->persist == 0; }
+static bool bvh_usable(const rt_ctx *c) { return c->scene.state.has_hierarchy() && c->wg_waves != 1 && c->persist == 0; }
 
 // What the instance needs from the context, checked against what the context has: the ONE place that sizes the
 // dynamic LDS and hands out the hierarchy.  An instance whose tables the context lacks is refused (RT_ERR_STATE),
@@ -129,14 +129,14 @@ static bool bvh_usable(const rt_ctx *c) { return c->bvh_ok && c->wg_waves != 1 &
 static int bind_tables(rt_ctx *c, const rt::Instance &inst, int n_samples, rt::LaunchParams &p, size_t *lds_out) {
     p.bvh = rt::BvhTables{};
     if (rt::walks_hierarchy(inst.tables)) {
-        if (!c->bvh_ok || !c->bvh.blob)
+        if (!c->scene.state.has_hierarchy() || !c->scene.bvh.blob)
             return fail(RT_ERR_STATE, "%s walks a hierarchy and the scene has none (fewer than %d small spheres?)", inst.name, c->bvh_min);
-        p.bvh = c->bvh;
+        p.bvh = c->scene.bvh;
     }
     size_t lds = 0;
     switch (inst.tables) {
         case rt::kTabSweepLds:
-            lds = rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, p.mat_in_lds != 0, n_samples);
+            lds = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, p.mat_in_lds != 0, n_samples);
             break;
         case rt::kTabSweepGlobal:
             p.mat_in_lds = 0;
@@ -148,23 +148,23 @@ static int bind_tables(rt_ctx *c, const rt::Instance &inst, int n_samples, rt::L
             break;
         case rt::kTabPairsGlobal:
             p.mat_in_lds = 0;
-            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, 1, 0, c->bvh.stack_depth, 64 * inst.waves);
+            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, 1, 0, c->scene.bvh.stack_depth, 64 * inst.waves);
             break;
         case rt::kTabPairsLdsSlotsGlobal:
             p.mat_in_lds = 0;
             lds = pairs_only_lds(c, n_samples, inst.waves);
             break;
         case rt::kTabPairsPacked:           // header | the packed table's frame | stacks
-            if (c->bvh.packed_at == 0 && c->bvh.n_leaves >= 2)      // (a tree of one leaf has no pairs: the walk starts at the leaf and the frame is never used)
+            if (c->scene.bvh.packed_at == 0 && c->scene.bvh.n_leaves >= 2)      // (a tree of one leaf has no pairs: the walk starts at the leaf and the frame is never used)
                 return fail(RT_ERR_STATE, "%s reads the packed pair table and this scene's hierarchy has none", inst.name);
             p.mat_in_lds = 0;
-            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, 1, 0, c->bvh.stack_depth, 64 * inst.waves) + 32;
+            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, 1, 0, c->scene.bvh.stack_depth, 64 * inst.waves) + 32;
             break;
         case rt::kTabPairsTopLds:           // header | the promoted top of the tree (n_top pairs = "n_top + 1 leaves") | stacks
-            if (c->bvh.n_top == 0 && c->bvh.n_leaves >= 2)          // (without a promoted top the root is not pair 0: rt_debug_set_bvh_layout asks for one)
+            if (c->scene.bvh.n_top == 0 && c->scene.bvh.n_leaves >= 2)          // (without a promoted top the root is not pair 0: rt_debug_set_bvh_layout asks for one)
                 return fail(RT_ERR_STATE, "%s stages the promoted top of the tree and this scene's hierarchy has none", inst.name);
             p.mat_in_lds = 0;
-            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, c->bvh.n_top + 1, 0, c->bvh.stack_depth, 64 * inst.waves);
+            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, c->scene.bvh.n_top + 1, 0, c->scene.bvh.stack_depth, 64 * inst.waves);
             break;
         default:
             return fail(RT_ERR_STATE, "%s: unknown table kind %d", inst.name, inst.tables);
@@ -180,17 +180,17 @@ static int bind_tables(rt_ctx *c, const rt::Instance &inst, int n_samples, rt::L
 // Which instance renders a launch of `form`, and the launch parameters that go with the choice.  Reads the context, changes nothing, calls nothing of HIP.
 struct Chosen { const rt::Instance *inst = nullptr; int mat_in_lds = 0, regen_gate = 0; };      // (regen_gate 0: the context's, make_params)
 static int choose_instance(const rt_ctx *c, int n_samples, Form form, Chosen *out) {
-    const size_t lds_all = rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, true, n_samples);
+    const size_t lds_all = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, true, n_samples);
     // materials ride along in LDS only while that keeps at least 6 workgroups per CU resident
     // (160 KiB / 24 KiB); larger scenes read them from L2 once per hit
     out->mat_in_lds = lds_all <= (size_t)c->mat_lds_limit;
-    const size_t lds_sweep = rt::lds_bytes(c->scene.n_spheres, c->scene.n_lights, out->mat_in_lds != 0, n_samples);
+    const size_t lds_sweep = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, out->mat_in_lds != 0, n_samples);
 
     // which instance: arithmetic mode x role x workgroup shape.  Single-wavefront workgroups (8x8 tiles) keep the wave
     // slots of a CU full (a 4-wavefront workgroup waits for four free slots at once) and give the heavy-first order a
     // finer granule; each stages its own copy of the tables, so only while 24 copies fit a CU.
     bool fast = c->mode == RT_MODE_FAST;
-    const bool coop = form == Form::SweepCoop ? true : (form == Form::SweepPlain ? false : (c->coop_min > 0 && c->scene.n_spheres >= (uint32_t)c->coop_min));
+    const bool coop = form == Form::SweepCoop ? true : (form == Form::SweepPlain ? false : (c->coop_min > 0 && c->scene.tables.n_spheres >= (uint32_t)c->coop_min));
     const bool w1 = c->wg_waves == 1 || (c->wg_waves == 0 && lds_sweep + (coop ? 1536u : 256u) <= 6 * 1024);   // + the instance's static LDS
     int role = coop ? rt::kRoleCoop : rt::kRolePlain, waves = w1 ? 1 : 4;
     if (!sweeps(form) && bvh_usable(c)) {
@@ -226,7 +226,7 @@ static int choose_instance(const rt_ctx *c, int n_samples, Form form, Chosen *ou
 
 // What launch_form and launch_tiles refuse alike ...
 static int check_launch_args(const rt_ctx *c, int n_samples) {
-    if (!c->have_scene || !c->have_cam) return fail(RT_ERR_STATE, "rt_set_scene and rt_set_camera must precede rendering");
+    if (!c->scene.state.renderable()) return fail(RT_ERR_STATE, "rt_set_scene and rt_set_camera must precede rendering");
     if (n_samples < 0) return fail(RT_ERR_ARG, "n_samples < 0");
     if (n_samples > 0x7fffffff - c->frame.current_sample)
         return fail(RT_ERR_ARG, "pass counter would overflow (%d + %d)", c->frame.current_sample, n_samples);
@@ -337,7 +337,7 @@ int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream) {
     const rt::FrameState &frame = c->frame;
     if (!frame.have_selection) return fail(RT_ERR_STATE, "rt_render_tiles_async: no selection (rt_select_tiles comes first; a reset drops it)");
     if (n_samples == 0 || frame.counts[0] == 0) return RT_OK;
-    if (c->tables_stale) {
+    if (c->scene.state.tables_stale) {
         rc = refresh_tables(c, stream);
         if (rc != RT_OK) return rc;
     }
@@ -414,19 +414,19 @@ void probe_poll(rt_ctx *c, bool wait) {
         (void)hipGetLastError();
         return;
     }
-    c->choice.times_arrived(a, b, c->bvh_n_tree, c->bvh.n_always);
+    c->choice.times_arrived(a, b, c->scene.state.n_tree, c->scene.bvh.n_always);
 }
 
 // what Choice::next_launch is told of the context and its scene for a call of n_samples passes
 static rt::Choice::Facts choice_facts(const rt_ctx *c, int n_samples) {
     rt::Choice::Facts f;
     f.diagnostics = c->walk_forced != 0 || c->mode >= 100;
-    f.nothing_to_render = n_samples <= 0 || c->local_rows == 0 || !c->have_scene || !c->have_cam;     // (or the error: launch_form says which)
+    f.nothing_to_render = n_samples <= 0 || c->local_rows == 0 || !c->scene.state.renderable();     // (or the error: launch_form says which)
     f.hierarchy = bvh_usable(c);
     f.tables_fit = tables_fit_lds(c, n_samples);
-    f.n_tree = c->bvh_n_tree;
-    f.n_always = c->bvh.n_always;
-    f.n_spheres = c->scene.n_spheres;
+    f.n_tree = c->scene.state.n_tree;
+    f.n_always = c->scene.bvh.n_always;
+    f.n_spheres = c->scene.tables.n_spheres;
     f.coop_min = c->coop_min;
     f.wg_waves = c->wg_waves;
     f.persist = c->persist;
@@ -434,7 +434,7 @@ static rt::Choice::Facts choice_facts(const rt_ctx *c, int n_samples) {
 }
 
 int launch(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block) {
-    if (c->tables_stale) {              // records updated on the device since the tables were built: build them now, once
+    if (c->scene.state.tables_stale) {              // records updated on the device since the tables were built: build them now, once
         const int rc = refresh_tables(c, stream);
         if (rc != RT_OK) return rc;
     }

@@ -127,13 +127,6 @@ struct rt_multi {
 
 namespace {
 
-int rows_of(int h, int rank, int n, int tile_rows) {
-    const int n_tiles = (h + tile_rows - 1) / tile_rows;
-    int rows = 0;
-    for (int t = rank; t < n_tiles; t += n) rows += (t * tile_rows + tile_rows <= h) ? tile_rows : (h - t * tile_rows);
-    return rows;
-}
-
 int refuse_if_broken(const rt_multi *m) {
     if (m->broken) return fail(RT_ERR_STATE, "this multi-device context is unusable since a gather failed (%s): destroy it", m->broken_why);
     return RT_OK;
@@ -291,7 +284,7 @@ RT_API int rt_create_multi_on(rt_ctx **out, int w, int h, const int *devices, in
     m->tile_rows = tile_rows;
     m->emulated = repeated && !g_repeated_counts_as_distinct;
     m->devices.assign(devices, devices + ngpus);
-    for (int r = 0; r < ngpus; ++r) m->pad_rows = rows_of(h, r, ngpus, tile_rows) > m->pad_rows ? rows_of(h, r, ngpus, tile_rows) : m->pad_rows;
+    for (int r = 0; r < ngpus; ++r) m->pad_rows = rt::rows_of_rank(h, r, ngpus, tile_rows) > m->pad_rows ? rt::rows_of_rank(h, r, ngpus, tile_rows) : m->pad_rows;
 
     auto build = [&]() -> int {
         if (!m->emulated && ngpus > 1) {               // (one device: nothing to move, no communicator, RCCL is not even loaded)

@@ -66,40 +66,20 @@ namespace rt {
 
 static bool light_test(const rt_sphere &s) { return !((s.e.x == 0.f) && (s.e.z == 0.f)); }   // .cl:135-138,266
 
-// the blocks sized by scene_cap given back (the staging of uploads and of host-built trees have capacities of their own and stay)
-static void free_scene(rt_ctx *c) {
-    c->owned.drop(c->d_spheres);
-    c->owned.drop(c->d_tables);
-    c->owned.drop(c->d_bvh);
-    c->owned.drop(c->d_dup);
-    c->owned.drop(c->h_dup_stage);
-    c->d_dup = nullptr;
-    c->h_dup_stage = nullptr;
-    c->dup_stage_used = false;
-    c->have_dups = false;
-    c->d_spheres = nullptr;
-    c->d_tables = nullptr;
-    c->d_bvh = nullptr;
-    c->bvh_ok = false;
-    c->scene_cap = 0;
-}
-
 int ensure_scene_capacity(rt_ctx *c, uint32_t count) {
-    if (count <= c->scene_cap && c->d_tables) return RT_OK;
+    if (count <= c->scene.cap && c->scene.d_tables) return RT_OK;
     uint32_t cap = 64;
     while (cap < count) cap *= 2;
     int rc = wait_all(c);               // nothing may still read the tables that are about to go
     if (rc != RT_OK) return rc;
-    // the new blocks first, the old ones after (free_scene): a failure leaves the scene the context holds as it was
+    // the new blocks first, the old ones after: a failure leaves the scene the context holds as it was
     rt::Owned &own = c->owned;
     rt_sphere *ns = nullptr;
     float4 *nt = nullptr, *nb = nullptr;
     uint8_t *nd = nullptr;
     RT_TRY(own_device(own, &ns, cap));
     hipError_t e = take_device(own, &nt, (size_t)cap * 5 + 1);
-    // blob: hdr 2 + slots (< cap + 8; up to twice that with the partial leaves of the shaped tree) + index (a quarter of the
-    // slots) + pairs (< cap / 2 + 4) + two material records per slot, in float4
-    if (e == hipSuccess) e = take_device(own, &nb, (size_t)cap * 6 + 64);
+    if (e == hipSuccess) e = take_device(own, &nb, rt::bvh_blob_capacity(cap));
     if (e == hipSuccess) e = take_device(own, &nd, cap);
     if (e != hipSuccess) {
         own.drop(ns);
@@ -107,29 +87,19 @@ int ensure_scene_capacity(rt_ctx *c, uint32_t count) {
         own.drop(nb);
         return fail(RT_ERR_ALLOC, "scene tables for %u spheres: %s", cap, hipGetErrorString(e));
     }
-    free_scene(c);
-    c->d_spheres = ns;
-    c->d_tables = nt;
-    c->d_bvh = nb;
-    c->d_dup = nd;
-    c->scene_cap = cap;
-    return RT_OK;
-}
-
-static int ensure_stage_capacity(rt_ctx *c, uint32_t count) {
-    if (count <= c->stage_cap) return RT_OK;
-    uint32_t cap = 64;
-    while (cap < count) cap *= 2;
-    for (int k = 0; k < 4; ++k)
-        if (c->stage_used[k]) {
-            HIP_TRY(hipEventSynchronize(c->stage_ev[k]));
-            c->stage_used[k] = false;
-        }
-    rt_sphere *grown = nullptr;
-    RT_TRY(own_pinned(c->owned, &grown, (size_t)cap * 4));
-    c->owned.drop(c->h_stage);
-    c->h_stage = grown;
-    c->stage_cap = cap;
+    // the blocks sized by the capacity given back (the staging of uploads and of host-built trees have capacities of their own and stay)
+    rt::Scene &sc = c->scene;
+    own.drop(sc.d_spheres);
+    own.drop(sc.d_tables);
+    own.drop(sc.d_bvh);
+    own.drop(sc.d_dup);
+    sc.dup_stage.give_back(own);
+    sc.d_spheres = ns;
+    sc.d_tables = nt;
+    sc.d_bvh = nb;
+    sc.d_dup = nd;
+    sc.cap = cap;
+    sc.state.capacity_replaced();
     return RT_OK;
 }
 
@@ -138,54 +108,48 @@ static int ensure_stage_capacity(rt_ctx *c, uint32_t count) {
 // whatever range it rewrites -- stays on the stream (rt_api.h: rt_update_spheres_async waits for nothing).
 static int build_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload);
 int upload_spheres(rt_ctx *c, uint32_t first, uint32_t count, const rt_sphere *spheres, uint32_t n_total, hipStream_t stream, bool full_upload) {
-    int rc = chain(c, stream);
-    if (rc != RT_OK) return rc;
+    RT_TRY(chain(c, stream));
     if (count) {
-        rc = ensure_stage_capacity(c, count);
-        if (rc != RT_OK) return rc;
-        const int slot = c->stage_next;
-        c->stage_next = (slot + 1) & 3;
-        if (c->stage_used[slot]) HIP_TRY(hipEventSynchronize(c->stage_ev[slot]));
-        rt_sphere *stage = c->h_stage + (size_t)slot * c->stage_cap;
+        rt_sphere *stage = nullptr;
+        RT_TRY(c->scene.ring.acquire(c->owned, count, &stage));
         memcpy(stage, spheres, (size_t)count * sizeof(rt_sphere));
-        HIP_TRY(hipMemcpyAsync(c->d_spheres + first, stage, (size_t)count * sizeof(rt_sphere), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(c->stage_ev[slot], stream));
-        c->stage_used[slot] = true;
-        for (uint32_t i = 0; i < count; ++i) c->is_light[first + i] = light_test(spheres[i]) ? 1 : 0;
+        HIP_TRY(hipMemcpyAsync(c->scene.d_spheres + first, stage, (size_t)count * sizeof(rt_sphere), hipMemcpyHostToDevice, stream));
+        RT_TRY(c->scene.ring.sent(c->owned, stream));
+        for (uint32_t i = 0; i < count; ++i) c->scene.is_light[first + i] = light_test(spheres[i]) ? 1 : 0;
     }
-    if (!full_upload && c->have_scene) {
+    if (!full_upload && c->scene.state.have_scene) {
         // a device-resident update: the records are on their way; the tables and the hierarchy are built from them when something reads them next
         // (refresh_tables: launch(), the diagnostics' readers) -- once for all the updates queued until then
-        c->tables_stale = true;
+        c->scene.state.records_updated();
         return RT_OK;
     }
     return build_tables(c, n_total, stream, full_upload);
 }
 
-// the scene tables (rt_build_tables_kernel) and the hierarchy from the records in c->d_spheres, on `stream`
+// the scene tables (rt_build_tables_kernel) and the hierarchy from the records in c->scene.d_spheres, on `stream`
 static int build_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, bool full_upload) {
     uint32_t nl = 0;
-    for (uint32_t i = 0; i < n_total; ++i) nl += c->is_light[i];
-    const size_t cap = c->scene_cap;
-    float4 *base = c->d_tables;
+    for (uint32_t i = 0; i < n_total; ++i) nl += c->scene.is_light[i];
+    const size_t cap = c->scene.cap;
+    float4 *base = c->scene.d_tables;
     float4 *d_geom = base, *d_emis = base + cap, *d_colr = base + 2 * cap, *d_la = base + 3 * cap, *d_lb = base + 4 * cap;
     if (n_total) {
-        hipLaunchKernelGGL(rt_build_tables_kernel, dim3(1), dim3(256), 0, stream, c->d_spheres, n_total, d_geom, d_emis, d_colr,
+        hipLaunchKernelGGL(rt_build_tables_kernel, dim3(1), dim3(256), 0, stream, c->scene.d_spheres, n_total, d_geom, d_emis, d_colr,
                            d_la, d_lb, reinterpret_cast<uint32_t *>(base + 5 * cap));
         HIP_TRY(hipGetLastError());
     }
-    c->scene = rt::SceneTables{ d_geom, d_emis, d_colr, d_la, d_lb, n_total, nl };
+    c->scene.tables = rt::SceneTables{ d_geom, d_emis, d_colr, d_la, d_lb, n_total, nl };
     const int rc = rt::build_bvh(c, n_total, stream, full_upload);
-    if (rc == RT_OK) c->tables_stale = false;       // (a build that failed half-way is tried again by the next reader)
+    if (rc == RT_OK) c->scene.state.tables_built();     // (a build that failed half-way is tried again by the next reader)
     return rc;
 }
 
 int refresh_tables(rt_ctx *c, hipStream_t stream) {
-    if (!c->tables_stale || !c->have_scene) return RT_OK;
+    if (!c->scene.state.needs_refresh()) return RT_OK;
     int rc = chain(c, stream);          // (behind the copies of the records, whatever streams the updates were given)
     if (rc != RT_OK) return rc;
-    rc = build_tables(c, c->scene.n_spheres, stream, false);
-    if (rc == RT_OK) c->choice.tables_rebuilt(c->bvh_ok, c->bvh_n_tree, c->bvh.n_always);
+    rc = build_tables(c, c->scene.tables.n_spheres, stream, false);
+    if (rc == RT_OK) c->choice.tables_rebuilt(c->scene.state.has_hierarchy(), c->scene.state.n_tree, c->scene.bvh.n_always);
     return rc;
 }
 

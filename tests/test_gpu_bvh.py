@@ -627,6 +627,56 @@ def test_many_scattered_updates_then_one_launch():
         assert bvh_check.check_structure(api.as_spheres(sph), bvh_check.read_bvh(ctx)) == []
 
 
+def test_staging_is_reused_behind_pending_copies_and_regrown():
+    """The three page-locked stagings of a scene (rt_internal.h Staged: the sphere ring of four slots, the host-built tree's buffer, the duplicate
+    flags') written again while the copies out of them are pending, given back and regrown -- one context, the hierarchy forced, every frame the
+    oracle's bit for bit: the ring wraps behind a long launch (six one-record updates: the fifth and sixth reuse slots 0 and 1); then 200 records with
+    a repeat (tree and flags staged, the ring grows to 256), at once 300 others (capacity 256 -> 512: the flags' staging given back and acquired
+    again, the tree's grows) with no read in between, and the 200 again (nothing grows: both stagings reused behind their pending copies)."""
+    w, h, spp = 48, 32, 2
+
+    def frame(ctx):
+        return {"pixels": ctx.read_pixels(), "colors": ctx.read_colors(), "seeds": ctx.read_seeds(), "stats": ctx.stats()}
+
+    with api.RtContext(w, h, diag=True) as ctx:
+        ctx._check(ctx._lib.rt_debug_set_bvh(ctx._h, 1, 152 * 1024))
+        ctx._check(ctx._lib.rt_debug_set_walk(ctx._h, 0, 0, 1))
+        demo = api.as_spheres(host.demo_scene()).copy()                     # (ring capacity 64)
+        cam = host.compute_camera(host.DEMO_ORIG, host.DEMO_TARGET, w, h)
+        ctx.set_scene(demo)
+        ctx.set_camera(cam)
+        ctx.render_async(spp, ctx.stream)
+        _same(frame(ctx), O.render(demo, cam, w, h, spp))
+        # the ring wraps: the copies wait behind 64 passes, the host does not
+        ctx.render_async(64, ctx.stream)
+        for i in range(6):
+            demo["p"][i] += np.float32(0.5 + 0.25 * i)
+            demo["c"][i] = (0.1 * (i + 1), 0.9 - 0.1 * i, 0.5)
+            ctx.update_spheres(i, demo[i:i + 1], ctx.stream)
+        ctx.reset_async(ctx.stream)
+        ctx.render_async(spp, ctx.stream)
+        _same(frame(ctx), O.render(demo, cam, w, h, spp))
+        # filled, given back, regrown
+        a, orig, target = scenes.random_spheres(200)
+        a = api.as_spheres(a).copy()
+        a[199] = a[198]
+        b = api.as_spheres(scenes.random_spheres(300)[0]).copy()
+        b["p"][2:, 0] += np.float32(2.0)
+        b[150] = b[17]
+        cam = host.compute_camera(orig, target, w, h)
+        ctx.set_camera(cam)
+        ctx.set_scene(a)
+        ctx.set_scene(b)                                                    # (no read in between)
+        ctx.reset_async(ctx.stream)
+        ctx.render_async(spp, ctx.stream)
+        _same(frame(ctx), O.render(b, cam, w, h, spp))
+        ctx.set_scene(a)
+        ctx.reset_async(ctx.stream)
+        ctx.render_async(spp, ctx.stream)
+        _same(frame(ctx), O.render(a, cam, w, h, spp))
+        assert "_pairs" in ctx.last_kernel, ctx.last_kernel
+
+
 @pytest.mark.parametrize("n_small,n_large,by_area", [(700, 300, 1), (3000, 600, 1), (3000, 600, 2), (9000, 1500, 1), (300, 700, 1)])
 def test_two_size_classes_both_hang_in_the_tree(n_small, n_large, by_area):
     """Round 6: the cut between the tree and the always-list is never below an eighth of the scene's extent, so the larger class of a scene of
