@@ -32,6 +32,7 @@
 #define RT_KERNEL_NAME rt_trace_fast_w1
 #define RT_OPT_WG_WAVES 1
 #define RT_OPT_DIRECT_CAMERA 1       /* the plain sweep only: the cooperative instances sit at 80 registers and spill with it */
+#define RT_OPT_SHARED_ORIGIN 1       /* as in rt_kernel_parity.hip */
 #include "rt_trace.inc.h"
 #include "rt_opts_reset.h"
 
@@ -104,6 +105,13 @@
 #include "rt_trace.inc.h"
 #include "rt_opts_reset.h"
 
+#define RT_NS fast_w1_twosweeps      /* A/B: rt_trace_fast_w1 with the loop it had before RT_OPT_SHARED_ORIGIN */
+#define RT_KERNEL_NAME rt_trace_fast_w1_twosweeps
+#define RT_OPT_WG_WAVES 1
+#define RT_OPT_DIRECT_CAMERA 1
+#include "rt_trace.inc.h"
+#include "rt_opts_reset.h"
+
 #define RT_NS fast_persist
 #define RT_KERNEL_NAME rt_trace_fast_persist
 #define RT_OPT_PERSIST 1
@@ -137,6 +145,7 @@ static const Instance kFastInstances[] = {
     { fastdx_coop_w1::rt_trace_fastdx_coop_w1, "rt_trace_fastdx_coop_w1", 1, kTabSweepLds, kRoleNone, kInstStaticCoop },
     { fastdx_coop::rt_trace_fastdx_coop, "rt_trace_fastdx_coop", 4, kTabSweepLds, kRoleNone, kInstStaticCoop },
     { fastdx_pairs::rt_trace_fastdx_pairs, "rt_trace_fastdx_pairs", 4, kTabPairsLds, kRoleNone, 0 },
+    { fast_w1_twosweeps::rt_trace_fast_w1_twosweeps, "rt_trace_fast_w1_twosweeps", 1, kTabSweepLds, kRoleNone, 0 },
     { fast_persist::rt_trace_fast_persist, "rt_trace_fast_persist", 4, kTabSweepLds, kRolePersist, kInstPersistent | kInstNoTileCost },
     { fast_persist_coop::rt_trace_fast_persist_coop, "rt_trace_fast_persist_coop", 4, kTabSweepLds, kRolePersistCoop,
       kInstPersistent | kInstNoTileCost | kInstStaticCoop },

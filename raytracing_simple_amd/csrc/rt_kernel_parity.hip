@@ -44,6 +44,7 @@
 #define RT_KERNEL_NAME rt_trace_parity_w1
 #define RT_OPT_WG_WAVES 1
 #define RT_OPT_DIRECT_CAMERA 1       /* the plain sweep only: the cooperative instances sit at 80 registers and spill with it */
+#define RT_OPT_SHARED_ORIGIN 1       /* ... and in its rotated wavefronts the last light's shadow ray rides the bounce ray's sweep */
 #define RT_OPT_MINWAVES 6
 #include "rt_trace.inc.h"
 #include "rt_opts_reset.h"
@@ -205,6 +206,14 @@
 #include "rt_trace.inc.h"
 #include "rt_opts_reset.h"
 
+#define RT_NS parity_w1_twosweeps    /* A/B: the headline instance with the loop it had before RT_OPT_SHARED_ORIGIN (a shadow ray always swept on its own) */
+#define RT_KERNEL_NAME rt_trace_parity_w1_twosweeps
+#define RT_OPT_WG_WAVES 1
+#define RT_OPT_DIRECT_CAMERA 1
+#define RT_OPT_MINWAVES 6
+#include "rt_trace.inc.h"
+#include "rt_opts_reset.h"
+
 #define RT_NS parity_tl              /* the shipped shape + device wall-clock logging (P.timelog / P.wavelog) */
 #define RT_KERNEL_NAME rt_trace_parity_tl
 #define RT_OPT_TIMELOG 1
@@ -247,6 +256,7 @@ static const Instance kParityInstances[] = {
       kInstPersistent | kInstNoTileCost | kInstStaticCoop },
     { parity_tl::rt_trace_parity_tl, "rt_trace_parity_tl", 4, kTabSweepLds, kRoleTimelog, 0 },
     { parity_w1_sweptcam::rt_trace_parity_w1_sweptcam, "rt_trace_parity_w1_sweptcam", 1, kTabSweepLds, kRoleNone, 0 },
+    { parity_w1_twosweeps::rt_trace_parity_w1_twosweeps, "rt_trace_parity_w1_twosweeps", 1, kTabSweepLds, kRoleNone, 0 },
 #endif
 };
 

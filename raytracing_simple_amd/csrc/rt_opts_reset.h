@@ -12,6 +12,7 @@
 #undef RT_OPT_MINWAVES
 #undef RT_OPT_PERSIST
 #undef RT_OPT_DIRECT_CAMERA
+#undef RT_OPT_SHARED_ORIGIN
 #undef RT_OPT_STAMPS
 #undef RT_OPT_TIMELOG
 #undef RT_OPT_EXACT_DECISIONS

@@ -51,6 +51,9 @@
 //                         ROTATED -- a regenerating lane resolves its camera ray itself against those 0..4 spheres, and the wave-wide sweep
 //                         carries bounce rays only; every other wavefront keeps the old order of a trip (the staged sweep instances; tables in
 //                         HBM / L2, the walk and the diagnostics arms have the old loop only)
+//   RT_OPT_SHARED_ORIGIN  1, with RT_OPT_DIRECT_CAMERA: in a rotated wavefront the shadow ray of a diffuse hit's LAST light and the hit's bounce ray --
+//                         both leave the hit point -- share one pass over the table (sweep_both); earlier lights, the old-order wavefronts and every
+//                         other instance sweep a shadow ray on its own (sweep_any)
 // Diagnostics build only:
 //   RT_OPT_PERSIST        persistent wavefronts: the grid only fills the machine, each wavefront pulls 8x8 pixel tiles
 //                         from a global queue and hands their pixels to its lanes one by one as lanes finish
@@ -79,6 +82,12 @@
 #endif
 #if RT_OPT_DIRECT_CAMERA && (RT_OPT_GLOBAL_TABLES || RT_OPT_WALK || RT_OPT_PERSIST || RT_OPT_STAMPS)
 #error "RT_OPT_DIRECT_CAMERA is for the staged sweep instances only"
+#endif
+#ifndef RT_OPT_SHARED_ORIGIN
+#define RT_OPT_SHARED_ORIGIN 0
+#endif
+#if RT_OPT_SHARED_ORIGIN && (!RT_OPT_DIRECT_CAMERA || RT_OPT_COOP)
+#error "RT_OPT_SHARED_ORIGIN is for the rotated loop of the plain sweep instances"
 #endif
 // Fused mode, diagnostics build only (the experiment VERDICT r4 item 1c asked for, profiles/r05_fast_gate.jsonl): every DECISION of
 // a path -- the sphere test's discriminant, root and epsilon compares (.cl:173-201), which side of a light and of the surface a
@@ -464,6 +473,70 @@ RT_DEV uint32_t sweep_any(const float4 *s_geom, uint32_t n, V3 o, V3 d, float ma
     return first;
 }
 
+#if RT_OPT_SHARED_ORIGIN
+// Two rays from ONE origin in one pass over the staged table: a shadow ray (any hit closer than max_t, .cl:234-247) and a bounce ray (closest hit,
+// .cl:215-232).  Of a test's discriminant, op = centre - o and op.op depend on the origin alone: formed once per record, they are the same operations
+// on the same operands as in hit_pre, so both halves see the bits the two separate sweeps see; the two b and the two discriminants follow in the
+// reference's association, b * b - op.op + r^2.  `first` is all there is of the shadow ray's state: n + 1 no ray, n looking, < n the first blocking
+// sphere (a lane that has its blocker asks for no more roots, as in sweep_any); `go` says the lane has a bounce ray.  Records in the reference's
+// order, no early exit (the bounce ray needs every record anyway).
+struct OriginPre {
+    V3 op;
+    float oo;
+};
+RT_DEV OriginPre origin_pre(float4 g, V3 o) {
+    const V3 op = mk(g.x - o.x, g.y - o.y, g.z - o.z);
+#if RT_OPT_EXACT_DECISIONS
+    return OriginPre{ op, dot_decision(op, op) };
+#else
+    return OriginPre{ op, dot(op, op) };
+#endif
+}
+RT_DEV HitPre hit_pre_from(OriginPre q, float r2, V3 d) {
+#if RT_OPT_EXACT_DECISIONS
+    const float b = dot_decision(q.op, d);
+    return HitPre{ b, mul_decision(b, b) - q.oo + r2 };
+#else
+    const float b = dot(q.op, d);
+    return HitPre{ b, b * b - q.oo + r2 };
+#endif
+}
+struct BothPre {
+    HitPre ps, pc;      // the shadow ray's and the bounce ray's
+};
+RT_DEV BothPre both_pre(float4 g, V3 o, V3 sd, V3 d) {
+    const OriginPre q = origin_pre(g, o);
+    return BothPre{ hit_pre_from(q, g.w, sd), hit_pre_from(q, g.w, d) };
+}
+RT_DEV void both_roots(BothPre p, uint32_t i, uint32_t n, uint32_t &first, float max_t, unsigned long long go_mask, float &t, uint32_t &id) {
+    const HitPre ps = p.ps, pc = p.pc;
+    if (__builtin_amdgcn_ballot_w64(first == n && ps.det >= 0.f) != 0ull) {
+        const HitRoots h = hit_roots(ps);
+        if (first == n && h.hit && h.t < max_t) first = i;
+    }
+    // (go && det >= 0 as one compare and one scalar AND: the ballot of the compare, masked by the ballot of `go`)
+    if ((__builtin_amdgcn_ballot_w64(pc.det >= 0.f) & go_mask) != 0ull) {
+        const HitRoots h = hit_roots(pc);
+        if (h.hit && h.t < t) { t = h.t; id = i; }       // (never on a lane without a bounce ray: its t is 0 through the sweep, and a hit's distance exceeds EPS)
+    }
+}
+RT_DEV void sweep_both(const float4 *s_geom, uint32_t n, V3 o, uint32_t &first, V3 sd, float max_t, bool go, V3 d, float &t, uint32_t &id) {
+    // What the loop keeps of `go` is its ballot, for the wave-level decision; the lane-level one rides in t: 0 on a lane without a bounce ray, so
+    // that no distance is ever closer, and back to "no hit" after the sweep (a lane WITH a bounce ray leaves with t > EPS or with the t it came with).
+    const unsigned long long go_mask = __builtin_amdgcn_ballot_w64(go);
+    if (!go) t = 0.f;
+    uint32_t i = 0;
+    for (; i + 2 <= n; i += 2) {
+        const float4 g0 = s_geom[i], g1 = s_geom[i + 1];
+        const BothPre p0 = both_pre(g0, o, sd, d), p1 = both_pre(g1, o, sd, d);
+        both_roots(p0, i, n, first, max_t, go_mask, t, id);
+        both_roots(p1, i + 1, n, first, max_t, go_mask, t, id);
+    }
+    for (; i < n; ++i) both_roots(both_pre(s_geom[i], o, sd, d), i, n, first, max_t, go_mask, t, id);
+    if (t == 0.f) t = 1e20f;        // (the kernel's "no hit")
+}
+#endif
+
 // .cl:438 and .cl:470: the two quantities a glass hit DECIDES on (total internal reflection; reflect or refract)
 RT_DEV float cos2t_of(float nnt, float ddn) {
 #if RT_OPT_EXACT_DECISIONS
@@ -480,14 +553,10 @@ RT_DEV float roulette_p(float Re) {
 #endif
 }
 
-// One light of SampleLights (.cl:258-295) up to the visibility test.  Draws its two numbers
-// whatever happens next, as the reference does.  Returns true when a shadow ray is needed and
+// One light of SampleLights (.cl:258-295) up to the visibility test, in two steps: the light's two numbers (sample_light draws them
+// whatever happens next, as the reference does), and everything that follows from them.  Returns true when a shadow ray is needed and
 // then gives its unit direction, its length and the numerator 4*pi*r^2*wi*wo of .cl:297.
-RT_DEV bool sample_light(float4 la, float4 lb, uint32_t &s0, uint32_t &s1, uint32_t &c_draws, V3 hp, V3 nl,
-                         V3 &sd, float &len, float &numer) {
-    float zc = next_random_z(s0, s1);                                      // .cl:203-213: 1 - 2 u1
-    float u2 = next_random(s0, s1);
-    c_draws += 2;
+RT_DEV bool sample_light_drawn(float4 la, float4 lb, float zc, float u2, V3 hp, V3 nl, V3 &sd, float &len, float &numer) {
     float ring = rt_sqrt_unit(fmaxf(0.f, 1.f - zc * zc));
     float sphi, cphi;
 #if RT_FAST
@@ -505,6 +574,13 @@ RT_DEV bool sample_light(float4 la, float4 lb, uint32_t &s0, uint32_t &s1, uint3
     float wi = dot_decision(sd, nl);
     numer = lb.w * wi * wo;
     return wi > 0.f;
+}
+RT_DEV bool sample_light(float4 la, float4 lb, uint32_t &s0, uint32_t &s1, uint32_t &c_draws, V3 hp, V3 nl,
+                         V3 &sd, float &len, float &numer) {
+    float zc = next_random_z(s0, s1);                                      // .cl:203-213: 1 - 2 u1
+    float u2 = next_random(s0, s1);
+    c_draws += 2;
+    return sample_light_drawn(la, lb, zc, u2, hp, nl, sd, len, numer);
 }
 
 #if RT_OPT_COOP
@@ -1016,8 +1092,16 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
             }
         }
 #else
+#if RT_OPT_SHARED_ORIGIN
+        // rotated: the LAST light's two numbers are drawn here, at the reference's place in the stream, and kept; its geometry and its shadow ray
+        // wait for the end of the trip, where the ray rides the bounce ray's sweep (both leave hp)
+        const uint32_t n_swept = (RT_ROTATED && n_lights != 0u) ? n_lights - 1u : n_lights;
+        float kept_zc = 0.f, kept_u2 = 0.f;
+#else
+        const uint32_t n_swept = n_lights;
+#endif
         if (is_diff) {
-            for (uint32_t j = 0; j < n_lights; ++j) {
+            for (uint32_t j = 0; j < n_swept; ++j) {
                 RT_STAMP(3);
 #if RT_OPT_GLOBAL_TABLES
                 const volatile __attribute__((address_space(4))) LaunchParams *lp =           // (as the material pointers above: once per light)
@@ -1045,10 +1129,20 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
                     ld = add(ld, scale(mk(lb.x, lb.y, lb.z), k));
                 }
             }
+#if RT_OPT_SHARED_ORIGIN
+            if (n_swept != n_lights) {
+                kept_zc = next_random_z(s0, s1);                           // .cl:203-213, as sample_light draws them
+                kept_u2 = next_random(s0, s1);
+                c_draws += 2;
+            }
+#endif
         }
 #endif
 
         if (is_diff) {
+#if RT_OPT_SHARED_ORIGIN
+            if (!RT_ROTATED)        // (rotated: behind the sweep at the end of the trip, once the last light is in ld; thr and ld rest meanwhile)
+#endif
             rad = add(rad, mul(thr, ld));                                  // .cl:377-378
             RT_STAMP(6);
             // ---- cosine-weighted bounce: its two draws, then cosine_direction ----
@@ -1119,12 +1213,50 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
         if (RT_ROTATED) {
             t = 1e20f;
             id = 0;
+#if RT_OPT_SHARED_ORIGIN
+            // The last light of a diffuse hit, from the numbers kept above: o is hp here.  `first` is the shadow ray's state (sweep_both): n + 1 none,
+            // n looking, < n blocked -- and n + 2 on a lane whose hit was not diffuse, so that is_diff is not one more lane mask held in scalar
+            // registers through the sweep.  A diffuse hit at the depth limit has a shadow ray and no bounce ray.
+            uint32_t first = is_diff ? n + 1u : n + 2u;
+            V3 sd = mk(0.f, 0.f, 1.f);
+            float max_t = 0.f, k = 0.f;
+            if (is_diff && n_swept != n_lights) {
+                float len, numer;
+                if (sample_light_drawn(s_lightA[n_swept], s_lightB[n_swept], kept_zc, kept_u2, o, nl, sd, len, numer)) {
+                    c_shadow += 1;
+                    first = n;
+                    max_t = len - RT_EPS;
+                    k = rt_div(numer, len * len);                          // .cl:297
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(first == n) != 0ull) {
+                // (lanes with neither ray ride along under the same execution mask -- no ballot counts them and nothing of theirs is written; a
+                // branch around the sweep for them would hold one more saved mask in scalar registers through it, and the loop has none to spare)
+                if (!path_done) c_closest += 1;
+                sweep_both(s_geom, n, o, first, sd, max_t, !path_done, d, t, id);
+            } else if (__builtin_amdgcn_ballot_w64(!path_done) != 0ull) {
+                if (!path_done) {
+                    sweep_closest(s_geom, n, o, d, t, id, st_roots_c);
+                    c_closest += 1;
+                }
+            }
+            if (first <= n) {
+                const bool blocked = first < n;
+                c_tests += blocked ? first + 1 : n;
+                if (!blocked) {
+                    const float4 lb = s_lightB[n_swept];                   // (read again: three registers less across the sweep)
+                    ld = add(ld, scale(mk(lb.x, lb.y, lb.z), k));
+                }
+            }
+            if (first != n + 2u) rad = add(rad, mul(thr, ld));             // .cl:377-378: the last light is still added last
+#else
             if (__builtin_amdgcn_ballot_w64(!path_done) != 0ull) {
                 if (!path_done) {
                     sweep_closest(s_geom, n, o, d, t, id, st_roots_c);
                     c_closest += 1;
                 }
             }
+#endif
         } else if (path_done) {
             acc = fold_sample(acc, rad, s, P.first_sample, s_k2, k2_in_lds);
             s += 1;
@@ -1195,19 +1327,27 @@ extern "C" __global__ void __launch_bounds__(64 * RT_OPT_WG_WAVES, RT_OPT_MINWAV
         atomicAdd(&s_stat[4], (unsigned long long)t_draws);
     }
     __syncthreads();
+#if RT_OPT_SHARED_ORIGIN && RT_OPT_WG_WAVES == 1
+    // (A single-wavefront workgroup: the thread's number is the lane's, formed after the loop.  From `tid` the compiler carries wg_begin's `tid < 5`
+    // mask in two scalar registers and tid * 8 in a vector register from the prologue to here; with this option's loop those were the registers it
+    // lacked -- the mask parked in lanes of a vector register, the address in an 8-byte private segment, both of which tests/test_abi.py refuses.)
+    const int tid_e = lane_e;
+#else
+    const int tid_e = tid;
+#endif
 #if !RT_OPT_PERSIST
     // (bit 1 of the launch flags: a SHORT launch inside an accumulation window -- its cost is added to what the window's launches before it left,
     // so that a host which only ever launches a pass or two at a time gets its tiles ordered from 16 passes' worth of costs: rt_launch.hip)
-    if (tid == 5 && Q.tile_cost) Q.tile_cost[tile_id] = (Q.skip_pixels & 2) ? Q.tile_cost[tile_id] + s_tile_cost : s_tile_cost;
+    if (tid_e == 5 && Q.tile_cost) Q.tile_cost[tile_id] = (Q.skip_pixels & 2) ? Q.tile_cost[tile_id] + s_tile_cost : s_tile_cost;
 #endif
-    if (tid < 5) {
+    if (tid_e < 5) {
 #if RT_OPT_PERSIST
         const unsigned block_linear = blockIdx.x + blockIdx.y * gridDim.x;
 #endif
 #if RT_OPT_PERSIST
-        atomicAdd(&P.stats[(block_linear % (unsigned)kStatReplicas) * 8u + (unsigned)tid], s_stat[tid]);
+        atomicAdd(&P.stats[(block_linear % (unsigned)kStatReplicas) * 8u + (unsigned)tid_e], s_stat[tid_e]);
 #else
-        atomicAdd(&Q.stats[(block_linear % (unsigned)kStatReplicas) * 8u + (unsigned)tid], s_stat[tid]);
+        atomicAdd(&Q.stats[(block_linear % (unsigned)kStatReplicas) * 8u + (unsigned)tid_e], s_stat[tid_e]);
 #endif
     }
 #if RT_OPT_STAMPS
