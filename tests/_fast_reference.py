@@ -8,8 +8,11 @@ control arm must equal the restatements here bit for bit; only then do the fast 
 THE LIMIT.  -ffp-contract=fast fuses whatever multiply and add end up next to each other, so the same source function
 can compile to different roundings in the probe and in each of the shipped rt_trace_fast_* kernels.  The probe
 therefore holds the SOURCE FUNCTIONS UNDER THE FAST FLAGS to envelopes that are valid for ANY fusing; it does not hold
-the shipped machine code.  The shipped kernels' own fusing is seen only by tests/test_gpu_fast_bias.py and the PSNR
-gates of tests/test_gpu_parity.py.
+the shipped machine code.  The shipped kernels' own fusing is seen by tests/test_gpu_fast_bias.py and the PSNR gates of
+tests/test_gpu_parity.py, and -- for the closest-hit decision of camera rays, ray by ray -- by the first-hit frames of
+tests/test_gpu_fast_first_hit.py (tests/_first_hit.py): every shipped rt_trace_fast_* instance renders one pass of a scene whose
+spheres are all emitters that carry their own index, and hit or miss, the winner and |n.d| of every pixel are held to pairs64 /
+scene64 on the camera ray formed in binary64 with its envelope (pairs64's o_env / d_env).
 
 REFERENCES.  Every binary64 reference is fed the very binary32 inputs the device gets (directions are normalised in
 binary32 on the host and those floats go to both), and is evaluated in binary64, whose own rounding (2^-53 per
@@ -46,8 +49,12 @@ That is a condition on the reference, never on what the code under test returned
 NOT REACHED by the probe, and why: everything that is open-coded in the kernel bodies rather than a function -- the
 refraction direction and the Fresnel terms (rt_trace.inc.h, the REFR branch), the throughput / radiance updates, the
 Russian-roulette compare itself, fold_sample's table read (it needs the workgroup's LDS table), coop_any (it needs a
-whole wavefront's pending rays and its LDS slots), the hierarchy walk (rt_walk.inc.h, kernel state throughout) and the
-rotated candidate loop of RT_OPT_DIRECT_CAMERA (it calls hit_pre / hit_roots, which ARE probed, on a kernel-held list).
+whole wavefront's pending rays and its LDS slots).  The hierarchy walk (rt_walk.inc.h, kernel state throughout) is not reached by
+THIS probe either, but its source under the fast flags is held ray by ray, closest-hit and shadow rays, by tests/walk_probe.hip
+(rt_walk.inc.h's own rays kernel, tests/test_gpu_fast_walk.py, tests/_walk_probe.py); the rotated candidate loop of
+RT_OPT_DIRECT_CAMERA (it calls hit_pre / hit_roots, which ARE probed, on a kernel-held list) and the walk as the shipped instances
+compile it are held for camera rays by the first-hit frames.  STILL OPEN: the REFR branch, coop_any's shadow decisions, and the
+shadow rays of the shipped kernels (an emitter ends the path of a first-hit frame before any light is sampled).
 camera_direction, sample_light and next_random* take the generator's state by reference and are called with a state
 per lane; the host replays the generator exactly (integers).  The reflected direction is one open-coded expression,
 d - nrm * (2 dp); the probe restates that expression from the library's sub / scale."""
@@ -71,14 +78,15 @@ OPS = {"sincos": 0, "gamma": 1, "to_int": 2, "rcp": 3, "div": 4, "sqrt": 5, "sqr
 
 
 # ---- the probe ----------------------------------------------------------------------------------------------------
-def build_probe(out_dir, fast):
-    """tests/fast_probe.hip -> a shared library in out_dir; the fast arm with rt_kernel_fast.hip's flags, the control arm with parity's."""
+def build_probe(out_dir, fast, source="fast_probe"):
+    """tests/<source>.hip (fast_probe, walk_probe) -> a shared library in out_dir; the fast arm with rt_kernel_fast.hip's flags, the
+    control arm with parity's."""
     from raytracing_simple_amd import _build
     extra = dict(_build.UNITS)["rt_kernel_fast.hip" if fast else "rt_kernel_parity.hip"]
     assert extra == (["-ffp-contract=fast"] if fast else ["-ffp-contract=off"]), extra
-    so = os.path.join(str(out_dir), "libfast_probe_%s.so" % ("fast" if fast else "control"))
+    so = os.path.join(str(out_dir), "lib%s_%s.so" % (source, "fast" if fast else "control"))
     cmd = [_build.hipcc()] + _build.COMMON + extra + ["-DRT_FAST=%d" % (1 if fast else 0), "-I" + _build.CSRC, "-shared",
-                                                      os.path.join(ROOT, "tests", "fast_probe.hip"), "-o", so]
+                                                      os.path.join(ROOT, "tests", source + ".hip"), "-o", so]
     subprocess.run(cmd, check=True, capture_output=True)
     return so
 
@@ -330,13 +338,16 @@ def mwc_word(s0, s1):
 
 
 # ---- (ray, sphere) pairs in binary64 with envelopes ------------------------------------------------------------------
-def pairs64(rays, table, k):
+def pairs64(rays, table, k, o_env=None, d_env=None):
     """-> dict of [R, S]: det, b, t1, t2 (Err); finite (records and rays the analysis covers); hit (the binary64 decision);
     decided (the exclusion rule lets the hit / miss decision be compared); t, t_env, t_decided (distance, envelope, and whether which
-    root is returned can be compared as well)"""
+    root is returned can be compared as well).
+    o_env, d_env: three Err columns [R] each -- the origin and the direction as binary64 values WITH envelopes (rays the device forms
+    itself, e.g. camera rays: shade64(0, ...)); they take the place of the columns of `rays`, which are then not read.  Absent: the rays
+    are exact binary32 inputs, as before."""
     with np.errstate(all="ignore"):
-        o = [Err(rays[:, None, j].astype(D)) for j in range(3)]
-        d = [Err(rays[:, None, 3 + j].astype(D)) for j in range(3)]
+        o = [Err(rays[:, None, j].astype(D)) for j in range(3)] if o_env is None else [Err(c.v[:, None], c.e[:, None]) for c in o_env]
+        d = [Err(rays[:, None, 3 + j].astype(D)) for j in range(3)] if d_env is None else [Err(c.v[:, None], c.e[:, None]) for c in d_env]
         op = [Err(table[None, :, j].astype(D)) - o[j] for j in range(3)]
         b = e_dot(op, d)
         det = (b * b - e_dot(op, op)) + Err(table[None, :, 3].astype(D))
