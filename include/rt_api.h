@@ -749,6 +749,98 @@ RT_API int rt_denoise_guided_planes(float *out, const float *merged, const float
 RT_API int rt_denoise_pair_guided_planes(float *out_a, float *out_b, const float *a, const float *b, const float *feat, int w, int h,
                                          const rt_denoise_params *p, const rt_guide_params *g);
 
+/* ---- temporal reprojection: carry a frame's samples to a moved camera ---------------------------------
+ * An interactive host throws every sample away each time something moves: rt_set_camera or rt_update_spheres_async is followed by a reset, and the
+ * new view starts at pass 0 with one-pass noise.  This section reprojects the previous view's accumulated colour into the new view through the
+ * first-hit geometry of the feature planes and blends it with the new view's few passes.  Spheres make it clean: a translation describes a sphere's
+ * motion completely, and the scene index identifies the surface.  THIS LIBRARY'S OWN EXTENSION: it reproduces no reference frame and touches no render
+ * kernel, and no call above changes behaviour.
+ *
+ * THE TEMPORAL PLANE is T[h][w][4] floats in the colour plane's row order, owned by dst: rgb and n, the effective sample count behind the pixel.
+ * Beside it goes the plane packed by the toInt of dst's mode (as rt_denoise_pair_async packs its planes), one uint32 per pixel in the PIXEL BUFFER's
+ * layout (row 0 = bottom).  Both are allocated on first use and freed by rt_destroy.  T is a frame to show and a history to reproject from, NEVER a
+ * state to render on from: dst's colour plane, seeds, pass number, counters, selection, tile order and rt_last_kernel stay, and nothing of src changes.
+ *
+ * THE ARITHMETIC, the same in rt_reproject_async's kernel and in rt_reproject_planes: all binary32, uncontracted, in the written order, IEEE division
+ * and square root -- ALWAYS parity's arithmetic, whatever rt_set_mode says.  dot(a, b) = (a0 * b0 + a1 * b1) + a2 * b2.  D = dst, S = src; F is a
+ * feature plane, C a colour plane, p the centres of the records.
+ *  15. the point and where it was.  Image pixel (x, y) of D: id = word 7 of FD, t = word 6.  id == 0xFFFFFFFF (or any id that is no record's: the
+ *      feature calls write none): NO HISTORY.  Otherwise (o, d) by rule 10 with D's camera, P = o + d * t per component, m = pD[id] - pS[id],
+ *      Pp = P - m.
+ *  16. where S saw it.  v = Pp - camS.orig; z = dot(v, camS.dir); !(z > 0.0f): no history.
+ *      kx = (dot(v, camS.x) * dot(camS.dir, camS.dir)) / (z * dot(camS.x, camS.x)), ky the same with camS.y;
+ *      fx = (kx + 0.5f) * (float)w, fy = (ky + 0.5f) * (float)h;  !(fx >= -1.0f && fx < (float)w && fy >= -1.0f && fy < (float)h): no history.
+ *      x0 = floorf(fx), ax = fx - x0; y0 and ay alike.  This inverts rule 10 for the orthogonal basis rt_compute_camera makes; for any other basis it
+ *      is still what both sides compute.
+ *  17. the taps: the four pixels (x0 + i, y0 + j) of S, j = 0, 1 outer and i = 0, 1 inner, weight b = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay).
+ *      A tap q COUNTS only when it lies inside the image; word 7 of FS[q] equals id; with (oq, dq) by rule 10 with S's camera at q and tq = word 6 of
+ *      FS[q]: Pq = oq + dq * tq, e = Pq - Pp, r = k_pos * (tq * (sqrtf(dot(camS.x, camS.x)) * (1.f / (float)w))) and dot(e, e) <= r * r -- S saw the same
+ *      place within k_pos pixel footprints, which rejects the far side of the same sphere (other surfaces fail on id); and the three colour words of
+ *      U[q] are finite and its n is > 0.0f.  Any NaN makes a comparison false: the tap does not count.  U is S's temporal plane while that is
+ *      current, otherwise S's colour plane with n = (float)rt_current_sample(S).
+ *  18. the history.  sw = sn = sc[c] = 0.0f; each counted tap, in tap order, adds b, b * U.n and b * U[c].  !(sw > 0.0f): no history.  Otherwise
+ *      H[c] = sc[c] / sw, nh = sn / sw, if (nh > max_history) nh = max_history.
+ *  19. the blend.  nd = (float)rt_current_sample(D).  No history: T = (CD, nd) -- with nd == 0 four 0.0f.  History and nd == 0: T = (H, nh), a pure
+ *      warp before the new view has a sample.  Otherwise inv = 1.0f / (nd + nh), T[c] = (CD[c] * nd + H[c] * nh) * inv, T.n = nd + nh.  D's colour
+ *      plane is not read at pass 0.
+ * INTENDED USE: two contexts take turns.  Frame k + 1 sets its camera or records on the OLDER context, resets it (rt_seed_stream_async gives frame k
+ * stream k + 1), forms its features, renders a pass or two and reprojects from the other.  Because S's temporal plane is used while it is current,
+ * history carries across many frames, capped by max_history.
+ * LIMITS: history follows the FIRST hit.  What a mirror or a glass sphere shows, and the shadows moved spheres cast, lag by up to max_history samples.
+ * A changed radius, material or emission is not detected.  Sky pixels have no history.
+ * MEASURED, in numpy on a CPU before any kernel existed (the prototype; tests/test_reproject_cpu.py holds the restatement), with frames of this
+ * project's oracle alone: 96x96, the camera's origin moved sideways by 2 % of its distance to the target, S at 16 passes of seed stream 1 from the
+ * old origin, D at 2 passes of stream 2 from the new one, truth 1024 oracle passes of the new origin, PSNR over 8-bit channels packed by
+ * clip ** (1 / 2.2) * 255 + .5, the defaults k_pos 4, max_history 64; dB:
+ *     scene                      D alone     T        gain      hit pixels without history
+ *     cornell (18 records)        11.60      20.77    +9.17            2.09 %
+ *     Demo                        13.19      24.51   +11.32            0.94 %
+ * (rt_reproject_planes gives the prototype's figures to the last digit: the two agree bit for bit.)  Two passes of a path tracer are mostly noise,
+ * so sixteen older passes that lie within a pixel of the right place gain 9 to 11 dB; nothing there spoke against the defaults, and they were kept.
+ * tests/test_reproject_cpu.py asserts half of each gain with rt_reproject_planes itself, and less than twice the share without history on cornell.
+ * MEASURED on an MI355X by tools/reproject_probe.py (profiles/r27_reproject.jsonl; device time between two events, the device idle before the first,
+ * medians of 12; NO TIME IS PROMISED), the Demo scene, 800x600 / 1920x1080:  rt_reproject_async from S's colour plane 0.019 / 0.057 ms, from S's
+ * temporal plane 0.019 / 0.057 ms -- beside rt_features_async 0.010 / 0.021 ms and ONE pass 0.044 / 0.103 ms in the same run: a little over half
+ * a pass.  A lane asks for words 4-7 of FD (16 bytes; words 0-3 are not needed and not read), per tap words 4-7 of FS and 12 or 16 bytes of U, 12
+ * bytes of CD and two centres, and stores 20 bytes: 160 or 176 bytes a pixel, the taps of neighbouring pixels sharing their cache lines.  The quality
+ * table from rendered contexts, reprojected on the device: 11.60 -> 20.77 dB and 2.09 % (cornell), 13.19 -> 24.51 dB and 0.94 % (Demo): the
+ * prototype's figures to the last digit.                                                                                                          */
+typedef struct { float k_pos; float max_history; uint32_t reserved[2]; } rt_reproject_params;   /* 16 bytes; both finite and > 0, reserved 0 */
+
+/* {4.0f, 64.0f, {0, 0}}.  Needs no device.                                                                                      */
+RT_API void rt_reproject_defaults(rt_reproject_params *p);
+
+/* Rules 15-19 on `hip_stream`, without a host wait: src's history carried into dst's view and blended with dst's colour plane, into dst's temporal
+ * plane and its packed plane.  Ordered behind everything both contexts have queued, and their later work behind it, as rt_merge_async; a table
+ * rebuild that rt_update_spheres_async left pending on either context runs first, as in rt_features_async.  `p` == NULL means the defaults.
+ * One kernel, one lane per pixel over 8x8 tiles as rt_features_async's, no LDS; the centres are read from the two contexts' geometry tables at id.
+ * T is CURRENT from this call until something moves dst's colour plane -- a launch, a reset, rt_seed_stream_async, a written or loaded state, a merge
+ * or a filter into it -- or ends dst's feature plane: rt_set_scene, rt_update_spheres_async, rt_set_camera.
+ * RT_ERR_ARG: a null context, dst == src, contexts that differ in size or device, any multi-device or sharded context, k_pos or max_history not finite
+ * or <= 0, reserved words not 0.  RT_ERR_STATE: either feature plane not current, either context ragged, scenes that differ in record count, a src with
+ * neither a current temporal plane nor a pass.  A refused call changes nothing.                                                                   */
+RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_params *p, void *hip_stream);
+
+/* The context's temporal plane, 4 floats per pixel, into `rgbn_host`, and its packed plane, one word per pixel as rt_read_pixels lays them out, into
+ * `packed_host`; either may be NULL, not both.  Blocking.  RT_ERR_STATE when T is not current; RT_ERR_ARG for a null, multi-device or sharded
+ * context or two null buffers.                                                                                                                   */
+RT_API int rt_read_temporal(rt_ctx *ctx, float *rgbn_host, uint32_t *packed_host);
+
+typedef struct {                 /* one side of the host statement */
+    const float *plane;          /* [h][w][channels], colour-plane row order; dst's may be NULL when its passes are 0 */
+    int channels;                /* 3 = a colour plane, every pixel at `passes`; 4 = a temporal plane (rgb, n).  dst: rgb are read, nd is `passes` */
+    int passes;
+    const float *feat;           /* [h][w][8], rt_features_planes' layout */
+    const rt_camera *cam;
+    const rt_sphere *spheres;    /* `count` records */
+} rt_reproject_view;
+
+/* Rules 15-19 as plain host loops into out_rgbn[h][w][4]: what the device is tested against bit for bit.  The output may not overlap the inputs.
+ * Needs no device.  RT_ERR_ARG: a null argument (a side's records may be null when count is 0), channels other than 3 or 4, negative passes, w or
+ * h < 1, parameters rt_reproject_async refuses.                                                                                                  */
+RT_API int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_reproject_view *src, uint32_t count, int w, int h,
+                               const rt_reproject_params *p);
+
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it
  * from the scene -- "rt_trace_parity_w1" (few spheres: one wavefront per workgroup), "..._coop_w1" / "..._coop"

@@ -28,7 +28,8 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_denoise_pair_async", "rt_denoise_pair_planes", "rt_read_filtered", "rt_compare_filtered_async", "rt_compare_filtered",
            "rt_render_converged_filtered", "rt_render_adaptive_filtered", "rt_denoise_pair_tiles_async", "rt_render_adaptive_filtered_tiles",
            "rt_guide_defaults", "rt_features_async", "rt_read_features", "rt_features_planes", "rt_set_denoise_guide",
-           "rt_denoise_guided_planes", "rt_denoise_pair_guided_planes"]
+           "rt_denoise_guided_planes", "rt_denoise_pair_guided_planes",
+           "rt_reproject_defaults", "rt_reproject_async", "rt_read_temporal", "rt_reproject_planes"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -80,6 +81,19 @@ class GuideParams(C.Structure):
 
     def as_dict(self):
         return {"k_albedo": float(self.k_albedo), "k_normal": float(self.k_normal), "k_depth": float(self.k_depth), "reserved": int(self.reserved)}
+
+
+class ReprojectParams(C.Structure):
+    """include/rt_api.h rt_reproject_params (16 bytes): k_pos, max_history, two reserved words (0)."""
+    _fields_ = [("k_pos", C.c_float), ("max_history", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {"k_pos": float(self.k_pos), "max_history": float(self.max_history), "reserved": [int(v) for v in self.reserved]}
+
+
+class ReprojectView(C.Structure):
+    """include/rt_api.h rt_reproject_view: one side of rt_reproject_planes."""
+    _fields_ = [("plane", C.c_void_p), ("channels", C.c_int), ("passes", C.c_int), ("feat", C.c_void_p), ("cam", C.c_void_p), ("spheres", C.c_void_p)]
 
 
 class _Scene(C.Structure):
@@ -178,6 +192,10 @@ def load_library(diag=False):
         "rt_set_denoise_guide": (i32, [vp, C.POINTER(GuideParams)]),
         "rt_denoise_guided_planes": (i32, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(DenoiseParams), C.POINTER(GuideParams)]),
         "rt_denoise_pair_guided_planes": (i32, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(DenoiseParams), C.POINTER(GuideParams)]),
+        "rt_reproject_defaults": (None, [C.POINTER(ReprojectParams)]),
+        "rt_reproject_async": (i32, [vp, vp, C.POINTER(ReprojectParams), vp]),
+        "rt_read_temporal": (i32, [vp, vp, vp]),
+        "rt_reproject_planes": (i32, [vp, C.POINTER(ReprojectView), C.POINTER(ReprojectView), u32, i32, i32, C.POINTER(ReprojectParams)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -568,6 +586,26 @@ class RtContext:
         """rt_set_denoise_guide: None switches the guide off; a GuideParams or a dict of fields laid over guide_defaults() switches it on."""
         self._check(self._lib.rt_set_denoise_guide(self._h, _guide_params(guide)))
 
+    # --- temporal reprojection (rt_reproject.hip) ---------------------------------------------------
+    def reproject_async(self, src, params=None, stream=None):
+        """rt_reproject_async: `src`'s history (its temporal plane while current, else its colour plane) carried into this context's view and
+        blended with this context's colour plane, into the temporal plane this context owns (read_temporal).  `params`: a ReprojectParams, a
+        dict of its fields over the defaults, or None for the defaults."""
+        self._check(self._lib.rt_reproject_async(self._h, src._h if src is not None else None, _reproject_params(params), C.c_void_p(stream or 0)))
+
+    def read_temporal(self, packed=True):
+        """rt_read_temporal: the temporal plane, float32 [h][w][4] (rgb, n) in the colour plane's row order, and -- packed=True -- its packed
+        plane, uint32 [h * w] as read_pixels() lays it out (row 0 = bottom)."""
+        rgbn = np.zeros((self.h, self.w, 4), np.float32)
+        px = np.zeros(self.h * self.w, np.uint32) if packed else None
+        self._check(self._lib.rt_read_temporal(self._h, _ptr(rgbn), _ptr(px) if packed else None))
+        return (rgbn, px) if packed else rgbn
+
+    @staticmethod
+    def reproject_defaults():
+        """rt_reproject_defaults (the module-level reproject_defaults)."""
+        return reproject_defaults()
+
     def read_filtered(self):
         """rt_read_filtered: the cross-filtered plane, float32 [3 * w * h] as read_colors() lays it out."""
         out = np.zeros(3 * self.w * self.h, np.float32)
@@ -750,6 +788,54 @@ def _guide_params(guide):
             raise ValueError("rt_guide_params has no field %r" % name)
         setattr(g, name, value)
     return C.byref(g)
+
+
+def reproject_defaults():
+    """rt_reproject_defaults: ReprojectParams {4.0, 64.0, {0, 0}}.  Needs no device."""
+    p = ReprojectParams()
+    load_library().rt_reproject_defaults(C.byref(p))
+    return p
+
+
+def _reproject_params(params):
+    """None (the library's defaults), a ReprojectParams, or a dict of fields laid over the defaults -> what the C call takes."""
+    if params is None or isinstance(params, ReprojectParams):
+        return C.byref(params) if params is not None else None
+    p = reproject_defaults()
+    for name, value in dict(params).items():
+        if name not in ("k_pos", "max_history"):
+            raise ValueError("rt_reproject_params has no field %r" % name)
+        setattr(p, name, value)
+    return C.byref(p)
+
+
+def reproject_planes(dst, src, w, h, params=None):
+    """rt_reproject_planes: rules 15-19 on HOST planes; returns the temporal plane, float32 [h][w][4].  `dst` and `src` are dicts, one per side:
+    plane ([h][w][3] as read_colors() returns it, or [h][w][4] as read_temporal() does; dst's may be None at passes 0), passes, feat ([h][w][8]),
+    cam (15 floats), spheres (records; both sides the same count).  Needs no device."""
+    keep, views = [], []
+    count = None
+    for side in (dst, src):
+        sph = as_spheres(side["spheres"])
+        if count is not None and len(sph) != count:
+            raise ValueError("the two sides hold %d and %d records" % (count, len(sph)))
+        count = len(sph)
+        cam = as_camera(side["cam"])
+        feat = np.ascontiguousarray(side["feat"], dtype=np.float32).reshape(-1)
+        if feat.size != 8 * w * h:
+            raise ValueError("a feature plane of %d floats, got %d" % (8 * w * h, feat.size))
+        plane, channels = side.get("plane"), 3
+        if plane is not None:
+            plane = np.ascontiguousarray(plane, dtype=np.float32).reshape(-1)
+            if plane.size not in (3 * w * h, 4 * w * h):
+                raise ValueError("a plane of %d or %d floats, got %d" % (3 * w * h, 4 * w * h, plane.size))
+            channels = plane.size // (w * h)
+        keep += [sph, cam, feat, plane]
+        views.append(ReprojectView(plane.ctypes.data if plane is not None else None, channels, int(side["passes"]), feat.ctypes.data, cam.ctypes.data,
+                                   sph.ctypes.data if count else None))
+    out = np.zeros((h, w, 4), np.float32)
+    _check(load_library().rt_reproject_planes(_ptr(out), C.byref(views[0]), C.byref(views[1]), count, w, h, _reproject_params(params)))
+    return out
 
 
 def features_planes(spheres, cam, w, h):

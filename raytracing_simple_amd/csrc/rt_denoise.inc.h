@@ -1,6 +1,6 @@
 // rt_denoise.inc.h -- the NL-means device body the filter kernels share (include/rt_api.h, "denoising", "the error of the filtered frame", "feature
 // planes"): included by rt_denoise.hip, whose kernels filter by colour alone, and by rt_denoise_guided.hip, whose kernels add the guide of rules 13-14.
-// Two units, so that the code object of the first holds exactly the kernels it held before the guide existed, at the addresses they had.
+// (rt_reproject.hip includes it for the pack alone: dn_to_int, dn_finite3.)  Two units, so that the code object of the first holds exactly the kernels it held before the guide existed, at the addresses they had.
 // Both units are compiled with -ffp-contract=off: every multiply, add and IEEE division below is an operation of its own, in the written order.
 #pragma once
 

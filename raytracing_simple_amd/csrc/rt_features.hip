@@ -128,6 +128,7 @@ RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
     hipLaunchKernelGGL(rt_features_kernel, grid, dim3(kFtLanes), 0, stream, reinterpret_cast<float4 *>(c->scene.d_features), c->scene.tables.geom, c->scene.tables.emis, c->scene.tables.colr,
                        c->scene.tables.n_spheres, cam, c->w, c->h);
     HIP_TRY(hipGetLastError());
+    if (!c->scene.state.features_current) c->frame.features_reformed();     // (a temporal plane formed under the plane that ended stays ended)
     c->scene.state.features_formed();
     return RT_OK;
 }

@@ -456,3 +456,136 @@ int rt_features_planes(float *out, const rt_sphere *spheres, uint32_t count, con
 }
 
 }  // extern "C"
+
+// ---- rt_reproject_planes: temporal reprojection of include/rt_api.h ("temporal reprojection"), rules 15-19, as plain loops ----
+// rt_reproject_async forms the same words on the device (rt_reproject.hip) and is tested against this function bit for bit.
+namespace {
+
+inline float rp_dot(const float *a, const float *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// rule 10 at image pixel (x, y): the ray (o, d) of rt_features_planes, step for step
+inline void rp_ray(const rt_camera &cam, int x, int y, float inv_w, float inv_h, float o[3], float d[3]) {
+    const float kcx = ((float)x + 0.0f) * inv_w - 0.5f, kcy = ((float)y + 0.0f) * inv_h - 0.5f;
+    const float rx = cam.x.x * kcx + cam.y.x * kcy + cam.dir.x;
+    const float ry = cam.x.y * kcx + cam.y.y * kcy + cam.dir.y;
+    const float rz = cam.x.z * kcx + cam.y.z * kcy + cam.dir.z;
+    o[0] = 0.1f * rx + cam.orig.x, o[1] = 0.1f * ry + cam.orig.y, o[2] = 0.1f * rz + cam.orig.z;
+    const float f = 1.f / std::sqrt(rx * rx + ry * ry + rz * rz);
+    d[0] = rx * f, d[1] = ry * f, d[2] = rz * f;
+}
+
+}  // namespace
+
+extern "C" {
+
+void rt_reproject_defaults(rt_reproject_params *p) {
+    if (!p) return;
+    p->k_pos = 4.0f;
+    p->max_history = 64.0f;
+    p->reserved[0] = p->reserved[1] = 0;
+}
+
+// the parameter rules both entry points share (`p` == null: the defaults); hidden, like rt_host_denoise_params
+int rt_host_reproject_params(const rt_reproject_params *p, rt_reproject_params *out) {
+    rt_reproject_defaults(out);
+    if (p) *out = *p;
+    if (!std::isfinite(out->k_pos) || out->k_pos <= 0.f) return host_fail("rt_reproject: k_pos %g (finite, > 0)", (double)out->k_pos);
+    if (!std::isfinite(out->max_history) || out->max_history <= 0.f) return host_fail("rt_reproject: max_history %g (finite, > 0)", (double)out->max_history);
+    if (out->reserved[0] != 0 || out->reserved[1] != 0) return host_fail("rt_reproject: reserved %u, %u (0)", out->reserved[0], out->reserved[1]);
+    return RT_OK;
+}
+
+int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_reproject_view *src, uint32_t count, int w, int h,
+                        const rt_reproject_params *p) {
+    if (!out_rgbn || !dst || !src) return host_fail("rt_reproject_planes: null argument");
+    if (w < 1 || h < 1) return host_fail("rt_reproject_planes: %dx%d", w, h);
+    for (const rt_reproject_view *v : { dst, src }) {
+        const char *side = v == dst ? "dst" : "src";
+        if (v->channels != 3 && v->channels != 4) return host_fail("rt_reproject_planes: %s has %d channels (3 or 4)", side, v->channels);
+        if (v->passes < 0) return host_fail("rt_reproject_planes: %s holds %d passes", side, v->passes);
+        if (!v->feat || !v->cam || (count > 0 && !v->spheres)) return host_fail("rt_reproject_planes: %s has a null feature plane, camera or records", side);
+    }
+    if (!src->plane) return host_fail("rt_reproject_planes: src has a null plane");
+    if (!dst->plane && dst->passes != 0) return host_fail("rt_reproject_planes: dst has a null plane and %d passes", dst->passes);
+    rt_reproject_params q;
+    if (rt_host_reproject_params(p, &q) != RT_OK) return RT_ERR_ARG;
+
+    const rt_camera &camD = *dst->cam, &camS = *src->cam;
+    const float inv_w = 1.f / (float)w, inv_h = 1.f / (float)h, fw = (float)w, fh = (float)h;
+    const float sdir[3] = { camS.dir.x, camS.dir.y, camS.dir.z }, sx[3] = { camS.x.x, camS.x.y, camS.x.z }, sy[3] = { camS.y.x, camS.y.y, camS.y.z };
+    const float dd = rp_dot(sdir, sdir), xx = rp_dot(sx, sx), yy = rp_dot(sy, sy);
+    const float foot = std::sqrt(xx) * (1.f / (float)w);              // rule 17: a pixel's footprint per unit of distance
+    const float nd = (float)dst->passes;
+    const int cs = src->channels, cd = dst->channels;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t at = (size_t)(h - 1 - y) * (size_t)w + (size_t)x;
+            float sw = 0.0f, sn = 0.0f, sc[3] = { 0.0f, 0.0f, 0.0f };
+            // 15. the point and where it was
+            uint32_t id;
+            memcpy(&id, dst->feat + 8 * at + 7, sizeof id);
+            if (id < count) {                                         // (0xFFFFFFFF: the sky)
+                const float t = dst->feat[8 * at + 6];
+                float o[3], d[3], Pp[3], v[3];
+                rp_ray(camD, x, y, inv_w, inv_h, o, d);
+                const rt_vec3 &pd = dst->spheres[id].p, &ps = src->spheres[id].p;
+                const float m[3] = { pd.x - ps.x, pd.y - ps.y, pd.z - ps.z };
+                for (int c = 0; c < 3; ++c) Pp[c] = (o[c] + d[c] * t) - m[c];
+                // 16. where S saw it
+                v[0] = Pp[0] - camS.orig.x, v[1] = Pp[1] - camS.orig.y, v[2] = Pp[2] - camS.orig.z;
+                const float z = rp_dot(v, sdir);
+                if (z > 0.0f) {
+                    const float kx = (rp_dot(v, sx) * dd) / (z * xx), ky = (rp_dot(v, sy) * dd) / (z * yy);
+                    const float fx = (kx + 0.5f) * fw, fy = (ky + 0.5f) * fh;
+                    if (fx >= -1.0f && fx < fw && fy >= -1.0f && fy < fh) {
+                        const float x0 = std::floor(fx), y0 = std::floor(fy), ax = fx - x0, ay = fy - y0;
+                        // 17. the taps
+                        for (int j = 0; j < 2; ++j)
+                            for (int i = 0; i < 2; ++i) {
+                                const int qx = (int)x0 + i, qy = (int)y0 + j;
+                                const float b = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+                                if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                                const size_t aq = (size_t)(h - 1 - qy) * (size_t)w + (size_t)qx;
+                                uint32_t idq;
+                                memcpy(&idq, src->feat + 8 * aq + 7, sizeof idq);
+                                if (idq != id) continue;
+                                const float tq = src->feat[8 * aq + 6];
+                                float oq[3], dq[3], e[3];
+                                rp_ray(camS, qx, qy, inv_w, inv_h, oq, dq);
+                                for (int c = 0; c < 3; ++c) e[c] = (oq[c] + dq[c] * tq) - Pp[c];
+                                const float r = q.k_pos * (tq * foot);
+                                if (!(rp_dot(e, e) <= r * r)) continue;
+                                const float *u = src->plane + (size_t)cs * aq;
+                                const float un = cs == 4 ? u[3] : (float)src->passes;
+                                if (!std::isfinite(u[0]) || !std::isfinite(u[1]) || !std::isfinite(u[2]) || !(un > 0.0f)) continue;
+                                // 18. the history
+                                sw = sw + b;
+                                sn = sn + b * un;
+                                for (int c = 0; c < 3; ++c) sc[c] = sc[c] + b * u[c];
+                            }
+                    }
+                }
+            }
+            // 19. the blend
+            float *T = out_rgbn + 4 * at;
+            const float *CD = dst->passes != 0 ? dst->plane + (size_t)cd * at : nullptr;
+            if (!(sw > 0.0f)) {
+                for (int c = 0; c < 3; ++c) T[c] = CD ? CD[c] : 0.0f;
+                T[3] = nd;
+                continue;
+            }
+            float nh = sn / sw;
+            if (nh > q.max_history) nh = q.max_history;
+            if (!CD) {
+                for (int c = 0; c < 3; ++c) T[c] = sc[c] / sw;
+                T[3] = nh;
+                continue;
+            }
+            const float inv = 1.0f / (nd + nh);
+            for (int c = 0; c < 3; ++c) T[c] = (CD[c] * nd + (sc[c] / sw) * nh) * inv;
+            T[3] = nd + nh;
+        }
+    return RT_OK;
+}
+
+}  // extern "C"

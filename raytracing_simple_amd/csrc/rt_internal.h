@@ -212,6 +212,9 @@ struct rt_ctx {
     float *d_filtered = nullptr;        // rt_denoise_pair_async: this half filtered with the other half's weights, a plane like d_colors; acquired on first use.
                                         // Whether it is current is frame.filtered_pair
     uint32_t *d_filtered_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom): what rt_compare_filtered reads
+    float *d_temporal = nullptr;        // rt_reproject_async into this context (rt_reproject.hip): [h][w][4], rgb and the effective sample count, rows as d_colors;
+                                        // acquired on first use.  Whether it is current is frame.temporal_current together with scene.state.features_current
+    uint32_t *d_temporal_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom)
     void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; acquired on first use)
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters

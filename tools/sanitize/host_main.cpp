@@ -18,4 +18,26 @@ int main() {
     rt_compute_camera(&c, 800, 600);
     rt_sphere d[6]; printf("demo %d %d\n", rt_demo_scene(d, 6), rt_demo_scene(d, 2));
     printf("seed0 %u cam %g\n", seeds[0], c.x.x);
+    // temporal reprojection's host statement on planes of exactly the sizes it may touch: the Demo scene from two origins at sizes with partial
+    // tiles and 1x1, the source with 3 and with 4 floats a texel, the destination with and without a pass (a null colour plane)
+    for (int size = 0; size < 3; ++size) {
+        const int w = size == 0 ? 41 : size == 1 ? 70 : 1, h = size == 0 ? 23 : size == 1 ? 19 : 1;
+        rt_camera cs{}, cd{};
+        cs.orig = {20, 100, 120}; cs.target = {0, 25, 0};
+        cd.orig = {23, 100, 119}; cd.target = {0, 25, 0};
+        rt_compute_camera(&cs, w, h);
+        rt_compute_camera(&cd, w, h);
+        const size_t px = (size_t)w * h;
+        std::vector<float> fs(8 * px), fd(8 * px), u3(3 * px, 0.5f), u4(4 * px, 2.0f), cdp(3 * px, 0.25f), out(4 * px);
+        rt_features_planes(fs.data(), d, 6, &cs, w, h);
+        rt_features_planes(fd.data(), d, 6, &cd, w, h);
+        int ok = 0;
+        for (int ch = 3; ch <= 4; ++ch)
+            for (int nd = 0; nd <= 2; nd += 2) {
+                const rt_reproject_view dst{ nd ? cdp.data() : nullptr, 3, nd, fd.data(), &cd, d };
+                const rt_reproject_view src{ ch == 3 ? u3.data() : u4.data(), ch, 16, fs.data(), &cs, d };
+                ok += rt_reproject_planes(out.data(), &dst, &src, 6, w, h, nullptr) == RT_OK;
+            }
+        printf("reproject %dx%d: %d of 4 ok, n %g\n", w, h, ok, out[3]);
+    }
 }
