@@ -53,8 +53,11 @@ whole wavefront's pending rays and its LDS slots).  The hierarchy walk (rt_walk.
 THIS probe either, but its source under the fast flags is held ray by ray, closest-hit and shadow rays, by tests/walk_probe.hip
 (rt_walk.inc.h's own rays kernel, tests/test_gpu_fast_walk.py, tests/_walk_probe.py); the rotated candidate loop of
 RT_OPT_DIRECT_CAMERA (it calls hit_pre / hit_roots, which ARE probed, on a kernel-held list) and the walk as the shipped instances
-compile it are held for camera rays by the first-hit frames.  STILL OPEN: the REFR branch, coop_any's shadow decisions, and the
-shadow rays of the shipped kernels (an emitter ends the path of a first-hit frame before any light is sampled).
+compile it are held for camera rays by the first-hit frames.  The shadow rays of the shipped kernels -- sweep_any, coop_any's shared
+decisions, sweep_both, the walk's any-hit in its three table placements, and rt_div(numer, len * len) -- are held pixel by pixel and
+light by light by the shadow frames (tests/_shadow_frames.py, tests/test_gpu_fast_shadow.py: one white receiver, a red and a blue light,
+black occluders; sample_light64 below and scene64's max_t with an envelope are theirs), for the shadow rays of the FIRST diffuse hit.
+STILL OPEN: the REFR branch, and paths beyond the first diffuse hit (the bounce ray's own hit and everything after it).
 camera_direction, sample_light and next_random* take the generator's state by reference and are called with a state
 per lane; the host replays the generator exactly (integers).  The reflected direction is one open-coded expression,
 d - nrm * (2 dp); the probe restates that expression from the library's sub / scale."""
@@ -378,8 +381,12 @@ def scene64(p, max_t):
     """The sweeps' answers in binary64 and which rays the exclusion rule lets be compared.  p = pairs64(...).
     -> id, any_hit, id_decided: the closest hit, whether there is one, and whether every pair of the ray is decided and the winner leads
        every other hit by more than the two envelopes together;
-       first, first_decided: the first blocker closer than max_t (n: none); decided when the blocker and every record in front of it are."""
+       first, first_decided: the first blocker closer than max_t (n: none); decided when the blocker and every record in front of it are.
+    max_t: a binary32 array (exact), or an Err [R] whose envelope then counts towards every tie with it."""
     n = p["t"].shape[1]
+    max_env = 0.0
+    if isinstance(max_t, Err):                  # a bound the device formed itself (len - EPS of a shadow ray): its envelope widens every tie with it
+        max_t, max_env = max_t.v, max_t.e[:, None]
     max_t = max_t.astype(D)[:, None]
     with np.errstate(all="ignore"):
         ok = ~p["finite"] | (p["decided"] & (~p["hit"] | p["t_decided"]))      # (a non-finite record never hits: asserted apart)
@@ -393,7 +400,7 @@ def scene64(p, max_t):
         lo_others[rows, idx] = np.inf
         id_decided = ok.all(1) & (~any_hit | (hi[rows, idx] < lo_others.min(1)))
         blocks = hit & (p["t"] < max_t)
-        block_clear = ok & (~hit | (np.abs(p["t"] - max_t) > p["t_env"]))
+        block_clear = ok & (~hit | (np.abs(p["t"] - max_t) > p["t_env"] + max_env))
         first = np.where(blocks.any(1), np.argmax(blocks, 1), n)
         first_unclear = np.where((~block_clear).any(1), np.argmax(~block_clear, 1), n)
         first_decided = first_unclear > np.minimum(first, n - 1)
@@ -780,6 +787,25 @@ def shade32(what, rec, extra):
     return out
 
 
+def sample_light64(zc, u2, centre, rad, area, hp, nl, k):
+    """sample_light_drawn (rt_trace.inc.h) in binary64 with envelopes.  zc: Err (exact: a 2^-22 grid), u2: binary32 (exact), centre: three
+    columns, rad / area (lightA.w, lightB.w): binary32 arrays, hp / nl: three Err columns each -- exact records (shade64(4, ...)) or the
+    hit point and facing normal a kernel formed itself, WITH their envelopes (tests/_shadow_frames.py).
+    -> us, on (the sampled point), sd, len, wo, wi, numer (Err) and want (binary64's decision wo <= 0 and wi > 0)"""
+    inner = 1.0 - zc * zc
+    ring = Err(np.maximum(inner.v, 0.0), inner.e).sqrt(k.sqrt)
+    sn, cs = e_sincos(u2, k)
+    us = [ring * cs, ring * sn, zc]
+    centre = [Err.of(c) for c in centre]
+    on = [us[c] * Err(np.asarray(rad).astype(D)) + centre[c] for c in range(3)]
+    sd = [on[c] - hp[c] for c in range(3)]
+    length, inv = e_sqrt_and_rcp(e_dot(sd, sd), k)
+    sd = [c * inv for c in sd]
+    wo, wi = e_dot(sd, us), e_dot(sd, nl)
+    numer = (Err(np.asarray(area).astype(D)) * wi) * (-wo)
+    return {"us": us, "on": on, "sd": sd, "len": length, "wo": wo, "wi": wi, "numer": numer, "want": (wo.v <= 0) & (wi.v > 0)}
+
+
 def shade64(what, rec, extra, k):
     """-> (list of (label, column(s) of the output, Err), decisions): each output of the step with its envelope.  The bound of every line
     is the running error of the operations written on it (module docstring); `decisions` are (label, Err, threshold) of the quantities
@@ -830,17 +856,8 @@ def shade64(what, rec, extra, k):
             s0, s1, f1 = mwc_word(words[:, 5].copy(), words[:, 6].copy())
             s0, s1, f2 = mwc_word(s0, s1)
             zc, u2 = Err(3.0 - f1.astype(D)), (f2.astype(D) * 0.5 - 1.0).astype(F)    # exact (2^-22 / 2^-23 grids)
-            inner = 1.0 - zc * zc
-            ring = Err(np.maximum(inner.v, 0.0), inner.e).sqrt(k.sqrt)
-            sn, cs = e_sincos(u2, k)
-            us = [ring * cs, ring * sn, zc]
-            hp, nl = e_vec(rec[:, 7:10]), e_vec(rec[:, 10:13])
-            sd = [(us[c] * Err(rec[:, 3].astype(D)) + Err(rec[:, c].astype(D))) - hp[c] for c in range(3)]
-            length, inv = e_sqrt_and_rcp(e_dot(sd, sd), k)
-            sd = [c * inv for c in sd]
-            wo, wi = e_dot(sd, us), e_dot(sd, nl)
-            numer = (Err(rec[:, 4].astype(D)) * wi) * (-wo)
-            want = (wo.v <= 0) & (wi.v > 0)
+            q = sample_light64(zc, u2, e_vec(rec[:, 0:3]), rec[:, 3], rec[:, 4], e_vec(rec[:, 7:10]), e_vec(rec[:, 10:13]), k)
+            sd, length, numer, wo, wi, want = q["sd"], q["len"], q["numer"], q["wo"], q["wi"], q["want"]
             items = [("light direction", slice(1, 4), sd), ("light distance", 4, length), ("light numerator", 5, numer)]
             ties = [("far side of the light", wo, 0.0), ("light behind the surface", wi, 0.0)]
             extra = dict(extra, want=want)
