@@ -132,7 +132,7 @@ int wait_all(rt_ctx *c) {
 int refresh_pixels(rt_ctx *c, hipStream_t stream) {
     if (c->frame.pixels_current || c->frame.current_sample <= 0) return RT_OK;
     rt::LaunchParams p = make_params(c, 0);
-    hipError_t e = (c->mode == RT_MODE_FAST || c->mode >= 200) ? rt::launch_pack_fast(p, stream) : rt::launch_pack_parity(p, stream);
+    hipError_t e = c->knobs.fast() ? rt::launch_pack_fast(p, stream) : rt::launch_pack_parity(p, stream);
     if (e != hipSuccess) return fail(RT_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
     c->frame.pixels_packed();
     return RT_OK;
@@ -218,7 +218,7 @@ RT_API int rt_create_sharded(rt_ctx **out, int w, int h, int device, int rank, i
     rt_ctx *c = new (std::nothrow) rt_ctx();
     if (!c) return fail(RT_ERR_ALLOC, "host allocation failed");
     c->device = device;
-    c->n_cus = n_cus;
+    c->knobs.n_cus = n_cus;
     c->w = w;
     c->h = h;
     c->rank = rank;
@@ -385,7 +385,7 @@ RT_API int rt_set_mode(rt_ctx *c, int mode) {
 #endif
     if (!ok) return fail(RT_ERR_ARG, "mode %d", mode);
     if (c->multi) return rt::multi_set_mode(c, mode);
-    c->mode = mode;
+    c->knobs.mode = mode;
 #if RT_DIAGNOSTICS
     return rt::debug_layout_for_mode(c);        // (an A/B instance gets the pair table it reads: rt_debug.hip)
 #else

@@ -683,12 +683,12 @@ static int promote_top(rt_ctx *c, hipStream_t stream) {
     (void)stream;
     return RT_OK;           // (the arm that stages the promoted top lost its A/B: the product library promotes nothing)
 #else
-    if (!c->scene.state.has_hierarchy() || c->scene.bvh.n_leaves < 2 || c->bvh_top_pairs <= 0) return RT_OK;
+    if (!c->scene.state.has_hierarchy() || c->scene.bvh.n_leaves < 2 || c->knobs.bvh_top_pairs <= 0) return RT_OK;
     const uint32_t n_pairs = c->scene.bvh.n_leaves - 1u;
     const size_t used = rt::bvh_blob_float4s(c->scene.bvh.n_leaves, c->scene.bvh.n_slots);
     const size_t scratch4 = 4 * (size_t)n_pairs + ((size_t)n_pairs * 2 + 15) / 16 + 1;
     if (used + scratch4 > rt::bvh_blob_capacity(c->scene.cap)) return RT_OK;                   // (no room behind the blob: the tree stays as it is, nothing is staged)
-    uint32_t top = std::min<uint32_t>((uint32_t)c->bvh_top_pairs, rt::kBvhTopPairs);
+    uint32_t top = std::min<uint32_t>((uint32_t)c->knobs.bvh_top_pairs, rt::kBvhTopPairs);
     if (const char *e = getenv("RT_TOP_PAIRS")) top = std::min<uint32_t>((uint32_t)atoi(e), 256u);       // (experiments: how much of the top is worth staging)
     if (top == 0u) return RT_OK;
     hipLaunchKernelGGL(rt_bvh_promote_kernel, dim3(1), dim3(1024), 0, stream, c->scene.d_bvh, c->scene.bvh.n_slots, c->scene.bvh.n_leaves, top, c->scene.d_bvh + used);
@@ -706,7 +706,7 @@ static int pack_pairs(rt_ctx *c, hipStream_t stream) {
     (void)stream;
     return RT_OK;           // (likewise: no product kernel reads a packed table)
 #else
-    if (!c->scene.state.has_hierarchy() || c->scene.bvh.n_leaves < 2 || c->bvh_packed == 0) return RT_OK;
+    if (!c->scene.state.has_hierarchy() || c->scene.bvh.n_leaves < 2 || c->knobs.bvh_packed == 0) return RT_OK;
     const uint32_t n_pairs = c->scene.bvh.n_leaves - 1u;
     const size_t used = rt::bvh_blob_float4s(c->scene.bvh.n_leaves, c->scene.bvh.n_slots);
     if (used + 2 + 2 * (size_t)n_pairs > rt::bvh_blob_capacity(c->scene.cap)) return RT_OK;
@@ -765,7 +765,7 @@ static int build_bvh_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, boo
     c->scene.state.hierarchy_voided();
     c->scene.bvh = {};
     if (full_upload) c->choice.uploading_without_estimate();     // (a device-resident update keeps the upload's estimate: Choice::tables_rebuilt decides when it is stale)
-    if (c->bvh_min <= 0 || n_total < (uint32_t)c->bvh_min || !c->scene.d_bvh) return RT_OK;
+    if (c->knobs.bvh_min <= 0 || n_total < (uint32_t)c->knobs.bvh_min || !c->scene.d_bvh) return RT_OK;
     {
         const int rc = mark_duplicates(c, n_total, stream);
         if (rc != RT_OK) return rc;
@@ -775,11 +775,11 @@ static int build_bvh_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, boo
     const uint8_t *d_dup = dups ? c->scene.d_dup : nullptr, *h_dup = dups ? c->scene.dup_stage.host() : nullptr;
     const rt_sphere *sph = c->scene.h_spheres.data();
     BvhPlan plan;
-    if (!bvh_plan(sph, n_total, h_dup, c->scene.state.n_dups, &plan) || plan.n_tree < (uint32_t)c->bvh_min) return RT_OK;
+    if (!bvh_plan(sph, n_total, h_dup, c->scene.state.n_dups, &plan) || plan.n_tree < (uint32_t)c->knobs.bvh_min) return RT_OK;
     const uint32_t n_tree = plan.n_tree, n_always = plan.n_always, n_leaves = (n_tree + rt::kBvhLeaf - 1) / rt::kBvhLeaf;
     // a full upload (rt_set_scene: the call blocks and the host has every record): the shape by surface area, on the host -- unless
     // the result does not fit the tables' allocation (ensure_scene_capacity) or the stack budget: then the shapes below
-    if (full_upload && c->bvh_sah == 1 && n_tree >= kSahMinTree && n_tree <= kSahMaxTree) {
+    if (full_upload && c->knobs.bvh_sah == 1 && n_tree >= kSahMinTree && n_tree <= kSahMaxTree) {
         BvhHostTree tree;
         if (!bvh_shape_by_area(sph, n_total, h_dup, plan, &tree)) return rt::fail(RT_ERR_STATE, "hierarchy: the split changed under the build");
         if (!tree.too_deep && tree.n_leaves() < rt::kBvhLeafRef && rt::bvh_blob_float4s(tree.n_leaves(), tree.n_slots()) <= rt::bvh_blob_capacity(c->scene.cap)) {
@@ -788,7 +788,7 @@ static int build_bvh_tables(rt_ctx *c, uint32_t n_total, hipStream_t stream, boo
         }
     }
     // device-resident updates, and uploads too large for the host to shape in passing: the shape by surface area, on the device
-    if (c->bvh_sah && n_tree >= kSahMinTree && n_tree <= kSahDeviceMaxTree) {
+    if (c->knobs.bvh_sah && n_tree >= kSahMinTree && n_tree <= kSahDeviceMaxTree) {
         const uint32_t n_pad = bvh_sort_pad(n_tree);
         uint32_t depth_cap = 1;
         while ((1u << depth_cap) < n_leaves) depth_cap += 1;

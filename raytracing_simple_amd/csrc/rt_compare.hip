@@ -149,7 +149,7 @@ int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles
     }
     const uint32_t *pa = what == Of::Frames ? frame_pixels(a) : a->d_filtered_px, *pb = what == Of::Frames ? frame_pixels(b) : b->d_filtered_px;
     const size_t items = (size_t)tile_row_count(a) * (size_t)((a->w + kCmpRun - 1) / kCmpRun);
-    const size_t blocks = std::min(items, (size_t)a->n_cus * 8);
+    const size_t blocks = std::min(items, (size_t)a->knobs.n_cus * 8);
     hipLaunchKernelGGL(rt_compare_kernel, dim3((unsigned)blocks), dim3(kCmpLanes), 0, stream, pa, pb, a->w, a->local_rows, reinterpret_cast<unsigned long long *>(result_dev), tiles_dev);
     HIP_TRY(hipGetLastError());
     return RT_OK;

@@ -150,13 +150,13 @@ RT_API int rt_debug_stage_tables(rt_ctx *c, int n_samples, int repeats) {
     if (rc != RT_OK) return rc;
     rc = chain(c, c->stream);
     if (rc != RT_OK) return rc;
-    const size_t lds_all = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, true, n_samples);
-    const int mat = lds_all <= (size_t)c->mat_lds_limit ? 1 : 0;
+    // (what the rule says of a plain sweep of this scene: whether the materials ride along, and the workgroup shape)
+    const rt::Shape shape = rt::pick_shape(c->knobs, scene_facts(c), n_samples, Form::Sweep);
+    const int mat = shape.mat_in_lds ? 1 : 0;
     const size_t lds = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, mat != 0, n_samples);
     if (lds > kLdsMax) return fail(RT_ERR_ARG, "tables of %zu B do not fit LDS", lds);
-    const bool coop = c->coop_min > 0 && c->scene.tables.n_spheres >= (uint32_t)c->coop_min;
-    const bool w1 = lds + (coop ? 1536u : 256u) <= 6 * 1024;
-    const int tile_w = w1 ? 8 : 32;
+    const bool w1 = shape.waves == 1;
+    const int tile_w = rt::tile_width(shape.waves, 0);
     const dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), tile_row_count(c));
     uint32_t *sink = reinterpret_cast<uint32_t *>(c->order.d_tile_cost);    // (scratch: n_tiles >= 1024 words are not needed -- index & 1023 of a buffer that large)
     if (!sink || c->order.n_tiles < 1024) return fail(RT_ERR_ARG, "image too small for the probe");
@@ -187,13 +187,13 @@ RT_API const char *rt_debug_instance_name(int fast, int row) {
     return (row >= 0 && row < n) ? t[row].name : "";
 }
 
-static int dbg_set_gate(rt_ctx *c, int v) { c->regen_gate = v; return RT_OK; }
-static int dbg_set_matlds(rt_ctx *c, int v) { c->mat_lds_limit = v; return RT_OK; }
-static int dbg_set_persist(rt_ctx *c, int v) { c->persist = v ? 1 : 0; return RT_OK; }
-static int dbg_set_ncus(rt_ctx *c, int v) { c->n_cus = v; return RT_OK; }
-static int dbg_set_coop(rt_ctx *c, int v) { c->coop_min = v & 0xffffff; c->coop_kmax = v >> 24; c->choice.coop_threshold_set_by_hand(); return RT_OK; }     // (a threshold set by hand decides alone: no measurement)
-static int dbg_set_wg(rt_ctx *c, int v) { c->wg_waves = v; return RT_OK; }
-static int dbg_set_direct(rt_ctx *c, int v) { c->direct_max = v; return RT_OK; }
+static int dbg_set_gate(rt_ctx *c, int v) { c->knobs.regen_gate = v; return RT_OK; }
+static int dbg_set_matlds(rt_ctx *c, int v) { c->knobs.mat_lds_limit = v; return RT_OK; }
+static int dbg_set_persist(rt_ctx *c, int v) { c->knobs.persist = v ? 1 : 0; return RT_OK; }
+static int dbg_set_ncus(rt_ctx *c, int v) { c->knobs.n_cus = v; return RT_OK; }
+static int dbg_set_coop(rt_ctx *c, int v) { c->knobs.coop_min = v & 0xffffff; c->knobs.coop_kmax = v >> 24; c->choice.coop_threshold_set_by_hand(); return RT_OK; }     // (a threshold set by hand decides alone: no measurement)
+static int dbg_set_wg(rt_ctx *c, int v) { c->knobs.wg_waves = v; return RT_OK; }
+static int dbg_set_direct(rt_ctx *c, int v) { c->knobs.direct_max = v; return RT_OK; }
 static int dbg_set_order(rt_ctx *c, int v) { c->order.enable(v != 0); return RT_OK; }
 static int dbg_apply(rt_ctx *c, int (*fn)(rt_ctx *, int), int v) { return c->multi ? rt::multi_debug_each(c, fn, v) : fn(c, v); }
 
@@ -294,9 +294,9 @@ RT_API int rt_debug_read_tile_list(rt_ctx *c, uint32_t *list_out, uint32_t cap, 
 }
 // the hierarchy of large scenes: min_spheres = smallest tree that is built and used (0 = never), lds_limit = largest
 // LDS footprint it is used at (0 = keep).  Takes effect at once: the current scene's tables are rebuilt.
-static int dbg_set_bvh_lds(rt_ctx *c, int v) { if (v > 0) c->bvh_lds_limit = v; return RT_OK; }
+static int dbg_set_bvh_lds(rt_ctx *c, int v) { if (v > 0) c->knobs.bvh_lds_limit = v; return RT_OK; }
 static int dbg_set_bvh_min(rt_ctx *c, int v) {
-    c->bvh_min = v;
+    c->knobs.bvh_min = v;
     c->choice.knob_set();
     if (!c->scene.state.have_scene) return RT_OK;
     int rc = select_device(c);
@@ -307,23 +307,23 @@ static int dbg_set_bvh_min(rt_ctx *c, int v) {
     return rc != RT_OK ? rc : rt::build_bvh(c, c->scene.tables.n_spheres, c->stream, true);
 }
 static int dbg_set_tree_shape(rt_ctx *c, int v) {
-    c->bvh_sah = v < 0 ? 0 : (v > 2 ? 2 : v);
-    return dbg_set_bvh_min(c, c->bvh_min);          // (rebuilds the current scene's tables, undecided again)
+    c->knobs.bvh_sah = v < 0 ? 0 : (v > 2 ? 2 : v);
+    return dbg_set_bvh_min(c, c->knobs.bvh_min);          // (rebuilds the current scene's tables, undecided again)
 }
 // rt_set_mode of an A/B instance that reads a table the product's layout lacks -- ..._gt / _gtp the promoted top, _gq the packed pair table --
 // asks for it as rt_debug_set_bvh_layout would (kept for the context's later scenes) and rebuilds the current scene's tables at once.  Any
 // other instance leaves the layout as it is.  (bind_tables still refuses such an instance on a tree without its table: a layout set back to
 // 0 after the mode, a blob without room behind it.)
 extern "C++" int rt::debug_layout_for_mode(rt_ctx *c) {
-    if (c->mode < 100 || c->mode >= 200) return RT_OK;
+    if (!c->knobs.by_row() || c->knobs.fast()) return RT_OK;
     int n = 0;
-    const rt::Instance &inst = rt::parity_instances(&n)[c->mode - 100];
-    const bool top = inst.tables == rt::kTabPairsTopLds && c->bvh_top_pairs <= 0;
-    const bool packed = inst.tables == rt::kTabPairsPacked && c->bvh_packed == 0;
+    const rt::Instance &inst = rt::parity_instances(&n)[c->knobs.row()];
+    const bool top = inst.tables == rt::kTabPairsTopLds && c->knobs.bvh_top_pairs <= 0;
+    const bool packed = inst.tables == rt::kTabPairsPacked && c->knobs.bvh_packed == 0;
     if (!top && !packed) return RT_OK;
-    if (top) c->bvh_top_pairs = (int)rt::kBvhTopPairs;
-    if (packed) c->bvh_packed = 1;
-    return dbg_set_bvh_min(c, c->bvh_min);          // (rebuilds the current scene's tables)
+    if (top) c->knobs.bvh_top_pairs = (int)rt::kBvhTopPairs;
+    if (packed) c->knobs.bvh_packed = 1;
+    return dbg_set_bvh_min(c, c->knobs.bvh_min);          // (rebuilds the current scene's tables)
 }
 // The hierarchy's shape.  1 (default): by surface area -- uploads whose choice of form is estimated (below 1500 tree spheres) on the host,
 // larger uploads and every device-resident update on the device; 2: on the device for every upload too; 0: the fixed (halved) shape
@@ -332,8 +332,8 @@ RT_API int rt_debug_set_tree_shape(rt_ctx *c, int by_area) {
     if (!c) return fail(RT_ERR_ARG, "ctx is null");
     return dbg_apply(c, dbg_set_tree_shape, by_area);
 }
-static int dbg_set_top_pairs(rt_ctx *c, int v) { c->bvh_top_pairs = v; return RT_OK; }
-static int dbg_set_packed(rt_ctx *c, int v) { c->bvh_packed = v ? 1 : 0; return RT_OK; }
+static int dbg_set_top_pairs(rt_ctx *c, int v) { c->knobs.bvh_top_pairs = v; return RT_OK; }
+static int dbg_set_packed(rt_ctx *c, int v) { c->knobs.bvh_packed = v ? 1 : 0; return RT_OK; }
 // The pair table's layout for the A/B walks (rt_bvh.hip promote_top, pack_pairs): top_pairs > 0 promotes the top of the tree to the front of the
 // table, packed != 0 writes the packed pair table.  0, 0 (default) is the product library's layout.  Applies from the next build of the tables.
 RT_API int rt_debug_set_bvh_layout(rt_ctx *c, int top_pairs, int packed) {
@@ -342,16 +342,16 @@ RT_API int rt_debug_set_bvh_layout(rt_ctx *c, int top_pairs, int packed) {
     const int rc = dbg_apply(c, dbg_set_top_pairs, top_pairs);
     return rc != RT_OK ? rc : dbg_apply(c, dbg_set_packed, packed);
 }
-static int dbg_set_walk_gate(rt_ctx *c, int v) { if (v > 0) c->walk_gate = v; return RT_OK; }
-static int dbg_set_walk_round(rt_ctx *c, int v) { c->walk_round = v; return RT_OK; }
-static int dbg_set_walk_tail(rt_ctx *c, int v) { c->walk_tail = v; return RT_OK; }
+static int dbg_set_walk_gate(rt_ctx *c, int v) { if (v > 0) c->knobs.walk_gate = v; return RT_OK; }
+static int dbg_set_walk_round(rt_ctx *c, int v) { c->knobs.walk_round = v; return RT_OK; }
+static int dbg_set_walk_tail(rt_ctx *c, int v) { c->knobs.walk_tail = v; return RT_OK; }
 
 RT_API int rt_debug_set_walk_round(rt_ctx *c, int steps) {
     if (!c || steps < 1) return fail(RT_ERR_ARG, "steps %d", steps);
     return dbg_apply(c, dbg_set_walk_round, steps);
 }
 
-static int dbg_set_walk_forced(rt_ctx *c, int v) { c->walk_forced = v ? 1 : 0; c->choice.knob_set(); return RT_OK; }
+static int dbg_set_walk_forced(rt_ctx *c, int v) { c->knobs.walk_forced = v ? 1 : 0; c->choice.knob_set(); return RT_OK; }
 // rt_walk.inc.h: pair steps per lane per loop trip, ready lanes that make a wavefront shade (0 = keep either), and
 // forced: 0 = hierarchy or plain sweep by measurement (the library's behaviour), 1 = the hierarchy whenever the scene has one
 RT_API int rt_debug_set_walk(rt_ctx *c, int steps, int gate, int forced) {

@@ -91,8 +91,6 @@ namespace {
 
 std::atomic<uint64_t> g_pair_calls{0};                     // numbers the calls that make cross-filtered planes (FrameState::filtered_pair)
 
-bool packs_fast(const rt_ctx *c) { return c->mode == RT_MODE_FAST || c->mode >= 200; }     // which pack kernel refresh_pixels launches (rt_api.hip)
-
 dim3 frame_grid(const rt_ctx *c) { return dim3((unsigned)((c->w + kDnTileW - 1) / kDnTileW), (unsigned)((c->h + kDnTileH - 1) / kDnTileH)); }
 
 int launch_variance(float *var, const float *a, const float *b, int w, int h, hipStream_t stream) {
@@ -137,11 +135,11 @@ int filter_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t st
     if (rc == RT_OK && tiles && a->frame.group_list_is_stale()) rc = tiles_build_group_list(a, stream);
     if (rc == RT_OK) rc = launch_variance(a->d_denoise_var, a->d_colors, b->d_colors, a->w, a->h, stream);
     if (rc != RT_OK) return rc;
-    const DnPlanes<2> k{ { a->d_colors, b->d_colors }, { a->d_filtered, b->d_filtered }, { a->d_filtered_px, b->d_filtered_px }, { packs_fast(a), packs_fast(b) } };
+    const DnPlanes<2> k{ { a->d_colors, b->d_colors }, { a->d_filtered, b->d_filtered }, { a->d_filtered_px, b->d_filtered_px }, { a->knobs.fast(), b->knobs.fast() } };
     const size_t lds = dn_lds_bytes(2, q.search_radius, q.patch_radius);
     const float kk = q.k * q.k;
     if (a->have_guide) {                                    // (guide_refuse has passed: b holds the same, both feature planes are current)
-        const GuidedFilter f{ { a->d_colors, b->d_colors }, { a->d_filtered, b->d_filtered }, { a->d_filtered_px, b->d_filtered_px }, { packs_fast(a), packs_fast(b) },
+        const GuidedFilter f{ { a->d_colors, b->d_colors }, { a->d_filtered, b->d_filtered }, { a->d_filtered_px, b->d_filtered_px }, { a->knobs.fast(), b->knobs.fast() },
                               a->d_denoise_var, tiles ? a->tiles.d_groups : nullptr, tiles ? a->frame.counts[0] : 0u };
         rc = launch_guided_filter(2, f, a, q, stream);
     } else with_patch_radius(q.patch_radius, [&](auto P) {

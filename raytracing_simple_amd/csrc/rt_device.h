@@ -7,6 +7,7 @@
 
 #include "../../include/rt_api.h"
 #include "rt_bvh_layout.h"     // kBvhLeaf, kBvhLeafRef, the offsets into the hierarchy's blob
+#include "rt_instance.h"       // what an instance is (tables, role, flags), the LDS it needs, kMaxK2Table, kBvhTopPairs, kLdsMax: shared with the HIP-free rule
 
 namespace rt {
 
@@ -15,7 +16,6 @@ constexpr int kTileW = 32;          // block tile: 32 x 8 pixels, one 8x8 sub-ti
 constexpr int kTileH = 8;
 constexpr int kMaxDepth = 8;        // .cl:320 (depth > 7 ends the path)
 constexpr int kStatReplicas = 64;    // work counters are summed into 64 separate 64-byte lines
-constexpr int kMaxK2Table = 1024;   // running-average reciprocals kept in LDS up to this many passes per launch
 
 // Sphere tables in HBM, written once by rt_set_scene and staged into LDS by every workgroup.
 //   geom[i] = { p.x, p.y, p.z, rad*rad }      closest-hit / any-hit loops read only this
@@ -66,16 +66,6 @@ struct BvhTables {
                             // scene indices >> kBvhLowShift.  Half the bytes per pair step for the walk that reads its tables from HBM / L2
 };
 constexpr uint32_t kBvhLowShift = 2;        // (262 144 scene indices in 16 bits: a lower bound of the lowest index below a child prunes as safely as the index itself)
-constexpr uint32_t kBvhTopPairs = 255;      // eight full levels: 16 KiB of LDS beside the stacks, five workgroups per CU still fit
-// LDS of the instance that walks the pairs: hdr | pairs | slots | per-lane stacks (u16) for `threads` lanes
-inline size_t lds_bytes_pairs(uint32_t n_spheres, uint32_t n_lights, bool mat_in_lds, int n_samples, uint32_t n_leaves,
-                              uint32_t n_slots, uint32_t stack_depth, int threads) {
-    size_t b = (2 + 4 * (size_t)(n_leaves ? n_leaves - 1 : 0) + n_slots) * 16 + (size_t)n_lights * 32;
-    b += (((size_t)stack_depth * threads * 2) + 15) & ~(size_t)15;
-    if (mat_in_lds) b += (size_t)n_spheres * 32;
-    if (n_samples <= kMaxK2Table) b += (size_t)(n_samples > 0 ? n_samples : 0) * 4;
-    return (b + 15) & ~(size_t)15;
-}
 
 struct LaunchParams {
     SceneTables scene;
@@ -114,56 +104,13 @@ struct LaunchParams {
     int direct_max;
 };
 
-// LDS bytes the kernels need for a scene
-inline size_t lds_bytes(uint32_t n_spheres, uint32_t n_lights, bool mat_in_lds, int n_samples = 0) {
-    size_t b = (size_t)n_spheres * 16 + (size_t)n_lights * 32;
-    if (mat_in_lds) b += (size_t)n_spheres * 32;
-    if (n_samples <= kMaxK2Table) b += (size_t)(n_samples > 0 ? n_samples : 0) * 4;
-    return (b + 15) & ~(size_t)15;
-}
-
 // Final-frame pack kernels (rt_read_pixels): pixels[lrow*w + x] = toInt of the colour plane, with the
 // arithmetic of the mode that renders (.cl:34,594-596), for frames whose launches skipped the pixel store.
 hipError_t launch_pack_parity(const LaunchParams &p, hipStream_t stream);
 hipError_t launch_pack_fast(const LaunchParams &p, hipStream_t stream);
 
 // ---- the kernel instances ------------------------------------------------------------------------------
-// One row per instance, written next to the instantiations in rt_kernel_parity.hip / rt_kernel_fast.hip: what the
-// instance is and what it needs.  rt_launch.hip picks an instance by ROLE, sizes its LDS from `tables` and refuses a
-// launch whose instance needs a table the context does not have -- nothing in the host code depends on the order of
-// the rows.  The product library holds the shipped rows only; the diagnostics build (librt_hip_diag.so) adds the
-// A/B and verification instances (rt_set_mode 100 + row / 200 + row, or by name: rt_debug_instance).
-enum InstanceTables : uint8_t {
-    kTabSweepLds = 0,       // geometry + light tables staged in LDS (lds_bytes)
-    kTabSweepGlobal = 1,    // ... read where they lie in HBM / L2
-    kTabPairsLds = 2,       // the hierarchy (pairs, slots, stacks) staged in LDS (lds_bytes_pairs); needs BvhTables
-    kTabPairsGlobal = 3,    // ... pairs and slots read where they lie; staged: header and stacks; needs BvhTables
-    kTabPairsLdsSlotsGlobal = 4,   // ... the pairs staged, the slots read where they lie (the pairs fit the LDS budget, the whole tables do not)
-    kTabPairsTopLds = 5,    // ... pairs and slots read where they lie but for the promoted top of the tree (BvhTables::n_top pairs), which is staged
-    kTabPairsPacked = 6,    // ... the PACKED pair table (BvhTables::packed_at) and the slots read where they lie; staged: header, frame and stacks
-};
-// the instance walks a hierarchy: it needs the scene's BvhTables
-inline bool walks_hierarchy(uint8_t tables) {
-    return tables == kTabPairsLds || tables == kTabPairsGlobal || tables == kTabPairsLdsSlotsGlobal || tables == kTabPairsTopLds || tables == kTabPairsPacked;
-}
-enum InstanceRole : uint8_t {
-    kRoleNone = 0,          // diagnostics: reachable by row / name only
-    kRolePlain,             // small scenes
-    kRoleCoop,              // 12 spheres and more: cooperative any-hit
-    kRolePairs,             // large scenes through the hierarchy
-    kRolePairsGlobal,       // ... tables beyond the LDS budget
-    kRolePairsMixed,        // ... whose pairs still fit it (rt_trace_*_pairs_m)
-    kRoleSweepGlobal,       // no hierarchy (or it lost the measurement) and a table beyond the sweep's LDS budget (rt_internal.h sweep_lds_limit)
-    kRolePersist,           // diagnostics: persistent wavefronts (rt_debug_set_persist)
-    kRolePersistCoop,
-    kRoleTimelog,           // diagnostics: the shipped shape + device wall-clock logging
-};
-enum InstanceFlags : uint8_t {
-    kInstPersistent = 1,    // the grid only fills the machine; tiles come from the queue at counters[30]
-    kInstNoTileCost = 2,    // neither reads the heavy-first order nor leaves per-tile costs
-    kInstStaticCoop = 4,    // carries the cooperative any-hit mailbox (1.5 KiB of static LDS per wavefront)
-    kInstTwoRays = 8,       // diagnostics: two pixels per lane -- a wavefront's tile is 16 x 8, and every lane has two stacks
-};
+// One row per instance, written next to the instantiations in rt_kernel_parity.hip / rt_kernel_fast.hip (rt_instance.h: table kinds, roles, flags)
 struct Instance {
     void (*fn)(const LaunchParams);
     const char *name;       // the kernel's symbol: what rocprofv3 lists and rt_last_kernel returns

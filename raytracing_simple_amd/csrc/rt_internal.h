@@ -1,5 +1,5 @@
 // rt_internal.h -- what the translation units of the library share behind the C ABI: the context record and the records embedded in it
-// (Choice, TileOrder, FrameState, Owned, Scene), error reporting, acquisition of device resources into the context's record, page-locked
+// (Choice, TileOrder, FrameState, Owned, Scene, Knobs), error reporting, acquisition of device resources into the context's record, page-locked
 // staging (Staged), the frame's geometry said once, the checks and the blocking read several units share, and the hooks of the multi-device
 // context (rt_multi.hip).
 #pragma once
@@ -223,37 +223,10 @@ struct rt_ctx {
     rt_camera cam{};                    // a kernel argument (scene.state.have_cam)
     rt_guide_params guide{};            // rt_set_denoise_guide: what the filters of a pair of halves add to their weights ...
     bool have_guide = false;            // ... when it is on
-    // the hierarchy's knobs
-    int bvh_sah = 1;                    // the hierarchy's shape is chosen by surface area (rt_bvh.hip): 1 = uploads below kAlwaysWalkFrom tree spheres on the host,
-                                        // larger uploads and every device-resident update on the device; 2 = the device for uploads too; 0 = the fixed (halved) shape
-    int bvh_min = 56;                   // scenes with at least this many spheres inside the tree use it (0 = never)
-    int bvh_lds_limit = 31 * 1024;      // its tables are staged in LDS while five workgroups of that size fit a CU (2048 spheres: 6.2 ms from L2 with
-                                        // 4-5 waves per SIMD against 9.5 ms from LDS with two workgroups per CU); larger ones are read from HBM / L2
-    int bvh_top_pairs = 0;              // pairs promoted to the front of the table for the A/B walks that stage the top (rt_bvh.hip promote_top; diagnostics only,
-                                        // rt_debug_set_bvh_layout: 0 = none -- the product's layout, which keeps the builders' numbering)
-    int bvh_packed = 0;                 // the packed pair table behind the blob for the A/B walk that reads it (rt_bvh.hip pack_pairs; diagnostics only, 0 = none)
-    int bvh_mixed = 1;                  // tables beyond that limit whose PAIRS fit it: pairs staged, slots from HBM / L2 (rt_trace_*_pairs_m); diagnostics knob: 0 = everything from L2
-    int walk_gate = 16, walk_round = 4; // rt_walk.inc.h: ready lanes that make the wavefront shade; pair steps in a row before a leaf step
-                                        // (round 4, this kernel: 2 / 3 / 4 / 6 in a row = 5.42 / 5.37 / 5.22 / 5.45 ms on C3, profiles/r04k_walk_sweep.jsonl)
-    int walk_tail = 0;                  // lanes that may be left walking when a trip's walk phase ends (0 = none: every walk runs to its end within the trip)
-    int walk_forced = 0;                // 0 = measured choice (`choice` below); diagnostics: 1 = the hierarchy whenever the scene has one
     rt::Choice choice;                  // hierarchy or sweep, cooperative any-hit or not: the verdicts for this scene, the measurement behind them, the estimate (rt_choice.h)
     hipEvent_t probe_ev[4] = { nullptr, nullptr, nullptr, nullptr };       // ... and the measurement's events: arm a's timed step lies between probe_ev[2 * a] and probe_ev[2 * a + 1]
     rt::TileOrder order;                // heavy-first tile schedule (rt_tile_order.h; rt_trace.inc.h reads and writes its arrays)
-    // what a launch is made of besides (rt_launch.hip choose_instance): arithmetic mode, thresholds, diagnostics knobs
-    int wg_waves = 0;                   // diagnostics knob: 0 = automatic, 1 / 4 = force the workgroup shape
-    int mode = RT_MODE_PARITY;
-    int regen_gate = 0;                 // 0 = choose from the scene size
-    int mat_lds_limit = 24 * 1024;
-    int sweep_lds_limit = 40 * 1024;    // the plain / cooperative sweep stages its tables while four workgroups of that size fit a CU; beyond, the table is read through the
-                                        // scalar cache at six wavefronts per SIMD whatever its size (rt_trace_*_g).  Measured at 1080p on scenes without a hierarchy
-                                        // (profiles/r06_g_threshold.jsonl): at 48 KB (3 per CU) rt_trace_*_g takes 0.62 / 0.92 x the staged sweep's time (NaN records / a closed
-                                        // box of mirrors), at 64 KB (2) 0.41 / 0.63, at 96 KB and more (1) 0.19; at 32 KB (4) 0.80 / 1.12, below that 0.9 ... 1.3
-    int coop_kmax = 0;                  // cooperative any-hit only while no more than this many shadow rays are pending in the wavefront (0 = no limit)
-    int direct_max = 3;                 // RT_OPT_DIRECT_CAMERA: candidate spheres per tile up to which camera rays are resolved lane by lane (-1 = never; rt_debug_set_direct_camera)
-    int coop_min = 12;                  // scenes with at least this many spheres use the cooperative any-hit instance (0 = never)
-    int persist = 0;                    // diagnostics: persistent-wavefront instances
-    int n_cus = 256;
+    rt::Knobs knobs;                    // what a launch is made of besides: arithmetic mode, thresholds, the hierarchy's and the walk's knobs, diagnostics knobs (rt_instance.h)
     const char *last_kernel = "";       // symbol of the instance the last launch used
     unsigned long long debug_counters[24] = {};   // diagnostic instances only
     hipStream_t stream = nullptr;       // the context's own (non-blocking) stream
@@ -309,9 +282,9 @@ int read_back(rt_ctx *c, void *host, const void *dev, size_t bytes, bool wait = 
 int same_frame(const rt_ctx *a, const rt_ctx *b, const char *call, const char *a_name, const char *b_name, bool sharding = true);
 
 // ---- rt_launch.hip: one launch of the render kernel ----
-constexpr size_t kLdsMax = 152 * 1024;              // what the kernels' dynamic-LDS attribute allows
 LaunchParams make_params(rt_ctx *c, int n_samples);
 const Instance *instances(bool fast, int *count);
+SceneFacts scene_facts(const rt_ctx *c);            // what the rule that picks the instance (rt_instance.h) reads of the context's scene
 bool tables_fit_lds(const rt_ctx *c, int n_samples);
 void probe_poll(rt_ctx *c, bool wait);              // the verdict of the measurement in flight, if its events have completed (Choice::times_arrived)
 int refresh_tables(rt_ctx *c, hipStream_t stream);     // rt_scene.hip: tables and hierarchy from the records as they are now, if updates made them stale

@@ -1,5 +1,5 @@
 // rt_launch.hip -- what one launch of the render kernel is made of: which kernel instance (rt_device.h Instance: arithmetic mode x
-// role x workgroup shape), its tables and LDS, the scheduling data it runs with (heavy-first tile order) and, for scenes
+// role x workgroup shape; the rule that picks role and shape and sizes the LDS is rt_instance.h), its tables, the scheduling data it runs with (heavy-first tile order) and, for scenes
 // that have a hierarchy, whether it is walked or the plain sweep runs -- settled by a
 // surface-area estimate at rt_set_scene, by measurement inside the estimate's band (rt_choice.h holds the rules; launch() carries them out).
 #include <hip/hip_runtime.h>
@@ -75,16 +75,15 @@ rt::LaunchParams make_params(rt_ctx *c, int n_samples) {
     p.skip_pixels = c->pixel_write ? 0 : 1;
     p.inv_w = 1.f / (float)c->w;          // correctly rounded on the host as on the device (-ffp-contract=off, IEEE division)
     p.inv_h = 1.f / (float)c->h;
-    p.regen_gate = c->regen_gate > 0 ? c->regen_gate : (c->scene.tables.n_spheres <= 512 ? 8 : 1);
-    p.coop_kmax = c->coop_kmax;
-    p.direct_max = c->direct_max;
+    p.coop_kmax = c->knobs.coop_kmax;
+    p.direct_max = c->knobs.direct_max;
     p.tiles_x = (int)tiles_per_row(c);
     p.n_tiles = (int)tile_count(c);
     return p;
 }
 
 
-// ---- which instance, and what it needs (rt_device.h Instance; the rows live next to the instantiations) ----
+// ---- which instance, and what it needs (rt_device.h Instance; the rows live next to the instantiations; the rule is rt_instance.h) ----
 
 const rt::Instance *instances(bool fast, int *count) { return fast ? rt::fast_instances(count) : rt::parity_instances(count); }
 
@@ -97,78 +96,39 @@ static const rt::Instance *find_role(bool fast, int role, int waves) {
     return nullptr;
 }
 
-// LDS the hierarchy's staged tables take for this scene
-static size_t pairs_lds(const rt_ctx *c, bool mat, int n_samples, int waves = 4) {
-    return rt::lds_bytes_pairs(c->scene.tables.n_spheres, c->scene.tables.n_lights, mat, n_samples, c->scene.bvh.n_leaves, c->scene.bvh.n_slots, c->scene.bvh.stack_depth, 64 * waves);
+// what the rule (rt_instance.h) reads of the context's scene
+rt::SceneFacts scene_facts(const rt_ctx *c) {
+    rt::SceneFacts s;
+    s.n_spheres = c->scene.tables.n_spheres;
+    s.n_lights = c->scene.tables.n_lights;
+    s.has_hierarchy = c->scene.state.has_hierarchy();
+    s.n_leaves = c->scene.bvh.n_leaves;
+    s.n_slots = c->scene.bvh.n_slots;
+    s.stack_depth = c->scene.bvh.stack_depth;
+    s.n_top = c->scene.bvh.n_top;
+    s.packed_at = c->scene.bvh.packed_at;
+    return s;
 }
 
 // the plain sweep's tables (geometry and lights) fit LDS for this launch
-bool tables_fit_lds(const rt_ctx *c, int n_samples) {
-    return rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, false, n_samples) <= kLdsMax;
-}
-// ... and are staged there: while at least four workgroups of that size fit a CU.  Larger tables go through the scalar cache (rt_trace_*_g), which
-// keeps six wavefronts per SIMD at any size: a sweep over 96 KB of staged tables runs ONE workgroup per CU and takes five times as long (rt_internal.h)
-static bool sweep_stages_tables(const rt_ctx *c, int n_samples) {
-    return rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, false, n_samples) <= (size_t)(c->sweep_lds_limit < (int)kLdsMax ? c->sweep_lds_limit : (int)kLdsMax);
-}
+bool tables_fit_lds(const rt_ctx *c, int n_samples) { return rt::sweep_tables_fit(scene_facts(c), n_samples); }
 
-// the hierarchy's tables fit the LDS budget given to them; otherwise the walk reads them from HBM / L2
-static bool bvh_fits_lds(const rt_ctx *c, int n_samples) { return pairs_lds(c, false, n_samples) <= (size_t)c->bvh_lds_limit; }
-// ... or at least its PAIRS do (header | pairs | stacks): the chain of dependent fetches a walk consists of then stays in LDS
-static size_t pairs_only_lds(const rt_ctx *c, int n_samples, int waves = 4) {
-    return rt::lds_bytes_pairs(0, 0, false, n_samples, c->scene.bvh.n_leaves, 0, c->scene.bvh.stack_depth, 64 * waves);
-}
-static bool bvh_pairs_fit_lds(const rt_ctx *c, int n_samples) { return c->bvh_mixed != 0 && pairs_only_lds(c, n_samples) <= (size_t)c->bvh_lds_limit; }
-
-// the scene has a hierarchy and the context may use it
-static bool bvh_usable(const rt_ctx *c) { return c->scene.state.has_hierarchy() && c->wg_waves != 1 && c->persist == 0; }
-
-// What the instance needs from the context, checked against what the context has: the ONE place that sizes the
-// dynamic LDS and hands out the hierarchy.  An instance whose tables the context lacks is refused (RT_ERR_STATE),
+// What the instance needs from the context, checked against what the context has: the ONE place that hands out the hierarchy and
+// the dynamic LDS (sized by instance_lds).  An instance whose tables the context lacks is refused (RT_ERR_STATE),
 // whatever route selected it -- the measured choice, a forced form, or a diagnostics mode.
-static int bind_tables(rt_ctx *c, const rt::Instance &inst, int n_samples, rt::LaunchParams &p, size_t *lds_out) {
+static int bind_tables(rt_ctx *c, const rt::Instance &inst, const rt::SceneFacts &facts, int n_samples, rt::LaunchParams &p, size_t *lds_out) {
+    size_t lds = 0;
+    const int rc = rt::instance_lds(inst.tables, inst.waves, inst.flags, facts, p.mat_in_lds != 0, n_samples, &lds);
     p.bvh = rt::BvhTables{};
     if (rt::walks_hierarchy(inst.tables)) {
-        if (!c->scene.state.has_hierarchy() || !c->scene.bvh.blob)
-            return fail(RT_ERR_STATE, "%s walks a hierarchy and the scene has none (fewer than %d small spheres?)", inst.name, c->bvh_min);
+        if (rc == rt::kLdsNoHierarchy || !c->scene.bvh.blob)
+            return fail(RT_ERR_STATE, "%s walks a hierarchy and the scene has none (fewer than %d small spheres?)", inst.name, c->knobs.bvh_min);
         p.bvh = c->scene.bvh;
     }
-    size_t lds = 0;
-    switch (inst.tables) {
-        case rt::kTabSweepLds:
-            lds = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, p.mat_in_lds != 0, n_samples);
-            break;
-        case rt::kTabSweepGlobal:
-            p.mat_in_lds = 0;
-            lds = rt::lds_bytes(0, 0, false, n_samples);
-            break;
-        case rt::kTabPairsLds:
-            p.mat_in_lds = 0;               // (the walk reads a hit's material by slot from the hierarchy's blob: nothing of it is staged)
-            lds = pairs_lds(c, false, n_samples, inst.waves * ((inst.flags & rt::kInstTwoRays) ? 2 : 1));
-            break;
-        case rt::kTabPairsGlobal:
-            p.mat_in_lds = 0;
-            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, 1, 0, c->scene.bvh.stack_depth, 64 * inst.waves);
-            break;
-        case rt::kTabPairsLdsSlotsGlobal:
-            p.mat_in_lds = 0;
-            lds = pairs_only_lds(c, n_samples, inst.waves);
-            break;
-        case rt::kTabPairsPacked:           // header | the packed table's frame | stacks
-            if (c->scene.bvh.packed_at == 0 && c->scene.bvh.n_leaves >= 2)      // (a tree of one leaf has no pairs: the walk starts at the leaf and the frame is never used)
-                return fail(RT_ERR_STATE, "%s reads the packed pair table and this scene's hierarchy has none", inst.name);
-            p.mat_in_lds = 0;
-            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, 1, 0, c->scene.bvh.stack_depth, 64 * inst.waves) + 32;
-            break;
-        case rt::kTabPairsTopLds:           // header | the promoted top of the tree (n_top pairs = "n_top + 1 leaves") | stacks
-            if (c->scene.bvh.n_top == 0 && c->scene.bvh.n_leaves >= 2)          // (without a promoted top the root is not pair 0: rt_debug_set_bvh_layout asks for one)
-                return fail(RT_ERR_STATE, "%s stages the promoted top of the tree and this scene's hierarchy has none", inst.name);
-            p.mat_in_lds = 0;
-            lds = rt::lds_bytes_pairs(0, 0, false, n_samples, c->scene.bvh.n_top + 1, 0, c->scene.bvh.stack_depth, 64 * inst.waves);
-            break;
-        default:
-            return fail(RT_ERR_STATE, "%s: unknown table kind %d", inst.name, inst.tables);
-    }
+    if (rc == rt::kLdsNoPackedTable) return fail(RT_ERR_STATE, "%s reads the packed pair table and this scene's hierarchy has none", inst.name);
+    if (rc == rt::kLdsNoPromotedTop) return fail(RT_ERR_STATE, "%s stages the promoted top of the tree and this scene's hierarchy has none", inst.name);
+    if (rc == rt::kLdsUnknownKind) return fail(RT_ERR_STATE, "%s: unknown table kind %d", inst.name, inst.tables);
+    if (inst.tables != rt::kTabSweepLds) p.mat_in_lds = 0;      // (only the staged sweep takes the materials along)
 #if RT_DIAGNOSTICS
     if (const char *pad = getenv("RT_LDS_PAD")) lds += (size_t)atoi(pad);       // occupancy experiments: fewer workgroups per CU
 #endif
@@ -177,50 +137,23 @@ static int bind_tables(rt_ctx *c, const rt::Instance &inst, int n_samples, rt::L
     return RT_OK;
 }
 
-// Which instance renders a launch of `form`, and the launch parameters that go with the choice.  Reads the context, changes nothing, calls nothing of HIP.
-struct Chosen { const rt::Instance *inst = nullptr; int mat_in_lds = 0, regen_gate = 0; };      // (regen_gate 0: the context's, make_params)
-static int choose_instance(const rt_ctx *c, int n_samples, Form form, Chosen *out) {
-    const size_t lds_all = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, true, n_samples);
-    // materials ride along in LDS only while that keeps at least 6 workgroups per CU resident
-    // (160 KiB / 24 KiB); larger scenes read them from L2 once per hit
-    out->mat_in_lds = lds_all <= (size_t)c->mat_lds_limit;
-    const size_t lds_sweep = rt::lds_bytes(c->scene.tables.n_spheres, c->scene.tables.n_lights, out->mat_in_lds != 0, n_samples);
-
-    // which instance: arithmetic mode x role x workgroup shape.  Single-wavefront workgroups (8x8 tiles) keep the wave
-    // slots of a CU full (a 4-wavefront workgroup waits for four free slots at once) and give the heavy-first order a
-    // finer granule; each stages its own copy of the tables, so only while 24 copies fit a CU.
-    bool fast = c->mode == RT_MODE_FAST;
-    const bool coop = form == Form::SweepCoop ? true : (form == Form::SweepPlain ? false : (c->coop_min > 0 && c->scene.tables.n_spheres >= (uint32_t)c->coop_min));
-    const bool w1 = c->wg_waves == 1 || (c->wg_waves == 0 && lds_sweep + (coop ? 1536u : 256u) <= 6 * 1024);   // + the instance's static LDS
-    int role = coop ? rt::kRoleCoop : rt::kRolePlain, waves = w1 ? 1 : 4;
-    if (!sweeps(form) && bvh_usable(c)) {
-        // large scenes: the walk over the hierarchy, from LDS while its tables leave room for five workgroups per CU
-        role = bvh_fits_lds(c, n_samples) ? rt::kRolePairs : (bvh_pairs_fit_lds(c, n_samples) ? rt::kRolePairsMixed : rt::kRolePairsGlobal);
-        waves = 4;
-        if (c->regen_gate <= 0) out->regen_gate = c->walk_gate;
-    } else if (!sweep_stages_tables(c, n_samples)) {
-        // no hierarchy (or it lost the measurement) and a table beyond the sweep's LDS budget: the plain sweep over the table in HBM / L2
-        role = rt::kRoleSweepGlobal;
-        waves = 4;
-    }
+// Which instance renders a launch of `form`: the row of the shape the rule picks (rt_instance.h pick_shape), or -- diagnostics -- the row the mode names.
+// Reads the context, changes nothing, calls nothing of HIP.
+static int choose_instance(const rt_ctx *c, const rt::Shape &shape, const rt::Instance **out) {
+    const rt::Knobs &k = c->knobs;
     const rt::Instance *inst = nullptr;
 #if RT_DIAGNOSTICS
-    if (c->persist != 0 && c->mode < 100) {
-        role = coop ? rt::kRolePersistCoop : rt::kRolePersist;
-        waves = 4;
-    } else if (c->mode >= 100) {           // a row of the table by number (rt_set_mode checked the range)
-        fast = c->mode >= 200;
+    if (k.by_row()) {                       // a row of the table by number (rt_set_mode checked the range)
         int n = 0;
-        const rt::Instance *t = instances(fast, &n);
-        inst = &t[c->mode - (fast ? 200 : 100)];
+        inst = &instances(k.fast(), &n)[k.row()];
     }
 #endif
-    if (!inst) inst = find_role(fast, role, waves);
-    // (the product library ships no 4-wavefront PLAIN sweep: below 12 spheres the tables always fit the single-wavefront budget above; should a
+    if (!inst) inst = find_role(k.fast(), shape.role, shape.waves);
+    // (the product library ships no 4-wavefront PLAIN sweep: below 12 spheres the tables always fit the single-wavefront budget; should a
     // launch get here all the same, the cooperative instance of that shape renders any scene -- same bits, it only shares its shadow sweeps)
-    if (!inst && role == rt::kRolePlain) inst = find_role(fast, rt::kRoleCoop, waves);
-    if (!inst) return fail(RT_ERR_STATE, "this library holds no %s instance of role %d with %d wavefronts per workgroup", fast ? "fast" : "parity", role, waves);
-    out->inst = inst;
+    if (!inst && shape.role == rt::kRolePlain) inst = find_role(k.fast(), rt::kRoleCoop, shape.waves);
+    if (!inst) return fail(RT_ERR_STATE, "this library holds no %s instance of role %d with %d wavefronts per workgroup", k.fast() ? "fast" : "parity", shape.role, shape.waves);
+    *out = inst;
     return RT_OK;
 }
 
@@ -237,17 +170,17 @@ static int check_launch_args(const rt_ctx *c, int n_samples) {
 // takes its tiles from a subset launch's list, which an instance of a wider tile, or one that walks no list at all, cannot render.
 struct Prepared { const rt::Instance *inst = nullptr; rt::LaunchParams p{}; size_t lds = 0; };
 static int prepare_launch(rt_ctx *c, int n_samples, Form form, bool from_list, Prepared *out) {
-    Chosen chosen;
-    int rc = choose_instance(c, n_samples, form, &chosen);
-    if (rc != RT_OK) return rc;
-    const rt::Instance *inst = out->inst = chosen.inst;
+    const rt::SceneFacts facts = scene_facts(c);
+    const rt::Shape shape = rt::pick_shape(c->knobs, facts, n_samples, form);
+    RT_TRY(choose_instance(c, shape, &out->inst));
+    const rt::Instance *inst = out->inst;
     if (from_list && ((inst->flags & (rt::kInstTwoRays | rt::kInstPersistent | rt::kInstNoTileCost)) != 0 || (inst->waves != 1 && inst->waves != 4)))
         return fail(RT_ERR_STATE, "rt_render_tiles_async: %s does not render a 32x8 group from a tile list (a wider tile, or no list at all)", inst->name);
     out->p = make_params(c, n_samples);
-    out->p.mat_in_lds = chosen.mat_in_lds;
-    if (chosen.regen_gate) out->p.regen_gate = chosen.regen_gate;
-    out->p.walk_round = (c->walk_round & 0xff) | (c->walk_tail << 8);       // (one kernel argument: pair steps in a row | tail lanes << 8)
-    return bind_tables(c, *inst, n_samples, out->p, &out->lds);
+    out->p.mat_in_lds = shape.mat_in_lds ? 1 : 0;
+    out->p.regen_gate = shape.regen_gate;
+    out->p.walk_round = (c->knobs.walk_round & 0xff) | (c->knobs.walk_tail << 8);       // (one kernel argument: pair steps in a row | tail lanes << 8)
+    return bind_tables(c, *inst, facts, n_samples, out->p, &out->lds);
 }
 
 // The launch is queued: the frame has its passes, and the form choice knows what rendered them
@@ -269,11 +202,19 @@ static int persist_grid(rt_ctx *c, int n_tiles, size_t lds_use, hipStream_t stre
     size_t per_cu = lds_use > 0 ? (160 * 1024) / (lds_use + 6 * 1024) : 6;
     if (per_cu > 6) per_cu = 6;
     if (per_cu < 1) per_cu = 1;
-    size_t blocks = (size_t)c->n_cus * per_cu;
+    size_t blocks = (size_t)c->knobs.n_cus * per_cu;
     const size_t needed = ((size_t)n_tiles + 3) / 4;
     if (blocks > needed) blocks = needed;
     *grid = dim3((unsigned)blocks, 1, 1);
     HIP_TRY(hipMemsetAsync(c->d_counters + 30, 0, sizeof(unsigned long long), stream));
+    return RT_OK;
+}
+
+// the instance goes into `stream` -- or the launch is reported as failed
+static int queue_instance(const rt::Instance &inst, const rt::LaunchParams &p, dim3 grid, size_t lds, hipStream_t stream) {
+    const hipError_t e = rt::launch_instance(inst, p, grid, lds, stream);
+    if (e != hipSuccess)
+        return fail(RT_ERR_HIP, "kernel launch failed: %s (%s, grid %ux%u, lds %zu B)", hipGetErrorString(e), inst.name, grid.x, grid.y, lds);
     return RT_OK;
 }
 
@@ -291,7 +232,7 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, Form form, 
     rt::LaunchParams &p = prep.p;
     const size_t lds_use = prep.lds;
 
-    const int tile_w = 8 * inst->waves * ((inst->flags & rt::kInstTwoRays) ? 2 : 1);
+    const int tile_w = rt::tile_width(inst->waves, inst->flags);
     dim3 grid((unsigned)((c->w + tile_w - 1) / tile_w), tile_row_count(c));
     const uint32_t n_tiles = grid.x * grid.y;
     const rt::TileOrder::Plan plan = c->order.plan(n_tiles, n_samples, natural_order, (inst->flags & rt::kInstNoTileCost) == 0);
@@ -316,9 +257,7 @@ static int launch_form(rt_ctx *c, int n_samples, hipStream_t stream, Form form, 
         p.wavelog = ((size_t)grid.x * grid.y * 4 <= c->wavelog_cap) ? c->d_wavelog : nullptr;
     }
 #endif
-    const hipError_t e = rt::launch_instance(*inst, p, grid, lds_use, stream);
-    if (e != hipSuccess)
-        return fail(RT_ERR_HIP, "kernel launch failed: %s (%s, grid %ux%u, lds %zu B)", hipGetErrorString(e), inst->name, grid.x, grid.y, lds_use);
+    RT_TRY(queue_instance(*inst, p, grid, lds_use, stream));
     c->order.launched(plan, n_samples, n_tiles);
     after_launch(c, *inst, n_samples, nullptr);
     return RT_OK;
@@ -350,7 +289,8 @@ int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream) {
     rt::LaunchParams &p = prep.p;
     const size_t lds_use = prep.lds;
 
-    const uint32_t tiles_x = (uint32_t)((c->w + 8 * inst->waves - 1) / (8 * inst->waves)), tiles_y = tile_row_count(c);
+    const int tile_w = rt::tile_width(inst->waves, inst->flags);       // (8 per wavefront: prepare_launch refused the wider tile)
+    const uint32_t tiles_x = (uint32_t)((c->w + tile_w - 1) / tile_w), tiles_y = tile_row_count(c);
     const uint32_t n_launch = tiles_x * tiles_y;
     const uint32_t m = inst->waves == 4 ? frame.counts[0] : frame.counts[1];       // launch tiles kept: a group is one 32x8 tile, or the 8x8 tiles it covers
     dim3 grid(tiles_x, (m + tiles_x - 1) / tiles_x);
@@ -369,9 +309,7 @@ int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream) {
     }
     p.order = c->tiles.d_list;
     p.tile_cost = nullptr;
-    const hipError_t e = rt::launch_instance(*inst, p, grid, lds_use, stream);
-    if (e != hipSuccess)
-        return fail(RT_ERR_HIP, "kernel launch failed: %s (%s, grid %ux%u, lds %zu B)", hipGetErrorString(e), inst->name, grid.x, grid.y, lds_use);
+    RT_TRY(queue_instance(*inst, p, grid, lds_use, stream));
     if (!all) {
         rc = tiles_advance(c, n_samples, stream);           // (reads current_sample as it was: the count the selected groups come from)
         if (rc != RT_OK) return rc;
@@ -417,29 +355,14 @@ void probe_poll(rt_ctx *c, bool wait) {
     c->choice.times_arrived(a, b, c->scene.state.n_tree, c->scene.bvh.n_always);
 }
 
-// what Choice::next_launch is told of the context and its scene for a call of n_samples passes
-static rt::Choice::Facts choice_facts(const rt_ctx *c, int n_samples) {
-    rt::Choice::Facts f;
-    f.diagnostics = c->walk_forced != 0 || c->mode >= 100;
-    f.nothing_to_render = n_samples <= 0 || c->local_rows == 0 || !c->scene.state.renderable();     // (or the error: launch_form says which)
-    f.hierarchy = bvh_usable(c);
-    f.tables_fit = tables_fit_lds(c, n_samples);
-    f.n_tree = c->scene.state.n_tree;
-    f.n_always = c->scene.bvh.n_always;
-    f.n_spheres = c->scene.tables.n_spheres;
-    f.coop_min = c->coop_min;
-    f.wg_waves = c->wg_waves;
-    f.persist = c->persist;
-    return f;
-}
-
 int launch(rt_ctx *c, int n_samples, hipStream_t stream, bool may_block) {
     if (c->scene.state.tables_stale) {              // records updated on the device since the tables were built: build them now, once
         const int rc = refresh_tables(c, stream);
         if (rc != RT_OK) return rc;
     }
     using Next = rt::Choice::Next;
-    const rt::Choice::Facts facts = choice_facts(c, n_samples);
+    const rt::Choice::Facts facts = rt::choice_facts(c->knobs, scene_facts(c), n_samples, c->local_rows != 0 && c->scene.state.renderable(),
+                                                    c->scene.state.n_tree, c->scene.bvh.n_always);
     Next nx, prev;
     for (bool first = true;; first = false, prev = nx) {
         nx = c->choice.next_launch(facts, n_samples, may_block, first ? nullptr : &prev);

@@ -139,8 +139,6 @@ using namespace rt;
 
 namespace {
 
-bool packs_fast(const rt_ctx *c) { return c->mode == RT_MODE_FAST || c->mode >= 200; }     // which pack kernel refresh_pixels launches (rt_api.hip)
-
 // T is current: formed, the colour plane has not moved since, and the feature plane it was formed under has not ended
 bool temporal_current(const rt_ctx *c) { return c->frame.temporal_current && c->scene.state.features_current && c->d_temporal && c->d_temporal_px; }
 
@@ -189,7 +187,7 @@ RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_param
                        reinterpret_cast<const float4 *>(dst->scene.d_features), reinterpret_cast<const float4 *>(src->scene.d_features),
                        (const float *)dst->d_colors, (const float *)(from_temporal ? src->d_temporal : src->d_colors), dst->scene.tables.geom, src->scene.tables.geom,
                        dst->scene.tables.n_spheres, kernel_camera(dst->cam), kernel_camera(src->cam), q.k_pos, q.max_history, (float)dst->frame.current_sample,
-                       (float)src->frame.current_sample, dst->w, dst->h, packs_fast(dst) ? 1 : 0);
+                       (float)src->frame.current_sample, dst->w, dst->h, dst->knobs.fast() ? 1 : 0);
     HIP_TRY(hipGetLastError());
     dst->frame.reprojected();
     return RT_OK;

@@ -243,7 +243,7 @@ RT_API int rt_merge_async(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, void *hi
         if (used[k] != dst) rc = chain(used[k], stream);
     if (rc != RT_OK) return rc;
     const size_t n_floats = color_floats(dst);
-    size_t blocks = (n_floats / 4 + 255) / 256, cap = (size_t)dst->n_cus * 8;
+    size_t blocks = (n_floats / 4 + 255) / 256, cap = (size_t)dst->knobs.n_cus * 8;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(rt_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dst->d_colors, a, n_floats);

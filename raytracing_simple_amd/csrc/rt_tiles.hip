@@ -217,7 +217,7 @@ int merge_by_tile(rt_ctx *dst, rt_ctx *const *srcs, int n_srcs, int total, hipSt
     }
     if (rc != RT_OK) return rc;
     const size_t n_floats = color_floats(dst);
-    const size_t blocks = std::max<size_t>(1, std::min((n_floats + 255) / 256, (size_t)dst->n_cus * 8));
+    const size_t blocks = std::max<size_t>(1, std::min((n_floats + 255) / 256, (size_t)dst->knobs.n_cus * 8));
     hipLaunchKernelGGL(rt_merge_tiles_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dst->d_colors, t, dst->w, dst->h, n_floats);
     HIP_TRY(hipGetLastError());
     const uint32_t n_tiles = tile_count(dst);

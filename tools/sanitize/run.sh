@@ -3,8 +3,9 @@
 # available on this pool): the oracle's renderer, the product's host helpers (scene reader with
 # good, truncated and missing files, seed stream, camera basis), the hierarchy's host builders,
 # the record of a context's resources (rt_owned.h, with a recorder in owned_free's place), the
-# record of which form renders a scene (rt_choice.h, with a log in the launches' place) and the
-# record of what a context holds of its scene (rt_scene_state.h).
+# record of which form renders a scene (rt_choice.h, with a log in the launches' place), the
+# rule that says which kernel instance a launch gets (rt_instance.h) and the record of what a
+# context holds of its scene (rt_scene_state.h).
 # Run from the repository root.
 set -eu
 R=$(cd "$(dirname "$0")/../.." && pwd)
@@ -32,6 +33,9 @@ $T/owned_san
 # which form renders a scene (rt_choice.h alone), driven as rt_launch.hip drives it
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/choice_main.cpp -o $T/choice_san
 $T/choice_san
+# which kernel instance a launch gets (rt_instance.h alone): the thresholds from either side, the LDS of every table kind, recorded real scenes
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/instance_main.cpp -o $T/instance_san
+$T/instance_san
 # what a context holds of its scene (rt_scene_state.h alone), driven in the order the API's calls report to it
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/scene_main.cpp -o $T/scene_san
 $T/scene_san
