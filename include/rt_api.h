@@ -841,6 +841,94 @@ typedef struct {                 /* one side of the host statement */
 RT_API int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_reproject_view *src, uint32_t count, int w, int h,
                                const rt_reproject_params *p);
 
+/* ---- edge-avoiding wavelet filter for the frame the interactive loop shows ------------------------------
+ * The interactive loop of the section above ends in the temporal plane T, and nothing filtered it: the table there puts T at 20.8 dB (cornell) and
+ * 24.5 dB (Demo) against 1024 passes, and pixels without history are raw one- or two-pass noise.  The filters of "denoising" need two independent
+ * halves and cost five to eight interactive frames.  This section is an edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010;
+ * the spatial stage of Schied et al.'s SVGF, 2017): ONE plane, 25 taps per level, steered by the feature plane rt_reproject_async needs anyway and
+ * weighted by the sample count n that T carries.  Spheres make the geometry test exact: the scene index identifies the surface, and on a sphere the
+ * normal identifies the point, so depth is not needed.  THIS LIBRARY'S OWN EXTENSION: it reproduces no reference frame, touches no render kernel and
+ * changes no call above.
+ *
+ * THE ARITHMETIC, the same in rt_atrous_async's kernels and in rt_atrous_planes: all binary32, uncontracted, in the written order, IEEE division --
+ * ALWAYS parity's arithmetic, whatever rt_set_mode says.  All planes are in the colour plane's row order; neighbours are ARRAY neighbours.
+ * THE INPUT U has rgb and n per pixel: while the context's temporal plane is current U is that plane, otherwise its colour plane with
+ * n = (float)rt_current_sample at every pixel (rule 17's convention).  F is the context's feature plane: id = word 7 compared as uint32 (0xFFFFFFFF is
+ * an id like any other: sky filters with sky), N = words 3-5.
+ *  20. luminance and usability.  lum(c) = (0.2126f * c0 + 0.7152f * c1) + 0.0722f * c2.  A pixel is USABLE when its three colour words of U are finite
+ *      and its n > 0.0f.  Usability is judged on U once, for all levels.
+ *  21. the variance estimate V0.  s0 = s1 = s2 = 0.0f; dy = -1 .. 1 outer, dx = -1 .. 1 inner, q = p + (dx, dy): a q inside the image that is usable
+ *      and has id_q == id_p adds 1.0f to s0, l_q to s1 and l_q * l_q to s2, l_q = lum(U[q]).  s0 > 0.0f: m = s1 / s0, v = s2 / s0 - m * m,
+ *      V0[p] = v > 0.0f ? v : 0.0f.  Otherwise V0[p] = 0.0f.
+ *  22. one level takes (Ci, Vi) to (Ci+1, Vi+1) with step s = 1 << i; C0 = U's rgb.  hk = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f},
+ *      in = 1.0f / (k_normal * k_normal), kl2 = k_lum * k_lum.  A pixel that is not usable KEEPS its Ci and Vi words: it stays what it was and spreads
+ *      nowhere.  A usable p: lp = lum(Ci[p]), acc[c] = aw = av = 0.0f; taps j = -2 .. 2 outer, i = -2 .. 2 inner, q = p + s * (i, j).
+ *      The centre tap (i = j = 0) always counts, wgt = (0.375f * 0.375f) * n_p.  Any other tap counts only when q is inside the image (no clamping),
+ *      usable, and id_q == id_p; then a = N_p - N_q per component, gn = ((a0 * a0 + a1 * a1) + a2 * a2) * in; d = lp - lum(Ci[q]),
+ *      gl = (d * d) / (kl2 * (Vi[p] + Vi[q]) + 1e-10f); g = 0.0f, if (gn > g) g = gn, if (gl > g) g = gl (a NaN term constrains nothing, as in rule 13);
+ *      wgt = ((hk[j + 2] * hk[i + 2]) * (1.0f / (1.0f + g * (1.0f + g * 0.5f)))) * n_q.
+ *      Each counted tap, in tap order, adds wgt * Ci[q][c] to acc[c], wgt to aw and (wgt * wgt) * Vi[q] to av.
+ *      Ci+1[p][c] = acc[c] / aw, Vi+1[p] = av / (aw * aw); aw > 0 because the centre counts.
+ *  23. the levels i = 0 .. levels - 1 run in turn; the output plane A[h][w][4] is (C_levels, V_levels).  With levels = 0, A = (U's rgb, V0) bit for bit.
+ *  24. the packed plane: A's rgb words packed by the toInt of the context's mode, one uint32 per pixel in the PIXEL BUFFER's layout (row 0 = bottom),
+ *      exactly as rt_reproject_async packs T.
+ * WHAT THE FILTER DOES NOT DO: it never feeds back.  T, the colour plane, seeds, pass number, counters, selection, tile order and rt_last_kernel stay
+ * as they are; rt_reproject_async reads T, never A, so history stays unfiltered and no bias accumulates across frames.  A is a frame to show.
+ * LIMITS: the guidance is the FIRST hit's: inside a mirror or a glass sphere only the luminance test protects edges.  The variance estimate is spatial
+ * (3x3, one frame) and over-estimates on shadow edges, which it therefore softens.
+ * MEASURED, in numpy on a CPU before any kernel existed (the prototype; tests/test_atrous_cpu.py holds the restatement), in the set-up of the table of
+ * "temporal reprojection" (origin moved sideways by 2 %, S 16 passes of stream 1, D 2 passes of stream 2, truth 1024 oracle passes -- 512 at 192x192 --
+ * PSNR over 8-bit channels), T = rt_reproject_planes' output, "D alone" = D's colour plane with n = 2 everywhere, k_lum 1.5, k_normal 0.3; dB:
+ *     scene, size          T       T filtered, levels 1 / 2 / 3 / 4 / 5          D alone   D alone filtered, levels 3
+ *     cornell 96x96      20.77    25.07 / 26.72 / 27.13 / 27.22 / 27.26          11.60        21.57
+ *     Demo 96x96         24.51    27.50 / 27.64 / 27.16 / 26.70 / 26.36          13.19        23.05
+ *     simple 96x96       28.14    29.55 / 29.30 / 29.13 / 28.86 / 28.62          16.54        25.97
+ *     Demo 192x192       24.89    28.37 / 29.17 / 29.15 / 28.87 / 28.59          13.25        23.88
+ *     cornell 192x192    20.07    24.53 / 26.40 / 27.05 / 27.29 / 27.39          11.60        22.14
+ * With levels 0 the output is T bit for bit.  Diffuse scenes gain with every level; scenes of glass and mirrors peak at one or two, because inside a
+ * reflection only the luminance test protects edges and the spatial variance estimate is inflated there.  Three levels is the compromise and the default.
+ * tests/test_atrous_cpu.py asserts half of each gain at 96x96 with rt_atrous_planes itself.
+ * MEASURED on an MI355X by tools/atrous_probe.py (profiles/r30_atrous.jsonl; device time between two events, the device idle before the first,
+ * medians of 12; NO TIME IS PROMISED), the Demo scene, 800x600 / 1920x1080: rt_atrous_async from T with 1 / 3 / 5 levels 0.072 / 0.160 / 0.236 ms and
+ * 0.247 / 0.581 / 0.865 ms, from the colour plane 0.070 / 0.159 / 0.234 ms and 0.253 / 0.587 / 0.861 ms; with no level -- the preparation kernel
+ * alone -- 0.024 / 0.073 ms.  Beside it in the same run: ONE pass 0.042 / 0.093 ms, rt_features_async 0.010 / 0.020 ms, rt_reproject_async 0.018 /
+ * 0.054 ms, rt_denoise_async (two halves of one pass, the defaults) 0.253 / 0.839 ms.  So the default three levels cost 0.63 / 0.69 of rt_denoise_async
+ * and 2.3 / 3.5 times the interactive frame they filter (features, one pass, reprojection: 0.070 / 0.167 ms); one level 1.0 / 1.5 times.
+ * A level is 0.17 ms at 1920x1080 at steps 1 to 4 and 0.14 ms at steps 8 and 16: the time does not grow with the taps' spread, and by instruction count
+ * most of it is the rules' own arithmetic, 25 taps of two IEEE divisions each.
+ * The quality table from rendered contexts, filtered on the device: at 96x96 and 192x192 the prototype's figures above to the last digit.  At
+ * 800x600, which the prototype had not measured (truth 1024 passes):
+ *     Demo 800x600       25.87    30.67 / 32.54 / 33.00 / 33.05 / 32.94          14.04        25.63
+ *     cornell 800x600    20.99    25.58 / 27.92 / 28.89 / 29.30 / 29.51          11.76        22.90
+ * -- larger frames gain more (+7.1 and +7.9 dB at three levels) and peak later: a pixel's footprint shrinks, so more taps lie on its surface.  Quality
+ * has not been measured at 1920x1080.                                                                                                             */
+typedef struct { int32_t levels; float k_lum; float k_normal; uint32_t reserved; } rt_atrous_params;   /* 16 bytes; levels 0 .. 5, both k finite and > 0, reserved 0 */
+
+/* {3, 1.5f, 0.3f, 0}.  Needs no device.                                                                                          */
+RT_API void rt_atrous_defaults(rt_atrous_params *p);
+
+/* Rules 20-24 on `hip_stream`, without a host wait: the context's temporal plane while that is current, otherwise its colour plane, filtered into the
+ * (rgb, variance) plane A and its packed plane, which the context owns (allocated on first use with three working planes, freed by rt_destroy).  Ordered
+ * behind everything the context has queued, its later work behind the call.  `p` == NULL means the defaults.  One preparation kernel (rules 20-21) and
+ * one kernel per level, one lane per pixel.
+ * A is CURRENT from this call until anything that ends the temporal plane -- a launch, a reset, rt_seed_stream_async, a written or loaded state, a
+ * merge or a filter into the context, rt_set_scene, rt_update_spheres_async, rt_set_camera -- a new rt_reproject_async into the context, or a feature
+ * plane formed again where none was current.
+ * RT_ERR_ARG: a null, multi-device or sharded context, levels outside 0 .. 5, k_lum or k_normal not finite or <= 0, reserved not 0.  RT_ERR_STATE:
+ * the feature plane is not current, the context is ragged, there is neither a current temporal plane nor a pass.  A refused call changes nothing.  */
+RT_API int rt_atrous_async(rt_ctx *ctx, const rt_atrous_params *p, void *hip_stream);
+
+/* The filtered plane, 4 floats per pixel (rgb, variance) in the colour plane's row order, into `rgbv_host`, and its packed plane, one word per pixel as
+ * rt_read_pixels lays them out, into `packed_host`; either may be NULL, not both.  Blocking.  RT_ERR_STATE when A is not current; RT_ERR_ARG for a
+ * null, multi-device or sharded context or two null buffers.                                                                                     */
+RT_API int rt_read_atrous(rt_ctx *ctx, float *rgbv_host, uint32_t *packed_host);
+
+/* Rules 20-23 as plain host loops into out_rgbv[h][w][4]: what the device is tested against bit for bit.  `plane` is [h][w][channels]: 3 = a colour
+ * plane, every pixel at n = (float)passes; 4 = a temporal plane (rgb, n), `passes` not read.  `feat` is [h][w][8], rt_features_planes' layout.  The
+ * output may not overlap the inputs.  Needs no device.  RT_ERR_ARG: a null plane, channels other than 3 or 4, negative passes, w or h < 1, parameters
+ * rt_atrous_async refuses.                                                                                                                       */
+RT_API int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int passes, const float *feat, int w, int h, const rt_atrous_params *p);
+
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it
  * from the scene -- "rt_trace_parity_w1" (few spheres: one wavefront per workgroup), "..._coop_w1" / "..._coop"

@@ -46,6 +46,7 @@ UNITS = [
     ("rt_denoise_guided.hip", ["-ffp-contract=off"]),
     ("rt_features.hip", ["-ffp-contract=off"]),
     ("rt_reproject.hip", ["-ffp-contract=off"]),
+    ("rt_atrous.hip", ["-ffp-contract=off"]),
     ("rt_host.cpp", ["-ffp-contract=off"]),
     ("rt_bvh_host.cpp", ["-ffp-contract=off"]),
     ("rt_build_id.cpp", []),

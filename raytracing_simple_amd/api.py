@@ -29,7 +29,8 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_render_converged_filtered", "rt_render_adaptive_filtered", "rt_denoise_pair_tiles_async", "rt_render_adaptive_filtered_tiles",
            "rt_guide_defaults", "rt_features_async", "rt_read_features", "rt_features_planes", "rt_set_denoise_guide",
            "rt_denoise_guided_planes", "rt_denoise_pair_guided_planes",
-           "rt_reproject_defaults", "rt_reproject_async", "rt_read_temporal", "rt_reproject_planes"]
+           "rt_reproject_defaults", "rt_reproject_async", "rt_read_temporal", "rt_reproject_planes",
+           "rt_atrous_defaults", "rt_atrous_async", "rt_read_atrous", "rt_atrous_planes"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -94,6 +95,14 @@ class ReprojectParams(C.Structure):
 class ReprojectView(C.Structure):
     """include/rt_api.h rt_reproject_view: one side of rt_reproject_planes."""
     _fields_ = [("plane", C.c_void_p), ("channels", C.c_int), ("passes", C.c_int), ("feat", C.c_void_p), ("cam", C.c_void_p), ("spheres", C.c_void_p)]
+
+
+class AtrousParams(C.Structure):
+    """include/rt_api.h rt_atrous_params (16 bytes): levels (0 .. 5), k_lum, k_normal, a reserved word (0)."""
+    _fields_ = [("levels", C.c_int32), ("k_lum", C.c_float), ("k_normal", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"levels": int(self.levels), "k_lum": float(self.k_lum), "k_normal": float(self.k_normal), "reserved": int(self.reserved)}
 
 
 class _Scene(C.Structure):
@@ -196,6 +205,10 @@ def load_library(diag=False):
         "rt_reproject_async": (i32, [vp, vp, C.POINTER(ReprojectParams), vp]),
         "rt_read_temporal": (i32, [vp, vp, vp]),
         "rt_reproject_planes": (i32, [vp, C.POINTER(ReprojectView), C.POINTER(ReprojectView), u32, i32, i32, C.POINTER(ReprojectParams)]),
+        "rt_atrous_defaults": (None, [C.POINTER(AtrousParams)]),
+        "rt_atrous_async": (i32, [vp, C.POINTER(AtrousParams), vp]),
+        "rt_read_atrous": (i32, [vp, vp, vp]),
+        "rt_atrous_planes": (i32, [vp, vp, i32, i32, vp, i32, i32, C.POINTER(AtrousParams)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -606,6 +619,25 @@ class RtContext:
         """rt_reproject_defaults (the module-level reproject_defaults)."""
         return reproject_defaults()
 
+    # --- edge-avoiding wavelet filter (rt_atrous.hip) ----------------------------------------------
+    def atrous_async(self, params=None, stream=None):
+        """rt_atrous_async: this context's temporal plane while current, else its colour plane, through the a-trous levels into the filtered
+        plane this context owns (read_atrous).  `params`: an AtrousParams, a dict of its fields over the defaults, or None for the defaults."""
+        self._check(self._lib.rt_atrous_async(self._h, _atrous_params(params), C.c_void_p(stream or 0)))
+
+    def read_atrous(self, packed=True):
+        """rt_read_atrous: the filtered plane, float32 [h][w][4] (rgb, variance) in the colour plane's row order, and -- packed=True -- its packed
+        plane, uint32 [h * w] as read_pixels() lays it out (row 0 = bottom)."""
+        rgbv = np.zeros((self.h, self.w, 4), np.float32)
+        px = np.zeros(self.h * self.w, np.uint32) if packed else None
+        self._check(self._lib.rt_read_atrous(self._h, _ptr(rgbv), _ptr(px) if packed else None))
+        return (rgbv, px) if packed else rgbv
+
+    @staticmethod
+    def atrous_defaults():
+        """rt_atrous_defaults (the module-level atrous_defaults)."""
+        return atrous_defaults()
+
     def read_filtered(self):
         """rt_read_filtered: the cross-filtered plane, float32 [3 * w * h] as read_colors() lays it out."""
         out = np.zeros(3 * self.w * self.h, np.float32)
@@ -835,6 +867,39 @@ def reproject_planes(dst, src, w, h, params=None):
                                    sph.ctypes.data if count else None))
     out = np.zeros((h, w, 4), np.float32)
     _check(load_library().rt_reproject_planes(_ptr(out), C.byref(views[0]), C.byref(views[1]), count, w, h, _reproject_params(params)))
+    return out
+
+
+def atrous_defaults():
+    """rt_atrous_defaults: AtrousParams {3, 1.5, 0.3, 0}.  Needs no device."""
+    p = AtrousParams()
+    load_library().rt_atrous_defaults(C.byref(p))
+    return p
+
+
+def _atrous_params(params):
+    """None (the library's defaults), an AtrousParams, or a dict of fields laid over the defaults -> what the C call takes."""
+    if params is None or isinstance(params, AtrousParams):
+        return C.byref(params) if params is not None else None
+    p = atrous_defaults()
+    for name, value in dict(params).items():
+        if name not in ("levels", "k_lum", "k_normal"):
+            raise ValueError("rt_atrous_params has no field %r" % name)
+        setattr(p, name, value)
+    return C.byref(p)
+
+
+def atrous_planes(plane, feat, w, h, passes=0, params=None):
+    """rt_atrous_planes: rules 20-23 on HOST planes; returns the filtered plane, float32 [h][w][4] (rgb, variance).  `plane` is [h][w][3] as
+    read_colors() returns it, every pixel at `passes` samples, or [h][w][4] as read_temporal() does; `feat` is [h][w][8].  Needs no device."""
+    plane = np.ascontiguousarray(plane, dtype=np.float32).reshape(-1)
+    if plane.size not in (3 * w * h, 4 * w * h):
+        raise ValueError("a plane of %d or %d floats, got %d" % (3 * w * h, 4 * w * h, plane.size))
+    feat = np.ascontiguousarray(feat, dtype=np.float32).reshape(-1)
+    if feat.size != 8 * w * h:
+        raise ValueError("a feature plane of %d floats, got %d" % (8 * w * h, feat.size))
+    out = np.zeros((h, w, 4), np.float32)
+    _check(load_library().rt_atrous_planes(_ptr(out), _ptr(plane), plane.size // (w * h), int(passes), _ptr(feat), w, h, _atrous_params(params)))
     return out
 
 

@@ -37,6 +37,9 @@ struct FrameState {
     // Temporal reprojection (rt_reproject.hip): the temporal plane beside the colour plane was formed by rt_reproject_async and nothing has moved the
     // colour plane since.  The plane is CURRENT while this holds and the scene's feature plane is current too (SceneState::features_current)
     bool temporal_current = false;
+    // The edge-avoiding wavelet filter (rt_atrous.hip): the filtered plane was formed by rt_atrous_async from the temporal plane -- or, where none was
+    // current, from the colour plane -- and neither has moved since.  CURRENT while this holds and the scene's feature plane is current too
+    bool atrous_current = false;
 
     // at pass 0 the next launch would read the default stream (nothing but a custom stream or a written state puts another one there)
     bool on_default_stream() const { return seeds_default || !seeds_custom; }
@@ -83,9 +86,9 @@ struct FrameState {
     void group_list_built() { group_list_serial = selection_serial; }          // rt_denoise_pair_tiles_async: once per selection
 
     // ---- the colour plane written by something else than a launch: rt_read_pixels packs it ----
-    void merged(int total) { current_sample = total; have_selection = false; pixels_current = false; filtered_pair = filtered_behind = 0; temporal_current = false; }     // (a selection was made at another pass number)
+    void merged(int total) { current_sample = total; have_selection = false; pixels_current = false; filtered_pair = filtered_behind = 0; temporal_current = atrous_current = false; }     // (a selection was made at another pass number)
     void merged_by_tile(int total) { merged(total); ragged = true; list_valid = false; }                    // every tile by its own weights: dst's front has moved
-    void colours_replaced() { pixels_current = false; filtered_pair = filtered_behind = 0; temporal_current = false; }     // rt_denoise_async
+    void colours_replaced() { pixels_current = false; filtered_pair = filtered_behind = 0; temporal_current = atrous_current = false; }     // rt_denoise_async
     void pixels_packed() { pixels_current = true; }             // refresh_pixels
     // rt_denoise_pair_async: the cross-filtered plane beside the colour plane is current, until anything moves the colour plane (a launch, a reset,
     // a written state, a merge or a filter into it); nothing else of the frame changes
@@ -94,15 +97,18 @@ struct FrameState {
     void pair_tiles_refreshed(uint64_t call) { pair_filtered(call); }
     // rt_reproject_async into this context: its temporal plane is current, until anything moves the colour plane (the same events that end the
     // cross-filtered plane) or ends the feature plane (the scene's record); nothing else of the frame changes
-    void reprojected() { temporal_current = true; }
+    void reprojected() { temporal_current = true; atrous_current = false; }     // (a plane filtered from the temporal plane that was is not a filter of this one)
     // rt_features_async forms a feature plane where none was current: a temporal plane formed under the one that ended does not come back with it
-    void features_reformed() { temporal_current = false; }
+    void features_reformed() { temporal_current = atrous_current = false; }
+    // rt_atrous_async: the filtered plane is current, until any event that ends the temporal plane, a new reprojection into the context or a feature
+    // plane formed again; nothing else of the frame changes -- the filter feeds nothing back
+    void atrous_filtered() { atrous_current = true; }
 
 private:
     // every tile holds `pass` passes; a selection does not outlive that, and the launch count starts again
-    void restart(int pass) { current_sample = pass; launches = 0; last_ms = 0.0; ragged = have_selection = list_valid = false; filtered_pair = filtered_behind = 0; temporal_current = false; }
+    void restart(int pass) { current_sample = pass; launches = 0; last_ms = 0.0; ragged = have_selection = list_valid = false; filtered_pair = filtered_behind = 0; temporal_current = atrous_current = false; }
     // a launch has written every seed pair it renders: the default stream is no longer read in place
-    void advance(int n_samples) { current_sample += n_samples; launches += 1; seeds_default = false; filtered_pair = 0; temporal_current = false; }
+    void advance(int n_samples) { current_sample += n_samples; launches += 1; seeds_default = false; filtered_pair = 0; temporal_current = atrous_current = false; }
 };
 
 }  // namespace rt

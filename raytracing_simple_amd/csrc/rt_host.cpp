@@ -589,3 +589,133 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
 }
 
 }  // extern "C"
+
+// ---- rt_atrous_planes: the edge-avoiding wavelet filter of include/rt_api.h ("edge-avoiding wavelet filter"), rules 20-23, as plain loops ----
+// rt_atrous_async forms the same words on the device (rt_atrous.hip) and is tested against this function bit for bit.
+namespace {
+
+inline float at_lum(const float *c) { return (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2]; }
+
+}  // namespace
+
+extern "C" {
+
+void rt_atrous_defaults(rt_atrous_params *p) {
+    if (!p) return;
+    p->levels = 3;
+    p->k_lum = 1.5f;
+    p->k_normal = 0.3f;
+    p->reserved = 0;
+}
+
+// the parameter rules both entry points share (`p` == null: the defaults); hidden, like rt_host_reproject_params
+int rt_host_atrous_params(const rt_atrous_params *p, rt_atrous_params *out) {
+    rt_atrous_defaults(out);
+    if (p) *out = *p;
+    if (out->levels < 0 || out->levels > 5) return host_fail("rt_atrous: levels %d (0 .. 5)", out->levels);
+    if (!std::isfinite(out->k_lum) || out->k_lum <= 0.f) return host_fail("rt_atrous: k_lum %g (finite, > 0)", (double)out->k_lum);
+    if (!std::isfinite(out->k_normal) || out->k_normal <= 0.f) return host_fail("rt_atrous: k_normal %g (finite, > 0)", (double)out->k_normal);
+    if (out->reserved != 0) return host_fail("rt_atrous: reserved %u (0)", out->reserved);
+    return RT_OK;
+}
+
+int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int passes, const float *feat, int w, int h, const rt_atrous_params *p) {
+    if (!out_rgbv || !plane || !feat) return host_fail("rt_atrous_planes: null argument");
+    if (w < 1 || h < 1) return host_fail("rt_atrous_planes: %dx%d", w, h);
+    if (channels != 3 && channels != 4) return host_fail("rt_atrous_planes: %d channels (3 or 4)", channels);
+    if (passes < 0) return host_fail("rt_atrous_planes: %d passes", passes);
+    rt_atrous_params q;
+    if (rt_host_atrous_params(p, &q) != RT_OK) return RT_ERR_ARG;
+
+    const size_t px = (size_t)w * (size_t)h;
+    std::vector<float> other(q.levels > 0 ? 4 * px : 0), n(px);
+    std::vector<uint32_t> id(px);
+    std::vector<unsigned char> usable(px);
+    // the levels alternate between the two planes and end in the caller's
+    float *cur = q.levels % 2 == 0 ? out_rgbv : other.data(), *nxt = q.levels % 2 == 0 ? other.data() : out_rgbv;
+    // 20. usability, judged on U once; C0 = U's rgb
+    for (size_t at = 0; at < px; ++at) {
+        const float *u = plane + (size_t)channels * at;
+        n[at] = channels == 4 ? u[3] : (float)passes;
+        usable[at] = std::isfinite(u[0]) && std::isfinite(u[1]) && std::isfinite(u[2]) && n[at] > 0.0f;
+        memcpy(&id[at], feat + 8 * at + 7, sizeof(uint32_t));
+        memcpy(cur + 4 * at, u, 3 * sizeof(float));
+    }
+    // 21. the variance estimate
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t at = (size_t)y * (size_t)w + (size_t)x;
+            float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int qx = x + dx, qy = y + dy;
+                    if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                    const size_t aq = (size_t)qy * (size_t)w + (size_t)qx;
+                    if (!usable[aq] || id[aq] != id[at]) continue;
+                    const float l = at_lum(cur + 4 * aq);
+                    s0 = s0 + 1.0f;
+                    s1 = s1 + l;
+                    s2 = s2 + l * l;
+                }
+            float v0 = 0.0f;
+            if (s0 > 0.0f) {
+                const float m = s1 / s0, v = s2 / s0 - m * m;
+                v0 = v > 0.0f ? v : 0.0f;
+            }
+            cur[4 * at + 3] = v0;
+        }
+    // 22., 23. the levels
+    const float hk[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float in = 1.0f / (q.k_normal * q.k_normal), kl2 = q.k_lum * q.k_lum;
+    for (int level = 0; level < q.levels; ++level) {
+        const int s = 1 << level;
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const size_t at = (size_t)y * (size_t)w + (size_t)x;
+                const float *cp = cur + 4 * at;
+                if (!usable[at]) {                                   // stays what it was and spreads nowhere
+                    memcpy(nxt + 4 * at, cp, 4 * sizeof(float));
+                    continue;
+                }
+                const float lp = at_lum(cp);
+                const float *np = feat + 8 * at + 3;
+                float acc[3] = { 0.0f, 0.0f, 0.0f }, aw = 0.0f, av = 0.0f;
+                for (int j = -2; j <= 2; ++j)
+                    for (int i = -2; i <= 2; ++i) {
+                        const float *cq;
+                        float wgt;
+                        if (i == 0 && j == 0) {
+                            cq = cp;
+                            wgt = (0.375f * 0.375f) * n[at];
+                        } else {
+                            const long qx = (long)x + (long)s * i, qy = (long)y + (long)s * j;
+                            if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                            const size_t aq = (size_t)qy * (size_t)w + (size_t)qx;
+                            if (!usable[aq] || id[aq] != id[at]) continue;
+                            cq = cur + 4 * aq;
+                            const float *nq = feat + 8 * aq + 3;
+                            const float a0 = np[0] - nq[0], a1 = np[1] - nq[1], a2 = np[2] - nq[2];
+                            const float gn = ((a0 * a0 + a1 * a1) + a2 * a2) * in;
+                            const float d = lp - at_lum(cq);
+                            const float gl = (d * d) / (kl2 * (cp[3] + cq[3]) + 1e-10f);
+                            float g = 0.0f;
+                            if (gn > g) g = gn;
+                            if (gl > g) g = gl;
+                            wgt = ((hk[j + 2] * hk[i + 2]) * (1.0f / (1.0f + g * (1.0f + g * 0.5f)))) * n[aq];
+                        }
+                        for (int c = 0; c < 3; ++c) acc[c] = acc[c] + wgt * cq[c];
+                        aw = aw + wgt;
+                        av = av + (wgt * wgt) * cq[3];
+                    }
+                float *o = nxt + 4 * at;
+                for (int c = 0; c < 3; ++c) o[c] = acc[c] / aw;
+                o[3] = av / (aw * aw);
+            }
+        float *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -215,6 +215,12 @@ struct rt_ctx {
     float *d_temporal = nullptr;        // rt_reproject_async into this context (rt_reproject.hip): [h][w][4], rgb and the effective sample count, rows as d_colors;
                                         // acquired on first use.  Whether it is current is frame.temporal_current together with scene.state.features_current
     uint32_t *d_temporal_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom)
+    float *d_atrous = nullptr;          // rt_atrous_async (rt_atrous.hip): [h][w][4], the filtered rgb and its variance, rows as d_colors; acquired on first use, like
+                                        // the four below.  Whether it is current is frame.atrous_current together with scene.state.features_current
+    uint32_t *d_atrous_px = nullptr;    // ... and its rgb packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom)
+    float *d_atrous_tmp = nullptr;      // ... the other (rgb, variance) plane the levels alternate with
+    float *d_atrous_guide = nullptr;    // ... [h][w][4]: the normal and the scene index of the feature plane, one aligned texel
+    float *d_atrous_n = nullptr;        // ... [h][w]: the sample count of a usable pixel, +0.0f for one that is not (rule 20)
     void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; acquired on first use)
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters
@@ -265,6 +271,8 @@ inline size_t image_pixels(const rt_ctx *c) { return (size_t)c->w * (size_t)c->h
 inline size_t local_pixels(const rt_ctx *c) { return (size_t)c->local_rows * (size_t)c->w; }
 inline size_t color_floats(const rt_ctx *c) { return 3 * image_pixels(c); }
 inline uint32_t *frame_pixels(const rt_ctx *c) { return c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels; }     // the buffer launches write
+// the temporal plane (rt_reproject.hip) is current: formed, the colour plane has not moved since, and the feature plane it was formed under has not ended
+inline bool temporal_current(const rt_ctx *c) { return c->frame.temporal_current && c->scene.state.features_current && c->d_temporal && c->d_temporal_px; }
 
 // a reset or a written state ends a frame of the current scene for the form choice too (Choice::frame_ended): end_frame(c).reset_in_place()
 inline FrameState &end_frame(rt_ctx *c) { c->choice.frame_ended(); return c->frame; }

@@ -139,9 +139,6 @@ using namespace rt;
 
 namespace {
 
-// T is current: formed, the colour plane has not moved since, and the feature plane it was formed under has not ended
-bool temporal_current(const rt_ctx *c) { return c->frame.temporal_current && c->scene.state.features_current && c->d_temporal && c->d_temporal_px; }
-
 RpCamera kernel_camera(const rt_camera &m) { return RpCamera{ m.orig.x, m.orig.y, m.orig.z, m.dir.x, m.dir.y, m.dir.z, m.x.x, m.x.y, m.x.z, m.y.x, m.y.y, m.y.z }; }
 
 }  // namespace

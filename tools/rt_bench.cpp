@@ -5,7 +5,7 @@
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
 //            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]
-//             [--denoise [--denoise-radius R]] [--filtered [--live-checks]] [--guided]]
+//             [--denoise [--denoise-radius R]] [--filtered [--live-checks]] [--guided]] [--atrous [--atrous-levels N]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -32,6 +32,10 @@
 //   --live-checks       with --until-psnr DB --filtered --adaptive: every check after the first cross-filters only the groups that were just
 //                       rendered (rt_render_adaptive_filtered_tiles): the same render bit for bit; the printed PSNR sums every group's
 //                       figure of its own last check
+//   --atrous            the context the frame ends in -- the one context, or with --until-psnr the merged (and filtered) one -- forms its
+//                       feature plane and runs the edge-avoiding wavelet filter over its colour plane (rt_features_async, rt_atrous_async;
+//                       --atrous-levels N: 0 .. 5, default 3); --out is written from the filtered frame.  A further line gives the
+//                       parameters and the wall time of the two calls and the read-back.  Not with --gpus / --rehearse
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
@@ -49,6 +53,17 @@
 static int die(const char* what) {
     fprintf(stderr, "%s: %s\n", what, rt_last_error());
     return 1;
+}
+
+// --atrous: the feature plane, the filter, and the filtered frame's packed words into `px`; prints its line
+static int filter_atrous(rt_ctx* ctx, const rt_atrous_params& at, std::vector<uint32_t>& px) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (rt_features_async(ctx, rt_stream(ctx)) != RT_OK) return die("rt_features_async");
+    if (rt_atrous_async(ctx, &at, rt_stream(ctx)) != RT_OK) return die("rt_atrous_async");
+    if (rt_read_atrous(ctx, nullptr, px.data()) != RT_OK) return die("rt_read_atrous");
+    printf("{\"atrous\": true, \"levels\": %d, \"k_lum\": %.3f, \"k_normal\": %.3f, \"atrous_wall_ms\": %.4f}\n", at.levels, (double)at.k_lum,
+           (double)at.k_normal, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
 }
 
 static bool write_ppm(const std::string& path, const std::vector<uint32_t>& px, int w, int h) {
@@ -85,8 +100,11 @@ int main(int argc, char** argv) {
     bool filtered = false;      // --until-psnr judged on the cross-filtered halves: the *_filtered loops, then merge and filter
     bool guided = false;        // --denoise / --filtered under the guide's defaults: feature planes formed, rt_set_denoise_guide on both halves
     bool live_checks = false;   // --filtered --adaptive: rt_render_adaptive_filtered_tiles instead of rt_render_adaptive_filtered
+    bool atrous = false;        // --atrous: the frame --out is written from goes through rt_atrous_async first
     rt_denoise_params dn;
     rt_denoise_defaults(&dn);
+    rt_atrous_params at;
+    rt_atrous_defaults(&at);
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -115,6 +133,8 @@ int main(int argc, char** argv) {
         else if (a == "--filtered") filtered = denoise = true;
         else if (a == "--guided") guided = true;
         else if (a == "--live-checks") live_checks = true;
+        else if (a == "--atrous") atrous = true;
+        else if (a == "--atrous-levels") at.levels = atoi(next());
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -136,6 +156,10 @@ int main(int argc, char** argv) {
     }
     if (live_checks && !(until && filtered && adaptive)) {
         fprintf(stderr, "--live-checks is a form of the filtered adaptive loop: it needs --until-psnr DB --filtered --adaptive\n");
+        return 1;
+    }
+    if (atrous && (gpus > 1 || rehearse > 0 || oneshot > 0)) {
+        fprintf(stderr, "--atrous filters the frame of one context on one device: not with --gpus, --rehearse or --oneshot\n");
         return 1;
     }
 
@@ -220,6 +244,7 @@ int main(int argc, char** argv) {
         }
         if (!denoise && rt_read_pixels(frame, merged.data()) != RT_OK) return die("rt_read_pixels");
         const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (atrous && filter_atrous(frame, at, merged) != 0) return 1;
         if (!out.empty() && !write_ppm(out, merged, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
         printf("{\"spheres\": %u, \"w\": %d, \"h\": %d, \"until_psnr\": %.3f, \"reached\": %s, \"passes_per_half\": %d, \"merged_passes\": %d, "
                "\"checks\": %d, \"check_every\": %d, \"%s\": %.3f, \"differing\": %llu, \"max_abs\": %u, \"wall_ms\": %.4f}\n",
@@ -281,6 +306,7 @@ int main(int argc, char** argv) {
     double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     rt_stats st;
     if (rt_get_stats(ctx, &st) != RT_OK) return die("rt_get_stats");
+    if (atrous && filter_atrous(ctx, at, px) != 0) return 1;
     if (!out.empty() && !write_ppm(out, px, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
     if (!save_state.empty() && rt_save_state(ctx, save_state.c_str()) != RT_OK) return die("rt_save_state");
 

@@ -39,5 +39,13 @@ int main() {
                 ok += rt_reproject_planes(out.data(), &dst, &src, 6, w, h, nullptr) == RT_OK;
             }
         printf("reproject %dx%d: %d of 4 ok, n %g\n", w, h, ok, out[3]);
+        // the wavelet filter's host statement on the same planes: five levels put steps 8 and 16 beyond all three sizes in one direction or both
+        rt_atrous_params at;
+        rt_atrous_defaults(&at);
+        at.levels = 5;
+        int filtered = 0;
+        filtered += rt_atrous_planes(out.data(), u3.data(), 3, 16, fd.data(), w, h, &at) == RT_OK;
+        filtered += rt_atrous_planes(out.data(), u4.data(), 4, 0, fd.data(), w, h, &at) == RT_OK;
+        printf("atrous %dx%d: %d of 2 ok, v %g\n", w, h, filtered, out[3]);
     }
 }
