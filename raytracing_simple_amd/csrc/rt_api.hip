@@ -147,6 +147,17 @@ int read_back(rt_ctx *c, void *host, const void *dev, size_t bytes, bool wait) {
     return RT_OK;
 }
 
+int read_plane4(rt_ctx *c, const char *call, float *plane_host, uint32_t *packed_host, bool (*current)(const rt_ctx *), float *rt_ctx::*plane, uint32_t *rt_ctx::*packed,
+                const char *absent) {
+    int rc = tiles_refuse(c, call);
+    if (rc != RT_OK) return rc;
+    if (!plane_host && !packed_host) return fail(RT_ERR_ARG, "%s: both buffers are null", call);
+    if (!current(c)) return fail(RT_ERR_STATE, "%s: the context holds no current %s", call, absent);
+    if (plane_host) RT_TRY(read_back(c, plane_host, c->*plane, 4 * image_pixels(c) * sizeof(float), packed_host == nullptr));
+    if (packed_host) RT_TRY(read_back(c, packed_host, c->*packed, image_pixels(c) * sizeof(uint32_t)));
+    return RT_OK;
+}
+
 int same_frame(const rt_ctx *a, const rt_ctx *b, const char *call, const char *a_name, const char *b_name, bool sharding) {
     if (!a || !b) return fail(RT_ERR_ARG, "%s: %s is null", call, a ? b_name : a_name);
     if (a == b) return fail(RT_ERR_ARG, "%s: %s is %s itself", call, a_name, b_name);

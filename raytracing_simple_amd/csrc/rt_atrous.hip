@@ -21,29 +21,12 @@
 // about 0.13 ms.  Most of a level is the rules' own arithmetic, which staging would not shorten.
 #include <hip/hip_runtime.h>
 
-#include "rt_denoise.inc.h"     // dn_to_int, dn_finite3: the pack of rt_denoise_pair_async's planes
 #include "rt_internal.h"
+#include "rt_plane.inc.h"
 
 using rt::fail;
 
 extern "C" int rt_host_atrous_params(const rt_atrous_params *p, rt_atrous_params *out);     // rt_host.cpp: the parameter rules (null = defaults)
-
-namespace {
-
-constexpr int kAtTileW = 32, kAtTileH = 8, kAtLanes = kAtTileW * kAtTileH;     // a workgroup's pixels: four wavefronts, an 8x8 tile each, as rt_reproject_kernel's
-
-__device__ __forceinline__ float at_lum(float c0, float c1, float c2) { return (0.2126f * c0 + 0.7152f * c1) + 0.0722f * c2; }      // rule 20
-
-__device__ __forceinline__ uint32_t at_pack(float4 c, bool fast) { return dn_to_int(c.x, fast) | (dn_to_int(c.y, fast) << 8) | (dn_to_int(c.z, fast) << 16); }
-
-// U at array position `at`: rgb and n
-template <int kCh>
-__device__ __forceinline__ float4 at_input(const float *__restrict__ u, size_t at, float n_all) {
-    if constexpr (kCh == 4) return reinterpret_cast<const float4 *>(u)[at];
-    else return make_float4(u[3 * at], u[3 * at + 1], u[3 * at + 2], n_all);
-}
-
-}  // namespace
 
 // Rules 20-21, one lane per pixel; x and y are ARRAY coordinates (the colour plane's row order).  kCh: U holds 3 floats a pixel (the colour plane, every
 // pixel at `n_all` samples) or 4 (the temporal plane).  px is null unless levels == 0 (rule 24 on (U's rgb, V0)).  No LDS, no barrier: a lane outside
@@ -51,13 +34,12 @@ __device__ __forceinline__ float4 at_input(const float *__restrict__ u, size_t a
 // Bounds: the lane's own texel of U and F and its four stores at x < w && y < h; a neighbour's texel of U and word 7 of F only for 0 <= qx < w &&
 // 0 <= qy < h (the test stands before the loads); the packed word at row h - 1 - y < h.
 template <int kCh>
-__global__ void __launch_bounds__(kAtLanes) rt_atrous_prepare_kernel(float4 *__restrict__ out, float4 *__restrict__ guide, float *__restrict__ n_out, uint32_t *__restrict__ px,
-                                                                     const float *__restrict__ u, const float4 *__restrict__ feat, float n_all, int w, int h, int fast) {
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int x = (int)blockIdx.x * kAtTileW + wave * 8 + (lane & 7), y = (int)blockIdx.y * kAtTileH + (lane >> 3);
+__global__ void __launch_bounds__(kPlaneLanes) rt_atrous_prepare_kernel(float4 *__restrict__ out, float4 *__restrict__ guide, float *__restrict__ n_out, uint32_t *__restrict__ px,
+                                                                        const float *__restrict__ u, const float4 *__restrict__ feat, float n_all, int w, int h, int fast) {
+    const auto [x, y] = plane_pixel();
     if (x >= w || y >= h) return;
     const size_t at = (size_t)y * (size_t)w + (size_t)x;
-    const float4 up = at_input<kCh>(u, at, n_all);
+    const float4 up = plane_texel<kCh>(u, at, n_all);
     const float4 f_lo = feat[2 * at], f_hi = feat[2 * at + 1];
     const uint32_t id = __float_as_uint(f_hi.w);
     // rule 21
@@ -70,24 +52,19 @@ __global__ void __launch_bounds__(kAtLanes) rt_atrous_prepare_kernel(float4 *__r
             if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
             const size_t aq = (size_t)qy * (size_t)w + (size_t)qx;
             if (__float_as_uint(feat[2 * aq + 1].w) != id) continue;
-            const float4 uq = at_input<kCh>(u, aq, n_all);
-            if (!dn_finite3(uq.x, uq.y, uq.z) || !(uq.w > 0.0f)) continue;
-            const float l = at_lum(uq.x, uq.y, uq.z);
+            const float4 uq = plane_texel<kCh>(u, aq, n_all);
+            if (!rt::usable(uq.x, uq.y, uq.z, uq.w)) continue;
+            const float l = rt::luminance(uq.x, uq.y, uq.z);
             s0 = s0 + 1.0f;
             s1 = s1 + l;
             s2 = s2 + l * l;
         }
-    float v0 = 0.0f;
-    if (s0 > 0.0f) {
-        const float m = s1 / s0, v = s2 / s0 - m * m;
-        v0 = v > 0.0f ? v : 0.0f;
-    }
-    const bool usable = dn_finite3(up.x, up.y, up.z) && up.w > 0.0f;      // rule 20
-    const float4 c = make_float4(up.x, up.y, up.z, v0);
-    out[at] = c;
+    const float v0 = rt::variance_of_sums(s0, s1, s2);
+    const bool usable = rt::usable(up.x, up.y, up.z, up.w);      // rule 20
+    out[at] = make_float4(up.x, up.y, up.z, v0);
     guide[at] = make_float4(f_lo.w, f_hi.x, f_hi.y, f_hi.w);
     n_out[at] = usable ? up.w : 0.0f;
-    if (px) px[(size_t)(h - 1 - y) * (size_t)w + (size_t)x] = at_pack(c, fast != 0);
+    if (px) px[(size_t)(h - 1 - y) * (size_t)w + (size_t)x] = pack_rgb(up.x, up.y, up.z, fast != 0);
 }
 
 // Rule 22, one lane per pixel, 25 taps at step s.  `n` is the preparation kernel's plane: n > 0.0f says usable.  The tap rows run as a loop, the five
@@ -96,11 +73,10 @@ __global__ void __launch_bounds__(kAtLanes) rt_atrous_prepare_kernel(float4 *__r
 // same words as the host's `continue`.  px is null unless this is the last level (rule 24).  No LDS, no barrier.
 // Bounds: the lane's own texels and stores at x < w && y < h; a tap's texels at (cx, cy) = (qx, qy) clamped to [0, w - 1] x [0, h - 1]; qx and qy are
 // formed in 32 bits: |s * i| <= 32 and x < w <= 65535 (rt_create's limit); the packed word at row h - 1 - y < h.
-__global__ void __launch_bounds__(kAtLanes) rt_atrous_level_kernel(float4 *__restrict__ out, uint32_t *__restrict__ px, const float4 *__restrict__ in_cv,
-                                                                   const float4 *__restrict__ guide, const float *__restrict__ n, int s, float inv_kn2, float kl2,
-                                                                   int w, int h, int fast) {
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int x = (int)blockIdx.x * kAtTileW + wave * 8 + (lane & 7), y = (int)blockIdx.y * kAtTileH + (lane >> 3);
+__global__ void __launch_bounds__(kPlaneLanes) rt_atrous_level_kernel(float4 *__restrict__ out, uint32_t *__restrict__ px, const float4 *__restrict__ in_cv,
+                                                                      const float4 *__restrict__ guide, const float *__restrict__ n, int s, float inv_kn2, float kl2,
+                                                                      int w, int h, int fast) {
+    const auto [x, y] = plane_pixel();
     if (x >= w || y >= h) return;
     const size_t at = (size_t)y * (size_t)w + (size_t)x;
     const float4 cp = in_cv[at];
@@ -109,13 +85,13 @@ __global__ void __launch_bounds__(kAtLanes) rt_atrous_level_kernel(float4 *__res
     if (np > 0.0f) {
         const float4 gp = guide[at];
         const uint32_t id = __float_as_uint(gp.w);
-        const float lp = at_lum(cp.x, cp.y, cp.z);
+        const float lp = rt::luminance(cp.x, cp.y, cp.z);
         float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, aw = 0.0f, av = 0.0f;
 #pragma unroll 1
         for (int j = -2; j <= 2; ++j) {
             const int qy = y + s * j, cy = min(max(qy, 0), h - 1);
             const bool row_in = qy == cy;
-            const float hj = j == 0 ? 0.375f : (j == -1 || j == 1) ? 0.25f : 0.0625f;
+            const float hj = rt::atrous_tap(j);
             const size_t row = (size_t)cy * (size_t)w;
 #pragma unroll
             for (int i = -2; i <= 2; ++i) {
@@ -124,18 +100,11 @@ __global__ void __launch_bounds__(kAtLanes) rt_atrous_level_kernel(float4 *__res
                 const float nq = n[aq];
                 const float4 gq = guide[aq];
                 const float4 cq = in_cv[aq];
-                const float hi = i == 0 ? 0.375f : (i == -1 || i == 1) ? 0.25f : 0.0625f;
+                const float hi = rt::atrous_tap(i);
                 const bool centre = i == 0 && j == 0;
                 const bool counts = centre || (row_in && qx == cx && nq > 0.0f && __float_as_uint(gq.w) == id);
-                const float a0 = gp.x - gq.x, a1 = gp.y - gq.y, a2 = gp.z - gq.z;
-                const float gn = ((a0 * a0 + a1 * a1) + a2 * a2) * inv_kn2;
-                const float d = lp - at_lum(cq.x, cq.y, cq.z);
-                const float gl = (d * d) / (kl2 * (cp.w + cq.w) + 1e-10f);
-                float g = 0.0f;
-                if (gn > g) g = gn;
-                if (gl > g) g = gl;
-                // (hk[j + 2] * hk[i + 2] is exact: 3/8, 1/4 and 1/16 have two significant bits at most)
-                const float wgt = centre ? (0.375f * 0.375f) * np : ((hj * hi) * (1.0f / (1.0f + g * (1.0f + g * 0.5f)))) * nq;
+                const float g = rt::atrous_edge(gp.x, gp.y, gp.z, gq.x, gq.y, gq.z, inv_kn2, lp, rt::luminance(cq.x, cq.y, cq.z), cp.w, cq.w, kl2);
+                const float wgt = centre ? rt::atrous_centre_weight(np) : rt::atrous_tap_weight(hj, hi, g, nq);
                 if (counts) {
                     acc0 = acc0 + wgt * cq.x;
                     acc1 = acc1 + wgt * cq.y;
@@ -148,7 +117,7 @@ __global__ void __launch_bounds__(kAtLanes) rt_atrous_level_kernel(float4 *__res
         res = make_float4(acc0 / aw, acc1 / aw, acc2 / aw, av / (aw * aw));
     }
     out[at] = res;
-    if (px) px[(size_t)(h - 1 - y) * (size_t)w + (size_t)x] = at_pack(res, fast != 0);
+    if (px) px[(size_t)(h - 1 - y) * (size_t)w + (size_t)x] = pack_rgb(res.x, res.y, res.z, fast != 0);
 }
 
 using namespace rt;
@@ -168,8 +137,7 @@ RT_API int rt_atrous_async(rt_ctx *c, const rt_atrous_params *p, void *hip_strea
     if (rc != RT_OK) return rc;
     rt_atrous_params q;
     if (rt_host_atrous_params(p, &q) != RT_OK) return RT_ERR_ARG;
-    if (!c->scene.state.features_current || !c->scene.d_features)
-        return fail(RT_ERR_STATE, "%s: the feature plane is not current (rt_features_async forms it; rt_set_scene, rt_update_spheres_async and rt_set_camera end it)", call);
+    RT_TRY(features_refuse(c, call));
     if (c->frame.ragged) return fail(RT_ERR_STATE, "%s: the context is ragged (its tiles hold different pass counts)", call);
     const bool from_temporal = temporal_current(c);
     if (!from_temporal && c->frame.current_sample <= 0) return fail(RT_ERR_STATE, "%s: the context holds neither a current temporal plane nor a pass", call);
@@ -183,20 +151,20 @@ RT_API int rt_atrous_async(rt_ctx *c, const rt_atrous_params *p, void *hip_strea
     RT_TRY(ensure_device(c->owned, &c->d_atrous_n, pixels));
     hipStream_t stream = (hipStream_t)hip_stream;
     RT_TRY(chain(c, stream));           // behind everything the context has queued, its later work behind the call
-    const dim3 grid((unsigned)((c->w + kAtTileW - 1) / kAtTileW), (unsigned)((c->h + kAtTileH - 1) / kAtTileH));
+    const dim3 grid = plane_grid(c->w, c->h);
     const int fast = c->knobs.fast() ? 1 : 0;
     // the levels alternate between the two planes and end in d_atrous
     float4 *cur = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? c->d_atrous : c->d_atrous_tmp);
     float4 *nxt = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? c->d_atrous_tmp : c->d_atrous);
     float4 *const guide = reinterpret_cast<float4 *>(c->d_atrous_guide);
     const auto prepare = from_temporal ? rt_atrous_prepare_kernel<4> : rt_atrous_prepare_kernel<3>;
-    hipLaunchKernelGGL(prepare, grid, dim3(kAtLanes), 0, stream, cur, guide, c->d_atrous_n, q.levels == 0 ? c->d_atrous_px : (uint32_t *)nullptr,
+    hipLaunchKernelGGL(prepare, grid, dim3(kPlaneLanes), 0, stream, cur, guide, c->d_atrous_n, q.levels == 0 ? c->d_atrous_px : (uint32_t *)nullptr,
                        (const float *)(from_temporal ? c->d_temporal : c->d_colors), reinterpret_cast<const float4 *>(c->scene.d_features),
                        (float)c->frame.current_sample, c->w, c->h, fast);
     HIP_TRY(hipGetLastError());
     const float inv_kn2 = 1.0f / (q.k_normal * q.k_normal), kl2 = q.k_lum * q.k_lum;
     for (int level = 0; level < q.levels; ++level) {
-        hipLaunchKernelGGL(rt_atrous_level_kernel, grid, dim3(kAtLanes), 0, stream, nxt, level == q.levels - 1 ? c->d_atrous_px : (uint32_t *)nullptr, cur, guide,
+        hipLaunchKernelGGL(rt_atrous_level_kernel, grid, dim3(kPlaneLanes), 0, stream, nxt, level == q.levels - 1 ? c->d_atrous_px : (uint32_t *)nullptr, cur, guide,
                            (const float *)c->d_atrous_n, 1 << level, inv_kn2, kl2, c->w, c->h, fast);
         HIP_TRY(hipGetLastError());
         float4 *t = cur;
@@ -208,15 +176,9 @@ RT_API int rt_atrous_async(rt_ctx *c, const rt_atrous_params *p, void *hip_strea
 }
 
 RT_API int rt_read_atrous(rt_ctx *c, float *rgbv_host, uint32_t *packed_host) {
-    int rc = tiles_refuse(c, "rt_read_atrous");
-    if (rc != RT_OK) return rc;
-    if (!rgbv_host && !packed_host) return fail(RT_ERR_ARG, "rt_read_atrous: both buffers are null");
-    if (!atrous_current(c))
-        return fail(RT_ERR_STATE, "rt_read_atrous: the context holds no current filtered plane (rt_atrous_async forms one; whatever ends the temporal plane, a new "
-                                  "rt_reproject_async into the context or a feature plane formed again ends it)");
-    if (rgbv_host) RT_TRY(read_back(c, rgbv_host, c->d_atrous, 4 * image_pixels(c) * sizeof(float), packed_host == nullptr));
-    if (packed_host) RT_TRY(read_back(c, packed_host, c->d_atrous_px, image_pixels(c) * sizeof(uint32_t)));
-    return RT_OK;
+    return read_plane4(c, "rt_read_atrous", rgbv_host, packed_host, atrous_current, &rt_ctx::d_atrous, &rt_ctx::d_atrous_px,
+                       "filtered plane (rt_atrous_async forms one; whatever ends the temporal plane, a new rt_reproject_async into the context or a feature plane formed "
+                       "again ends it)");
 }
 
 }  // extern "C"

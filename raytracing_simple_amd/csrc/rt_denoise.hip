@@ -53,9 +53,9 @@ __global__ void __launch_bounds__(256) rt_denoise_variance_kernel(float *__restr
 
 // ... over the frame: the plane tiled from its row 0, a workgroup per 32x8 pixels -- the merged frame with its own weights,
 template <int P>
-__global__ void __launch_bounds__(kDnLanes) rt_denoise_kernel(DnPlanes<1> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk) {
+__global__ void __launch_bounds__(kPlaneLanes) rt_denoise_kernel(DnPlanes<1> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk) {
     extern __shared__ float dn_lds[];
-    dn_body<P, 1, false>(dn_lds, (int)blockIdx.x * kDnTileW, (int)blockIdx.y * kDnTileH, k, vs, w, h, R, alpha, kk);
+    dn_body<P, 1, false>(dn_lds, (int)blockIdx.x * kPlaneTileW, (int)blockIdx.y * kPlaneTileH, k, vs, w, h, R, alpha, kk);
 }
 
 // ... the two halves.  (waves_per_eu: at the default radii, R 5 and P 1 -- the only ones it was measured at -- LDS admits four workgroups a CU, a
@@ -64,10 +64,10 @@ __global__ void __launch_bounds__(kDnLanes) rt_denoise_kernel(DnPlanes<1> k, con
 // at run time and the register counts are the same with it, 60 / 74 / 93.  It ALLOWS the compiler 128 registers, though: at small radii (R 1, P 0:
 // nine workgroups a CU by LDS) occupancy is bound by registers, so a body that grows must be looked at again with the hint taken off.)
 template <int P>
-__global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kDnLanes)
+__global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kPlaneLanes)
 rt_denoise_pair_kernel(DnPlanes<2> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk) {
     extern __shared__ float dn_lds[];
-    dn_body<P, 2, false>(dn_lds, (int)blockIdx.x * kDnTileW, (int)blockIdx.y * kDnTileH, k, vs, w, h, R, alpha, kk);
+    dn_body<P, 2, false>(dn_lds, (int)blockIdx.x * kPlaneTileW, (int)blockIdx.y * kPlaneTileH, k, vs, w, h, R, alpha, kk);
 }
 
 // ... and the halves over the groups of a selection (rt_tiles.hip): workgroup i takes group list[i] -- g = gy * groups_x + gx in the PIXEL BUFFER's tile
@@ -75,14 +75,14 @@ rt_denoise_pair_kernel(DnPlanes<2> k, const float *__restrict__ vs, int w, int h
 // negative for the top, partial, group row.  Every other pixel of the four output planes keeps its words.  A list entry that names no group is skipped
 // by the whole workgroup, ahead of the first barrier.
 template <int P>
-__global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kDnLanes)
+__global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kPlaneLanes)
 rt_denoise_pair_tiles_kernel(DnPlanes<2> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, const uint32_t *__restrict__ list,
                              uint32_t groups_x, uint32_t n_groups) {
     extern __shared__ float dn_lds[];
     const uint32_t g = list[blockIdx.x];
     if (g >= n_groups) return;
     const uint32_t gy = g / groups_x, gx = g - gy * groups_x;
-    dn_body<P, 2, true>(dn_lds, (int)gx * kDnTileW, h - kDnTileH * ((int)gy + 1), k, vs, w, h, R, alpha, kk);
+    dn_body<P, 2, true>(dn_lds, (int)gx * kPlaneTileW, h - kPlaneTileH * ((int)gy + 1), k, vs, w, h, R, alpha, kk);
 }
 
 using namespace rt;
@@ -91,7 +91,7 @@ namespace {
 
 std::atomic<uint64_t> g_pair_calls{0};                     // numbers the calls that make cross-filtered planes (FrameState::filtered_pair)
 
-dim3 frame_grid(const rt_ctx *c) { return dim3((unsigned)((c->w + kDnTileW - 1) / kDnTileW), (unsigned)((c->h + kDnTileH - 1) / kDnTileH)); }
+dim3 frame_grid(const rt_ctx *c) { return plane_grid(c->w, c->h); }
 
 int launch_variance(float *var, const float *a, const float *b, int w, int h, hipStream_t stream) {
     hipLaunchKernelGGL(rt_denoise_variance_kernel, dim3((unsigned)((3 * (size_t)w + 255) / 256), (unsigned)std::min(h, 65535)), dim3(256), 0, stream, var, a, b, w, h);
@@ -144,10 +144,10 @@ int filter_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t st
         rc = launch_guided_filter(2, f, a, q, stream);
     } else with_patch_radius(q.patch_radius, [&](auto P) {
         if (tiles)
-            hipLaunchKernelGGL(rt_denoise_pair_tiles_kernel<decltype(P)::value>, dim3(a->frame.counts[0]), dim3(kDnLanes), lds, stream, k, a->d_denoise_var, a->w,
+            hipLaunchKernelGGL(rt_denoise_pair_tiles_kernel<decltype(P)::value>, dim3(a->frame.counts[0]), dim3(kPlaneLanes), lds, stream, k, a->d_denoise_var, a->w,
                                a->h, q.search_radius, q.alpha, kk, a->tiles.d_groups, groups_per_row(a), group_count(a));
         else
-            hipLaunchKernelGGL(rt_denoise_pair_kernel<decltype(P)::value>, frame_grid(a), dim3(kDnLanes), lds, stream, k, a->d_denoise_var, a->w, a->h,
+            hipLaunchKernelGGL(rt_denoise_pair_kernel<decltype(P)::value>, frame_grid(a), dim3(kPlaneLanes), lds, stream, k, a->d_denoise_var, a->w, a->h,
                                q.search_radius, q.alpha, kk);
     });
     if (rc != RT_OK) return rc;
@@ -229,7 +229,7 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
         const GuidedFilter f{ { dst->d_colors, nullptr }, { dst->d_denoise, nullptr }, { nullptr, nullptr }, { 0, 0 }, dst->d_denoise_var, nullptr, 0u };
         rc = launch_guided_filter(1, f, a, q, stream);
     } else with_patch_radius(q.patch_radius, [&](auto P) {
-        hipLaunchKernelGGL(rt_denoise_kernel<decltype(P)::value>, frame_grid(dst), dim3(kDnLanes), dn_lds_bytes(1, q.search_radius, q.patch_radius), stream, k,
+        hipLaunchKernelGGL(rt_denoise_kernel<decltype(P)::value>, frame_grid(dst), dim3(kPlaneLanes), dn_lds_bytes(1, q.search_radius, q.patch_radius), stream, k,
                            dst->d_denoise_var, dst->w, dst->h, q.search_radius, q.alpha, q.k * q.k);
     });
     if (rc != RT_OK) return rc;

@@ -1,32 +1,21 @@
 // rt_denoise.inc.h -- the NL-means device body the filter kernels share (include/rt_api.h, "denoising", "the error of the filtered frame", "feature
 // planes"): included by rt_denoise.hip, whose kernels filter by colour alone, and by rt_denoise_guided.hip, whose kernels add the guide of rules 13-14.
-// (rt_reproject.hip includes it for the pack alone: dn_to_int, dn_finite3.)  Two units, so that the code object of the first holds exactly the kernels it held before the guide existed, at the addresses they had.
+// Two units, so that the code object of the first holds exactly the kernels it held before the guide existed, at the addresses they had.
+// The workgroup's shape and the pack are rt_plane.inc.h's (a workgroup's 32x8 output pixels: a row of 32 per half-wave here); the arithmetic of rules
+// 3, 5 and 13 is rt_rules.h's.
 // Both units are compiled with -ffp-contract=off: every multiply, add and IEEE division below is an operation of its own, in the written order.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <type_traits>
 
-#include "rt_detmath.h"
 #include "rt_internal.h"
+#include "rt_plane.inc.h"
 
 namespace {
 
-constexpr int kDnTileW = 32, kDnTileH = 8, kDnLanes = kDnTileW * kDnTileH;      // a workgroup's output pixels: four wavefronts, a row of 32 per half-wave
-
 __device__ __forceinline__ int dn_clamp(int v, int n) { return min(max(v, 0), n - 1); }
-
-// .cl:34, the pack kernel's toInt (rt_trace.inc.h to_int): parity's restated powf, or fast mode's exp2 / log2 with the fused multiply-add that
-// unit's contraction makes of g * 255 + .5 (this unit contracts nothing, so it is written out)
-__device__ __forceinline__ uint32_t dn_to_int(float v, bool fast) {
-    const float c = fminf(fmaxf(v, 0.f), 1.f);
-    if (fast) return (uint32_t)(int)__builtin_fmaf(rt::fm_powf(c, 1.f / 2.2f), 255.f, .5f);
-    return (uint32_t)(int)(rt::dm_powf(c, 1.f / 2.2f) * 255.f + .5f);
-}
-
-__device__ __forceinline__ bool dn_finite3(float a, float b, float c) { return fabsf(a) <= FLT_MAX && fabsf(b) <= FLT_MAX && fabsf(c) <= FLT_MAX; }
 
 // What a filter kernel reads and writes per image: the plane, the filtered plane, and -- the halves only -- the filtered plane packed by the toInt
 // of that context's mode
@@ -72,15 +61,15 @@ struct DnGuide {
 template <int P, int N, bool kAnyRow, bool kGuided = false>
 __device__ __forceinline__ void dn_body(float *dn_lds, const int x0, const int y0, const DnPlanes<N> &k, const float *__restrict__ vs, int w, int h, int R,
                                         float alpha, float kk, const DnGuide gd = DnGuide{}) {
-    constexpr int EW = kDnTileW + 2 * P, EH = kDnTileH + 2 * P, EN = EW * EH;      // 256 / 340 / 432 positions: at most two per lane
-    const int H = R + P, LW = kDnTileW + 2 * H, LH = kDnTileH + 2 * H, LN = LW * LH;
+    constexpr int EW = kPlaneTileW + 2 * P, EH = kPlaneTileH + 2 * P, EN = EW * EH;      // 256 / 340 / 432 positions: at most two per lane
+    const int H = R + P, LW = kPlaneTileW + 2 * H, LH = kPlaneTileH + 2 * H, LN = LW * LH;
     float *const sI = dn_lds, *const sV = dn_lds + 3 * N * LN, *const sE = dn_lds + 3 * (N + 1) * LN;     // image i, channel c: sI + (3 i + c) LN
     const int tid = (int)threadIdx.x;
     const int wx0 = x0 - H, wy0 = y0 - H;                   // the window's origin in the plane
-    const int FW = kDnTileW + 2 * R, FN = FW * (kDnTileH + 2 * R), fx0 = x0 - R, fy0 = y0 - R;        // kGuided: the feature window
+    const int FW = kPlaneTileW + 2 * R, FN = FW * (kPlaneTileH + 2 * R), fx0 = x0 - R, fy0 = y0 - R;        // kGuided: the feature window
     float *const sF = sE + 2 * N * EN;                      // feature word c: sF + c * FN
 
-    for (int l = tid; l < LN; l += kDnLanes) {
+    for (int l = tid; l < LN; l += kPlaneLanes) {
         const int ly = l / LW, lx = l - ly * LW;
         const size_t at = 3 * ((size_t)dn_clamp(wy0 + ly, h) * (size_t)w + (size_t)dn_clamp(wx0 + lx, w));
 #pragma unroll
@@ -92,7 +81,7 @@ __device__ __forceinline__ void dn_body(float *dn_lds, const int x0, const int y
         }
     }
     if constexpr (kGuided) {
-        for (int l = tid; l < FN; l += kDnLanes) {
+        for (int l = tid; l < FN; l += kPlaneLanes) {
             const int fy = l / FW, fx = l - fy * FW;
             const size_t at = (size_t)dn_clamp(fy0 + fy, h) * (size_t)w + (size_t)dn_clamp(fx0 + fx, w);
             const float4 lo = gd.feat[2 * at], hi = gd.feat[2 * at + 1];
@@ -108,8 +97,8 @@ __device__ __forceinline__ void dn_body(float *dn_lds, const int x0, const int y
     bool have[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-        have[s] = tid + s * kDnLanes < EN;
-        const int idx = have[s] ? tid + s * kDnLanes : 0, iy = idx / EW, ix = idx - iy * EW;
+        have[s] = tid + s * kPlaneLanes < EN;
+        const int idx = have[s] ? tid + s * kPlaneLanes : 0, iy = idx / EW, ix = idx - iy * EW;
         ex[s] = dn_clamp(x0 - P + ix, w);
         ey[s] = dn_clamp(y0 - P + iy, h);
         const int l = (ey[s] - wy0) * LW + (ex[s] - wx0);
@@ -121,7 +110,7 @@ __device__ __forceinline__ void dn_body(float *dn_lds, const int x0, const int y
         }
     }
 
-    const int tx = tid & (kDnTileW - 1), ty = tid / kDnTileW, px = x0 + tx, py = y0 + ty;
+    const int tx = tid & (kPlaneTileW - 1), ty = tid / kPlaneTileW, px = x0 + tx, py = y0 + ty;
     const bool inside = px < w && py < h && (!kAnyRow || py >= 0);
     const float inv = 1.0f / (float)(3 * (2 * P + 1) * (2 * P + 1));
     float pf[7];                                            // kGuided: the pixel's own feature words (a lane outside the image: those of the clamped pixel)
@@ -147,16 +136,12 @@ __device__ __forceinline__ void dn_body(float *dn_lds, const int x0, const int y
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {           // rule 3, for every guide
                         const float qv = sV[c * LN + l];
-                        const float m = qv < pv[s][c] ? qv : pv[s][c];
-                        const float off = alpha * (pv[s][c] + m), dnm = 1e-10f + kk * (pv[s][c] + qv);
+                        const float off = rt::nlm_offset(alpha, pv[s][c], qv), dnm = rt::nlm_denominator(kk, pv[s][c], qv);
 #pragma unroll
-                        for (int g = 0; g < N; ++g) {
-                            const float t = pi[s][g][c] - sI[(3 * g + c) * LN + l];
-                            d[g][c] = (t * t - off) / dnm;
-                        }
+                        for (int g = 0; g < N; ++g) d[g][c] = rt::nlm_term(pi[s][g][c] - sI[(3 * g + c) * LN + l], off, dnm);
                     }
 #pragma unroll
-                    for (int g = 0; g < N; ++g) e[g * EN + tid + s * kDnLanes] = (d[g][0] + d[g][1]) + d[g][2];
+                    for (int g = 0; g < N; ++g) e[g * EN + tid + s * kPlaneLanes] = (d[g][0] + d[g][1]) + d[g][2];
                 }
             }
             __syncthreads();
@@ -189,26 +174,16 @@ __device__ __forceinline__ void dn_body(float *dn_lds, const int x0, const int y
 #pragma unroll
                     for (int i = 0; i < N; ++i) {
                         const float T = S[N - 1 - i] * inv;
-                        take[i] = T == T && dn_finite3(q[i][0], q[i][1], q[i][2]);
+                        take[i] = T == T && rt::finite3(q[i][0], q[i][1], q[i][2]);
                         const float g = T > 0.f ? T : 0.f;
-                        wgt[i] = 1.0f / (1.0f + g * (1.0f + g * 0.5f));
+                        wgt[i] = rt::falloff(g);
                     }
                     if constexpr (kGuided) {
                         const int fl = (qy - fy0) * FW + (qx - fx0);
                         float df[7];
 #pragma unroll
                         for (int c = 0; c < 7; ++c) df[c] = sF[c * FN + fl];
-                        const float a0 = pf[0] - df[0], a1 = pf[1] - df[1], a2 = pf[2] - df[2];
-                        const float n0 = pf[3] - df[3], n1 = pf[4] - df[4], n2 = pf[5] - df[5];
-                        const float pa = ((a0 * a0 + a1 * a1) + a2 * a2) * gd.ia;       // rule 13
-                        const float pn = ((n0 * n0 + n1 * n1) + n2 * n2) * gd.in;
-                        const float r = (pf[6] - df[6]) / ((pf[6] + df[6]) + 1e-10f);
-                        const float pd = (r * r) * gd.id;
-                        float phi = 0.0f;
-                        if (pa > phi) phi = pa;
-                        if (pn > phi) phi = pn;
-                        if (pd > phi) phi = pd;
-                        const float wf = 1.0f / (1.0f + phi * (1.0f + phi * 0.5f));
+                        const float wf = rt::guide_weight(pf, df, gd.ia, gd.in, gd.id);      // rule 13
 #pragma unroll
                         for (int i = 0; i < N; ++i) wgt[i] = wf < wgt[i] ? wf : wgt[i];      // rule 14
                     }
@@ -238,6 +213,7 @@ __device__ __forceinline__ void dn_body(float *dn_lds, const int x0, const int y
         k.out[i][at + 2] = f2;
         if constexpr (N == 2) {
             const bool fast = k.fast[i] != 0;
+            // (pack_rgb, written out: called here, the pair kernels' stores and the other image's divisions are scheduled differently -- profiles/HISTORY.md)
             k.px[i][(size_t)(h - 1 - py) * (size_t)w + (size_t)px] = dn_to_int(f0, fast) | (dn_to_int(f1, fast) << 8) | (dn_to_int(f2, fast) << 16);
         }
     }
@@ -247,8 +223,8 @@ namespace {
 
 size_t dn_lds_bytes(int N, int R, int P, bool guided = false) {      // dn_body's layout (its own name: rt::lds_bytes is the sweep's, rt_device.h)
     const int H = R + P;
-    return ((size_t)3 * (N + 1) * (kDnTileW + 2 * H) * (kDnTileH + 2 * H) + (size_t)2 * N * (kDnTileW + 2 * P) * (kDnTileH + 2 * P) +
-            (guided ? (size_t)7 * (kDnTileW + 2 * R) * (kDnTileH + 2 * R) : 0)) * sizeof(float);
+    return ((size_t)3 * (N + 1) * (kPlaneTileW + 2 * H) * (kPlaneTileH + 2 * H) + (size_t)2 * N * (kPlaneTileW + 2 * P) * (kPlaneTileH + 2 * P) +
+            (guided ? (size_t)7 * (kPlaneTileW + 2 * R) * (kPlaneTileH + 2 * R) : 0)) * sizeof(float);
 }
 
 // f(std::integral_constant<int, P>) for the instantiated patch radius (rt_host_denoise_params allows 0, 1, 2)

@@ -14,27 +14,27 @@ using rt::fail;
 // six workgroups -- ask for more wavefronts than the hint's four, and that instance's 83 registers admit six.  So the hint is kept for what it was measured
 // to do in the unguided body, keeping rule 3's divisions interleaved, and bounds nothing here.)
 template <int P>
-__global__ void __launch_bounds__(kDnLanes) rt_denoise_guided_kernel(DnPlanes<1> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, DnGuide gd) {
+__global__ void __launch_bounds__(kPlaneLanes) rt_denoise_guided_kernel(DnPlanes<1> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, DnGuide gd) {
     extern __shared__ float dn_lds[];
-    dn_body<P, 1, false, true>(dn_lds, (int)blockIdx.x * kDnTileW, (int)blockIdx.y * kDnTileH, k, vs, w, h, R, alpha, kk, gd);
+    dn_body<P, 1, false, true>(dn_lds, (int)blockIdx.x * kPlaneTileW, (int)blockIdx.y * kPlaneTileH, k, vs, w, h, R, alpha, kk, gd);
 }
 
 template <int P>
-__global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kDnLanes)
+__global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kPlaneLanes)
 rt_denoise_pair_guided_kernel(DnPlanes<2> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, DnGuide gd) {
     extern __shared__ float dn_lds[];
-    dn_body<P, 2, false, true>(dn_lds, (int)blockIdx.x * kDnTileW, (int)blockIdx.y * kDnTileH, k, vs, w, h, R, alpha, kk, gd);
+    dn_body<P, 2, false, true>(dn_lds, (int)blockIdx.x * kPlaneTileW, (int)blockIdx.y * kPlaneTileH, k, vs, w, h, R, alpha, kk, gd);
 }
 
 template <int P>
-__global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kDnLanes)
+__global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kPlaneLanes)
 rt_denoise_pair_tiles_guided_kernel(DnPlanes<2> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, const uint32_t *__restrict__ list,
                                     uint32_t groups_x, uint32_t n_groups, DnGuide gd) {
     extern __shared__ float dn_lds[];
     const uint32_t g = list[blockIdx.x];
     if (g >= n_groups) return;
     const uint32_t gy = g / groups_x, gx = g - gy * groups_x;
-    dn_body<P, 2, true, true>(dn_lds, (int)gx * kDnTileW, h - kDnTileH * ((int)gy + 1), k, vs, w, h, R, alpha, kk, gd);
+    dn_body<P, 2, true, true>(dn_lds, (int)gx * kPlaneTileW, h - kPlaneTileH * ((int)gy + 1), k, vs, w, h, R, alpha, kk, gd);
 }
 
 namespace rt {
@@ -45,14 +45,14 @@ int launch_guided_filter(int n_images, const GuidedFilter &f, const rt_ctx *a, c
     const rt_guide_params &g = a->guide;
     const DnGuide gd{ reinterpret_cast<const float4 *>(a->scene.d_features), 1.0f / (g.k_albedo * g.k_albedo), 1.0f / (g.k_normal * g.k_normal), 1.0f / (g.k_depth * g.k_depth) };
     const size_t lds = dn_lds_bytes(n_images, q.search_radius, q.patch_radius, true);
-    const dim3 grid((unsigned)((a->w + kDnTileW - 1) / kDnTileW), (unsigned)((a->h + kDnTileH - 1) / kDnTileH));
+    const dim3 grid = plane_grid(a->w, a->h);
     const float kk = q.k * q.k;
     hipError_t e = hipSuccess;
     // (each kernel by its symbol, as every launch of the library: the limit, then the launch)
 #define DN_LAUNCH_GUIDED(kernel, blocks, ...)                                                                                                        \
     do {                                                                                                                                             \
         if (lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax); \
-        if (e == hipSuccess) hipLaunchKernelGGL(kernel, blocks, dim3(kDnLanes), lds, stream, __VA_ARGS__);                                           \
+        if (e == hipSuccess) hipLaunchKernelGGL(kernel, blocks, dim3(kPlaneLanes), lds, stream, __VA_ARGS__);                                           \
     } while (0)
     with_patch_radius(q.patch_radius, [&](auto P) {
         constexpr int kP = decltype(P)::value;

@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "rt_internal.h"
+#include "rt_plane.inc.h"
 
 using rt::fail;
 
@@ -20,12 +21,7 @@ extern "C" int rt_host_guide_params(const rt_guide_params *g);     // rt_host.cp
 
 namespace {
 
-constexpr int kFtTileW = 32, kFtTileH = 8, kFtLanes = kFtTileW * kFtTileH;     // a workgroup's pixels: four wavefronts, an 8x8 tile each, as the render kernels'
 constexpr uint32_t kFtChunk = 1024;                                             // records staged at a time: 16 KiB of LDS
-
-struct FtCamera {
-    float ox, oy, oz, dx, dy, dz, xx, xy, xz, yx, yy, yz;
-};
 
 }  // namespace
 
@@ -34,39 +30,25 @@ struct FtCamera {
 // barrier -- a lane outside the image traces the ray of a pixel that does not exist and stores nothing.
 // Bounds: a chunk stages records [base, min(base + kFtChunk, n)) of a table of n and tests exactly those; the hit's records are read at id < n; the
 // store is guarded by x < w && y < h.
-__global__ void __launch_bounds__(kFtLanes) rt_features_kernel(float4 *__restrict__ out, const float4 *__restrict__ geom, const float4 *__restrict__ emis,
-                                                               const float4 *__restrict__ colr, uint32_t n, FtCamera cam, int w, int h) {
+__global__ void __launch_bounds__(kPlaneLanes) rt_features_kernel(float4 *__restrict__ out, const float4 *__restrict__ geom, const float4 *__restrict__ emis,
+                                                                  const float4 *__restrict__ colr, uint32_t n, rt::PixelCamera cam, int w, int h) {
     __shared__ float4 s_geom[kFtChunk];
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int x = (int)blockIdx.x * kFtTileW + wave * 8 + (lane & 7), y = (int)blockIdx.y * kFtTileH + (lane >> 3);
+    const int tid = (int)threadIdx.x;
+    const auto [x, y] = plane_pixel();
 
     // rule 10: the ray through the pixel's centre
-    const float kcx = ((float)x + 0.0f) * (1.f / (float)w) - 0.5f, kcy = ((float)y + 0.0f) * (1.f / (float)h) - 0.5f;
-    const float rx = cam.xx * kcx + cam.yx * kcy + cam.dx;
-    const float ry = cam.xy * kcx + cam.yy * kcy + cam.dy;
-    const float rz = cam.xz * kcx + cam.yz * kcy + cam.dz;
-    const float ox = 0.1f * rx + cam.ox, oy = 0.1f * ry + cam.oy, oz = 0.1f * rz + cam.oz;
-    const float f = 1.f / sqrtf(rx * rx + ry * ry + rz * rz);
-    const float dx = rx * f, dy = ry * f, dz = rz * f;
+    const rt::PixelRay r = rt::pixel_ray(cam, x, y, 1.f / (float)w, 1.f / (float)h);
 
     // rule 11: the nearest record in scene order
     float t = 1e20f;
     uint32_t id = 0xFFFFFFFFu;
     for (uint32_t base = 0; base < n; base += kFtChunk) {
         const uint32_t m = min(kFtChunk, n - base);
-        for (uint32_t i = (uint32_t)tid; i < m; i += (uint32_t)kFtLanes) s_geom[i] = geom[base + i];
+        for (uint32_t i = (uint32_t)tid; i < m; i += (uint32_t)kPlaneLanes) s_geom[i] = geom[base + i];
         __syncthreads();
         for (uint32_t i = 0; i < m; ++i) {
             const float4 g = s_geom[i];
-            const float px = g.x - ox, py = g.y - oy, pz = g.z - oz;
-            const float b = px * dx + py * dy + pz * dz;
-            float det = b * b - (px * px + py * py + pz * pz) + g.w;
-            float dist = 0.f;
-            if (!(det < 0.f)) {
-                det = sqrtf(det);
-                const float t1 = b - det, t2 = b + det;
-                dist = t1 > 0.01f ? t1 : (t2 > 0.01f ? t2 : 0.f);
-            }
+            const float dist = rt::sphere_distance(g.x, g.y, g.z, g.w, r);
             if (dist != 0.f && dist < t) {
                 t = dist;
                 id = base + i;
@@ -80,10 +62,9 @@ __global__ void __launch_bounds__(kFtLanes) rt_features_kernel(float4 *__restric
     float4 lo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
     if (t < 1e20f) {
         const float4 g = geom[id], e = emis[id], c = colr[id];
-        const float nx = (ox + dx * t) - g.x, ny = (oy + dy * t) - g.y, nz = (oz + dz * t) - g.z;
-        const float nf = 1.f / sqrtf(nx * nx + ny * ny + nz * nz);
-        lo = make_float4(c.x + e.x, c.y + e.y, c.z + e.z, nx * nf);
-        hi = make_float4(ny * nf, nz * nf, t, __uint_as_float(id));
+        const rt::Float3 nrm = rt::hit_normal(r, t, g.x, g.y, g.z);
+        lo = make_float4(c.x + e.x, c.y + e.y, c.z + e.z, nrm.x);
+        hi = make_float4(nrm.y, nrm.z, t, __uint_as_float(id));
     }
     const size_t at = (size_t)(h - 1 - y) * (size_t)w + (size_t)x;
     out[2 * at] = lo;
@@ -92,14 +73,20 @@ __global__ void __launch_bounds__(kFtLanes) rt_features_kernel(float4 *__restric
 
 namespace rt {
 
+int features_refuse(const rt_ctx *c, const char *call, const char *lead, const char *of_whom) {
+    if (c->scene.state.features_current && c->scene.d_features) return RT_OK;
+    return fail(RT_ERR_STATE, "%s: %sthe feature plane%s is not current (rt_features_async forms it; rt_set_scene, rt_update_spheres_async and rt_set_camera end it)", call,
+                lead, of_whom);
+}
+
 int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guided) {
     if (guided) *guided = false;
     if (a->have_guide != b->have_guide || (a->have_guide && memcmp(&a->guide, &b->guide, sizeof a->guide) != 0))
         return fail(RT_ERR_STATE, "%s: the halves differ in their guide (rt_set_denoise_guide: both off, or both on with the same parameters)", call);
     if (!a->have_guide) return RT_OK;
-    if (!a->scene.state.features_current || !b->scene.state.features_current || !a->scene.d_features)
-        return fail(RT_ERR_STATE, "%s: a guide is set and the feature plane of %s is not current (rt_features_async forms it; rt_set_scene, "
-                                  "rt_update_spheres_async and rt_set_camera end it)", call, !a->scene.state.features_current || !a->scene.d_features ? "the first half" : "the second half");
+    // (a plane is current only after rt_features_async has acquired its block: SceneState::features_formed)
+    RT_TRY(features_refuse(a, call, "a guide is set and ", " of the first half"));
+    RT_TRY(features_refuse(b, call, "a guide is set and ", " of the second half"));
     if (guided) *guided = true;
     return RT_OK;
 }
@@ -122,11 +109,8 @@ RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
     rc = chain(c, stream);
     if (rc == RT_OK) rc = refresh_tables(c, stream);
     if (rc != RT_OK) return rc;
-    const rt_camera &m = c->cam;
-    const FtCamera cam{ m.orig.x, m.orig.y, m.orig.z, m.dir.x, m.dir.y, m.dir.z, m.x.x, m.x.y, m.x.z, m.y.x, m.y.y, m.y.z };
-    const dim3 grid((unsigned)((c->w + kFtTileW - 1) / kFtTileW), (unsigned)((c->h + kFtTileH - 1) / kFtTileH));
-    hipLaunchKernelGGL(rt_features_kernel, grid, dim3(kFtLanes), 0, stream, reinterpret_cast<float4 *>(c->scene.d_features), c->scene.tables.geom, c->scene.tables.emis, c->scene.tables.colr,
-                       c->scene.tables.n_spheres, cam, c->w, c->h);
+    hipLaunchKernelGGL(rt_features_kernel, plane_grid(c->w, c->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(c->scene.d_features), c->scene.tables.geom,
+                       c->scene.tables.emis, c->scene.tables.colr, c->scene.tables.n_spheres, pixel_camera(c->cam), c->w, c->h);
     HIP_TRY(hipGetLastError());
     if (!c->scene.state.features_current) c->frame.features_reformed();     // (a temporal plane formed under the plane that ended stays ended)
     c->scene.state.features_formed();

@@ -1,6 +1,10 @@
-// rt_host.cpp -- host-side pieces either side of the render path, C ABI:
-// the seed stream the reference draws from the C library, the camera basis, the built-in
-// scene and the .scn reader.  Plain C++, strict binary32/binary64 (-ffp-contract=off).
+// rt_host.cpp -- the library's host-side code that needs no GPU, C ABI.  Plain C++, strict binary32/binary64 (-ffp-contract=off).
+//   Either side of the render path: the seed streams (the one the reference draws from the C library, and the numbered ones), the
+//   camera basis, the built-in scene and the .scn reader.
+//   The host statements of the library's extensions, as plain loops, with their defaults and parameter rules: rt_denoise_planes and
+//   rt_denoise_pair_planes with their guided forms (rules 1-6, 13-14), rt_features_planes (rules 10-12), rt_reproject_planes (rules 15-19) and
+//   rt_atrous_planes (rules 20-23).  The kernels are tested against them bit for bit.  The loops, the clamping and the order of the sums are written
+//   here; the arithmetic of a rule is rt_rules.h's, which the kernels call too.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -9,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rt_api.h"
+#include "rt_rules.h"
 
 // rt_last_error()'s thread-local text lives in rt_api.hip; host helpers report through this
 extern "C" void rt_host_set_error(const char *msg);
@@ -251,21 +256,6 @@ namespace {
 
 inline int dn_cl(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
-// rule 13: the feature weight of two pixels from their records of the feature plane (8 words each; word 7 is not read)
-inline float guide_weight(const float *fp, const float *fq, float ia, float in, float id) {
-    const float a0 = fp[0] - fq[0], a1 = fp[1] - fq[1], a2 = fp[2] - fq[2];
-    const float n0 = fp[3] - fq[3], n1 = fp[4] - fq[4], n2 = fp[5] - fq[5];
-    const float pa = ((a0 * a0 + a1 * a1) + a2 * a2) * ia;
-    const float pn = ((n0 * n0 + n1 * n1) + n2 * n2) * in;
-    const float r = (fp[6] - fq[6]) / ((fp[6] + fq[6]) + 1e-10f);
-    const float pd = (r * r) * id;
-    float phi = 0.0f;
-    if (pa > phi) phi = pa;                                  // (a NaN term constrains nothing)
-    if (pn > phi) phi = pn;
-    if (pd > phi) phi = pd;
-    return 1.0f / (1.0f + phi * (1.0f + phi * 0.5f));
-}
-
 // rules 1 and 2: the variance of the mean of the two halves, smoothed over 3x3, clamped
 std::vector<float> smoothed_variance(const float *a, const float *b, int w, int h) {
     const auto at = [w](int y, int x) { return 3 * ((size_t)y * (size_t)w + (size_t)x); };
@@ -315,10 +305,8 @@ void nlm_planes(float *out, const float *img, const float *guide, const std::vec
                     const size_t ip = at(y, x), iq = at(dn_cl(y + oy, h), dn_cl(x + ox, w));
                     float d[3];
                     for (int c = 0; c < 3; ++c) {
-                        const float t = guide[ip + c] - guide[iq + c];
                         const float vp = var[ip + c], vq = var[iq + c];
-                        const float m = vq < vp ? vq : vp;
-                        d[c] = (t * t - alpha * (vp + m)) / (1e-10f + kk * (vp + vq));
+                        d[c] = rt::nlm_term(guide[ip + c] - guide[iq + c], rt::nlm_offset(alpha, vp, vq), rt::nlm_denominator(kk, vp, vq));
                     }
                     e[(size_t)y * w + x] = (d[0] + d[1]) + d[2];
                 }
@@ -334,12 +322,12 @@ void nlm_planes(float *out, const float *img, const float *guide, const std::vec
                         }
                     const float T = S * inv;
                     const float *dq = img + at(qy, qx);
-                    if (std::isnan(T) || !std::isfinite(dq[0]) || !std::isfinite(dq[1]) || !std::isfinite(dq[2])) continue;
+                    if (std::isnan(T) || !rt::finite3(dq[0], dq[1], dq[2])) continue;
                     const float g = T > 0.f ? T : 0.f;
-                    float wgt = 1.0f / (1.0f + g * (1.0f + g * 0.5f));
+                    float wgt = rt::falloff(g);
                     const size_t i = (size_t)y * w + x;
-                    if (gd) {                                                 // 14.
-                        const float wf = guide_weight(feat + 8 * i, feat + 8 * ((size_t)qy * w + qx), ia, in, id);
+                    if (gd) {                                                 // 14. (13.: words 0-6 of the two records; word 7 is not read)
+                        const float wf = rt::guide_weight(feat + 8 * i, feat + 8 * ((size_t)qy * w + qx), ia, in, id);
                         wgt = wf < wgt ? wf : wgt;
                     }
                     for (int c = 0; c < 3; ++c) num[3 * i + c] = num[3 * i + c] + wgt * dq[c];
@@ -407,44 +395,30 @@ int rt_denoise_pair_planes(float *out_a, float *out_b, const float *a, const flo
 int rt_features_planes(float *out, const rt_sphere *spheres, uint32_t count, const rt_camera *cam, int w, int h) {
     if (!out || !cam || (count > 0 && !spheres)) return host_fail("rt_features_planes: null argument");
     if (w < 1 || h < 1) return host_fail("rt_features_planes: %dx%d", w, h);
+    const rt::PixelCamera pc = rt::pixel_camera(*cam);
     const float inv_w = 1.f / (float)w, inv_h = 1.f / (float)h;
     for (int y = 0; y < h; ++y)
         for (int x = 0; x < w; ++x) {
-            // 10. the ray through the pixel's centre (.cl:494-549 with both random numbers 0.5)
-            const float kcx = ((float)x + 0.0f) * inv_w - 0.5f, kcy = ((float)y + 0.0f) * inv_h - 0.5f;
-            const float rx = cam->x.x * kcx + cam->y.x * kcy + cam->dir.x;
-            const float ry = cam->x.y * kcx + cam->y.y * kcy + cam->dir.y;
-            const float rz = cam->x.z * kcx + cam->y.z * kcy + cam->dir.z;
-            const float ox = 0.1f * rx + cam->orig.x, oy = 0.1f * ry + cam->orig.y, oz = 0.1f * rz + cam->orig.z;
-            const float f = 1.f / std::sqrt(rx * rx + ry * ry + rz * rz);
-            const float dx = rx * f, dy = ry * f, dz = rz * f;
-            // 11. the nearest record in scene order (.cl:215-232 over .cl:173-201)
+            // 10. the ray through the pixel's centre
+            const rt::PixelRay r = rt::pixel_ray(pc, x, y, inv_w, inv_h);
+            // 11. the nearest record in scene order (.cl:215-232)
             float t = 1e20f;
             uint32_t id = 0xFFFFFFFFu;
             for (uint32_t i = 0; i < count; ++i) {
                 const rt_sphere &s = spheres[i];
-                const float px = s.p.x - ox, py = s.p.y - oy, pz = s.p.z - oz;
-                const float b = px * dx + py * dy + pz * dz;
-                float det = b * b - (px * px + py * py + pz * pz) + s.rad * s.rad;
-                float dist = 0.f;
-                if (!(det < 0.f)) {
-                    det = std::sqrt(det);
-                    const float t1 = b - det, t2 = b + det;
-                    dist = t1 > 0.01f ? t1 : (t2 > 0.01f ? t2 : 0.f);
-                }
+                const float dist = rt::sphere_distance(s.p.x, s.p.y, s.p.z, s.rad * s.rad, r);
                 if (dist != 0.f && dist < t) {
                     t = dist;
                     id = i;
                 }
             }
-            // 12. the values (.cl:338-347; the normal is not turned towards the ray)
+            // 12. the values
             float *o = out + 8 * ((size_t)(h - 1 - y) * (size_t)w + (size_t)x);
             if (t < 1e20f) {
                 const rt_sphere &s = spheres[id];
-                const float nx = (ox + dx * t) - s.p.x, ny = (oy + dy * t) - s.p.y, nz = (oz + dz * t) - s.p.z;
-                const float nf = 1.f / std::sqrt(nx * nx + ny * ny + nz * nz);
+                const rt::Float3 nrm = rt::hit_normal(r, t, s.p.x, s.p.y, s.p.z);
                 o[0] = s.c.x + s.e.x, o[1] = s.c.y + s.e.y, o[2] = s.c.z + s.e.z;
-                o[3] = nx * nf, o[4] = ny * nf, o[5] = nz * nf;
+                o[3] = nrm.x, o[4] = nrm.y, o[5] = nrm.z;
                 o[6] = t;
             } else {
                 for (int k = 0; k < 7; ++k) o[k] = 0.0f;
@@ -461,18 +435,7 @@ int rt_features_planes(float *out, const rt_sphere *spheres, uint32_t count, con
 // rt_reproject_async forms the same words on the device (rt_reproject.hip) and is tested against this function bit for bit.
 namespace {
 
-inline float rp_dot(const float *a, const float *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-// rule 10 at image pixel (x, y): the ray (o, d) of rt_features_planes, step for step
-inline void rp_ray(const rt_camera &cam, int x, int y, float inv_w, float inv_h, float o[3], float d[3]) {
-    const float kcx = ((float)x + 0.0f) * inv_w - 0.5f, kcy = ((float)y + 0.0f) * inv_h - 0.5f;
-    const float rx = cam.x.x * kcx + cam.y.x * kcy + cam.dir.x;
-    const float ry = cam.x.y * kcx + cam.y.y * kcy + cam.dir.y;
-    const float rz = cam.x.z * kcx + cam.y.z * kcy + cam.dir.z;
-    o[0] = 0.1f * rx + cam.orig.x, o[1] = 0.1f * ry + cam.orig.y, o[2] = 0.1f * rz + cam.orig.z;
-    const float f = 1.f / std::sqrt(rx * rx + ry * ry + rz * rz);
-    d[0] = rx * f, d[1] = ry * f, d[2] = rz * f;
-}
+inline float rp_dot(const float *a, const float *b) { return rt::dot3(a[0], a[1], a[2], b[0], b[1], b[2]); }
 
 }  // namespace
 
@@ -510,11 +473,12 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
     rt_reproject_params q;
     if (rt_host_reproject_params(p, &q) != RT_OK) return RT_ERR_ARG;
 
-    const rt_camera &camD = *dst->cam, &camS = *src->cam;
+    const rt_camera &camS = *src->cam;
+    const rt::PixelCamera pcD = rt::pixel_camera(*dst->cam), pcS = rt::pixel_camera(camS);
     const float inv_w = 1.f / (float)w, inv_h = 1.f / (float)h, fw = (float)w, fh = (float)h;
     const float sdir[3] = { camS.dir.x, camS.dir.y, camS.dir.z }, sx[3] = { camS.x.x, camS.x.y, camS.x.z }, sy[3] = { camS.y.x, camS.y.y, camS.y.z };
     const float dd = rp_dot(sdir, sdir), xx = rp_dot(sx, sx), yy = rp_dot(sy, sy);
-    const float foot = std::sqrt(xx) * (1.f / (float)w);              // rule 17: a pixel's footprint per unit of distance
+    const float foot = sqrtf(xx) * (1.f / (float)w);             // rule 17: a pixel's footprint per unit of distance
     const float nd = (float)dst->passes;
     const int cs = src->channels, cd = dst->channels;
     for (int y = 0; y < h; ++y)
@@ -526,8 +490,9 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
             memcpy(&id, dst->feat + 8 * at + 7, sizeof id);
             if (id < count) {                                         // (0xFFFFFFFF: the sky)
                 const float t = dst->feat[8 * at + 6];
-                float o[3], d[3], Pp[3], v[3];
-                rp_ray(camD, x, y, inv_w, inv_h, o, d);
+                float Pp[3], v[3];
+                const rt::PixelRay r = rt::pixel_ray(pcD, x, y, inv_w, inv_h);
+                const float o[3] = { r.ox, r.oy, r.oz }, d[3] = { r.dx, r.dy, r.dz };
                 const rt_vec3 &pd = dst->spheres[id].p, &ps = src->spheres[id].p;
                 const float m[3] = { pd.x - ps.x, pd.y - ps.y, pd.z - ps.z };
                 for (int c = 0; c < 3; ++c) Pp[c] = (o[c] + d[c] * t) - m[c];
@@ -550,14 +515,15 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
                                 memcpy(&idq, src->feat + 8 * aq + 7, sizeof idq);
                                 if (idq != id) continue;
                                 const float tq = src->feat[8 * aq + 6];
-                                float oq[3], dq[3], e[3];
-                                rp_ray(camS, qx, qy, inv_w, inv_h, oq, dq);
+                                const rt::PixelRay rq = rt::pixel_ray(pcS, qx, qy, inv_w, inv_h);
+                                const float oq[3] = { rq.ox, rq.oy, rq.oz }, dq[3] = { rq.dx, rq.dy, rq.dz };
+                                float e[3];
                                 for (int c = 0; c < 3; ++c) e[c] = (oq[c] + dq[c] * tq) - Pp[c];
-                                const float r = q.k_pos * (tq * foot);
-                                if (!(rp_dot(e, e) <= r * r)) continue;
+                                const float rr = q.k_pos * (tq * foot);
+                                if (!(rp_dot(e, e) <= rr * rr)) continue;
                                 const float *u = src->plane + (size_t)cs * aq;
                                 const float un = cs == 4 ? u[3] : (float)src->passes;
-                                if (!std::isfinite(u[0]) || !std::isfinite(u[1]) || !std::isfinite(u[2]) || !(un > 0.0f)) continue;
+                                if (!rt::usable(u[0], u[1], u[2], un)) continue;
                                 // 18. the history
                                 sw = sw + b;
                                 sn = sn + b * un;
@@ -566,24 +532,10 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
                     }
                 }
             }
-            // 19. the blend
-            float *T = out_rgbn + 4 * at;
+            // 19. the blend (D's plane is not read at pass 0)
             const float *CD = dst->passes != 0 ? dst->plane + (size_t)cd * at : nullptr;
-            if (!(sw > 0.0f)) {
-                for (int c = 0; c < 3; ++c) T[c] = CD ? CD[c] : 0.0f;
-                T[3] = nd;
-                continue;
-            }
-            float nh = sn / sw;
-            if (nh > q.max_history) nh = q.max_history;
-            if (!CD) {
-                for (int c = 0; c < 3; ++c) T[c] = sc[c] / sw;
-                T[3] = nh;
-                continue;
-            }
-            const float inv = 1.0f / (nd + nh);
-            for (int c = 0; c < 3; ++c) T[c] = (CD[c] * nd + (sc[c] / sw) * nh) * inv;
-            T[3] = nd + nh;
+            float *T = out_rgbn + 4 * at;
+            rt::temporal_blend(T[0], T[1], T[2], T[3], CD ? CD[0] : 0.0f, CD ? CD[1] : 0.0f, CD ? CD[2] : 0.0f, nd, CD != nullptr, sw, sn, sc[0], sc[1], sc[2], q.max_history);
         }
     return RT_OK;
 }
@@ -592,12 +544,6 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
 
 // ---- rt_atrous_planes: the edge-avoiding wavelet filter of include/rt_api.h ("edge-avoiding wavelet filter"), rules 20-23, as plain loops ----
 // rt_atrous_async forms the same words on the device (rt_atrous.hip) and is tested against this function bit for bit.
-namespace {
-
-inline float at_lum(const float *c) { return (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2]; }
-
-}  // namespace
-
 extern "C" {
 
 void rt_atrous_defaults(rt_atrous_params *p) {
@@ -637,7 +583,7 @@ int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int pass
     for (size_t at = 0; at < px; ++at) {
         const float *u = plane + (size_t)channels * at;
         n[at] = channels == 4 ? u[3] : (float)passes;
-        usable[at] = std::isfinite(u[0]) && std::isfinite(u[1]) && std::isfinite(u[2]) && n[at] > 0.0f;
+        usable[at] = rt::usable(u[0], u[1], u[2], n[at]);
         memcpy(&id[at], feat + 8 * at + 7, sizeof(uint32_t));
         memcpy(cur + 4 * at, u, 3 * sizeof(float));
     }
@@ -652,21 +598,16 @@ int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int pass
                     if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
                     const size_t aq = (size_t)qy * (size_t)w + (size_t)qx;
                     if (!usable[aq] || id[aq] != id[at]) continue;
-                    const float l = at_lum(cur + 4 * aq);
+                    const float *cq = cur + 4 * aq;
+                    const float l = rt::luminance(cq[0], cq[1], cq[2]);
                     s0 = s0 + 1.0f;
                     s1 = s1 + l;
                     s2 = s2 + l * l;
                 }
-            float v0 = 0.0f;
-            if (s0 > 0.0f) {
-                const float m = s1 / s0, v = s2 / s0 - m * m;
-                v0 = v > 0.0f ? v : 0.0f;
-            }
-            cur[4 * at + 3] = v0;
+            cur[4 * at + 3] = rt::variance_of_sums(s0, s1, s2);
         }
     // 22., 23. the levels
-    const float hk[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
-    const float in = 1.0f / (q.k_normal * q.k_normal), kl2 = q.k_lum * q.k_lum;
+    const float in =1.0f / (q.k_normal * q.k_normal), kl2 = q.k_lum * q.k_lum;
     for (int level = 0; level < q.levels; ++level) {
         const int s = 1 << level;
         for (int y = 0; y < h; ++y)
@@ -677,7 +618,7 @@ int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int pass
                     memcpy(nxt + 4 * at, cp, 4 * sizeof(float));
                     continue;
                 }
-                const float lp = at_lum(cp);
+                const float lp = rt::luminance(cp[0], cp[1], cp[2]);
                 const float *np = feat + 8 * at + 3;
                 float acc[3] = { 0.0f, 0.0f, 0.0f }, aw = 0.0f, av = 0.0f;
                 for (int j = -2; j <= 2; ++j)
@@ -686,7 +627,7 @@ int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int pass
                         float wgt;
                         if (i == 0 && j == 0) {
                             cq = cp;
-                            wgt = (0.375f * 0.375f) * n[at];
+                            wgt = rt::atrous_centre_weight(n[at]);
                         } else {
                             const long qx = (long)x + (long)s * i, qy = (long)y + (long)s * j;
                             if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
@@ -694,14 +635,8 @@ int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int pass
                             if (!usable[aq] || id[aq] != id[at]) continue;
                             cq = cur + 4 * aq;
                             const float *nq = feat + 8 * aq + 3;
-                            const float a0 = np[0] - nq[0], a1 = np[1] - nq[1], a2 = np[2] - nq[2];
-                            const float gn = ((a0 * a0 + a1 * a1) + a2 * a2) * in;
-                            const float d = lp - at_lum(cq);
-                            const float gl = (d * d) / (kl2 * (cp[3] + cq[3]) + 1e-10f);
-                            float g = 0.0f;
-                            if (gn > g) g = gn;
-                            if (gl > g) g = gl;
-                            wgt = ((hk[j + 2] * hk[i + 2]) * (1.0f / (1.0f + g * (1.0f + g * 0.5f)))) * n[aq];
+                            const float g = rt::atrous_edge(np[0], np[1], np[2], nq[0], nq[1], nq[2], in, lp, rt::luminance(cq[0], cq[1], cq[2]), cp[3], cq[3], kl2);
+                            wgt = rt::atrous_tap_weight(rt::atrous_tap(j), rt::atrous_tap(i), g, n[aq]);
                         }
                         for (int c = 0; c < 3; ++c) acc[c] = acc[c] + wgt * cq[c];
                         aw = aw + wgt;

@@ -285,6 +285,10 @@ int refresh_pixels(rt_ctx *c, hipStream_t stream); // the packed frame brought u
 const double *create_breakdown();                   // host ms of the last rt_create by phase (rt_debug_create_breakdown)
 // blocking read of `bytes` from the context's device: behind everything it has queued, on its own stream (wait = false: the copy is queued, a later call waits)
 int read_back(rt_ctx *c, void *host, const void *dev, size_t bytes, bool wait = true);
+// rt_read_temporal, rt_read_atrous: a context's [h][w][4] plane and / or its packed plane, either buffer null for "not this one".  RT_ERR_ARG for a context
+// the adaptive calls do not take or two null buffers; RT_ERR_STATE "<call>: the context holds no current <absent>" unless current(c)
+int read_plane4(rt_ctx *c, const char *call, float *plane_host, uint32_t *packed_host, bool (*current)(const rt_ctx *), float *rt_ctx::*plane, uint32_t *rt_ctx::*packed,
+                const char *absent);
 // `a` and `b` show the same frame on the same device: non-null, distinct, neither multi-device, same size (`sharding`: and rank, ranks, rows per
 // tile), same device -- or RT_ERR_ARG with a message that names `call`, the two contexts as the caller knows them, and the property that differs
 int same_frame(const rt_ctx *a, const rt_ctx *b, const char *call, const char *a_name, const char *b_name, bool sharding = true);
@@ -315,6 +319,9 @@ int denoise_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t s
 // RT_OK and nothing launched if they are current; RT_ERR_STATE for anything else, `call` named in the message
 int denoise_pair_tiles(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream, const char *call);
 
+// ---- rt_features.hip: the feature plane, for every call that reads it ----
+// RT_ERR_STATE unless c's feature plane is current; the message reads "<call>: <lead>the feature plane<of_whom> is not current (...)"
+int features_refuse(const rt_ctx *c, const char *call, const char *lead = "", const char *of_whom = "");
 // the guide of a pair of halves (rt_set_denoise_guide): RT_ERR_STATE when the two settings differ, or -- on -- a feature plane is not current.  *guided: on
 int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guided = nullptr);
 // ---- rt_denoise_guided.hip: the filter kernels under a guide, launched for rt_denoise.hip ----

@@ -9,38 +9,13 @@
 // The render kernels are not touched, and nothing here writes anything but the two temporal planes.
 #include <hip/hip_runtime.h>
 
-#include "rt_denoise.inc.h"     // dn_to_int, dn_finite3: the pack of rt_denoise_pair_async's planes
 #include "rt_internal.h"
+#include "rt_plane.inc.h"
 
+using rt::dot3;
 using rt::fail;
 
 extern "C" int rt_host_reproject_params(const rt_reproject_params *p, rt_reproject_params *out);     // rt_host.cpp: the parameter rules (null = defaults)
-
-namespace {
-
-constexpr int kRpTileW = 32, kRpTileH = 8, kRpLanes = kRpTileW * kRpTileH;     // a workgroup's pixels: four wavefronts, an 8x8 tile each, as rt_features_kernel's
-
-struct RpCamera {
-    float ox, oy, oz, dx, dy, dz, xx, xy, xz, yx, yy, yz;
-};
-
-struct RpRay {
-    float ox, oy, oz, dx, dy, dz;
-};
-
-__device__ __forceinline__ float rp_dot(float a0, float a1, float a2, float b0, float b1, float b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
-
-// rule 10: the ray through the centre of image pixel (x, y)
-__device__ __forceinline__ RpRay rp_ray(const RpCamera &cam, int x, int y, float inv_w, float inv_h) {
-    const float kcx = ((float)x + 0.0f) * inv_w - 0.5f, kcy = ((float)y + 0.0f) * inv_h - 0.5f;
-    const float rx = cam.xx * kcx + cam.yx * kcy + cam.dx;
-    const float ry = cam.xy * kcx + cam.yy * kcy + cam.dy;
-    const float rz = cam.xz * kcx + cam.yz * kcy + cam.dz;
-    const float f = 1.f / sqrtf(rx * rx + ry * ry + rz * rz);
-    return RpRay{ 0.1f * rx + cam.ox, 0.1f * ry + cam.oy, 0.1f * rz + cam.oz, rx * f, ry * f, rz * f };
-}
-
-}  // namespace
 
 // One lane per pixel of D.  kCh: the source plane U holds 3 floats a pixel (S's colour plane, every pixel at `ns` samples) or 4 (S's temporal plane).
 // Both cameras, the parameters and nd are kernel arguments and stay in scalar registers.  FD and each tap's words of FS are read as two float4, a
@@ -49,12 +24,11 @@ __device__ __forceinline__ RpRay rp_ray(const RpCamera &cam, int x, int y, float
 // Bounds: FD, CD and the two stores at the lane's own pixel, x < w && y < h; the centres at id < n, the size of both tables (the host refuses scenes
 // that differ in it); a tap's words of FS and U only for 0 <= qx < w && 0 <= qy < h.
 template <int kCh>
-__global__ void __launch_bounds__(kRpLanes) rt_reproject_kernel(float4 *__restrict__ out, uint32_t *__restrict__ out_px, const float4 *__restrict__ feat_d,
-                                                                const float4 *__restrict__ feat_s, const float *__restrict__ col_d, const float *__restrict__ u_s,
-                                                                const float4 *__restrict__ geom_d, const float4 *__restrict__ geom_s, uint32_t n, RpCamera cam_d,
-                                                                RpCamera cam_s, float k_pos, float max_history, float nd, float ns, int w, int h, int fast) {
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int x = (int)blockIdx.x * kRpTileW + wave * 8 + (lane & 7), y = (int)blockIdx.y * kRpTileH + (lane >> 3);
+__global__ void __launch_bounds__(kPlaneLanes) rt_reproject_kernel(float4 *__restrict__ out, uint32_t *__restrict__ out_px, const float4 *__restrict__ feat_d,
+                                                                   const float4 *__restrict__ feat_s, const float *__restrict__ col_d, const float *__restrict__ u_s,
+                                                                   const float4 *__restrict__ geom_d, const float4 *__restrict__ geom_s, uint32_t n, rt::PixelCamera cam_d,
+                                                                   rt::PixelCamera cam_s, float k_pos, float max_history, float nd, float ns, int w, int h, int fast) {
+    const auto [x, y] = plane_pixel();
     if (x >= w || y >= h) return;
     const size_t at = (size_t)(h - 1 - y) * (size_t)w + (size_t)x;
     const float inv_w = 1.f / (float)w, inv_h = 1.f / (float)h, fw = (float)w, fh = (float)h;
@@ -65,18 +39,18 @@ __global__ void __launch_bounds__(kRpLanes) rt_reproject_kernel(float4 *__restri
     const uint32_t id = __float_as_uint(fd_hi.w);
     if (id < n) {
         const float t = fd_hi.z;
-        const RpRay r = rp_ray(cam_d, x, y, inv_w, inv_h);
+        const rt::PixelRay r = rt::pixel_ray(cam_d, x, y, inv_w, inv_h);       // rule 10
         const float4 gd = geom_d[id], gs = geom_s[id];
         const float ppx = (r.ox + r.dx * t) - (gd.x - gs.x), ppy = (r.oy + r.dy * t) - (gd.y - gs.y), ppz = (r.oz + r.dz * t) - (gd.z - gs.z);
         // rule 16: where S saw it
         const float vx = ppx - cam_s.ox, vy = ppy - cam_s.oy, vz = ppz - cam_s.oz;
-        const float z = rp_dot(vx, vy, vz, cam_s.dx, cam_s.dy, cam_s.dz);
+        const float z = dot3(vx, vy, vz, cam_s.dx, cam_s.dy, cam_s.dz);
         if (z > 0.0f) {
-            const float dd = rp_dot(cam_s.dx, cam_s.dy, cam_s.dz, cam_s.dx, cam_s.dy, cam_s.dz);
-            const float xx = rp_dot(cam_s.xx, cam_s.xy, cam_s.xz, cam_s.xx, cam_s.xy, cam_s.xz);
-            const float yy = rp_dot(cam_s.yx, cam_s.yy, cam_s.yz, cam_s.yx, cam_s.yy, cam_s.yz);
-            const float kx = (rp_dot(vx, vy, vz, cam_s.xx, cam_s.xy, cam_s.xz) * dd) / (z * xx);
-            const float ky = (rp_dot(vx, vy, vz, cam_s.yx, cam_s.yy, cam_s.yz) * dd) / (z * yy);
+            const float dd = dot3(cam_s.dx, cam_s.dy, cam_s.dz, cam_s.dx, cam_s.dy, cam_s.dz);
+            const float xx = dot3(cam_s.xx, cam_s.xy, cam_s.xz, cam_s.xx, cam_s.xy, cam_s.xz);
+            const float yy = dot3(cam_s.yx, cam_s.yy, cam_s.yz, cam_s.yx, cam_s.yy, cam_s.yz);
+            const float kx = (dot3(vx, vy, vz, cam_s.xx, cam_s.xy, cam_s.xz) * dd) / (z * xx);
+            const float ky = (dot3(vx, vy, vz, cam_s.yx, cam_s.yy, cam_s.yz) * dd) / (z * yy);
             const float fx = (kx + 0.5f) * fw, fy = (ky + 0.5f) * fh;
             if (fx >= -1.0f && fx < fw && fy >= -1.0f && fy < fh) {
                 const float x0 = floorf(fx), y0 = floorf(fy), ax = fx - x0, ay = fy - y0;
@@ -93,24 +67,18 @@ __global__ void __launch_bounds__(kRpLanes) rt_reproject_kernel(float4 *__restri
                         const float4 fs_hi = feat_s[2 * aq + 1];
                         if (__float_as_uint(fs_hi.w) != id) continue;
                         const float tq = fs_hi.z;
-                        const RpRay rq = rp_ray(cam_s, qx, qy, inv_w, inv_h);
+                        const rt::PixelRay rq = rt::pixel_ray(cam_s, qx, qy, inv_w, inv_h);
                         const float ex = (rq.ox + rq.dx * tq) - ppx, ey = (rq.oy + rq.dy * tq) - ppy, ez = (rq.oz + rq.dz * tq) - ppz;
                         const float rr = k_pos * (tq * foot);
-                        if (!(rp_dot(ex, ey, ez, ex, ey, ez) <= rr * rr)) continue;
-                        float u0, u1, u2, un;
-                        if constexpr (kCh == 4) {
-                            const float4 u = reinterpret_cast<const float4 *>(u_s)[aq];
-                            u0 = u.x, u1 = u.y, u2 = u.z, un = u.w;
-                        } else {
-                            u0 = u_s[3 * aq], u1 = u_s[3 * aq + 1], u2 = u_s[3 * aq + 2], un = ns;
-                        }
-                        if (!dn_finite3(u0, u1, u2) || !(un > 0.0f)) continue;
+                        if (!(dot3(ex, ey, ez, ex, ey, ez) <= rr * rr)) continue;
+                        const float4 u = plane_texel<kCh>(u_s, aq, ns);
+                        if (!rt::usable(u.x, u.y, u.z, u.w)) continue;
                         // rule 18: the history
                         sw = sw + b;
-                        sn = sn + b * un;
-                        sc0 = sc0 + b * u0;
-                        sc1 = sc1 + b * u1;
-                        sc2 = sc2 + b * u2;
+                        sn = sn + b * u.w;
+                        sc0 = sc0 + b * u.x;
+                        sc1 = sc1 + b * u.y;
+                        sc2 = sc2 + b * u.z;
                     }
             }
         }
@@ -119,29 +87,13 @@ __global__ void __launch_bounds__(kRpLanes) rt_reproject_kernel(float4 *__restri
     const bool have_d = nd != 0.0f;
     float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
     if (have_d) c0 = col_d[3 * at], c1 = col_d[3 * at + 1], c2 = col_d[3 * at + 2];
-    float4 T = make_float4(c0, c1, c2, nd);
-    if (sw > 0.0f) {
-        float nh = sn / sw;
-        if (nh > max_history) nh = max_history;
-        const float h0 = sc0 / sw, h1 = sc1 / sw, h2 = sc2 / sw;
-        if (!have_d) T = make_float4(h0, h1, h2, nh);
-        else {
-            const float inv = 1.0f / (nd + nh);
-            T = make_float4((c0 * nd + h0 * nh) * inv, (c1 * nd + h1 * nh) * inv, (c2 * nd + h2 * nh) * inv, nd + nh);
-        }
-    }
-    out[at] = T;
-    const bool f = fast != 0;
-    out_px[(size_t)y * (size_t)w + (size_t)x] = dn_to_int(T.x, f) | (dn_to_int(T.y, f) << 8) | (dn_to_int(T.z, f) << 16);
+    float t0, t1, t2, tn;
+    rt::temporal_blend(t0, t1, t2, tn, c0, c1, c2, nd, have_d, sw, sn, sc0, sc1, sc2, max_history);
+    out[at] = make_float4(t0, t1, t2, tn);
+    out_px[(size_t)y * (size_t)w + (size_t)x] = pack_rgb(t0, t1, t2, fast != 0);
 }
 
 using namespace rt;
-
-namespace {
-
-RpCamera kernel_camera(const rt_camera &m) { return RpCamera{ m.orig.x, m.orig.y, m.orig.z, m.dir.x, m.dir.y, m.dir.z, m.x.x, m.x.y, m.x.z, m.y.x, m.y.y, m.y.z }; }
-
-}  // namespace
 
 extern "C" {
 
@@ -157,9 +109,7 @@ RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_param
     if (rt_host_reproject_params(p, &q) != RT_OK) return RT_ERR_ARG;
     for (const rt_ctx *c : { dst, src }) {
         const char *who = c == dst ? "the destination" : "the source";
-        if (!c->scene.state.features_current || !c->scene.d_features)
-            return fail(RT_ERR_STATE, "%s: the feature plane of %s is not current (rt_features_async forms it; rt_set_scene, rt_update_spheres_async and "
-                                      "rt_set_camera end it)", call, who);
+        RT_TRY(features_refuse(c, call, "", c == dst ? " of the destination" : " of the source"));
         if (c->frame.ragged) return fail(RT_ERR_STATE, "%s: %s is ragged (its tiles hold different pass counts)", call, who);
     }
     if (dst->scene.tables.n_spheres != src->scene.tables.n_spheres)
@@ -178,12 +128,11 @@ RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_param
     if (rc == RT_OK) rc = refresh_tables(dst, stream);
     if (rc == RT_OK) rc = refresh_tables(src, stream);
     if (rc != RT_OK) return rc;
-    const dim3 grid((unsigned)((dst->w + kRpTileW - 1) / kRpTileW), (unsigned)((dst->h + kRpTileH - 1) / kRpTileH));
     const auto kernel = from_temporal ? rt_reproject_kernel<4> : rt_reproject_kernel<3>;
-    hipLaunchKernelGGL(kernel, grid, dim3(kRpLanes), 0, stream, reinterpret_cast<float4 *>(dst->d_temporal), dst->d_temporal_px,
+    hipLaunchKernelGGL(kernel, plane_grid(dst->w, dst->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(dst->d_temporal), dst->d_temporal_px,
                        reinterpret_cast<const float4 *>(dst->scene.d_features), reinterpret_cast<const float4 *>(src->scene.d_features),
                        (const float *)dst->d_colors, (const float *)(from_temporal ? src->d_temporal : src->d_colors), dst->scene.tables.geom, src->scene.tables.geom,
-                       dst->scene.tables.n_spheres, kernel_camera(dst->cam), kernel_camera(src->cam), q.k_pos, q.max_history, (float)dst->frame.current_sample,
+                       dst->scene.tables.n_spheres, pixel_camera(dst->cam), pixel_camera(src->cam), q.k_pos, q.max_history, (float)dst->frame.current_sample,
                        (float)src->frame.current_sample, dst->w, dst->h, dst->knobs.fast() ? 1 : 0);
     HIP_TRY(hipGetLastError());
     dst->frame.reprojected();
@@ -191,15 +140,8 @@ RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_param
 }
 
 RT_API int rt_read_temporal(rt_ctx *c, float *rgbn_host, uint32_t *packed_host) {
-    int rc = tiles_refuse(c, "rt_read_temporal");
-    if (rc != RT_OK) return rc;
-    if (!rgbn_host && !packed_host) return fail(RT_ERR_ARG, "rt_read_temporal: both buffers are null");
-    if (!temporal_current(c))
-        return fail(RT_ERR_STATE, "rt_read_temporal: the context holds no current temporal plane (rt_reproject_async forms one; whatever moves the colour plane or "
-                                  "ends the feature plane ends it)");
-    if (rgbn_host) RT_TRY(read_back(c, rgbn_host, c->d_temporal, 4 * image_pixels(c) * sizeof(float), packed_host == nullptr));
-    if (packed_host) RT_TRY(read_back(c, packed_host, c->d_temporal_px, image_pixels(c) * sizeof(uint32_t)));
-    return RT_OK;
+    return read_plane4(c, "rt_read_temporal", rgbn_host, packed_host, temporal_current, &rt_ctx::d_temporal, &rt_ctx::d_temporal_px,
+                       "temporal plane (rt_reproject_async forms one; whatever moves the colour plane or ends the feature plane ends it)");
 }
 
 }  // extern "C"

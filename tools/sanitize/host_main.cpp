@@ -47,5 +47,27 @@ int main() {
         filtered += rt_atrous_planes(out.data(), u3.data(), 3, 16, fd.data(), w, h, &at) == RT_OK;
         filtered += rt_atrous_planes(out.data(), u4.data(), 4, 0, fd.data(), w, h, &at) == RT_OK;
         printf("atrous %dx%d: %d of 2 ok, v %g\n", w, h, filtered, out[3]);
+        // the NL-means host statements on halves of the same sizes, with and without the guide (the feature plane above), search radius 0 and 2, patch
+        // radius 0 and 2: with the calls above, every function of rt_rules.h has run
+        std::vector<float> ha(3 * px), hb(3 * px), merged(3 * px), fa(3 * px), fb(3 * px);
+        for (size_t i = 0; i < 3 * px; ++i) {
+            ha[i] = 0.25f + 0.001f * (float)(i % 97);
+            hb[i] = 0.30f - 0.002f * (float)(i % 53);
+            merged[i] = (ha[i] + hb[i]) * 0.5f;
+        }
+        rt_guide_params gp;
+        rt_guide_defaults(&gp);
+        int denoised = 0;
+        for (int guided = 0; guided <= 1; ++guided)
+            for (int R = 0; R <= 2; R += 2)
+                for (int P = 0; P <= 2; P += 2) {
+                    rt_denoise_params dp;
+                    rt_denoise_defaults(&dp);
+                    dp.search_radius = R;
+                    dp.patch_radius = P;
+                    denoised += rt_denoise_guided_planes(fa.data(), merged.data(), ha.data(), hb.data(), guided ? fd.data() : nullptr, w, h, &dp, guided ? &gp : nullptr) == RT_OK;
+                    denoised += rt_denoise_pair_guided_planes(fa.data(), fb.data(), ha.data(), hb.data(), guided ? fd.data() : nullptr, w, h, &dp, guided ? &gp : nullptr) == RT_OK;
+                }
+        printf("denoise %dx%d: %d of 16 ok, f %g\n", w, h, denoised, fa[0]);
     }
 }

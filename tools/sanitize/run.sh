@@ -21,6 +21,7 @@ PY
 gcc -std=c11 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -mfma -ffp-contract=off -I$R/oracle \
     $R/tools/sanitize/oracle_main.c $R/oracle/rt_oracle.c -o $T/oracle_san -lm -lpthread
 $T/oracle_san
+# (rt_host.cpp finds csrc/rt_rules.h beside itself: the host statements of the filters, and through them every rule, run in host_san)
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -ffp-contract=off -I$R/include \
     $R/tools/sanitize/host_main.cpp $R/raytracing_simple_amd/csrc/rt_host.cpp -o $T/host_san
 # the hierarchy's host builders (rt_bvh_host.cpp alone: plain C++), both shapes, on generated record sets
