@@ -875,7 +875,8 @@ RT_API int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, co
  * WHAT THE FILTER DOES NOT DO: it never feeds back.  T, the colour plane, seeds, pass number, counters, selection, tile order and rt_last_kernel stay
  * as they are; rt_reproject_async reads T, never A, so history stays unfiltered and no bias accumulates across frames.  A is a frame to show.
  * LIMITS: the guidance is the FIRST hit's: inside a mirror or a glass sphere only the luminance test protects edges.  The variance estimate is spatial
- * (3x3, one frame) and over-estimates on shadow edges, which it therefore softens.
+ * (3x3, one frame) and over-estimates on shadow edges, which it therefore softens ("temporal luminance moments" below offers an estimate from the
+ * pixel's history in its place, off by default).
  * MEASURED, in numpy on a CPU before any kernel existed (the prototype; tests/test_atrous_cpu.py holds the restatement), in the set-up of the table of
  * "temporal reprojection" (origin moved sideways by 2 %, S 16 passes of stream 1, D 2 passes of stream 2, truth 1024 oracle passes -- 512 at 192x192 --
  * PSNR over 8-bit channels), T = rt_reproject_planes' output, "D alone" = D's colour plane with n = 2 everywhere, k_lum 1.5, k_normal 0.3; dB:
@@ -928,6 +929,94 @@ RT_API int rt_read_atrous(rt_ctx *ctx, float *rgbv_host, uint32_t *packed_host);
  * output may not overlap the inputs.  Needs no device.  RT_ERR_ARG: a null plane, channels other than 3 or 4, negative passes, w or h < 1, parameters
  * rt_atrous_async refuses.                                                                                                                       */
 RT_API int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int passes, const float *feat, int w, int h, const rt_atrous_params *p);
+
+/* ---- temporal luminance moments: the a-trous variance from a pixel's history -----------------------------
+ * Rule 21 estimates the variance the a-trous filter is steered by from ONE frame, a 3x3 neighbourhood, and so mistakes structure for noise: it
+ * over-estimates on shadow edges and inside mirrors and glass.  The interactive loop already follows a surface point through many frames, each
+ * rendered on a seed stream of its own, so how a pixel's luminance varied FROM FRAME TO FRAME measures its noise and not its neighbourhood: a static
+ * shadow edge has low temporal variance, a noisy flat wall a high one.  This section carries the first and second luminance moments and a frame count
+ * through rt_reproject_async and lets rt_atrous_async take V0 from them (Schied et al.'s SVGF, 2017).  THIS LIBRARY'S OWN EXTENSION: it reproduces no
+ * reference frame and touches no render kernel, and WITH THE SETTING OFF, WHICH IS THE DEFAULT, every call above is what it was.
+ *
+ * THE MOMENTS PLANE is M[h][w][4] floats in the colour plane's row order, owned by dst: (m1, m2, k, v) -- the mean luminance of the pixel's history,
+ * the mean of its square, the number of frames behind it, and the variance estimate of rule 27.  rt_reproject_async(dst, src, ..) forms it beside T
+ * while the setting is ON FOR dst; it is allocated on first use and freed by rt_destroy.  M IS CURRENT exactly while dst's temporal plane is current
+ * AND that plane's last rt_reproject_async ran with the setting on: its currency is derived from T's, not a state of its own.  rt_atrous_async(ctx, ..)
+ * applies rule 28 when the setting is on for ctx AND M is current -- that test alone decides; turning the setting off or on moves no plane.
+ *
+ * THE ARITHMETIC, the same in the kernels and in the two host functions: binary32, uncontracted, in the written order, IEEE division -- ALWAYS
+ * parity's arithmetic.  lum is rule 20's; D, S, U, b, sw, sn, nd, nh and inv are those of rules 15-19.
+ *  25. a tap's moments.  The taps COUNT exactly as in rule 17; moments never decide whether a tap counts.  While S's moments plane MS is current,
+ *      (m1q, m2q, kq) are words 0-2 of MS[q].  Otherwise lq = lum(U[q]) and (m1q, m2q, kq) = (lq, lq * lq, 1.0f): an S without the setting, an S whose
+ *      temporal plane was formed without it, and an S read through its colour plane -- whatever S holds then counts as ONE frame.
+ *  26. the history's moments.  s1 = s2 = sk = 0.0f; each counted tap, in tap order, adds b * m1q, b * m2q and b * kq.  With history (sw > 0.0f):
+ *      h1 = s1 / sw, h2 = s2 / sw, hk = sk / sw, and with nr = sn / sw (rule 18's nh before its cap): if (nr > max_history) hk = hk * (max_history / nr)
+ *      -- frames are capped in proportion to samples.
+ *  27. the blend.  lD = lum(CD).  No history and nd == 0: four 0.0f.  No history otherwise: (lD, lD * lD, 1.0f, 0.0f).  History and nd == 0:
+ *      (h1, h2, hk, v).  Otherwise m1 = (lD * nd + h1 * nh) * inv, m2 = ((lD * lD) * nd + h2 * nh) * inv, k = hk + 1.0f.
+ *      The estimate: d = m2 - m1 * m1; v = (k > 1.0f && d > 0.0f) ? d / (k - 1.0f) : 0.0f (a NaN makes both comparisons false).
+ *      Why this form: T is the sample-weighted mean of per-frame means l_k, and for K frames of equal counts
+ *      Var(T) = sum (l_k - m1)^2 / (K (K - 1)) = (m2 - m1^2) / (K - 1).  With unequal counts and under the cap it is an APPROXIMATION.
+ *  28. V0 from history.  In rt_atrous_async's preparation step, for a pixel p that is usable (rule 20) with M[p].k >= k_min: V0[p] = M[p].v.  Every
+ *      other pixel keeps rule 21.  Rules 22-24 are unchanged.  When rt_atrous_async filters the colour plane (no current T), M is not consulted.
+ * INVARIANTS: (a) T and its packed plane are bit for bit the same with the setting on or off.  (b) With k_min larger than any k present the a-trous
+ * output is bit for bit the plain one.  (c) With levels = 0, A's variance word is M's v where rule 28 applies.
+ * LIMITS: like T, the moments follow the FIRST hit: what a mirror shows of a moving scene lags, and its frame-to-frame change counts as noise.  The
+ * estimate is an approximation where frames hold unequal sample counts and under max_history's cap; below k_min frames rule 21 stands in.
+ * k is a weighted MEAN of the taps' frame counts, not an integer: a pixel whose four taps all held 3 frames may come out a rounding below 4 after the
+ * next blend, and then needs one frame more to reach k_min 4.
+ * MEASURED, in numpy on a CPU before any kernel existed (the prototype; tests/test_moments_cpu.py holds the restatement), with frames of this
+ * project's oracle alone: 96x96, EIGHT frames of 2 passes, frame f on seed stream f from an origin moved sideways by f * 0.5 % of its distance to
+ * the target, two sides taking turns as INTENDED USE above has it (the first frame's colour plane is the second's source), the defaults of
+ * rt_reproject_async, truth 1024 oracle passes of the last view, PSNR over 8-bit channels as in the tables above; A by rule 21 against A by rule 28
+ * (k_min 4) at EQUAL levels, dB:
+ *     scene      last T    rule 21, levels 1 / 3 / 5    rule 28, levels 1 / 3 / 5    gain at 3     pixels at k >= 4
+ *     cornell    22.13     25.26 / 26.68 / 26.81        26.07 / 27.94 / 27.95        +1.26            99.9 %
+ *     simple     27.68     29.16 / 28.89 / 28.52        29.58 / 29.61 / 29.19        +0.72            52.9 %
+ *     Demo       24.69     27.34 / 27.03 / 26.21        27.59 / 27.10 / 26.26        +0.06            78.5 %
+ * The same over the pixels within 2 pixels of a SHADOW EDGE -- defined on the truth frame: a pair of 4-neighbours that show the same diffuse record
+ * with normals within 0.1 of each other, both luminances below 1, differing by more than 35 % of the larger; on these scenes the rims of shadows and,
+ * under glass spheres, of caustics; 10.6 / 10.3 / 20.4 % of the pixels:
+ *     cornell    21.49     24.13 / 24.38 / 24.37        24.62 / 24.45 / 24.34        +0.07
+ *     simple     22.50     23.26 / 22.46 / 22.35        24.11 / 23.92 / 23.80        +1.47
+ *     Demo       20.95     23.46 / 22.78 / 22.16        23.53 / 22.58 / 21.98        -0.20
+ * So the estimate pays on the whole frame of the two fixtures (+1.3 and +0.7 dB at three levels, at every level measured) and does nothing for Demo
+ * (+0.06 dB); at shadow edges, which it was meant for, it gains 1.5 dB on `simple`, nothing on cornell beyond one level, and LOSES 0.2 dB on Demo at
+ * three and five levels, where the edges lie under glass spheres whose caustics flicker from frame to frame: a high temporal variance there opens the
+ * luminance stop across the edge.  k_min stays at 4.  tests/test_moments_cpu.py asserts half of the two whole-frame gains and, for Demo, no more than
+ * 0.3 dB below rule 21, with the two host functions.
+ * MEASURED on an MI355X by tools/moments_probe.py (profiles/r32_moments.jsonl; device time between two events, the device idle before the first, the
+ * setting ON and OFF alternating call by call in one process, medians of 12 each; NO TIME IS PROMISED), the Demo scene, 800x600 / 1920x1080, on against
+ * off: rt_reproject_async from a source's colour plane 0.0213 against 0.0195 ms / 0.0612 against 0.0568 ms (+8 %: the 16-byte store and the sums);
+ * from a source's temporal and moments planes 0.0231 against 0.0196 ms / 0.0764 against 0.0578 ms (+32 % at 1920x1080: the extra 16-byte load per
+ * tap costs more than the estimate of one load in five assumed); rt_atrous_async with no level -- the preparation kernel alone -- 0.0238 against
+ * 0.0238 ms / 0.0786 against 0.0757 ms, with three levels 0.1598 against 0.1582 ms / 0.5773 against 0.5744 ms.  The interactive frame (features, a
+ * pass, reprojection, three levels: about 0.75 ms at 1920x1080) grows by some 0.02 ms.  The quality table from rendered contexts, reprojected and
+ * filtered on the device: the prototype's figures above to the last digit, all three scenes, both tables.                                           */
+typedef struct { float k_min; uint32_t reserved[3]; } rt_moments_params;   /* 16 bytes; k_min finite and >= 1, reserved 0 */
+
+/* {4.0f, {0, 0, 0}} -- SVGF's four frames.  Needs no device.                                                                     */
+RT_API void rt_moments_defaults(rt_moments_params *p);
+
+/* The context's setting that rt_reproject_async INTO it and rt_atrous_async OF it consult, as rt_set_denoise_guide's is consulted by the filters;
+ * NULL turns it off (the default).  Moves no plane and ends none.  RT_ERR_ARG: a null, multi-device or sharded context, k_min not finite or < 1,
+ * reserved words not 0.  A refused call changes nothing.                                                                                          */
+RT_API int rt_set_temporal_moments(rt_ctx *ctx, const rt_moments_params *m);
+
+/* The context's moments plane, 4 floats per pixel (m1, m2, k, v) in the colour plane's row order.  Blocking.  RT_ERR_STATE when M is not current;
+ * RT_ERR_ARG for a null, multi-device or sharded context or a null buffer.                                                                         */
+RT_API int rt_read_moments(rt_ctx *ctx, float *m_host);
+
+/* Rules 15-19 and 25-27 as plain host loops into out_rgbn[h][w][4] and out_m[h][w][4]: what the device is tested against bit for bit.  out_rgbn is
+ * rt_reproject_planes' output bit for bit.  `src_m` is S's moments plane [h][w][4], or NULL for rule 25's luminance of U.  RT_ERR_ARG: a null
+ * output, and whatever rt_reproject_planes refuses.                                                                                               */
+RT_API int rt_reproject_moments_planes(float *out_rgbn, float *out_m, const rt_reproject_view *dst, const rt_reproject_view *src,
+                                        const float *src_m /* [h][w][4] or NULL */, uint32_t count, int w, int h, const rt_reproject_params *p);
+
+/* Rules 20-23 with rule 28 as plain host loops; `m` is the moments plane [h][w][4], NULL = rule 21 everywhere (rt_atrous_planes bit for bit).  `mp`
+ * == NULL means the defaults.  RT_ERR_ARG: whatever rt_atrous_planes refuses, and parameters rt_set_temporal_moments refuses.                       */
+RT_API int rt_atrous_moments_planes(float *out_rgbv, const float *plane, int channels, int passes, const float *m /* NULL = rule 21 everywhere */,
+                                     const float *feat, int w, int h, const rt_atrous_params *p, const rt_moments_params *mp);
 
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it

@@ -30,7 +30,8 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_guide_defaults", "rt_features_async", "rt_read_features", "rt_features_planes", "rt_set_denoise_guide",
            "rt_denoise_guided_planes", "rt_denoise_pair_guided_planes",
            "rt_reproject_defaults", "rt_reproject_async", "rt_read_temporal", "rt_reproject_planes",
-           "rt_atrous_defaults", "rt_atrous_async", "rt_read_atrous", "rt_atrous_planes"]
+           "rt_atrous_defaults", "rt_atrous_async", "rt_read_atrous", "rt_atrous_planes",
+           "rt_moments_defaults", "rt_set_temporal_moments", "rt_read_moments", "rt_reproject_moments_planes", "rt_atrous_moments_planes"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -103,6 +104,14 @@ class AtrousParams(C.Structure):
 
     def as_dict(self):
         return {"levels": int(self.levels), "k_lum": float(self.k_lum), "k_normal": float(self.k_normal), "reserved": int(self.reserved)}
+
+
+class MomentsParams(C.Structure):
+    """include/rt_api.h rt_moments_params (16 bytes): k_min (finite, >= 1), three reserved words (0)."""
+    _fields_ = [("k_min", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {"k_min": float(self.k_min), "reserved": [int(v) for v in self.reserved]}
 
 
 class _Scene(C.Structure):
@@ -209,6 +218,11 @@ def load_library(diag=False):
         "rt_atrous_async": (i32, [vp, C.POINTER(AtrousParams), vp]),
         "rt_read_atrous": (i32, [vp, vp, vp]),
         "rt_atrous_planes": (i32, [vp, vp, i32, i32, vp, i32, i32, C.POINTER(AtrousParams)]),
+        "rt_moments_defaults": (None, [C.POINTER(MomentsParams)]),
+        "rt_set_temporal_moments": (i32, [vp, C.POINTER(MomentsParams)]),
+        "rt_read_moments": (i32, [vp, vp]),
+        "rt_reproject_moments_planes": (i32, [vp, vp, C.POINTER(ReprojectView), C.POINTER(ReprojectView), vp, u32, i32, i32, C.POINTER(ReprojectParams)]),
+        "rt_atrous_moments_planes": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, C.POINTER(AtrousParams), C.POINTER(MomentsParams)]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -638,6 +652,23 @@ class RtContext:
         """rt_atrous_defaults (the module-level atrous_defaults)."""
         return atrous_defaults()
 
+    # --- temporal luminance moments (rt_reproject.hip, rt_atrous.hip) ------------------------------
+    def set_temporal_moments(self, moments=None):
+        """rt_set_temporal_moments: None switches the setting off; a MomentsParams or a dict of fields laid over moments_defaults() switches it
+        on: reproject_async INTO this context then forms its moments plane too, and atrous_async takes V0 from it (rule 28) while it is current."""
+        self._check(self._lib.rt_set_temporal_moments(self._h, _moments_params(moments)))
+
+    def read_moments(self):
+        """rt_read_moments: the moments plane, float32 [h][w][4] (m1, m2, k, v) in the colour plane's row order."""
+        m = np.zeros((self.h, self.w, 4), np.float32)
+        self._check(self._lib.rt_read_moments(self._h, _ptr(m)))
+        return m
+
+    @staticmethod
+    def moments_defaults():
+        """rt_moments_defaults (the module-level moments_defaults)."""
+        return moments_defaults()
+
     def read_filtered(self):
         """rt_read_filtered: the cross-filtered plane, float32 [3 * w * h] as read_colors() lays it out."""
         out = np.zeros(3 * self.w * self.h, np.float32)
@@ -845,6 +876,14 @@ def reproject_planes(dst, src, w, h, params=None):
     """rt_reproject_planes: rules 15-19 on HOST planes; returns the temporal plane, float32 [h][w][4].  `dst` and `src` are dicts, one per side:
     plane ([h][w][3] as read_colors() returns it, or [h][w][4] as read_temporal() does; dst's may be None at passes 0), passes, feat ([h][w][8]),
     cam (15 floats), spheres (records; both sides the same count).  Needs no device."""
+    keep, views, count = _reproject_views(dst, src, w, h)
+    out = np.zeros((h, w, 4), np.float32)
+    _check(load_library().rt_reproject_planes(_ptr(out), C.byref(views[0]), C.byref(views[1]), count, w, h, _reproject_params(params)))
+    return out
+
+
+def _reproject_views(dst, src, w, h):
+    """The two rt_reproject_view records of the sides' dicts, the arrays they point into (to be kept alive) and the record count."""
     keep, views = [], []
     count = None
     for side in (dst, src):
@@ -865,9 +904,41 @@ def reproject_planes(dst, src, w, h, params=None):
         keep += [sph, cam, feat, plane]
         views.append(ReprojectView(plane.ctypes.data if plane is not None else None, channels, int(side["passes"]), feat.ctypes.data, cam.ctypes.data,
                                    sph.ctypes.data if count else None))
-    out = np.zeros((h, w, 4), np.float32)
-    _check(load_library().rt_reproject_planes(_ptr(out), C.byref(views[0]), C.byref(views[1]), count, w, h, _reproject_params(params)))
-    return out
+    return keep, views, count
+
+
+def moments_defaults():
+    """rt_moments_defaults: MomentsParams {4.0, {0, 0, 0}}.  Needs no device."""
+    p = MomentsParams()
+    load_library().rt_moments_defaults(C.byref(p))
+    return p
+
+
+def _moments_params(params):
+    """None, a MomentsParams, or a dict of fields laid over the defaults -> what the C call takes."""
+    if params is None or isinstance(params, MomentsParams):
+        return C.byref(params) if params is not None else None
+    p = moments_defaults()
+    for name, value in dict(params).items():
+        if name != "k_min":
+            raise ValueError("rt_moments_params has no field %r" % name)
+        setattr(p, name, value)
+    return C.byref(p)
+
+
+def reproject_moments_planes(dst, src, w, h, src_m=None, params=None):
+    """rt_reproject_moments_planes: rules 15-19 and 25-27 on HOST planes; returns (the temporal plane, the moments plane), float32 [h][w][4] each.
+    `dst` and `src` as reproject_planes takes them; `src_m` is the source's moments plane [h][w][4], or None for rule 25's luminance of its plane.
+    Needs no device."""
+    keep, views, count = _reproject_views(dst, src, w, h)
+    if src_m is not None:
+        src_m = np.ascontiguousarray(src_m, dtype=np.float32).reshape(-1)
+        if src_m.size != 4 * w * h:
+            raise ValueError("a moments plane of %d floats, got %d" % (4 * w * h, src_m.size))
+    out, out_m = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+    _check(load_library().rt_reproject_moments_planes(_ptr(out), _ptr(out_m), C.byref(views[0]), C.byref(views[1]), _ptr(src_m) if src_m is not None else None,
+                                                      count, w, h, _reproject_params(params)))
+    return out, out_m
 
 
 def atrous_defaults():
@@ -900,6 +971,26 @@ def atrous_planes(plane, feat, w, h, passes=0, params=None):
         raise ValueError("a feature plane of %d floats, got %d" % (8 * w * h, feat.size))
     out = np.zeros((h, w, 4), np.float32)
     _check(load_library().rt_atrous_planes(_ptr(out), _ptr(plane), plane.size // (w * h), int(passes), _ptr(feat), w, h, _atrous_params(params)))
+    return out
+
+
+def atrous_moments_planes(plane, feat, w, h, passes=0, m=None, params=None, moments=None):
+    """rt_atrous_moments_planes: rules 20-23 with rule 28 on HOST planes; returns the filtered plane, float32 [h][w][4] (rgb, variance).  `plane`,
+    `feat`, `passes` and `params` as atrous_planes takes them; `m` is the moments plane [h][w][4] (None: rule 21 everywhere); `moments`: a
+    MomentsParams, a dict of its fields over the defaults, or None for the defaults.  Needs no device."""
+    plane = np.ascontiguousarray(plane, dtype=np.float32).reshape(-1)
+    if plane.size not in (3 * w * h, 4 * w * h):
+        raise ValueError("a plane of %d or %d floats, got %d" % (3 * w * h, 4 * w * h, plane.size))
+    feat = np.ascontiguousarray(feat, dtype=np.float32).reshape(-1)
+    if feat.size != 8 * w * h:
+        raise ValueError("a feature plane of %d floats, got %d" % (8 * w * h, feat.size))
+    if m is not None:
+        m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+        if m.size != 4 * w * h:
+            raise ValueError("a moments plane of %d floats, got %d" % (4 * w * h, m.size))
+    out = np.zeros((h, w, 4), np.float32)
+    _check(load_library().rt_atrous_moments_planes(_ptr(out), _ptr(plane), plane.size // (w * h), int(passes), _ptr(m) if m is not None else None, _ptr(feat), w, h,
+                                                   _atrous_params(params), _moments_params(moments)))
     return out
 
 

@@ -6,7 +6,8 @@
 // the comments below name the rule a line implements.  The reference filters nothing: this is the library's own extension.
 // This unit is compiled with parity's flags (-ffp-contract=off, correctly rounded division): every multiply, add and division below is an operation of
 // its own, in the written order -- whatever rt_set_mode says.
-// The render kernels are not touched, and nothing here writes anything but the context's five filter planes.
+// The render kernels are not touched, and nothing here writes anything but the context's five filter planes.  The preparation kernel's STATEMENTS
+// are rt_atrous_prepare_body.inc.h, shared with rt_moments.hip, whose instance takes V0 from the moments plane (rule 28) when the setting is on.
 //
 // The shape.  rt_atrous_prepare_kernel evaluates rules 20-21 once: it writes (rgb, V0), a 16-byte guide texel (N, id) and beside it one float that is
 // n for a usable pixel and +0.0f for any other -- so a level reads three aligned words per tap (4, 16 and 16 bytes) instead of picking words 3-5 and 7
@@ -36,35 +37,10 @@ extern "C" int rt_host_atrous_params(const rt_atrous_params *p, rt_atrous_params
 template <int kCh>
 __global__ void __launch_bounds__(kPlaneLanes) rt_atrous_prepare_kernel(float4 *__restrict__ out, float4 *__restrict__ guide, float *__restrict__ n_out, uint32_t *__restrict__ px,
                                                                         const float *__restrict__ u, const float4 *__restrict__ feat, float n_all, int w, int h, int fast) {
-    const auto [x, y] = plane_pixel();
-    if (x >= w || y >= h) return;
-    const size_t at = (size_t)y * (size_t)w + (size_t)x;
-    const float4 up = plane_texel<kCh>(u, at, n_all);
-    const float4 f_lo = feat[2 * at], f_hi = feat[2 * at + 1];
-    const uint32_t id = __float_as_uint(f_hi.w);
-    // rule 21
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-            const int qx = x + dx, qy = y + dy;
-            if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
-            const size_t aq = (size_t)qy * (size_t)w + (size_t)qx;
-            if (__float_as_uint(feat[2 * aq + 1].w) != id) continue;
-            const float4 uq = plane_texel<kCh>(u, aq, n_all);
-            if (!rt::usable(uq.x, uq.y, uq.z, uq.w)) continue;
-            const float l = rt::luminance(uq.x, uq.y, uq.z);
-            s0 = s0 + 1.0f;
-            s1 = s1 + l;
-            s2 = s2 + l * l;
-        }
-    const float v0 = rt::variance_of_sums(s0, s1, s2);
-    const bool usable = rt::usable(up.x, up.y, up.z, up.w);      // rule 20
-    out[at] = make_float4(up.x, up.y, up.z, v0);
-    guide[at] = make_float4(f_lo.w, f_hi.x, f_hi.y, f_hi.w);
-    n_out[at] = usable ? up.w : 0.0f;
-    if (px) px[(size_t)(h - 1 - y) * (size_t)w + (size_t)x] = pack_rgb(up.x, up.y, up.z, fast != 0);
+    constexpr bool kMom = false;                            // the moments arm (rt_moments.hip) is discarded: its plane and k_min are not arguments here
+    constexpr const float2 *m = nullptr;
+    constexpr float k_min = 0.0f;
+#include "rt_atrous_prepare_body.inc.h"
 }
 
 // Rule 22, one lane per pixel, 25 taps at step s.  `n` is the preparation kernel's plane: n > 0.0f says usable.  The tap rows run as a loop, the five
@@ -157,11 +133,15 @@ RT_API int rt_atrous_async(rt_ctx *c, const rt_atrous_params *p, void *hip_strea
     float4 *cur = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? c->d_atrous : c->d_atrous_tmp);
     float4 *nxt = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? c->d_atrous_tmp : c->d_atrous);
     float4 *const guide = reinterpret_cast<float4 *>(c->d_atrous_guide);
-    const auto prepare = from_temporal ? rt_atrous_prepare_kernel<4> : rt_atrous_prepare_kernel<3>;
-    hipLaunchKernelGGL(prepare, grid, dim3(kPlaneLanes), 0, stream, cur, guide, c->d_atrous_n, q.levels == 0 ? c->d_atrous_px : (uint32_t *)nullptr,
-                       (const float *)(from_temporal ? c->d_temporal : c->d_colors), reinterpret_cast<const float4 *>(c->scene.d_features),
-                       (float)c->frame.current_sample, c->w, c->h, fast);
-    HIP_TRY(hipGetLastError());
+    if (c->have_moments && moments_current(c)) {        // rule 28: the setting on AND M current (which implies from_temporal); nothing else decides
+        RT_TRY(atrous_prepare_moments(c, cur, q.levels == 0, stream));       // rt_moments.hip: the preparation kernel with the moments arm
+    } else {
+        const auto prepare = from_temporal ? rt_atrous_prepare_kernel<4> : rt_atrous_prepare_kernel<3>;
+        hipLaunchKernelGGL(prepare, grid, dim3(kPlaneLanes), 0, stream, cur, guide, c->d_atrous_n, q.levels == 0 ? c->d_atrous_px : (uint32_t *)nullptr,
+                           (const float *)(from_temporal ? c->d_temporal : c->d_colors), reinterpret_cast<const float4 *>(c->scene.d_features),
+                           (float)c->frame.current_sample, c->w, c->h, fast);
+        HIP_TRY(hipGetLastError());
+    }
     const float inv_kn2 = 1.0f / (q.k_normal * q.k_normal), kl2 = q.k_lum * q.k_lum;
     for (int level = 0; level < q.levels; ++level) {
         hipLaunchKernelGGL(rt_atrous_level_kernel, grid, dim3(kPlaneLanes), 0, stream, nxt, level == q.levels - 1 ? c->d_atrous_px : (uint32_t *)nullptr, cur, guide,

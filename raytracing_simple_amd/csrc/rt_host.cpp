@@ -2,8 +2,8 @@
 //   Either side of the render path: the seed streams (the one the reference draws from the C library, and the numbered ones), the
 //   camera basis, the built-in scene and the .scn reader.
 //   The host statements of the library's extensions, as plain loops, with their defaults and parameter rules: rt_denoise_planes and
-//   rt_denoise_pair_planes with their guided forms (rules 1-6, 13-14), rt_features_planes (rules 10-12), rt_reproject_planes (rules 15-19) and
-//   rt_atrous_planes (rules 20-23).  The kernels are tested against them bit for bit.  The loops, the clamping and the order of the sums are written
+//   rt_denoise_pair_planes with their guided forms (rules 1-6, 13-14), rt_features_planes (rules 10-12), rt_reproject_planes (rules 15-19),
+//   rt_atrous_planes (rules 20-23) and their forms with temporal moments, rt_reproject_moments_planes and rt_atrous_moments_planes (rules 25-28).  The kernels are tested against them bit for bit.  The loops, the clamping and the order of the sums are written
 //   here; the arithmetic of a rule is rt_rules.h's, which the kernels call too.
 #include <cmath>
 #include <cstdarg>
@@ -458,18 +458,24 @@ int rt_host_reproject_params(const rt_reproject_params *p, rt_reproject_params *
     return RT_OK;
 }
 
-int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_reproject_view *src, uint32_t count, int w, int h,
-                        const rt_reproject_params *p) {
-    if (!out_rgbn || !dst || !src) return host_fail("rt_reproject_planes: null argument");
-    if (w < 1 || h < 1) return host_fail("rt_reproject_planes: %dx%d", w, h);
+}  // extern "C"
+
+namespace {
+
+// rules 15-19 and, where out_m is not null, rules 25-27 beside them (src_m: S's moments plane, or null for rule 25's luminance of U): the loops of
+// rt_reproject_planes and rt_reproject_moments_planes, which therefore cannot differ in a word of out_rgbn
+int reproject_loops(const char *call, float *out_rgbn, float *out_m, const rt_reproject_view *dst, const rt_reproject_view *src, const float *src_m, uint32_t count,
+                    int w, int h, const rt_reproject_params *p) {
+    if (!out_rgbn || !dst || !src) return host_fail("%s: null argument", call);
+    if (w < 1 || h < 1) return host_fail("%s: %dx%d", call, w, h);
     for (const rt_reproject_view *v : { dst, src }) {
         const char *side = v == dst ? "dst" : "src";
-        if (v->channels != 3 && v->channels != 4) return host_fail("rt_reproject_planes: %s has %d channels (3 or 4)", side, v->channels);
-        if (v->passes < 0) return host_fail("rt_reproject_planes: %s holds %d passes", side, v->passes);
-        if (!v->feat || !v->cam || (count > 0 && !v->spheres)) return host_fail("rt_reproject_planes: %s has a null feature plane, camera or records", side);
+        if (v->channels != 3 && v->channels != 4) return host_fail("%s: %s has %d channels (3 or 4)", call, side, v->channels);
+        if (v->passes < 0) return host_fail("%s: %s holds %d passes", call, side, v->passes);
+        if (!v->feat || !v->cam || (count > 0 && !v->spheres)) return host_fail("%s: %s has a null feature plane, camera or records", call, side);
     }
-    if (!src->plane) return host_fail("rt_reproject_planes: src has a null plane");
-    if (!dst->plane && dst->passes != 0) return host_fail("rt_reproject_planes: dst has a null plane and %d passes", dst->passes);
+    if (!src->plane) return host_fail("%s: src has a null plane", call);
+    if (!dst->plane && dst->passes != 0) return host_fail("%s: dst has a null plane and %d passes", call, dst->passes);
     rt_reproject_params q;
     if (rt_host_reproject_params(p, &q) != RT_OK) return RT_ERR_ARG;
 
@@ -485,6 +491,7 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
         for (int x = 0; x < w; ++x) {
             const size_t at = (size_t)(h - 1 - y) * (size_t)w + (size_t)x;
             float sw = 0.0f, sn = 0.0f, sc[3] = { 0.0f, 0.0f, 0.0f };
+            float s1 = 0.0f, s2 = 0.0f, sk = 0.0f;                    // 26. the history's moments
             // 15. the point and where it was
             uint32_t id;
             memcpy(&id, dst->feat + 8 * at + 7, sizeof id);
@@ -528,6 +535,17 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
                                 sw = sw + b;
                                 sn = sn + b * un;
                                 for (int c = 0; c < 3; ++c) sc[c] = sc[c] + b * u[c];
+                                if (!out_m) continue;
+                                // 25. the tap's moments, 26. their sums
+                                float m1q, m2q, kq;
+                                if (src_m) m1q = src_m[4 * aq], m2q = src_m[4 * aq + 1], kq = src_m[4 * aq + 2];
+                                else {
+                                    const float lq = rt::luminance(u[0], u[1], u[2]);
+                                    m1q = lq, m2q = lq * lq, kq = 1.0f;
+                                }
+                                s1 = s1 + b * m1q;
+                                s2 = s2 + b * m2q;
+                                sk = sk + b * kq;
                             }
                     }
                 }
@@ -536,8 +554,28 @@ int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_
             const float *CD = dst->passes != 0 ? dst->plane + (size_t)cd * at : nullptr;
             float *T = out_rgbn + 4 * at;
             rt::temporal_blend(T[0], T[1], T[2], T[3], CD ? CD[0] : 0.0f, CD ? CD[1] : 0.0f, CD ? CD[2] : 0.0f, nd, CD != nullptr, sw, sn, sc[0], sc[1], sc[2], q.max_history);
+            if (!out_m) continue;
+            // 27. the moments' blend
+            float *M = out_m + 4 * at;
+            const float lD = CD ? rt::luminance(CD[0], CD[1], CD[2]) : 0.0f;
+            rt::moments_blend(M[0], M[1], M[2], M[3], lD, nd, CD != nullptr, sw, sn, s1, s2, sk, q.max_history);
         }
     return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_reproject_view *src, uint32_t count, int w, int h,
+                        const rt_reproject_params *p) {
+    return reproject_loops("rt_reproject_planes", out_rgbn, nullptr, dst, src, nullptr, count, w, h, p);
+}
+
+int rt_reproject_moments_planes(float *out_rgbn, float *out_m, const rt_reproject_view *dst, const rt_reproject_view *src, const float *src_m, uint32_t count, int w,
+                                int h, const rt_reproject_params *p) {
+    if (!out_m) return host_fail("rt_reproject_moments_planes: null argument");
+    return reproject_loops("rt_reproject_moments_planes", out_rgbn, out_m, dst, src, src_m, count, w, h, p);
 }
 
 }  // extern "C"
@@ -565,11 +603,34 @@ int rt_host_atrous_params(const rt_atrous_params *p, rt_atrous_params *out) {
     return RT_OK;
 }
 
-int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int passes, const float *feat, int w, int h, const rt_atrous_params *p) {
-    if (!out_rgbv || !plane || !feat) return host_fail("rt_atrous_planes: null argument");
-    if (w < 1 || h < 1) return host_fail("rt_atrous_planes: %dx%d", w, h);
-    if (channels != 3 && channels != 4) return host_fail("rt_atrous_planes: %d channels (3 or 4)", channels);
-    if (passes < 0) return host_fail("rt_atrous_planes: %d passes", passes);
+void rt_moments_defaults(rt_moments_params *p) {
+    if (!p) return;
+    p->k_min = 4.0f;                    // SVGF's four frames
+    p->reserved[0] = p->reserved[1] = p->reserved[2] = 0;
+}
+
+// the parameter rule rt_set_temporal_moments and rt_atrous_moments_planes share (`p` == null: the defaults); hidden, like rt_host_atrous_params
+int rt_host_moments_params(const rt_moments_params *p, rt_moments_params *out) {
+    rt_moments_defaults(out);
+    if (p) *out = *p;
+    if (!std::isfinite(out->k_min) || !(out->k_min >= 1.f)) return host_fail("rt_moments: k_min %g (finite, >= 1)", (double)out->k_min);
+    if (out->reserved[0] != 0 || out->reserved[1] != 0 || out->reserved[2] != 0)
+        return host_fail("rt_moments: reserved %u, %u, %u (0)", out->reserved[0], out->reserved[1], out->reserved[2]);
+    return RT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// rules 20-23 and, where m is not null, rule 28 in place of rule 21 (k_min from the caller's checked parameters): the loops of rt_atrous_planes and
+// rt_atrous_moments_planes
+int atrous_loops(const char *call, float *out_rgbv, const float *plane, int channels, int passes, const float *m, float k_min, const float *feat, int w, int h,
+                 const rt_atrous_params *p) {
+    if (!out_rgbv || !plane || !feat) return host_fail("%s: null argument", call);
+    if (w < 1 || h < 1) return host_fail("%s: %dx%d", call, w, h);
+    if (channels != 3 && channels != 4) return host_fail("%s: %d channels (3 or 4)", call, channels);
+    if (passes < 0) return host_fail("%s: %d passes", call, passes);
     rt_atrous_params q;
     if (rt_host_atrous_params(p, &q) != RT_OK) return RT_ERR_ARG;
 
@@ -604,7 +665,9 @@ int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int pass
                     s1 = s1 + l;
                     s2 = s2 + l * l;
                 }
-            cur[4 * at + 3] = rt::variance_of_sums(s0, s1, s2);
+            const float v21 = rt::variance_of_sums(s0, s1, s2);
+            // 28. ... or the one the pixel's history holds
+            cur[4 * at + 3] = m ? rt::variance_from_history(usable[at] != 0, m[4 * at + 2], m[4 * at + 3], k_min, v21) : v21;
         }
     // 22., 23. the levels
     const float in =1.0f / (q.k_normal * q.k_normal), kl2 = q.k_lum * q.k_lum;
@@ -651,6 +714,21 @@ int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int pass
         nxt = t;
     }
     return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_atrous_planes(float *out_rgbv, const float *plane, int channels, int passes, const float *feat, int w, int h, const rt_atrous_params *p) {
+    return atrous_loops("rt_atrous_planes", out_rgbv, plane, channels, passes, nullptr, 0.0f, feat, w, h, p);
+}
+
+int rt_atrous_moments_planes(float *out_rgbv, const float *plane, int channels, int passes, const float *m, const float *feat, int w, int h,
+                             const rt_atrous_params *p, const rt_moments_params *mp) {
+    rt_moments_params mq;
+    if (rt_host_moments_params(mp, &mq) != RT_OK) return RT_ERR_ARG;
+    return atrous_loops("rt_atrous_moments_planes", out_rgbv, plane, channels, passes, m, mq.k_min, feat, w, h, p);
 }
 
 }  // extern "C"

@@ -215,6 +215,11 @@ struct rt_ctx {
     float *d_temporal = nullptr;        // rt_reproject_async into this context (rt_reproject.hip): [h][w][4], rgb and the effective sample count, rows as d_colors;
                                         // acquired on first use.  Whether it is current is frame.temporal_current together with scene.state.features_current
     uint32_t *d_temporal_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom)
+    float *d_moments = nullptr;         // ... and, with rt_set_temporal_moments on, the moments plane M beside it: [h][w][4], (m1, m2, k, v), rows as d_colors; acquired
+                                        // on first use.  Whether it is current is temporal_current(c) together with ...
+    bool moments_formed = false;        // ... this: the last rt_reproject_async into this context formed M (written by every such call; no state of its own)
+    rt_moments_params moments{};        // rt_set_temporal_moments: what rt_reproject_async into the context and rt_atrous_async of it consult ...
+    bool have_moments = false;          // ... when it is on
     float *d_atrous = nullptr;          // rt_atrous_async (rt_atrous.hip): [h][w][4], the filtered rgb and its variance, rows as d_colors; acquired on first use, like
                                         // the four below.  Whether it is current is frame.atrous_current together with scene.state.features_current
     uint32_t *d_atrous_px = nullptr;    // ... and its rgb packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom)
@@ -273,6 +278,8 @@ inline size_t color_floats(const rt_ctx *c) { return 3 * image_pixels(c); }
 inline uint32_t *frame_pixels(const rt_ctx *c) { return c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels; }     // the buffer launches write
 // the temporal plane (rt_reproject.hip) is current: formed, the colour plane has not moved since, and the feature plane it was formed under has not ended
 inline bool temporal_current(const rt_ctx *c) { return c->frame.temporal_current && c->scene.state.features_current && c->d_temporal && c->d_temporal_px; }
+// ... and the moments plane beside it: the temporal plane is, and the reprojection that formed it formed M too
+inline bool moments_current(const rt_ctx *c) { return temporal_current(c) && c->moments_formed && c->d_moments; }
 
 // a reset or a written state ends a frame of the current scene for the form choice too (Choice::frame_ended): end_frame(c).reset_in_place()
 inline FrameState &end_frame(rt_ctx *c) { c->choice.frame_ended(); return c->frame; }
@@ -324,6 +331,9 @@ int denoise_pair_tiles(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStre
 int features_refuse(const rt_ctx *c, const char *call, const char *lead = "", const char *of_whom = "");
 // the guide of a pair of halves (rt_set_denoise_guide): RT_ERR_STATE when the two settings differ, or -- on -- a feature plane is not current.  *guided: on
 int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guided = nullptr);
+// ---- rt_moments.hip: the kernels with a moments arm, launched for rt_reproject.hip and rt_atrous.hip (which have checked, chained and acquired) ----
+int reproject_moments(rt_ctx *dst, const rt_ctx *src, const rt_reproject_params &q, bool from_temporal, bool from_moments, hipStream_t stream);
+int atrous_prepare_moments(rt_ctx *c, float4 *out, bool pack, hipStream_t stream);
 // ---- rt_denoise_guided.hip: the filter kernels under a guide, launched for rt_denoise.hip ----
 struct GuidedFilter {
     const float *img[2];                // the frame, or the two halves

@@ -12,6 +12,10 @@ namespace {
 
 constexpr int kPlaneTileW = 32, kPlaneTileH = 8, kPlaneLanes = kPlaneTileW * kPlaneTileH;      // a workgroup's pixels: four wavefronts, as the render kernels'
 
+// The moments arm of the reprojection kernel's statements (rt_reproject_body.inc.h; include/rt_api.h, rule 25): none, a tap's moments from the luminance
+// of U, or from S's moments plane
+enum { kNoMoments = 0, kMomentsOfLuminance = 1, kMomentsOfPlane = 2 };
+
 struct PlanePixel {
     int x, y;
 };

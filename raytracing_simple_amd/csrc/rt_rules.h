@@ -1,6 +1,6 @@
 // rt_rules.h -- the arithmetic of the numbered rules of include/rt_api.h's extensions (feature planes, NL-means and its guide, temporal reprojection,
-// the a-trous filter), stated ONCE: the plain loops of rt_host.cpp (rt_*_planes) and the kernels (rt_features.hip, rt_reproject.hip, rt_atrous.hip,
-// rt_denoise.inc.h) call these functions, so the two sides the GPU tests hold together bit for bit cannot drift apart by a copied line.  Usable from plain
+// the a-trous filter, temporal luminance moments), stated ONCE: the plain loops of rt_host.cpp (rt_*_planes) and the kernels (rt_features.hip,
+// rt_reproject.hip, rt_atrous.hip, rt_moments.hip, rt_denoise.inc.h) call these functions, so the two sides the GPU tests hold together bit for bit cannot drift apart by a copied line.  Usable from plain
 // C++ and from HIP, like rt_bvh_layout.h, whose RT_HD it takes.  Every unit that includes it is compiled with -ffp-contract=off: every multiply, add,
 // division and square root below is an operation of its own, in the written order and parenthesisation -- which is part of the rule.
 // What is NOT here: loops, staging, clamping, and whether a tap that does not count is skipped or predicated.  Those belong to each side.
@@ -149,5 +149,36 @@ RT_RULE void temporal_blend(float &t0, float &t1, float &t2, float &tn, float c0
         }
     }
 }
+
+// rule 27: the variance of a temporal mean from its moments m1 and m2 over k frames; 0 below two frames, never negative (a NaN fails both tests)
+RT_RULE float moments_variance(float m1, float m2, float k) {
+    const float d = m2 - m1 * m1;
+    return (k > 1.0f && d > 0.0f) ? d / (k - 1.0f) : 0.0f;
+}
+
+// rules 26-27: the blend of D's luminance ld (at nd samples; have_d false at pass 0: ld is not counted) with the history of rule 18's sums sw and sn
+// and rule 26's sums s1, s2 and sk, into (m1, m2, k, v).  nh and inv are formed as temporal_blend forms them.
+RT_RULE void moments_blend(float &m1, float &m2, float &k, float &v, float ld, float nd, bool have_d, float sw, float sn, float s1, float s2, float sk,
+                           float max_history) {
+    m1 = have_d ? ld : 0.0f, m2 = have_d ? ld * ld : 0.0f, k = have_d ? 1.0f : 0.0f;
+    if (sw > 0.0f) {
+        float nh = sn / sw;
+        const float h1 = s1 / sw, h2 = s2 / sw;
+        float hk = sk / sw;
+        if (nh > max_history) {
+            hk = hk * (max_history / nh);                          // frames are capped in proportion to samples
+            nh = max_history;
+        }
+        if (!have_d) m1 = h1, m2 = h2, k = hk;
+        else {
+            const float inv = 1.0f / (nd + nh);
+            m1 = (ld * nd + h1 * nh) * inv, m2 = ((ld * ld) * nd + h2 * nh) * inv, k = hk + 1.0f;
+        }
+    }
+    v = moments_variance(m1, m2, k);
+}
+
+// rule 28: V0 of a pixel whose moments texel holds k frames and the estimate v, where rule 21 gives v21
+RT_RULE float variance_from_history(bool usable, float k, float v, float k_min, float v21) { return (usable && k >= k_min) ? v : v21; }
 
 }  // namespace rt

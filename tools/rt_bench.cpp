@@ -5,7 +5,7 @@
 //            [--w W] [--h H] [--spp N] [--passes-per-launch K] [--pin] [--readback-ms T] [--mode parity|fast]
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
 //            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]
-//             [--denoise [--denoise-radius R]] [--filtered [--live-checks]] [--guided]] [--atrous [--atrous-levels N]]
+//             [--denoise [--denoise-radius R]] [--filtered [--live-checks]] [--guided]] [--atrous [--atrous-levels N] [--moments [--moments-kmin K]]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -36,6 +36,11 @@
 //                       feature plane and runs the edge-avoiding wavelet filter over its colour plane (rt_features_async, rt_atrous_async;
 //                       --atrous-levels N: 0 .. 5, default 3); --out is written from the filtered frame.  A further line gives the
 //                       parameters and the wall time of the two calls and the read-back.  Not with --gpus / --rehearse
+//   --moments           with --atrous: the filter takes its variance from a pixel's history (rt_set_temporal_moments; --moments-kmin K: the
+//                       frames a pixel needs, default 4).  A history has to exist for that: two helper contexts of the same scene, view and
+//                       mode take turns for four frames of two passes each on seed streams of their own, reprojecting with the setting on;
+//                       the frame's context then reprojects from the last of them, and the filter runs over ITS TEMPORAL PLANE -- the frame
+//                       blended with those eight older passes -- not over its colour plane.  The line gains the setting and the history
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
@@ -53,6 +58,38 @@
 static int die(const char* what) {
     fprintf(stderr, "%s: %s\n", what, rt_last_error());
     return 1;
+}
+
+// --moments: four frames of history in two helper contexts taking turns, then `ctx` reprojects from the last of them with the setting on
+static int history_moments(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n, const rt_camera& cam, int w, int h, int mode, const rt_moments_params& mp) {
+    const int kFrames = 4, kPasses = 2;
+    rt_ctx* hist[2] = { nullptr, nullptr };
+    for (int k = 0; k < 2; ++k) {
+        if (rt_create(&hist[k], w, h) != RT_OK) return die("rt_create");
+        if (rt_set_scene(hist[k], spheres, n) != RT_OK) return die("rt_set_scene");
+        if (rt_set_camera(hist[k], &cam) != RT_OK) return die("rt_set_camera");
+        if (rt_set_mode(hist[k], mode) != RT_OK) return die("rt_set_mode");
+        if (rt_set_temporal_moments(hist[k], &mp) != RT_OK) return die("rt_set_temporal_moments");
+        if (rt_features_async(hist[k], rt_stream(hist[k])) != RT_OK) return die("rt_features_async");
+    }
+    for (int f = 0; f < kFrames; ++f) {
+        rt_ctx* d = hist[f % 2];
+        if (rt_seed_stream_async(d, 100 + (unsigned)f, rt_stream(d)) != RT_OK) return die("rt_seed_stream_async");
+        if (rt_render_async(d, kPasses, rt_stream(d)) != RT_OK) return die("rt_render_async");
+        if (f > 0 && rt_reproject_async(d, hist[(f - 1) % 2], nullptr, rt_stream(d)) != RT_OK) return die("rt_reproject_async");
+    }
+    if (rt_set_temporal_moments(ctx, &mp) != RT_OK) return die("rt_set_temporal_moments");
+    if (rt_features_async(ctx, rt_stream(ctx)) != RT_OK) return die("rt_features_async");
+    if (rt_reproject_async(ctx, hist[(kFrames - 1) % 2], nullptr, rt_stream(ctx)) != RT_OK) return die("rt_reproject_async");
+    std::vector<float> m(4 * static_cast<size_t>(w) * h);
+    if (rt_read_moments(ctx, m.data()) != RT_OK) return die("rt_read_moments");      // (blocking: the helpers may go)
+    size_t reached = 0;
+    for (size_t i = 0; i < m.size(); i += 4) reached += m[i + 2] >= mp.k_min;
+    printf("{\"moments\": true, \"k_min\": %.3f, \"history_frames\": %d, \"history_passes\": %d, \"pixels_at_k_min\": %.4f}\n", (double)mp.k_min, kFrames, kPasses,
+           (double)reached / (double)(m.size() / 4));
+    rt_destroy(hist[0]);
+    rt_destroy(hist[1]);
+    return 0;
 }
 
 // --atrous: the feature plane, the filter, and the filtered frame's packed words into `px`; prints its line
@@ -105,6 +142,9 @@ int main(int argc, char** argv) {
     rt_denoise_defaults(&dn);
     rt_atrous_params at;
     rt_atrous_defaults(&at);
+    bool moments = false;       // --moments: with --atrous, the variance from a pixel's history (history_moments)
+    rt_moments_params mp;
+    rt_moments_defaults(&mp);
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -135,6 +175,8 @@ int main(int argc, char** argv) {
         else if (a == "--live-checks") live_checks = true;
         else if (a == "--atrous") atrous = true;
         else if (a == "--atrous-levels") at.levels = atoi(next());
+        else if (a == "--moments") moments = true;
+        else if (a == "--moments-kmin") mp.k_min = (float)atof(next());
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -156,6 +198,10 @@ int main(int argc, char** argv) {
     }
     if (live_checks && !(until && filtered && adaptive)) {
         fprintf(stderr, "--live-checks is a form of the filtered adaptive loop: it needs --until-psnr DB --filtered --adaptive\n");
+        return 1;
+    }
+    if (moments && !atrous) {
+        fprintf(stderr, "--moments steers the wavelet filter: it needs --atrous\n");
         return 1;
     }
     if (atrous && (gpus > 1 || rehearse > 0 || oneshot > 0)) {
@@ -244,6 +290,7 @@ int main(int argc, char** argv) {
         }
         if (!denoise && rt_read_pixels(frame, merged.data()) != RT_OK) return die("rt_read_pixels");
         const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (moments && history_moments(frame, spheres.data(), n, cam, w, h, mode, mp) != 0) return 1;
         if (atrous && filter_atrous(frame, at, merged) != 0) return 1;
         if (!out.empty() && !write_ppm(out, merged, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
         printf("{\"spheres\": %u, \"w\": %d, \"h\": %d, \"until_psnr\": %.3f, \"reached\": %s, \"passes_per_half\": %d, \"merged_passes\": %d, "
@@ -306,6 +353,7 @@ int main(int argc, char** argv) {
     double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     rt_stats st;
     if (rt_get_stats(ctx, &st) != RT_OK) return die("rt_get_stats");
+    if (moments && history_moments(ctx, spheres.data(), n, cam, w, h, mode, mp) != 0) return 1;
     if (atrous && filter_atrous(ctx, at, px) != 0) return 1;
     if (!out.empty() && !write_ppm(out, px, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
     if (!save_state.empty() && rt_save_state(ctx, save_state.c_str()) != RT_OK) return die("rt_save_state");

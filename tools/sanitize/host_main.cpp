@@ -47,6 +47,28 @@ int main() {
         filtered += rt_atrous_planes(out.data(), u3.data(), 3, 16, fd.data(), w, h, &at) == RT_OK;
         filtered += rt_atrous_planes(out.data(), u4.data(), 4, 0, fd.data(), w, h, &at) == RT_OK;
         printf("atrous %dx%d: %d of 2 ok, v %g\n", w, h, filtered, out[3]);
+        // the temporal moments' host statements on the same planes (all three sizes are odd one way or both): a first frame from the luminance of a
+        // 3-float source, a second from that frame's moments plane with the cap running (max_history 3 < 16), a pure warp; then the filter with rule 28
+        // on both sides of k_min, and without a moments plane
+        {
+            std::vector<float> t1(4 * px), m1(4 * px), t2(4 * px), m2(4 * px);
+            rt_reproject_params rp;
+            rt_reproject_defaults(&rp);
+            rp.max_history = 3.0f;
+            rt_moments_params mp;
+            rt_moments_defaults(&mp);
+            mp.k_min = 2.0f;
+            const rt_reproject_view dst{ cdp.data(), 3, 2, fd.data(), &cd, d }, dst0{ nullptr, 3, 0, fd.data(), &cd, d };
+            const rt_reproject_view src3{ u3.data(), 3, 16, fs.data(), &cs, d }, src4{ t1.data(), 4, 0, fd.data(), &cd, d };
+            int moments = 0;
+            moments += rt_reproject_moments_planes(t1.data(), m1.data(), &dst, &src3, nullptr, 6, w, h, &rp) == RT_OK;
+            moments += rt_reproject_moments_planes(t2.data(), m2.data(), &dst, &src4, m1.data(), 6, w, h, &rp) == RT_OK;
+            moments += rt_reproject_moments_planes(out.data(), m1.data(), &dst0, &src4, m2.data(), 6, w, h, nullptr) == RT_OK;
+            moments += rt_atrous_moments_planes(out.data(), t2.data(), 4, 0, m2.data(), fd.data(), w, h, &at, &mp) == RT_OK;
+            moments += rt_atrous_moments_planes(out.data(), u3.data(), 3, 16, m2.data(), fd.data(), w, h, nullptr, nullptr) == RT_OK;
+            moments += rt_atrous_moments_planes(out.data(), t2.data(), 4, 0, nullptr, fd.data(), w, h, &at, &mp) == RT_OK;
+            printf("moments %dx%d: %d of 6 ok, k %g v %g\n", w, h, moments, m2[2], m2[3]);
+        }
         // the NL-means host statements on halves of the same sizes, with and without the guide (the feature plane above), search radius 0 and 2, patch
         // radius 0 and 2: with the calls above, every function of rt_rules.h has run
         std::vector<float> ha(3 * px), hb(3 * px), merged(3 * px), fa(3 * px), fb(3 * px);
