@@ -121,6 +121,11 @@ int chain(rt_ctx *c, hipStream_t stream) {
     return RT_OK;
 }
 
+int chain_all(hipStream_t stream, std::initializer_list<rt_ctx *> ctxs) {
+    for (rt_ctx *c : ctxs) RT_TRY(chain(c, stream));
+    return RT_OK;
+}
+
 // host waits for everything the context has queued
 int wait_all(rt_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->last_stream));
@@ -147,14 +152,21 @@ int read_back(rt_ctx *c, void *host, const void *dev, size_t bytes, bool wait) {
     return RT_OK;
 }
 
-int read_plane4(rt_ctx *c, const char *call, float *plane_host, uint32_t *packed_host, bool (*current)(const rt_ctx *), float *rt_ctx::*plane, uint32_t *rt_ctx::*packed,
-                const char *absent) {
-    int rc = tiles_refuse(c, call);
-    if (rc != RT_OK) return rc;
-    if (!plane_host && !packed_host) return fail(RT_ERR_ARG, "%s: both buffers are null", call);
-    if (!current(c)) return fail(RT_ERR_STATE, "%s: the context holds no current %s", call, absent);
-    if (plane_host) RT_TRY(read_back(c, plane_host, c->*plane, 4 * image_pixels(c) * sizeof(float), packed_host == nullptr));
-    if (packed_host) RT_TRY(read_back(c, packed_host, c->*packed, image_pixels(c) * sizeof(uint32_t)));
+int read_plane(rt_ctx *c, const char *call, Plane which, float *host, uint32_t *packed_host) {
+    RT_TRY(tiles_refuse(c, call));
+    const PlaneView v = plane_view(c, which);
+    if (!host && !packed_host) return v.host_name ? fail(RT_ERR_ARG, "%s: %s is null", call, v.host_name) : fail(RT_ERR_ARG, "%s: both buffers are null", call);
+    if (!v.current) return fail(RT_ERR_STATE, "%s: the context holds no current %s", call, v.absent);
+    if (host) RT_TRY(read_back(c, host, v.plane, v.floats * sizeof(float), packed_host == nullptr));
+    if (packed_host) RT_TRY(read_back(c, packed_host, v.packed, image_pixels(c) * sizeof(uint32_t)));
+    return RT_OK;
+}
+
+int filter_input(const rt_ctx *c, const char *call, const char *who, bool want_moments, PlaneInput *out) {
+    const bool from_temporal = temporal_current(c);
+    if (!from_temporal && c->frame.current_sample <= 0) return fail(RT_ERR_STATE, "%s: %s holds neither a current temporal plane nor a pass", call, who);
+    *out = { from_temporal ? c->planes.temporal : c->d_colors, from_temporal ? 4 : 3, (float)c->frame.current_sample,
+             want_moments && moments_current(c) ? reinterpret_cast<const float4 *>(c->planes.moments) : nullptr };
     return RT_OK;
 }
 

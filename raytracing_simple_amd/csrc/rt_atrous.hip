@@ -1,7 +1,7 @@
 // rt_atrous.hip -- the edge-avoiding wavelet filter (include/rt_api.h, "edge-avoiding wavelet filter"): the frame the interactive loop shows, filtered --
 //   rt_atrous_async          the context's temporal plane (or, where none is current, its colour plane) through `levels` a-trous levels steered by the
 //                            feature plane and weighted by sample counts, into a plane (rgb, variance) and its packed plane that the context owns
-//   rt_read_atrous           those two planes
+//   rt_read_atrous           those two planes (read_plane, rt_internal.h)
 // and the two kernels behind the first.  rt_atrous_planes (rt_host.cpp) is the same arithmetic as plain loops; the header states it as rules 20-24, and
 // the comments below name the rule a line implements.  The reference filters nothing: this is the library's own extension.
 // This unit is compiled with parity's flags (-ffp-contract=off, correctly rounded division): every multiply, add and division below is an operation of
@@ -98,54 +98,45 @@ __global__ void __launch_bounds__(kPlaneLanes) rt_atrous_level_kernel(float4 *__
 
 using namespace rt;
 
-namespace {
-
-// A is current: formed, neither its input nor the feature plane it was steered by has ended since
-bool atrous_current(const rt_ctx *c) { return c->frame.atrous_current && c->scene.state.features_current && c->d_atrous && c->d_atrous_px; }
-
-}  // namespace
-
 extern "C" {
 
 RT_API int rt_atrous_async(rt_ctx *c, const rt_atrous_params *p, void *hip_stream) {
     const char *const call = "rt_atrous_async";
-    int rc = tiles_refuse(c, call);
-    if (rc != RT_OK) return rc;
+    RT_TRY(tiles_refuse(c, call));
     rt_atrous_params q;
     if (rt_host_atrous_params(p, &q) != RT_OK) return RT_ERR_ARG;
     RT_TRY(features_refuse(c, call));
-    if (c->frame.ragged) return fail(RT_ERR_STATE, "%s: the context is ragged (its tiles hold different pass counts)", call);
-    const bool from_temporal = temporal_current(c);
-    if (!from_temporal && c->frame.current_sample <= 0) return fail(RT_ERR_STATE, "%s: the context holds neither a current temporal plane nor a pass", call);
-    rc = select_device(c);
-    if (rc != RT_OK) return rc;
+    RT_TRY(ragged_refuse(c, call, "the context"));
+    PlaneInput in;
+    RT_TRY(filter_input(c, call, "the context", c->planes.moments_set.on, &in));
+    RT_TRY(select_device(c));
     const size_t pixels = image_pixels(c);
-    RT_TRY(ensure_device(c->owned, &c->d_atrous, 4 * pixels));
-    RT_TRY(ensure_device(c->owned, &c->d_atrous_px, pixels));
-    RT_TRY(ensure_device(c->owned, &c->d_atrous_tmp, 4 * pixels));
-    RT_TRY(ensure_device(c->owned, &c->d_atrous_guide, 4 * pixels));
-    RT_TRY(ensure_device(c->owned, &c->d_atrous_n, pixels));
+    Planes &pl = c->planes;
+    RT_TRY(ensure_device(c->owned, &pl.atrous, 4 * pixels));
+    RT_TRY(ensure_device(c->owned, &pl.atrous_px, pixels));
+    RT_TRY(ensure_device(c->owned, &pl.tmp, 4 * pixels));
+    RT_TRY(ensure_device(c->owned, &pl.guide, 4 * pixels));
+    RT_TRY(ensure_device(c->owned, &pl.n, pixels));
     hipStream_t stream = (hipStream_t)hip_stream;
     RT_TRY(chain(c, stream));           // behind everything the context has queued, its later work behind the call
     const dim3 grid = plane_grid(c->w, c->h);
     const int fast = c->knobs.fast() ? 1 : 0;
-    // the levels alternate between the two planes and end in d_atrous
-    float4 *cur = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? c->d_atrous : c->d_atrous_tmp);
-    float4 *nxt = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? c->d_atrous_tmp : c->d_atrous);
-    float4 *const guide = reinterpret_cast<float4 *>(c->d_atrous_guide);
-    if (c->have_moments && moments_current(c)) {        // rule 28: the setting on AND M current (which implies from_temporal); nothing else decides
-        RT_TRY(atrous_prepare_moments(c, cur, q.levels == 0, stream));       // rt_moments.hip: the preparation kernel with the moments arm
+    // the levels alternate between the two planes and end in pl.atrous
+    float4 *cur = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? pl.atrous : pl.tmp);
+    float4 *nxt = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? pl.tmp : pl.atrous);
+    float4 *const guide = reinterpret_cast<float4 *>(pl.guide);
+    if (in.m) {                                         // rule 28: the setting on AND M current (which implies the temporal plane); nothing else decides
+        RT_TRY(atrous_prepare_moments(c, in, cur, q.levels == 0, stream));       // rt_moments.hip: the preparation kernel with the moments arm
     } else {
-        const auto prepare = from_temporal ? rt_atrous_prepare_kernel<4> : rt_atrous_prepare_kernel<3>;
-        hipLaunchKernelGGL(prepare, grid, dim3(kPlaneLanes), 0, stream, cur, guide, c->d_atrous_n, q.levels == 0 ? c->d_atrous_px : (uint32_t *)nullptr,
-                           (const float *)(from_temporal ? c->d_temporal : c->d_colors), reinterpret_cast<const float4 *>(c->scene.d_features),
-                           (float)c->frame.current_sample, c->w, c->h, fast);
+        const auto prepare = in.channels == 4 ? rt_atrous_prepare_kernel<4> : rt_atrous_prepare_kernel<3>;
+        hipLaunchKernelGGL(prepare, grid, dim3(kPlaneLanes), 0, stream, cur, guide, pl.n, q.levels == 0 ? pl.atrous_px : (uint32_t *)nullptr, in.u,
+                           reinterpret_cast<const float4 *>(c->scene.d_features), in.passes, c->w, c->h, fast);
         HIP_TRY(hipGetLastError());
     }
     const float inv_kn2 = 1.0f / (q.k_normal * q.k_normal), kl2 = q.k_lum * q.k_lum;
     for (int level = 0; level < q.levels; ++level) {
-        hipLaunchKernelGGL(rt_atrous_level_kernel, grid, dim3(kPlaneLanes), 0, stream, nxt, level == q.levels - 1 ? c->d_atrous_px : (uint32_t *)nullptr, cur, guide,
-                           (const float *)c->d_atrous_n, 1 << level, inv_kn2, kl2, c->w, c->h, fast);
+        hipLaunchKernelGGL(rt_atrous_level_kernel, grid, dim3(kPlaneLanes), 0, stream, nxt, level == q.levels - 1 ? pl.atrous_px : (uint32_t *)nullptr, cur, guide,
+                           (const float *)pl.n, 1 << level, inv_kn2, kl2, c->w, c->h, fast);
         HIP_TRY(hipGetLastError());
         float4 *t = cur;
         cur = nxt;
@@ -155,10 +146,6 @@ RT_API int rt_atrous_async(rt_ctx *c, const rt_atrous_params *p, void *hip_strea
     return RT_OK;
 }
 
-RT_API int rt_read_atrous(rt_ctx *c, float *rgbv_host, uint32_t *packed_host) {
-    return read_plane4(c, "rt_read_atrous", rgbv_host, packed_host, atrous_current, &rt_ctx::d_atrous, &rt_ctx::d_atrous_px,
-                       "filtered plane (rt_atrous_async forms one; whatever ends the temporal plane, a new rt_reproject_async into the context or a feature plane formed "
-                       "again ends it)");
-}
+RT_API int rt_read_atrous(rt_ctx *c, float *rgbv_host, uint32_t *packed_host) { return read_plane(c, "rt_read_atrous", Plane::Atrous, rgbv_host, packed_host); }
 
 }  // extern "C"

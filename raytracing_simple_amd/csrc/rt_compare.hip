@@ -137,9 +137,7 @@ enum class Of { Frames, FilteredPlanes };
 int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles_dev, hipStream_t stream, Of what = Of::Frames) {
     int rc = select_device(a);
     if (rc != RT_OK) return rc;
-    rc = chain(a, stream);
-    if (rc == RT_OK) rc = chain(b, stream);
-    if (rc != RT_OK) return rc;
+    RT_TRY(chain_all(stream, { a, b }));
     HIP_TRY(hipMemsetAsync(result_dev, 0, sizeof(rt_frame_error), stream));     // the accumulators; the whole answer of a context without rows
     if (a->local_rows == 0) return RT_OK;
     if (what == Of::Frames) {
@@ -147,7 +145,7 @@ int compare_on(rt_ctx *a, rt_ctx *b, rt_frame_error *result_dev, uint32_t *tiles
         if (rc == RT_OK) rc = refresh_pixels(b, stream);
         if (rc != RT_OK) return rc;
     }
-    const uint32_t *pa = what == Of::Frames ? frame_pixels(a) : a->d_filtered_px, *pb = what == Of::Frames ? frame_pixels(b) : b->d_filtered_px;
+    const uint32_t *pa = what == Of::Frames ? frame_pixels(a) : a->planes.filtered_px, *pb = what == Of::Frames ? frame_pixels(b) : b->planes.filtered_px;
     const size_t items = (size_t)tile_row_count(a) * (size_t)((a->w + kCmpRun - 1) / kCmpRun);
     const size_t blocks = std::min(items, (size_t)a->knobs.n_cus * 8);
     hipLaunchKernelGGL(rt_compare_kernel, dim3((unsigned)blocks), dim3(kCmpLanes), 0, stream, pa, pb, a->w, a->local_rows, reinterpret_cast<unsigned long long *>(result_dev), tiles_dev);

@@ -6,7 +6,7 @@
 // "The error of the filtered frame" of the same header lives here too --
 //   rt_denoise_pair_async    each half filtered with weights taken from the OTHER half, into planes of their own beside the colour planes
 //   rt_denoise_pair_tiles_async   ... of the groups in the current selection alone (adaptive sampling's groups: rt_tiles.hip), the rest kept
-//   rt_read_filtered         that plane of one context
+//   rt_read_filtered         that plane of one context (read_plane, rt_internal.h)
 // (rt_denoise_pair_planes is the host statement; rt_compare.hip compares the packed planes).
 // As rt_host.cpp filters through one nlm_planes(out, img, guide, ...), the device filters through ONE body, dn_body<P, N, kAnyRow>: N = 1 is the frame
 // filtered with its own weights, N = 2 the two halves, each with the other's.  Three kernels give it an origin: the frame, the frame's halves, a list
@@ -125,29 +125,29 @@ int check_three(const rt_ctx *dst, const rt_ctx *a, const rt_ctx *b) {
 int filter_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t stream, bool tiles) {
     const size_t n_floats = color_floats(a), n_words = image_pixels(a);
     for (rt_ctx *c : { a, b }) {
-        RT_TRY(ensure_device(c->owned, &c->d_filtered, n_floats));
-        RT_TRY(ensure_device(c->owned, &c->d_filtered_px, n_words));
+        RT_TRY(ensure_device(c->owned, &c->planes.filtered, n_floats));
+        RT_TRY(ensure_device(c->owned, &c->planes.filtered_px, n_words));
     }
-    RT_TRY(ensure_device(a->owned, &a->d_denoise_var, n_floats));
+    RT_TRY(ensure_device(a->owned, &a->planes.var, n_floats));
     // behind everything the two contexts have queued; their later work behind the filter
-    int rc = chain(a, stream);
-    if (rc == RT_OK) rc = chain(b, stream);
+    int rc = chain_all(stream, { a, b });
     if (rc == RT_OK && tiles && a->frame.group_list_is_stale()) rc = tiles_build_group_list(a, stream);
-    if (rc == RT_OK) rc = launch_variance(a->d_denoise_var, a->d_colors, b->d_colors, a->w, a->h, stream);
+    if (rc == RT_OK) rc = launch_variance(a->planes.var, a->d_colors, b->d_colors, a->w, a->h, stream);
     if (rc != RT_OK) return rc;
-    const DnPlanes<2> k{ { a->d_colors, b->d_colors }, { a->d_filtered, b->d_filtered }, { a->d_filtered_px, b->d_filtered_px }, { a->knobs.fast(), b->knobs.fast() } };
+    const Planes &pa = a->planes, &pb = b->planes;
+    const DnPlanes<2> k{ { a->d_colors, b->d_colors }, { pa.filtered, pb.filtered }, { pa.filtered_px, pb.filtered_px }, { a->knobs.fast(), b->knobs.fast() } };
     const size_t lds = dn_lds_bytes(2, q.search_radius, q.patch_radius);
     const float kk = q.k * q.k;
-    if (a->have_guide) {                                    // (guide_refuse has passed: b holds the same, both feature planes are current)
-        const GuidedFilter f{ { a->d_colors, b->d_colors }, { a->d_filtered, b->d_filtered }, { a->d_filtered_px, b->d_filtered_px }, { a->knobs.fast(), b->knobs.fast() },
-                              a->d_denoise_var, tiles ? a->tiles.d_groups : nullptr, tiles ? a->frame.counts[0] : 0u };
+    if (a->planes.guide_set.on) {                           // (guide_refuse has passed: b holds the same, both feature planes are current)
+        const GuidedFilter f{ { a->d_colors, b->d_colors }, { pa.filtered, pb.filtered }, { pa.filtered_px, pb.filtered_px }, { a->knobs.fast(), b->knobs.fast() },
+                              pa.var, tiles ? a->tiles.d_groups : nullptr, tiles ? a->frame.counts[0] : 0u };
         rc = launch_guided_filter(2, f, a, q, stream);
     } else with_patch_radius(q.patch_radius, [&](auto P) {
         if (tiles)
-            hipLaunchKernelGGL(rt_denoise_pair_tiles_kernel<decltype(P)::value>, dim3(a->frame.counts[0]), dim3(kPlaneLanes), lds, stream, k, a->d_denoise_var, a->w,
+            hipLaunchKernelGGL(rt_denoise_pair_tiles_kernel<decltype(P)::value>, dim3(a->frame.counts[0]), dim3(kPlaneLanes), lds, stream, k, a->planes.var, a->w,
                                a->h, q.search_radius, q.alpha, kk, a->tiles.d_groups, groups_per_row(a), group_count(a));
         else
-            hipLaunchKernelGGL(rt_denoise_pair_kernel<decltype(P)::value>, frame_grid(a), dim3(kPlaneLanes), lds, stream, k, a->d_denoise_var, a->w, a->h,
+            hipLaunchKernelGGL(rt_denoise_pair_kernel<decltype(P)::value>, frame_grid(a), dim3(kPlaneLanes), lds, stream, k, a->planes.var, a->w, a->h,
                                q.search_radius, q.alpha, kk);
     });
     if (rc != RT_OK) return rc;
@@ -185,7 +185,7 @@ int denoise_pair_tiles(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStre
     if (!fa.filtered_behind_with(fb))
         return fail(RT_ERR_STATE, "%s: the cross-filtered planes are not one selection behind -- they were never made, were made by different calls, or something "
                                   "else than rt_render_tiles_async of the selection in hand has moved a colour plane since (rt_denoise_pair_async makes them whole)", call);
-    if (!a->d_filtered || !b->d_filtered || !a->d_filtered_px || !b->d_filtered_px || !a->d_denoise_var || !a->tiles.d_selected)
+    if (!a->planes.filtered || !b->planes.filtered || !a->planes.filtered_px || !b->planes.filtered_px || !a->planes.var || !a->tiles.d_selected)
         return fail(RT_ERR_STATE, "%s: a plane that the frame record calls made does not exist", call);
     const int rc = select_device(a);
     if (rc != RT_OK) return rc;
@@ -215,26 +215,24 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
     rc = select_device(dst);
     if (rc != RT_OK) return rc;
     const size_t n_floats = color_floats(dst);
-    RT_TRY(ensure_device(dst->owned, &dst->d_denoise, n_floats));
-    RT_TRY(ensure_device(dst->owned, &dst->d_denoise_var, n_floats));
+    RT_TRY(ensure_device(dst->owned, &dst->planes.denoise, n_floats));
+    RT_TRY(ensure_device(dst->owned, &dst->planes.var, n_floats));
     // behind everything the three contexts have queued; their later work behind the filter
     hipStream_t stream = (hipStream_t)hip_stream;
-    rc = chain(dst, stream);
-    if (rc == RT_OK) rc = chain(a, stream);
-    if (rc == RT_OK) rc = chain(b, stream);
-    if (rc == RT_OK) rc = launch_variance(dst->d_denoise_var, a->d_colors, b->d_colors, dst->w, dst->h, stream);
+    rc = chain_all(stream, { dst, a, b });
+    if (rc == RT_OK) rc = launch_variance(dst->planes.var, a->d_colors, b->d_colors, dst->w, dst->h, stream);
     if (rc != RT_OK) return rc;
-    const DnPlanes<1> k{ { dst->d_colors }, { dst->d_denoise }, { nullptr }, { 0 } };       // (nothing is packed: rt_read_pixels packs the colour plane)
+    const DnPlanes<1> k{ { dst->d_colors }, { dst->planes.denoise }, { nullptr }, { 0 } };      // (nothing is packed: rt_read_pixels packs the colour plane)
     if (guided) {                                           // (the feature plane is a's)
-        const GuidedFilter f{ { dst->d_colors, nullptr }, { dst->d_denoise, nullptr }, { nullptr, nullptr }, { 0, 0 }, dst->d_denoise_var, nullptr, 0u };
+        const GuidedFilter f{ { dst->d_colors, nullptr }, { dst->planes.denoise, nullptr }, { nullptr, nullptr }, { 0, 0 }, dst->planes.var, nullptr, 0u };
         rc = launch_guided_filter(1, f, a, q, stream);
     } else with_patch_radius(q.patch_radius, [&](auto P) {
         hipLaunchKernelGGL(rt_denoise_kernel<decltype(P)::value>, frame_grid(dst), dim3(kPlaneLanes), dn_lds_bytes(1, q.search_radius, q.patch_radius), stream, k,
-                           dst->d_denoise_var, dst->w, dst->h, q.search_radius, q.alpha, q.k * q.k);
+                           dst->planes.var, dst->w, dst->h, q.search_radius, q.alpha, q.k * q.k);
     });
     if (rc != RT_OK) return rc;
     HIP_TRY(hipGetLastError());
-    std::swap(dst->d_colors, dst->d_denoise);               // the filtered plane IS the colour plane now; the old one is the next call's scratch
+    std::swap(dst->d_colors, dst->planes.denoise);          // the filtered plane IS the colour plane now; the old one is the next call's scratch
     dst->frame.colours_replaced();                          // rt_read_pixels packs the filtered plane
     return RT_OK;
 }
@@ -255,13 +253,6 @@ RT_API int rt_denoise_pair_tiles_async(rt_ctx *a, rt_ctx *b, const rt_denoise_pa
     return denoise_pair_tiles(a, b, q, (hipStream_t)hip_stream, "rt_denoise_pair_tiles_async");
 }
 
-RT_API int rt_read_filtered(rt_ctx *c, float *out_host) {
-    int rc = tiles_refuse(c, "rt_read_filtered");
-    if (rc != RT_OK) return rc;
-    if (!out_host) return fail(RT_ERR_ARG, "rt_read_filtered: out_host is null");
-    if (c->frame.filtered_pair == 0)
-        return fail(RT_ERR_STATE, "rt_read_filtered: the context holds no current cross-filtered plane (rt_denoise_pair_async makes one; whatever moves the colour plane ends it)");
-    return read_back(c, out_host, c->d_filtered, color_floats(c) * sizeof(float));
-}
+RT_API int rt_read_filtered(rt_ctx *c, float *out_host) { return read_plane(c, "rt_read_filtered", Plane::Filtered, out_host); }
 
 }  // extern "C"

@@ -42,7 +42,7 @@ namespace rt {
 // `n_images` = 1: rt_denoise_async's frame; 2: the halves, over the frame or (f.groups) over a list of groups.  The guide and the feature plane are `a`'s.
 // Dynamic LDS beyond the 64 KiB every kernel may ask for: the limit is raised for that kernel on the selected device.
 int launch_guided_filter(int n_images, const GuidedFilter &f, const rt_ctx *a, const rt_denoise_params &q, hipStream_t stream) {
-    const rt_guide_params &g = a->guide;
+    const rt_guide_params &g = a->planes.guide_set.params;
     const DnGuide gd{ reinterpret_cast<const float4 *>(a->scene.d_features), 1.0f / (g.k_albedo * g.k_albedo), 1.0f / (g.k_normal * g.k_normal), 1.0f / (g.k_depth * g.k_depth) };
     const size_t lds = dn_lds_bytes(n_images, q.search_radius, q.patch_radius, true);
     const dim3 grid = plane_grid(a->w, a->h);

@@ -1,6 +1,6 @@
 // rt_features.hip -- feature planes from camera rays (include/rt_api.h, "feature planes"): what lies under every pixel --
 //   rt_features_async        albedo, normal, distance and scene index of the pixel-centre ray's first hit, into a plane the context owns
-//   rt_read_features         that plane
+//   rt_read_features         that plane (read_plane, rt_internal.h)
 //   rt_set_denoise_guide     the per-context setting that lets the filters of rt_denoise.hip restrict their weights by it
 // and the kernel behind the first.  rt_features_planes (rt_host.cpp) is the same arithmetic as plain loops; the header states it as rules 10-12, and
 // the comments below name the rule a line implements.  The reference hands out no such plane: this is the library's own extension.
@@ -74,16 +74,17 @@ __global__ void __launch_bounds__(kPlaneLanes) rt_features_kernel(float4 *__rest
 namespace rt {
 
 int features_refuse(const rt_ctx *c, const char *call, const char *lead, const char *of_whom) {
-    if (c->scene.state.features_current && c->scene.d_features) return RT_OK;
+    if (features_current(c)) return RT_OK;
     return fail(RT_ERR_STATE, "%s: %sthe feature plane%s is not current (rt_features_async forms it; rt_set_scene, rt_update_spheres_async and rt_set_camera end it)", call,
                 lead, of_whom);
 }
 
 int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guided) {
     if (guided) *guided = false;
-    if (a->have_guide != b->have_guide || (a->have_guide && memcmp(&a->guide, &b->guide, sizeof a->guide) != 0))
+    const auto &ga = a->planes.guide_set, &gb = b->planes.guide_set;
+    if (ga.on != gb.on || (ga.on && memcmp(&ga.params, &gb.params, sizeof ga.params) != 0))
         return fail(RT_ERR_STATE, "%s: the halves differ in their guide (rt_set_denoise_guide: both off, or both on with the same parameters)", call);
-    if (!a->have_guide) return RT_OK;
+    if (!ga.on) return RT_OK;
     // (a plane is current only after rt_features_async has acquired its block: SceneState::features_formed)
     RT_TRY(features_refuse(a, call, "a guide is set and ", " of the first half"));
     RT_TRY(features_refuse(b, call, "a guide is set and ", " of the second half"));
@@ -117,22 +118,12 @@ RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
     return RT_OK;
 }
 
-RT_API int rt_read_features(rt_ctx *c, float *out_host) {
-    int rc = tiles_refuse(c, "rt_read_features");
-    if (rc != RT_OK) return rc;
-    if (!out_host) return fail(RT_ERR_ARG, "rt_read_features: out_host is null");
-    if (!c->scene.state.features_current || !c->scene.d_features)
-        return fail(RT_ERR_STATE, "rt_read_features: the context holds no current feature plane (rt_features_async forms one; rt_set_scene, rt_update_spheres_async "
-                                  "and rt_set_camera end it)");
-    return read_back(c, out_host, c->scene.d_features, 8 * image_pixels(c) * sizeof(float));
-}
+RT_API int rt_read_features(rt_ctx *c, float *out_host) { return read_plane(c, "rt_read_features", Plane::Features, out_host); }
 
 RT_API int rt_set_denoise_guide(rt_ctx *c, const rt_guide_params *g) {
-    int rc = tiles_refuse(c, "rt_set_denoise_guide");
-    if (rc != RT_OK) return rc;
+    RT_TRY(tiles_refuse(c, "rt_set_denoise_guide"));
     if (g && rt_host_guide_params(g) != RT_OK) return RT_ERR_ARG;
-    c->have_guide = g != nullptr;
-    c->guide = g ? *g : rt_guide_params{};
+    c->planes.guide_set = { g ? *g : rt_guide_params{}, g != nullptr };
     return RT_OK;
 }
 

@@ -40,6 +40,8 @@ struct FrameState {
     // The edge-avoiding wavelet filter (rt_atrous.hip): the filtered plane was formed by rt_atrous_async from the temporal plane -- or, where none was
     // current, from the colour plane -- and neither has moved since.  CURRENT while this holds and the scene's feature plane is current too
     bool atrous_current = false;
+    // Temporal luminance moments (rt_moments.hip): the reprojection that formed the temporal plane formed the moments plane too.  CURRENT while both hold
+    bool moments_formed = false;
 
     // at pass 0 the next launch would read the default stream (nothing but a custom stream or a written state puts another one there)
     bool on_default_stream() const { return seeds_default || !seeds_custom; }
@@ -86,9 +88,9 @@ struct FrameState {
     void group_list_built() { group_list_serial = selection_serial; }          // rt_denoise_pair_tiles_async: once per selection
 
     // ---- the colour plane written by something else than a launch: rt_read_pixels packs it ----
-    void merged(int total) { current_sample = total; have_selection = false; pixels_current = false; filtered_pair = filtered_behind = 0; temporal_current = atrous_current = false; }     // (a selection was made at another pass number)
+    void merged(int total) { current_sample = total; have_selection = false; pixels_current = false; filtered_behind = 0; colour_plane_moved(); }     // (a selection was made at another pass number)
     void merged_by_tile(int total) { merged(total); ragged = true; list_valid = false; }                    // every tile by its own weights: dst's front has moved
-    void colours_replaced() { pixels_current = false; filtered_pair = filtered_behind = 0; temporal_current = atrous_current = false; }     // rt_denoise_async
+    void colours_replaced() { pixels_current = false; filtered_behind = 0; colour_plane_moved(); }     // rt_denoise_async
     void pixels_packed() { pixels_current = true; }             // refresh_pixels
     // rt_denoise_pair_async: the cross-filtered plane beside the colour plane is current, until anything moves the colour plane (a launch, a reset,
     // a written state, a merge or a filter into it); nothing else of the frame changes
@@ -96,19 +98,22 @@ struct FrameState {
     // rt_denoise_pair_tiles_async: the selected groups' part of a plane that was one selection behind has been formed again -- current, under a new id
     void pair_tiles_refreshed(uint64_t call) { pair_filtered(call); }
     // rt_reproject_async into this context: its temporal plane is current, until anything moves the colour plane (the same events that end the
-    // cross-filtered plane) or ends the feature plane (the scene's record); nothing else of the frame changes
-    void reprojected() { temporal_current = true; atrous_current = false; }     // (a plane filtered from the temporal plane that was is not a filter of this one)
+    // cross-filtered plane) or ends the feature plane (the scene's record); nothing else of the frame changes.  `with_moments`: the call formed the
+    // moments plane beside it (rt_set_temporal_moments on for this context).  A plane filtered from the temporal plane that was is not a filter of this one
+    void reprojected(bool with_moments = false) { temporal_current = true; moments_formed = with_moments; atrous_current = false; }
     // rt_features_async forms a feature plane where none was current: a temporal plane formed under the one that ended does not come back with it
-    void features_reformed() { temporal_current = atrous_current = false; }
+    void features_reformed() { temporal_current = atrous_current = moments_formed = false; }
     // rt_atrous_async: the filtered plane is current, until any event that ends the temporal plane, a new reprojection into the context or a feature
     // plane formed again; nothing else of the frame changes -- the filter feeds nothing back
     void atrous_filtered() { atrous_current = true; }
 
 private:
+    // something has written the colour plane, or will before it is read again: every plane derived from it is stale.  (filtered_behind is each caller's own)
+    void colour_plane_moved() { filtered_pair = 0; temporal_current = atrous_current = moments_formed = false; }
     // every tile holds `pass` passes; a selection does not outlive that, and the launch count starts again
-    void restart(int pass) { current_sample = pass; launches = 0; last_ms = 0.0; ragged = have_selection = list_valid = false; filtered_pair = filtered_behind = 0; temporal_current = atrous_current = false; }
+    void restart(int pass) { current_sample = pass; launches = 0; last_ms = 0.0; ragged = have_selection = list_valid = false; filtered_behind = 0; colour_plane_moved(); }
     // a launch has written every seed pair it renders: the default stream is no longer read in place
-    void advance(int n_samples) { current_sample += n_samples; launches += 1; seeds_default = false; filtered_pair = 0; temporal_current = atrous_current = false; }
+    void advance(int n_samples) { current_sample += n_samples; launches += 1; seeds_default = false; colour_plane_moved(); }
 };
 
 }  // namespace rt

@@ -1,5 +1,5 @@
 // rt_internal.h -- what the translation units of the library share behind the C ABI: the context record and the records embedded in it
-// (Choice, TileOrder, FrameState, Owned, Scene, Knobs), error reporting, acquisition of device resources into the context's record, page-locked
+// (Choice, TileOrder, FrameState, Owned, Scene, Planes, Knobs), error reporting, acquisition of device resources into the context's record, page-locked
 // staging (Staged), the frame's geometry said once, the checks and the blocking read several units share, and the hooks of the multi-device
 // context (rt_multi.hip).
 #pragma once
@@ -180,6 +180,27 @@ struct Scene {
     float *d_features = nullptr;        // [h][w][8]: albedo, normal, distance, scene index; acquired on first use
 };
 
+// The planes a context derives from its colour plane, and the two settings that steer how (turning one on or off moves no plane).  Raw pointers, freed
+// by value through Owned; every block is acquired on first use by the call that forms it.  Rows run as the colour plane's; "packed" is one word per pixel
+// by toInt in the pixel buffer's layout (row 0 at the bottom).  WHEN a plane is current is the frame record's and the scene record's to say, through the
+// predicates below rt_ctx (features_current ... atrous_current); the feature plane itself is the scene's (Scene::d_features).
+//   plane          layout                              formed by
+//   denoise        [h][w][3]                           rt_denoise_async: what the filter writes, EXCHANGED with rt_ctx::d_colors after every call
+//   var            [h][w][3]                           rt_denoise_async, rt_denoise_pair*_async: the smoothed variance (of a pair: the first context's, for both)
+//   filtered, _px  [h][w][3], packed                   rt_denoise_pair*_async: this half filtered with the other half's weights (rt_compare_filtered reads _px)
+//   temporal, _px  [h][w][4] (rgb, n), packed          rt_reproject_async INTO this context
+//   moments        [h][w][4] (m1, m2, k, v)            ... while the moments setting of this context is on
+//   atrous, _px    [h][w][4] (rgb, variance), packed   rt_atrous_async, like the three below
+//   tmp            [h][w][4]                           the other (rgb, variance) plane the levels alternate with
+//   guide          [h][w][4]                           the normal and the scene index of the feature plane, one aligned texel
+//   n              [h][w]                              the sample count of a usable pixel, +0.0f for one that is not (rule 20)
+struct Planes {
+    float *denoise = nullptr, *var = nullptr, *filtered = nullptr, *temporal = nullptr, *moments = nullptr, *atrous = nullptr, *tmp = nullptr, *guide = nullptr, *n = nullptr;
+    uint32_t *filtered_px = nullptr, *temporal_px = nullptr, *atrous_px = nullptr;
+    struct { rt_guide_params params{}; bool on = false; } guide_set;        // rt_set_denoise_guide: what the filters of a pair of halves add to their weights
+    struct { rt_moments_params params{}; bool on = false; } moments_set;    // rt_set_temporal_moments: what rt_reproject_async into the context and rt_atrous_async of it consult
+};
+
 // the rows of an image of `h` that rank `rank` of `nranks` renders, the image dealt out in tiles of `tile_rows` (api.local_rows_of says the same in Python)
 inline int rows_of_rank(int h, int rank, int nranks, int tile_rows) {
     const int n_tiles = (h + tile_rows - 1) / tile_rows;
@@ -206,34 +227,13 @@ struct rt_ctx {
     int pixel_write = 1;                // rt_set_pixel_write
     rt::FrameState frame;               // what the progressive frame currently is: pass number, seed stream, packed pixels, launch count, tile bookkeeping
     rt::TileSubset tiles;               // adaptive sampling (rt_tiles.hip): a pass count per 8x8 tile, the selected groups, the launch list of a subset launch
-    float *d_denoise = nullptr;         // rt_denoise_async (rt_denoise.hip): the plane the filter writes, EXCHANGED with d_colors after every call (the record
-                                        // frees by value: whichever block a member holds at teardown goes once); acquired on first use
-    float *d_denoise_var = nullptr;     // ... and the smoothed variance plane it is steered by (rt_denoise_pair_async: the first context's, for both halves)
-    float *d_filtered = nullptr;        // rt_denoise_pair_async: this half filtered with the other half's weights, a plane like d_colors; acquired on first use.
-                                        // Whether it is current is frame.filtered_pair
-    uint32_t *d_filtered_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom): what rt_compare_filtered reads
-    float *d_temporal = nullptr;        // rt_reproject_async into this context (rt_reproject.hip): [h][w][4], rgb and the effective sample count, rows as d_colors;
-                                        // acquired on first use.  Whether it is current is frame.temporal_current together with scene.state.features_current
-    uint32_t *d_temporal_px = nullptr;  // ... and that plane packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom)
-    float *d_moments = nullptr;         // ... and, with rt_set_temporal_moments on, the moments plane M beside it: [h][w][4], (m1, m2, k, v), rows as d_colors; acquired
-                                        // on first use.  Whether it is current is temporal_current(c) together with ...
-    bool moments_formed = false;        // ... this: the last rt_reproject_async into this context formed M (written by every such call; no state of its own)
-    rt_moments_params moments{};        // rt_set_temporal_moments: what rt_reproject_async into the context and rt_atrous_async of it consult ...
-    bool have_moments = false;          // ... when it is on
-    float *d_atrous = nullptr;          // rt_atrous_async (rt_atrous.hip): [h][w][4], the filtered rgb and its variance, rows as d_colors; acquired on first use, like
-                                        // the four below.  Whether it is current is frame.atrous_current together with scene.state.features_current
-    uint32_t *d_atrous_px = nullptr;    // ... and its rgb packed by toInt, one word per pixel in the pixel buffer's layout (row 0 = bottom)
-    float *d_atrous_tmp = nullptr;      // ... the other (rgb, variance) plane the levels alternate with
-    float *d_atrous_guide = nullptr;    // ... [h][w][4]: the normal and the scene index of the feature plane, one aligned texel
-    float *d_atrous_n = nullptr;        // ... [h][w]: the sample count of a usable pixel, +0.0f for one that is not (rule 20)
+    rt::Planes planes;                  // what is derived from the colour plane: the filters' and the reprojection's planes, and the two settings (above)
     void *d_compare = nullptr;          // scratch of the blocking rt_compare / rt_render_converged: one rt_frame_error, then the tile map (rt_compare.hip; acquired on first use)
     unsigned long long *d_counters = nullptr;
     unsigned long long *d_stats = nullptr;      // rt::kStatReplicas x 8 partial work counters
     rt::Scene scene;                    // what the context holds of its scene: records, tables, hierarchy, duplicate flags, feature plane, their staging -- and what of
                                         // that is currently true (rt_scene_state.h)
     rt_camera cam{};                    // a kernel argument (scene.state.have_cam)
-    rt_guide_params guide{};            // rt_set_denoise_guide: what the filters of a pair of halves add to their weights ...
-    bool have_guide = false;            // ... when it is on
     rt::Choice choice;                  // hierarchy or sweep, cooperative any-hit or not: the verdicts for this scene, the measurement behind them, the estimate (rt_choice.h)
     hipEvent_t probe_ev[4] = { nullptr, nullptr, nullptr, nullptr };       // ... and the measurement's events: arm a's timed step lies between probe_ev[2 * a] and probe_ev[2 * a + 1]
     rt::TileOrder order;                // heavy-first tile schedule (rt_tile_order.h; rt_trace.inc.h reads and writes its arrays)
@@ -276,10 +276,38 @@ inline size_t image_pixels(const rt_ctx *c) { return (size_t)c->w * (size_t)c->h
 inline size_t local_pixels(const rt_ctx *c) { return (size_t)c->local_rows * (size_t)c->w; }
 inline size_t color_floats(const rt_ctx *c) { return 3 * image_pixels(c); }
 inline uint32_t *frame_pixels(const rt_ctx *c) { return c->d_pixels_ext ? c->d_pixels_ext : c->d_pixels; }     // the buffer launches write
-// the temporal plane (rt_reproject.hip) is current: formed, the colour plane has not moved since, and the feature plane it was formed under has not ended
-inline bool temporal_current(const rt_ctx *c) { return c->frame.temporal_current && c->scene.state.features_current && c->d_temporal && c->d_temporal_px; }
-// ... and the moments plane beside it: the temporal plane is, and the reprojection that formed it formed M too
-inline bool moments_current(const rt_ctx *c) { return temporal_current(c) && c->moments_formed && c->d_moments; }
+
+// ---- when a derived plane is CURRENT, said once: the frame record's flag, the scene record's where it applies, and the blocks ----
+inline bool features_current(const rt_ctx *c) { return c->scene.state.features_current && c->scene.d_features; }
+inline bool filtered_current(const rt_ctx *c) { return c->frame.filtered_pair != 0 && c->planes.filtered && c->planes.filtered_px; }
+inline bool temporal_current(const rt_ctx *c) { return c->frame.temporal_current && features_current(c) && c->planes.temporal && c->planes.temporal_px; }
+inline bool moments_current(const rt_ctx *c) { return temporal_current(c) && c->frame.moments_formed && c->planes.moments; }
+inline bool atrous_current(const rt_ctx *c) { return c->frame.atrous_current && features_current(c) && c->planes.atrous && c->planes.atrous_px; }
+// ... and what a reader of one needs beside that: the name of its buffer in the "is null" refusal (null: the call takes two buffers), what the
+// context "holds no current" of, the plane with its length in floats, and the packed plane of a call that hands out two
+enum class Plane { Features, Filtered, Temporal, Moments, Atrous };
+struct PlaneView { bool current; const char *host_name, *absent; const float *plane; size_t floats; const uint32_t *packed; };
+inline PlaneView plane_view(const rt_ctx *c, Plane which) {
+    const size_t px = image_pixels(c);
+    switch (which) {
+    case Plane::Features:
+        return { features_current(c), "out_host", "feature plane (rt_features_async forms one; rt_set_scene, rt_update_spheres_async and rt_set_camera end it)",
+                 c->scene.d_features, 8 * px, nullptr };
+    case Plane::Filtered:
+        return { filtered_current(c), "out_host", "cross-filtered plane (rt_denoise_pair_async makes one; whatever moves the colour plane ends it)", c->planes.filtered,
+                 3 * px, nullptr };
+    case Plane::Temporal:
+        return { temporal_current(c), nullptr, "temporal plane (rt_reproject_async forms one; whatever moves the colour plane or ends the feature plane ends it)",
+                 c->planes.temporal, 4 * px, c->planes.temporal_px };
+    case Plane::Moments:
+        return { moments_current(c), "m_host", "moments plane (rt_reproject_async into it forms one while rt_set_temporal_moments is on; whatever ends the temporal plane, "
+                 "or a reprojection into the context with the setting off, ends it)", c->planes.moments, 4 * px, nullptr };
+    case Plane::Atrous:
+        break;
+    }
+    return { atrous_current(c), nullptr, "filtered plane (rt_atrous_async forms one; whatever ends the temporal plane, a new rt_reproject_async into the context or a "
+             "feature plane formed again ends it)", c->planes.atrous, 4 * px, c->planes.atrous_px };
+}
 
 // a reset or a written state ends a frame of the current scene for the form choice too (Choice::frame_ended): end_frame(c).reset_in_place()
 inline FrameState &end_frame(rt_ctx *c) { c->choice.frame_ended(); return c->frame; }
@@ -287,15 +315,22 @@ inline FrameState &end_frame(rt_ctx *c) { c->choice.frame_ended(); return c->fra
 // ---- rt_api.hip: the context's device and the order of its work ----
 int select_device(const rt_ctx *c);
 int chain(rt_ctx *c, hipStream_t stream);          // `stream` waits for whatever the context queued last elsewhere (ALL its work runs in issue order)
+int chain_all(hipStream_t stream, std::initializer_list<rt_ctx *> ctxs);      // ... for each context in turn, up to the first failure
 int wait_all(rt_ctx *c);                            // host waits for everything the context has queued
 int refresh_pixels(rt_ctx *c, hipStream_t stream); // the packed frame brought up to date on `stream` (already chained): the pack kernel, if the last launches ran with the pixel store off
 const double *create_breakdown();                   // host ms of the last rt_create by phase (rt_debug_create_breakdown)
 // blocking read of `bytes` from the context's device: behind everything it has queued, on its own stream (wait = false: the copy is queued, a later call waits)
 int read_back(rt_ctx *c, void *host, const void *dev, size_t bytes, bool wait = true);
-// rt_read_temporal, rt_read_atrous: a context's [h][w][4] plane and / or its packed plane, either buffer null for "not this one".  RT_ERR_ARG for a context
-// the adaptive calls do not take or two null buffers; RT_ERR_STATE "<call>: the context holds no current <absent>" unless current(c)
-int read_plane4(rt_ctx *c, const char *call, float *plane_host, uint32_t *packed_host, bool (*current)(const rt_ctx *), float *rt_ctx::*plane, uint32_t *rt_ctx::*packed,
-                const char *absent);
+// the five rt_read_* calls: a plane of the context (plane_view above) and / or, for Temporal and Atrous, its packed plane, either buffer null for "not this one".
+// RT_ERR_ARG for a context the adaptive calls do not take or no buffer at all; RT_ERR_STATE unless the plane is current.  Two copies: the wait is for the last one
+int read_plane(rt_ctx *c, const char *call, Plane which, float *host, uint32_t *packed_host = nullptr);
+// What a filter of the frame reads: the temporal plane (4 floats a pixel, each with its own n) while that is current, else the colour plane (3 floats, every
+// pixel at `passes`), else RT_ERR_STATE "<call>: <who> holds neither a current temporal plane nor a pass".  m: the moments plane, if wanted and current
+struct PlaneInput { const float *u; int channels; float passes; const float4 *m; };      // (passes: current_sample, whichever plane)
+int filter_input(const rt_ctx *c, const char *call, const char *who, bool want_moments, PlaneInput *out);
+inline int ragged_refuse(const rt_ctx *c, const char *call, const char *who) {      // ... and both take whole frames only
+    return c->frame.ragged ? fail(RT_ERR_STATE, "%s: %s is ragged (its tiles hold different pass counts)", call, who) : RT_OK;
+}
 // `a` and `b` show the same frame on the same device: non-null, distinct, neither multi-device, same size (`sharding`: and rank, ranks, rows per
 // tile), same device -- or RT_ERR_ARG with a message that names `call`, the two contexts as the caller knows them, and the property that differs
 int same_frame(const rt_ctx *a, const rt_ctx *b, const char *call, const char *a_name, const char *b_name, bool sharding = true);
@@ -332,8 +367,8 @@ int features_refuse(const rt_ctx *c, const char *call, const char *lead = "", co
 // the guide of a pair of halves (rt_set_denoise_guide): RT_ERR_STATE when the two settings differ, or -- on -- a feature plane is not current.  *guided: on
 int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guided = nullptr);
 // ---- rt_moments.hip: the kernels with a moments arm, launched for rt_reproject.hip and rt_atrous.hip (which have checked, chained and acquired) ----
-int reproject_moments(rt_ctx *dst, const rt_ctx *src, const rt_reproject_params &q, bool from_temporal, bool from_moments, hipStream_t stream);
-int atrous_prepare_moments(rt_ctx *c, float4 *out, bool pack, hipStream_t stream);
+int reproject_moments(rt_ctx *dst, const rt_ctx *src, const rt_reproject_params &q, const PlaneInput &in, hipStream_t stream);
+int atrous_prepare_moments(rt_ctx *c, const PlaneInput &in, float4 *out, bool pack, hipStream_t stream);
 // ---- rt_denoise_guided.hip: the filter kernels under a guide, launched for rt_denoise.hip ----
 struct GuidedFilter {
     const float *img[2];                // the frame, or the two halves

@@ -1,6 +1,6 @@
 // rt_moments.hip -- temporal luminance moments (include/rt_api.h, "temporal luminance moments"): the a-trous variance from a pixel's history --
 //   rt_set_temporal_moments  the per-context setting that rt_reproject_async INTO the context and rt_atrous_async OF it consult
-//   rt_read_moments          the context's moments plane M, (m1, m2, k, v) per pixel
+//   rt_read_moments          the context's moments plane M, (m1, m2, k, v) per pixel (read_plane, rt_internal.h)
 // and the kernel instances behind the setting: the reprojection kernel with its moments arm (rules 25-27) and the a-trous preparation kernel with
 // its own (rule 28).  Their statements are those of rt_reproject_kernel and rt_atrous_prepare_kernel -- rt_reproject_body.inc.h and
 // rt_atrous_prepare_body.inc.h, ONE text each -- with the arm chosen at compile time.  They are instantiated HERE, in a unit of their own, so that the
@@ -46,24 +46,24 @@ __global__ void __launch_bounds__(kPlaneLanes) rt_atrous_prepare_moments_kernel(
 
 namespace rt {
 
-// for rt_reproject_async, which has checked, chained and acquired everything: T, its packed plane and M of dst on `stream`
-int reproject_moments(rt_ctx *dst, const rt_ctx *src, const rt_reproject_params &q, bool from_temporal, bool from_moments, hipStream_t stream) {
-    const auto kernel = from_moments ? rt_reproject_moments_kernel<4, true> : from_temporal ? rt_reproject_moments_kernel<4, false> : rt_reproject_moments_kernel<3, false>;
-    hipLaunchKernelGGL(kernel, plane_grid(dst->w, dst->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(dst->d_temporal), dst->d_temporal_px,
-                       reinterpret_cast<float4 *>(dst->d_moments), reinterpret_cast<const float4 *>(dst->scene.d_features),
-                       reinterpret_cast<const float4 *>(src->scene.d_features), (const float *)dst->d_colors,
-                       (const float *)(from_temporal ? src->d_temporal : src->d_colors), reinterpret_cast<const float4 *>(from_moments ? src->d_moments : nullptr),
-                       dst->scene.tables.geom, src->scene.tables.geom, dst->scene.tables.n_spheres, pixel_camera(dst->cam), pixel_camera(src->cam), q.k_pos,
-                       q.max_history, (float)dst->frame.current_sample, (float)src->frame.current_sample, dst->w, dst->h, dst->knobs.fast() ? 1 : 0);
+// for rt_reproject_async, which has checked, chained and acquired everything: T, its packed plane and M of dst on `stream`, from `in` (filter_input of src)
+int reproject_moments(rt_ctx *dst, const rt_ctx *src, const rt_reproject_params &q, const PlaneInput &in, hipStream_t stream) {
+    const auto kernel = in.m ? rt_reproject_moments_kernel<4, true> : in.channels == 4 ? rt_reproject_moments_kernel<4, false> : rt_reproject_moments_kernel<3, false>;
+    hipLaunchKernelGGL(kernel, plane_grid(dst->w, dst->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(dst->planes.temporal), dst->planes.temporal_px,
+                       reinterpret_cast<float4 *>(dst->planes.moments), reinterpret_cast<const float4 *>(dst->scene.d_features),
+                       reinterpret_cast<const float4 *>(src->scene.d_features), (const float *)dst->d_colors, in.u, in.m, dst->scene.tables.geom,
+                       src->scene.tables.geom, dst->scene.tables.n_spheres, pixel_camera(dst->cam), pixel_camera(src->cam), q.k_pos, q.max_history,
+                       (float)dst->frame.current_sample, in.passes, dst->w, dst->h, dst->knobs.fast() ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
-// for rt_atrous_async, the same: (U's rgb, V0 by rule 28) into `out`, the guide and n planes, and -- `pack`: no level follows -- the packed plane
-int atrous_prepare_moments(rt_ctx *c, float4 *out, bool pack, hipStream_t stream) {
-    hipLaunchKernelGGL(rt_atrous_prepare_moments_kernel, plane_grid(c->w, c->h), dim3(kPlaneLanes), 0, stream, out, reinterpret_cast<float4 *>(c->d_atrous_guide),
-                       c->d_atrous_n, pack ? c->d_atrous_px : (uint32_t *)nullptr, (const float *)c->d_temporal, reinterpret_cast<const float4 *>(c->scene.d_features),
-                       reinterpret_cast<const float2 *>(c->d_moments), c->moments.k_min, c->w, c->h, c->knobs.fast() ? 1 : 0);
+// for rt_atrous_async, the same, from `in` with its moments plane (filter_input of c): (U's rgb, V0 by rule 28) into `out`, the guide and n planes, and --
+// `pack`: no level follows -- the packed plane
+int atrous_prepare_moments(rt_ctx *c, const PlaneInput &in, float4 *out, bool pack, hipStream_t stream) {
+    hipLaunchKernelGGL(rt_atrous_prepare_moments_kernel, plane_grid(c->w, c->h), dim3(kPlaneLanes), 0, stream, out, reinterpret_cast<float4 *>(c->planes.guide),
+                       c->planes.n, pack ? c->planes.atrous_px : (uint32_t *)nullptr, in.u, reinterpret_cast<const float4 *>(c->scene.d_features),
+                       reinterpret_cast<const float2 *>(in.m), c->planes.moments_set.params.k_min, c->w, c->h, c->knobs.fast() ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -75,23 +75,13 @@ using namespace rt;
 extern "C" {
 
 RT_API int rt_set_temporal_moments(rt_ctx *c, const rt_moments_params *m) {
-    int rc = tiles_refuse(c, "rt_set_temporal_moments");
-    if (rc != RT_OK) return rc;
+    RT_TRY(tiles_refuse(c, "rt_set_temporal_moments"));
     rt_moments_params q{};
     if (m && rt_host_moments_params(m, &q) != RT_OK) return RT_ERR_ARG;
-    c->have_moments = m != nullptr;
-    c->moments = q;
+    c->planes.moments_set = { q, m != nullptr };
     return RT_OK;
 }
 
-RT_API int rt_read_moments(rt_ctx *c, float *m_host) {
-    int rc = tiles_refuse(c, "rt_read_moments");
-    if (rc != RT_OK) return rc;
-    if (!m_host) return fail(RT_ERR_ARG, "rt_read_moments: m_host is null");
-    if (!moments_current(c))
-        return fail(RT_ERR_STATE, "rt_read_moments: the context holds no current moments plane (rt_reproject_async into it forms one while rt_set_temporal_moments is "
-                                  "on; whatever ends the temporal plane, or a reprojection into the context with the setting off, ends it)");
-    return read_back(c, m_host, c->d_moments, 4 * image_pixels(c) * sizeof(float));
-}
+RT_API int rt_read_moments(rt_ctx *c, float *m_host) { return read_plane(c, "rt_read_moments", Plane::Moments, m_host); }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // it registered, events, streams -- one entry per handle, in order of acquisition.  Whoever acquires a handle enters it here (the typed
 // helpers of rt_internal.h do both at once); teardown is release(), which gives everything back in reverse order, or forget(), which
 // gives nothing back -- the context whose streams may hold work that never completes.  The members that hold the handles (rt_ctx,
-// rt_multi) stay raw pointers: the record frees by value, so exchanging two of them (d_colors / d_denoise) needs nothing here.
+// rt_multi) stay raw pointers: the record frees by value, so exchanging two of them (d_colors / planes.denoise) needs nothing here.
 // No HIP in here -- giving back goes through owned_free(), which rt_api.hip defines; tools/sanitize/owned_main.cpp defines its own
 // and drives the record with the host compiler alone.
 #pragma once

@@ -1,7 +1,7 @@
 // rt_reproject.hip -- temporal reprojection (include/rt_api.h, "temporal reprojection"): a frame's samples carried to a moved camera --
 //   rt_reproject_async       src's history warped into dst's view through the first-hit geometry of the two feature planes and blended with dst's
 //                            colour plane, into a temporal plane (rgb, n) and its packed plane that dst owns
-//   rt_read_temporal         those two planes
+//   rt_read_temporal         those two planes (read_plane, rt_internal.h)
 // and the kernel behind the first.  rt_reproject_planes (rt_host.cpp) is the same arithmetic as plain loops; the header states it as rules 15-19, and
 // the comments below name the rule a line implements.  The reference reprojects nothing: this is the library's own extension.
 // This unit is compiled with parity's flags (-ffp-contract=off, correctly rounded division and square root): every multiply, add, division and square
@@ -50,47 +50,37 @@ RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_param
     rt_reproject_params q;
     if (rt_host_reproject_params(p, &q) != RT_OK) return RT_ERR_ARG;
     for (const rt_ctx *c : { dst, src }) {
-        const char *who = c == dst ? "the destination" : "the source";
         RT_TRY(features_refuse(c, call, "", c == dst ? " of the destination" : " of the source"));
-        if (c->frame.ragged) return fail(RT_ERR_STATE, "%s: %s is ragged (its tiles hold different pass counts)", call, who);
+        RT_TRY(ragged_refuse(c, call, c == dst ? "the destination" : "the source"));
     }
     if (dst->scene.tables.n_spheres != src->scene.tables.n_spheres)
         return fail(RT_ERR_STATE, "%s: the destination's scene holds %u records, the source's %u", call, dst->scene.tables.n_spheres, src->scene.tables.n_spheres);
-    const bool from_temporal = temporal_current(src);
-    if (!from_temporal && src->frame.current_sample <= 0)
-        return fail(RT_ERR_STATE, "%s: the source holds neither a current temporal plane nor a pass", call);
-    rc = select_device(dst);
-    if (rc != RT_OK) return rc;
-    RT_TRY(ensure_device(dst->owned, &dst->d_temporal, 4 * image_pixels(dst)));
-    RT_TRY(ensure_device(dst->owned, &dst->d_temporal_px, image_pixels(dst)));
-    const bool moments = dst->have_moments;                // the setting of dst: M is formed beside T (rules 25-27) ...
-    const bool from_moments = moments && moments_current(src);     // ... from S's M while that is current (which implies from_temporal), else from U's luminance
-    if (moments) RT_TRY(ensure_device(dst->owned, &dst->d_moments, 4 * image_pixels(dst)));
+    const bool moments = dst->planes.moments_set.on;       // the setting of dst: M is formed beside T (rules 25-27), from S's M while that is current, else from U's luminance
+    PlaneInput in;
+    RT_TRY(filter_input(src, call, "the source", moments, &in));
+    RT_TRY(select_device(dst));
+    Planes &pl = dst->planes;
+    RT_TRY(ensure_device(dst->owned, &pl.temporal, 4 * image_pixels(dst)));
+    RT_TRY(ensure_device(dst->owned, &pl.temporal_px, image_pixels(dst)));
+    if (moments) RT_TRY(ensure_device(dst->owned, &pl.moments, 4 * image_pixels(dst)));
     // behind everything the two contexts have queued, their later work behind the call; the tables from the records as they are now
     hipStream_t stream = (hipStream_t)hip_stream;
-    rc = chain(dst, stream);
-    if (rc == RT_OK) rc = chain(src, stream);
-    if (rc == RT_OK) rc = refresh_tables(dst, stream);
-    if (rc == RT_OK) rc = refresh_tables(src, stream);
-    if (rc != RT_OK) return rc;
-    if (moments) RT_TRY(reproject_moments(dst, src, q, from_temporal, from_moments, stream));       // rt_moments.hip: the kernel with the moments arm
+    RT_TRY(chain_all(stream, { dst, src }));
+    RT_TRY(refresh_tables(dst, stream));
+    RT_TRY(refresh_tables(src, stream));
+    if (moments) RT_TRY(reproject_moments(dst, src, q, in, stream));       // rt_moments.hip: the kernel with the moments arm
     else {
-        const auto kernel = from_temporal ? rt_reproject_kernel<4> : rt_reproject_kernel<3>;
-        hipLaunchKernelGGL(kernel, plane_grid(dst->w, dst->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(dst->d_temporal), dst->d_temporal_px,
+        const auto kernel = in.channels == 4 ? rt_reproject_kernel<4> : rt_reproject_kernel<3>;
+        hipLaunchKernelGGL(kernel, plane_grid(dst->w, dst->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(pl.temporal), pl.temporal_px,
                            reinterpret_cast<const float4 *>(dst->scene.d_features), reinterpret_cast<const float4 *>(src->scene.d_features),
-                           (const float *)dst->d_colors, (const float *)(from_temporal ? src->d_temporal : src->d_colors), dst->scene.tables.geom, src->scene.tables.geom,
-                           dst->scene.tables.n_spheres, pixel_camera(dst->cam), pixel_camera(src->cam), q.k_pos, q.max_history, (float)dst->frame.current_sample,
-                           (float)src->frame.current_sample, dst->w, dst->h, dst->knobs.fast() ? 1 : 0);
+                           (const float *)dst->d_colors, in.u, dst->scene.tables.geom, src->scene.tables.geom, dst->scene.tables.n_spheres, pixel_camera(dst->cam),
+                           pixel_camera(src->cam), q.k_pos, q.max_history, (float)dst->frame.current_sample, in.passes, dst->w, dst->h, dst->knobs.fast() ? 1 : 0);
         HIP_TRY(hipGetLastError());
     }
-    dst->frame.reprojected();
-    dst->moments_formed = moments;      // M is current exactly while T is and this says so
+    dst->frame.reprojected(moments);
     return RT_OK;
 }
 
-RT_API int rt_read_temporal(rt_ctx *c, float *rgbn_host, uint32_t *packed_host) {
-    return read_plane4(c, "rt_read_temporal", rgbn_host, packed_host, temporal_current, &rt_ctx::d_temporal, &rt_ctx::d_temporal_px,
-                       "temporal plane (rt_reproject_async forms one; whatever moves the colour plane or ends the feature plane ends it)");
-}
+RT_API int rt_read_temporal(rt_ctx *c, float *rgbn_host, uint32_t *packed_host) { return read_plane(c, "rt_read_temporal", Plane::Temporal, rgbn_host, packed_host); }
 
 }  // extern "C"

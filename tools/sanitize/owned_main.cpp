@@ -97,7 +97,7 @@ int main() {
         }
         check("destructor_releases", g_freed.size() == 2 && g_freed[0].handle == b && g_freed[1].handle == a && g_double_frees == 0 && g_live.empty(), "order or count");
     }
-    // two handles exchanged between the variables that hold them (d_colors / d_denoise after every rt_denoise_async): both once
+    // two handles exchanged between the variables that hold them (d_colors / planes.denoise after every rt_denoise_async): both once
     {
         reset();
         void *colors = handle(0), *denoise = handle(1);
