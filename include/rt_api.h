@@ -786,7 +786,8 @@ RT_API int rt_denoise_pair_guided_planes(float *out_a, float *out_b, const float
  * INTENDED USE: two contexts take turns.  Frame k + 1 sets its camera or records on the OLDER context, resets it (rt_seed_stream_async gives frame k
  * stream k + 1), forms its features, renders a pass or two and reprojects from the other.  Because S's temporal plane is used while it is current,
  * history carries across many frames, capped by max_history.
- * LIMITS: history follows the FIRST hit.  What a mirror or a glass sphere shows, and the shadows moved spheres cast, lag by up to max_history samples.
+ * LIMITS: history follows the FIRST hit.  What a mirror or a glass sphere shows, and the shadows moved spheres cast, lag by up to max_history samples
+ * ("shadow-aware history" below ends the history of pixels where such a shadow came or went, while its setting is on).
  * A changed radius, material or emission is not detected.  Sky pixels have no history.
  * MEASURED, in numpy on a CPU before any kernel existed (the prototype; tests/test_reproject_cpu.py holds the restatement), with frames of this
  * project's oracle alone: 96x96, the camera's origin moved sideways by 2 % of its distance to the target, S at 16 passes of seed stream 1 from the
@@ -1017,6 +1018,97 @@ RT_API int rt_reproject_moments_planes(float *out_rgbn, float *out_m, const rt_r
  * == NULL means the defaults.  RT_ERR_ARG: whatever rt_atrous_planes refuses, and parameters rt_set_temporal_moments refuses.                       */
 RT_API int rt_atrous_moments_planes(float *out_rgbv, const float *plane, int channels, int passes, const float *m /* NULL = rule 21 everywhere */,
                                      const float *feat, int w, int h, const rt_atrous_params *p, const rt_moments_params *mp);
+
+/* ---- shadow-aware history: a pixel's history ends where a moved sphere's shadow comes or goes ---------------
+ * History follows the first hit ("temporal reprojection", LIMITS): a floor pixel under a shadow that has just left keeps up to max_history dark
+ * samples against two new lit ones, and the filter then smooths the ghost instead of removing it.  In this renderer the occluders are spheres and
+ * the host knows which records changed, so the question "did the direct light at this point change?" has a geometric answer: for the point under a
+ * pixel and a light, decide whether a changed sphere stands in the cone from the point to the light, before and after the change.  Where that state
+ * differs, or is a penumbra, the pixel's history is capped at `keep` samples.  THIS LIBRARY'S OWN EXTENSION: it reproduces no reference frame and
+ * touches no render kernel, and WITH THE SETTING OFF, WHICH IS THE DEFAULT, every call above is what it was and launches the kernel it launched.
+ *
+ * THE FLAG PLANE is K[h][w], one byte per pixel, 0 or 1, in the colour plane's row order, owned by dst.  rt_reproject_async(dst, src, ..) forms it
+ * beside T while the setting is ON FOR dst; it is allocated on first use and freed by rt_destroy.  K IS CURRENT exactly while dst's temporal plane is
+ * current AND that plane's last rt_reproject_async ran with the setting on -- derived from T's currency, as M's is.
+ *
+ * THE ARITHMETIC, the same in the kernels and in rt_reproject_shadow_planes: binary32, uncontracted, in the written order, IEEE division -- ALWAYS
+ * parity's arithmetic; no square root.  dot is rule 15's; D, S, P, Pp, id, nd, nh, sw and hk are those of rules 15-19 and 26.  The records are
+ * read from the two contexts' host mirrors (device) or the two views (host function) to build the lists, and from the lists afterwards.
+ *  29. the lists.  Record j is a LIGHT when the library's own light test holds for D's record j: !(e.x == 0.f && e.z == 0.f).  Record j is CHANGED
+ *      when any of the four words {centre, radius} of S's and D's record j differ BITWISE.  Records whose radius is 0.0f on both sides are neither
+ *      (the loader's phantom records).  A PAIR (l, j) exists when l is a light, j != l, j is no such zero-radius record, and l or j is changed.
+ *      Pairs are ordered l ascending outer, j ascending inner.  A pair carries S's and D's {centre, radius} of l and of j.  No pair: no flag.
+ *  30. a pair's state at a point, state(X, L, rl, c, r).  seg = L - X per component, ll = dot(seg, seg); !(ll > 0.0f): state 0.
+ *      s = dot(c - X, seg) / ll;  if (!(s > 0.0f)) s = 0.0f;  if (s > 1.0f) s = 1.0f.
+ *      e = (X + seg * s) - c, d2 = dot(e, e), pen = rl * s, a = r + pen, b = r - pen.
+ *      State 0 (clear) when d2 > a * a; otherwise state 2 (umbra) when b > 0.0f && d2 < b * b; otherwise state 1 (penumbra).  A NaN makes every
+ *      comparison false and so gives state 1.  The cone is that of the light's bounding sphere, seen from the point.
+ *  31. the flag of pixel p.  p is flagged only when it has history (sw > 0.0f) and nd != 0: at pass 0 the call is a pure warp and nothing newer
+ *      exists to prefer.  For each pair in order with id != l and id != j:  old = state(Pp, S's l, S's j), new = state(P, D's l, D's j); the pair
+ *      CHANGES p when old != new || old == 1 || new == 1.  p is FLAGGED when any pair changes it.  (The host loop stops at the first such pair; the
+ *      device predicates.)
+ *  32. the effect.  For a flagged pixel, after rule 18's cap:  if (nh > keep) { hk = hk * (keep / nh); nh = keep; } -- the hk part in the moments arm
+ *      only, in proportion as rule 26 caps frames.  Rules 19 and 27 then run unchanged.  With keep 0 a flagged pixel comes out as (CD, nd).
+ * INVARIANTS: (a) with no changed record T, its packed plane and M are bit for bit what they are with the setting off, and K is all 0.  (b) With
+ * keep >= max_history T and M are bit for bit the plain ones while K may hold ones.  (c) At nd == 0, K is all 0.
+ * LIMITS: a moved sphere's own shading, a moved light's falloff on unshadowed surfaces, reflections, refractions and caustics still lag.  (A mirror
+ * rule -- flag a mirror pixel whose reflected ray meets a moved sphere -- was prototyped: it changed A by -0.07 and 0.00 dB and is not part of this.)
+ * A changed material or emission is not detected; a record that BECOMES a light is a light (D's record decides), one that ceases to be is not.
+ * REJECTED: textbook variance clipping -- the history clipped to mean +- k sigma of the new frame's 5x5 or 7x7 same-record neighbourhood, sigma of
+ * the pixels or the standard error of the mean, k 1 .. 6, with and without shrinking nh.  At two passes the box is as wide as the change it should
+ * catch: T moved by -0.1 .. +1.9 dB, the filtered frame A (three levels) by -1.8 .. +0.0 dB, and a static scene lost 0.1 .. 1.1 dB.
+ * MEASURED with rt_reproject_shadow_planes and rt_atrous_planes on a CPU (tests/test_shadow_history_cpu.py), frames of this project's oracle alone:
+ * 96x96, TWELVE frames of 2 passes, frame f on seed stream f with one record moved by (f - 1) steps, the camera still, two sides taking turns, the
+ * defaults (keep 2), truth 512 oracle passes of the last frame's scene, PSNR over 8-bit channels as in the tables above; off -> on, dB:
+ *     scene, moved record, step per frame        T                  A, 3 levels              A over the changed region (share)   flagged, last frame
+ *     cornell, glass sphere 16, (-1.5, 0, 0)     19.52 -> 19.58     24.56 -> 25.52 (+0.97)   18.36 -> 21.19 (9.5 %)                   3.9 %
+ *     Demo, sphere 4, (-2, 0, 0)                 22.72 -> 23.01     25.58 -> 26.65 (+1.07)   15.74 -> 19.45 (3.6 %)                   1.0 %
+ *     simple, sphere 6, (-2.5, 0, 0)             26.52 -> 26.74     28.26 -> 28.53 (+0.27)   12.17 -> 13.14 (0.7 %)                   0.2 %
+ * CHANGED REGION: pixels of the last view whose first hit is the same record as with the sphere where it stood six frames earlier, both truth
+ * luminances below 1 and differing by more than 25 % of the larger.  (The numpy prototype that preceded the rules -- binary64, a square root, both
+ * states at the new point, the sphere a step further in every frame -- gave A 24.76 -> 25.81, 25.43 -> 26.52 and 28.20 -> 28.57.)  T hardly moves
+ * -- a flagged pixel trades a biased mean for a noisy one -- and the FILTER gains: it spreads the right two samples instead of the wrong
+ * sixty-four, by 1 to 3.7 dB where the light changed.  `simple` gains less than 0.3 dB over the frame because 0.2 % of it is flagged.  The test
+ * asserts half of the two larger whole-frame gains and, for `simple`, no more than 0.3 dB below "off".
+ * MEASURED on an MI355X by tools/shadow_history_probe.py (profiles/r33_shadow_history.jsonl; device time of rt_reproject_async between two events,
+ * the device idle before the first, the setting ON and OFF alternating call by call in one process, medians of 12; NO TIME IS PROMISED), the Demo
+ * scene followed by small spheres buried in the ground, that many of them moved -- they shadow nothing, so no pixel is flagged and every pixel with
+ * history walks the WHOLE list, the worst case -- from a source's colour plane, 800x600 / 1920x1080, on against off:
+ *     1 pair       0.0262 against 0.0188 ms  /  0.0640 against 0.0555 ms
+ *     16 pairs     0.0408 against 0.0189 ms  /  0.1069 against 0.0554 ms
+ *     1024 pairs   1.0227 against 0.0181 ms  /  3.2008 against 0.0537 ms
+ * The instance itself (one pair: the flag plane's byte, the LDS chunk, two barriers, lanes that stay) costs 0.008 ms at either size; a pair costs
+ * 1.5 ps per pixel at 1920x1080 (2.0 ps at 800x600): two states -- two IEEE divisions and some forty other operations -- per pair and pixel with
+ * history.  A few moved spheres under a light or two are a fraction of a pass (0.103 ms at 1920x1080); a moved LIGHT in a scene of a thousand records
+ * costs thirty passes, and the caller who moves one should leave the setting off for that frame.  The quality table from rendered contexts,
+ * reprojected and filtered on the device: the CPU table's T and A figures and flagged shares to the last digit, all three scenes.
+ */
+#define RT_SHADOW_PAIR_CHUNK 64     /* pairs of rule 29 that the kernels stage in LDS at a time (80 bytes each) */
+typedef struct { float keep; uint32_t reserved[3]; } rt_shadow_history_params;   /* 16 bytes; keep finite and >= 0, reserved 0 */
+
+/* {2.0f, {0, 0, 0}}.  Needs no device.                                                                                           */
+RT_API void rt_shadow_history_defaults(rt_shadow_history_params *p);
+
+/* The context's setting that rt_reproject_async INTO it consults, as rt_set_temporal_moments' is; NULL turns it off (the default).  Moves no plane and
+ * ends none.  RT_ERR_ARG: a null, multi-device or sharded context, keep not finite or < 0, reserved words not 0.  A refused call changes nothing.   */
+RT_API int rt_set_shadow_history(rt_ctx *ctx, const rt_shadow_history_params *params);
+
+/* The context's flag plane K, one byte per pixel (0 or 1) in the colour plane's row order.  Blocking.  RT_ERR_STATE unless the temporal plane is
+ * current and its last rt_reproject_async ran with the setting on; RT_ERR_ARG for a null, multi-device or sharded context or a null buffer.        */
+RT_API int rt_read_history_flags(rt_ctx *ctx, uint8_t *k_host);
+
+/* Rules 15-19, 25-27 and 29-32 as plain host loops: what the device is tested against bit for bit.  out_rgbn[h][w][4] always; out_m[h][w][4] (rules
+ * 25-27) and out_k[h][w] (rule 31's flags) where not NULL; `src_m` as rt_reproject_moments_planes takes it (read only with out_m).  `sp` == NULL: no
+ * shadow rules -- rt_reproject_planes and rt_reproject_moments_planes are calls of this function with sp NULL -- and out_k, if given, is all 0.
+ * RT_ERR_ARG: whatever rt_reproject_planes refuses, and parameters rt_set_shadow_history refuses.                                                 */
+RT_API int rt_reproject_shadow_planes(float *out_rgbn, float *out_m /* or NULL */, uint8_t *out_k /* or NULL */, const rt_reproject_view *dst,
+                                       const rt_reproject_view *src, const float *src_m /* [h][w][4] or NULL */, uint32_t count, int w, int h,
+                                       const rt_reproject_params *p, const rt_shadow_history_params *sp /* NULL = off */);
+
+/* Rule 29's pair list of the records S (before) and D (after), `count` each, in rule 29's order: the indices (l, j) of up to `cap` pairs into
+ * out_lj[2 * k], out_lj[2 * k + 1] (NULL with cap 0 to count).  Returns the number of pairs the records have, or -1 for a null argument.  Needs no
+ * device.                                                                                                                                        */
+RT_API int rt_shadow_history_pairs(const rt_sphere *src_spheres, const rt_sphere *dst_spheres, uint32_t count, uint32_t *out_lj, uint32_t cap);
 
 RT_API int rt_get_stats(rt_ctx *ctx, rt_stats *out);
 /* The kernel instance the context's last launch used, by its symbol (what a profiler lists): the library picks it

@@ -48,6 +48,7 @@ UNITS = [
     ("rt_reproject.hip", ["-ffp-contract=off"]),
     ("rt_atrous.hip", ["-ffp-contract=off"]),
     ("rt_moments.hip", ["-ffp-contract=off"]),
+    ("rt_shadow_history.hip", ["-ffp-contract=off"]),
     ("rt_host.cpp", ["-ffp-contract=off"]),
     ("rt_bvh_host.cpp", ["-ffp-contract=off"]),
     ("rt_build_id.cpp", []),

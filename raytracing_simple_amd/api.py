@@ -31,7 +31,8 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_denoise_guided_planes", "rt_denoise_pair_guided_planes",
            "rt_reproject_defaults", "rt_reproject_async", "rt_read_temporal", "rt_reproject_planes",
            "rt_atrous_defaults", "rt_atrous_async", "rt_read_atrous", "rt_atrous_planes",
-           "rt_moments_defaults", "rt_set_temporal_moments", "rt_read_moments", "rt_reproject_moments_planes", "rt_atrous_moments_planes"]
+           "rt_moments_defaults", "rt_set_temporal_moments", "rt_read_moments", "rt_reproject_moments_planes", "rt_atrous_moments_planes",
+           "rt_shadow_history_defaults", "rt_set_shadow_history", "rt_read_history_flags", "rt_reproject_shadow_planes", "rt_shadow_history_pairs"]
 # include/rt_debug.h: what librt_hip_diag.so exports on top of that
 DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instance_name", "rt_debug_shard_kernel", "rt_debug_break_gather", "rt_debug_set_rccl_library", "rt_debug_stage_tables", "rt_debug_eval", "rt_debug_sqrt_mismatches", "rt_debug_hitpost_mismatches",
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
@@ -112,6 +113,17 @@ class MomentsParams(C.Structure):
 
     def as_dict(self):
         return {"k_min": float(self.k_min), "reserved": [int(v) for v in self.reserved]}
+
+
+class ShadowHistoryParams(C.Structure):
+    """include/rt_api.h rt_shadow_history_params (16 bytes): keep (finite, >= 0), three reserved words (0)."""
+    _fields_ = [("keep", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {"keep": float(self.keep), "reserved": [int(v) for v in self.reserved]}
+
+
+SHADOW_PAIR_CHUNK = 64      # include/rt_api.h RT_SHADOW_PAIR_CHUNK: the pairs of rule 29 the kernels stage in LDS at a time
 
 
 class _Scene(C.Structure):
@@ -223,6 +235,12 @@ def load_library(diag=False):
         "rt_read_moments": (i32, [vp, vp]),
         "rt_reproject_moments_planes": (i32, [vp, vp, C.POINTER(ReprojectView), C.POINTER(ReprojectView), vp, u32, i32, i32, C.POINTER(ReprojectParams)]),
         "rt_atrous_moments_planes": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, C.POINTER(AtrousParams), C.POINTER(MomentsParams)]),
+        "rt_shadow_history_defaults": (None, [C.POINTER(ShadowHistoryParams)]),
+        "rt_set_shadow_history": (i32, [vp, C.POINTER(ShadowHistoryParams)]),
+        "rt_read_history_flags": (i32, [vp, vp]),
+        "rt_reproject_shadow_planes": (i32, [vp, vp, vp, C.POINTER(ReprojectView), C.POINTER(ReprojectView), vp, u32, i32, i32, C.POINTER(ReprojectParams),
+                                             C.POINTER(ShadowHistoryParams)]),
+        "rt_shadow_history_pairs": (i32, [vp, vp, u32, vp, u32]),
         "rt_demo_scene": (i32, [vp, u32]),
         "rt_read_scene": (i32, [C.c_char_p, vp, u32, C.POINTER(u32), vp, vp, i32]),
     }
@@ -669,6 +687,24 @@ class RtContext:
         """rt_moments_defaults (the module-level moments_defaults)."""
         return moments_defaults()
 
+    # --- shadow-aware history (rt_shadow_history.hip) -----------------------------------------------
+    def set_shadow_history(self, shadow=None):
+        """rt_set_shadow_history: None switches the setting off; a ShadowHistoryParams or a dict of fields laid over shadow_history_defaults()
+        switches it on: reproject_async INTO this context then caps the history of pixels where a changed record's shadow came or went (rules 29-32)
+        and forms the flag plane (read_history_flags)."""
+        self._check(self._lib.rt_set_shadow_history(self._h, _shadow_history_params(shadow)))
+
+    def read_history_flags(self):
+        """rt_read_history_flags: the flag plane, uint8 [h][w] (0 or 1) in the colour plane's row order."""
+        k = np.zeros((self.h, self.w), np.uint8)
+        self._check(self._lib.rt_read_history_flags(self._h, _ptr(k)))
+        return k
+
+    @staticmethod
+    def shadow_history_defaults():
+        """rt_shadow_history_defaults (the module-level shadow_history_defaults)."""
+        return shadow_history_defaults()
+
     def read_filtered(self):
         """rt_read_filtered: the cross-filtered plane, float32 [3 * w * h] as read_colors() lays it out."""
         out = np.zeros(3 * self.w * self.h, np.float32)
@@ -939,6 +975,57 @@ def reproject_moments_planes(dst, src, w, h, src_m=None, params=None):
     _check(load_library().rt_reproject_moments_planes(_ptr(out), _ptr(out_m), C.byref(views[0]), C.byref(views[1]), _ptr(src_m) if src_m is not None else None,
                                                       count, w, h, _reproject_params(params)))
     return out, out_m
+
+
+def shadow_history_defaults():
+    """rt_shadow_history_defaults: ShadowHistoryParams {2.0, {0, 0, 0}}.  Needs no device."""
+    p = ShadowHistoryParams()
+    load_library().rt_shadow_history_defaults(C.byref(p))
+    return p
+
+
+def _shadow_history_params(params):
+    """None, a ShadowHistoryParams, or a dict of fields laid over the defaults -> what the C call takes."""
+    if params is None or isinstance(params, ShadowHistoryParams):
+        return C.byref(params) if params is not None else None
+    p = shadow_history_defaults()
+    for name, value in dict(params).items():
+        if name != "keep":
+            raise ValueError("rt_shadow_history_params has no field %r" % name)
+        setattr(p, name, value)
+    return C.byref(p)
+
+
+def reproject_shadow_planes(dst, src, w, h, src_m=None, params=None, shadow=None, moments=True):
+    """rt_reproject_shadow_planes: rules 15-19, 25-27 and 29-32 on HOST planes; returns (the temporal plane float32 [h][w][4], the moments plane
+    float32 [h][w][4] or None with moments=False, the flag plane uint8 [h][w]).  `dst`, `src`, `src_m` and `params` as reproject_moments_planes takes
+    them; `shadow`: a ShadowHistoryParams, a dict of its fields over the defaults, or None for no shadow rules (the flags are then all 0).
+    Needs no device."""
+    keep, views, count = _reproject_views(dst, src, w, h)
+    if src_m is not None:
+        src_m = np.ascontiguousarray(src_m, dtype=np.float32).reshape(-1)
+        if src_m.size != 4 * w * h:
+            raise ValueError("a moments plane of %d floats, got %d" % (4 * w * h, src_m.size))
+    out, out_m, out_k = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32) if moments else None, np.zeros((h, w), np.uint8)
+    _check(load_library().rt_reproject_shadow_planes(_ptr(out), _ptr(out_m) if moments else None, _ptr(out_k), C.byref(views[0]), C.byref(views[1]),
+                                                     _ptr(src_m) if src_m is not None else None, count, w, h, _reproject_params(params),
+                                                     _shadow_history_params(shadow)))
+    return out, out_m, out_k
+
+
+def shadow_history_pairs(src_spheres, dst_spheres):
+    """rt_shadow_history_pairs: rule 29's pair list of the records before (`src_spheres`) and after (`dst_spheres`), int64 [n][2] of (l, j) in rule
+    29's order.  Needs no device."""
+    s, d = as_spheres(src_spheres), as_spheres(dst_spheres)
+    if len(s) != len(d):
+        raise ValueError("the two sides hold %d and %d records" % (len(s), len(d)))
+    lib = load_library()
+    n = lib.rt_shadow_history_pairs(s.ctypes.data if len(s) else None, d.ctypes.data if len(s) else None, len(s), None, 0)
+    if n < 0:
+        raise RtError(-1, lib.rt_last_error().decode(errors="replace"))
+    out = np.zeros((n, 2), np.uint32)
+    lib.rt_shadow_history_pairs(s.ctypes.data if len(s) else None, d.ctypes.data if len(s) else None, len(s), _ptr(out) if n else None, n)
+    return out.astype(np.int64)
 
 
 def atrous_defaults():

@@ -3,8 +3,9 @@
 //   camera basis, the built-in scene and the .scn reader.
 //   The host statements of the library's extensions, as plain loops, with their defaults and parameter rules: rt_denoise_planes and
 //   rt_denoise_pair_planes with their guided forms (rules 1-6, 13-14), rt_features_planes (rules 10-12), rt_reproject_planes (rules 15-19),
-//   rt_atrous_planes (rules 20-23) and their forms with temporal moments, rt_reproject_moments_planes and rt_atrous_moments_planes (rules 25-28).  The kernels are tested against them bit for bit.  The loops, the clamping and the order of the sums are written
+//   rt_atrous_planes (rules 20-23), their forms with temporal moments, rt_reproject_moments_planes and rt_atrous_moments_planes (rules 25-28), and rt_reproject_shadow_planes (rules 29-32 beside them).  The kernels are tested against them bit for bit.  The loops, the clamping and the order of the sums are written
 //   here; the arithmetic of a rule is rt_rules.h's, which the kernels call too.
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -458,14 +459,68 @@ int rt_host_reproject_params(const rt_reproject_params *p, rt_reproject_params *
     return RT_OK;
 }
 
+void rt_shadow_history_defaults(rt_shadow_history_params *p) {
+    if (!p) return;
+    p->keep = 2.0f;                     // what the prototype measured best (include/rt_api.h, "shadow-aware history")
+    p->reserved[0] = p->reserved[1] = p->reserved[2] = 0;
+}
+
+// the parameter rule rt_set_shadow_history and rt_reproject_shadow_planes share; hidden, like rt_host_moments_params
+int rt_host_shadow_history_params(const rt_shadow_history_params *p, rt_shadow_history_params *out) {
+    rt_shadow_history_defaults(out);
+    if (p) *out = *p;
+    if (!std::isfinite(out->keep) || !(out->keep >= 0.f)) return host_fail("rt_shadow_history: keep %g (finite, >= 0)", (double)out->keep);
+    if (out->reserved[0] != 0 || out->reserved[1] != 0 || out->reserved[2] != 0)
+        return host_fail("rt_shadow_history: reserved %u, %u, %u (0)", out->reserved[0], out->reserved[1], out->reserved[2]);
+    return RT_OK;
+}
+
+// rule 29: the pair list of the records S and D, `count` each, in its order; the first `cap` pairs into `out` (rt::kShadowPairFloats floats each: S's and
+// D's {centre, radius} of l, then of j, then l and j as words and two zero words), or nothing (out null).  Returns how many pairs there are.  Hidden:
+// the host loops below and rt_reproject_async (rt_shadow_history.hip, over the two contexts' mirrors) build their lists with it
+size_t rt_host_shadow_pairs(const rt_sphere *S, const rt_sphere *D, uint32_t count, float *out, size_t cap) {
+    const auto changed = [&](uint32_t j) { return memcmp(&S[j], &D[j], 4 * sizeof(float)) != 0; };        // {rad, p}: the record's first four words
+    const auto phantom = [&](uint32_t j) { return S[j].rad == 0.0f && D[j].rad == 0.0f; };
+    const auto put = [](float *o, const rt_sphere &s) { o[0] = s.p.x, o[1] = s.p.y, o[2] = s.p.z, o[3] = s.rad; };
+    size_t n = 0;
+    for (uint32_t l = 0; l < count; ++l) {
+        if (phantom(l) || !rt::light_record(D[l])) continue;
+        const bool l_changed = changed(l);
+        for (uint32_t j = 0; j < count; ++j) {
+            if (j == l || phantom(j) || !(l_changed || changed(j))) continue;
+            if (out && n < cap) {
+                float *o = out + rt::kShadowPairFloats * n;
+                put(o, S[l]), put(o + 4, D[l]), put(o + 8, S[j]), put(o + 12, D[j]);
+                const uint32_t words[4] = { l, j, 0, 0 };
+                memcpy(o + 16, words, sizeof words);
+            }
+            ++n;
+        }
+    }
+    return n;
+}
+
+int rt_shadow_history_pairs(const rt_sphere *src_spheres, const rt_sphere *dst_spheres, uint32_t count, uint32_t *out_lj, uint32_t cap) {
+    if ((count > 0 && (!src_spheres || !dst_spheres)) || (cap > 0 && !out_lj)) {
+        host_fail("rt_shadow_history_pairs: null argument");
+        return -1;
+    }
+    const size_t n = rt_host_shadow_pairs(src_spheres, dst_spheres, count, nullptr, 0);
+    std::vector<float> list(rt::kShadowPairFloats * std::min<size_t>(n, cap));
+    rt_host_shadow_pairs(src_spheres, dst_spheres, count, list.data(), std::min<size_t>(n, cap));
+    for (size_t k = 0; k < std::min<size_t>(n, cap); ++k) memcpy(out_lj + 2 * k, list.data() + rt::kShadowPairFloats * k + 16, 2 * sizeof(uint32_t));
+    return (int)n;
+}
+
 }  // extern "C"
 
 namespace {
 
 // rules 15-19 and, where out_m is not null, rules 25-27 beside them (src_m: S's moments plane, or null for rule 25's luminance of U): the loops of
-// rt_reproject_planes and rt_reproject_moments_planes, which therefore cannot differ in a word of out_rgbn
-int reproject_loops(const char *call, float *out_rgbn, float *out_m, const rt_reproject_view *dst, const rt_reproject_view *src, const float *src_m, uint32_t count,
-                    int w, int h, const rt_reproject_params *p) {
+// rt_reproject_planes and rt_reproject_moments_planes, which therefore cannot differ in a word of out_rgbn.  sp not null: rules 29-32 between the
+// history and the blend (out_k, where not null: rule 31's flags; all 0 without sp)
+int reproject_loops(const char *call, float *out_rgbn, float *out_m, uint8_t *out_k, const rt_reproject_view *dst, const rt_reproject_view *src, const float *src_m,
+                    uint32_t count, int w, int h, const rt_reproject_params *p, const rt_shadow_history_params *sp) {
     if (!out_rgbn || !dst || !src) return host_fail("%s: null argument", call);
     if (w < 1 || h < 1) return host_fail("%s: %dx%d", call, w, h);
     for (const rt_reproject_view *v : { dst, src }) {
@@ -478,6 +533,14 @@ int reproject_loops(const char *call, float *out_rgbn, float *out_m, const rt_re
     if (!dst->plane && dst->passes != 0) return host_fail("%s: dst has a null plane and %d passes", call, dst->passes);
     rt_reproject_params q;
     if (rt_host_reproject_params(p, &q) != RT_OK) return RT_ERR_ARG;
+    rt_shadow_history_params sq{};
+    if (sp && rt_host_shadow_history_params(sp, &sq) != RT_OK) return RT_ERR_ARG;
+    // 29. the lists
+    std::vector<float> pairs;
+    if (sp) {
+        pairs.resize(rt::kShadowPairFloats * rt_host_shadow_pairs(src->spheres, dst->spheres, count, nullptr, 0));
+        rt_host_shadow_pairs(src->spheres, dst->spheres, count, pairs.data(), pairs.size() / rt::kShadowPairFloats);
+    }
 
     const rt_camera &camS = *src->cam;
     const rt::PixelCamera pcD = rt::pixel_camera(*dst->cam), pcS = rt::pixel_camera(camS);
@@ -495,14 +558,15 @@ int reproject_loops(const char *call, float *out_rgbn, float *out_m, const rt_re
             // 15. the point and where it was
             uint32_t id;
             memcpy(&id, dst->feat + 8 * at + 7, sizeof id);
+            float P[3] = { 0.0f, 0.0f, 0.0f }, Pp[3] = { 0.0f, 0.0f, 0.0f };
             if (id < count) {                                         // (0xFFFFFFFF: the sky)
                 const float t = dst->feat[8 * at + 6];
-                float Pp[3], v[3];
+                float v[3];
                 const rt::PixelRay r = rt::pixel_ray(pcD, x, y, inv_w, inv_h);
                 const float o[3] = { r.ox, r.oy, r.oz }, d[3] = { r.dx, r.dy, r.dz };
                 const rt_vec3 &pd = dst->spheres[id].p, &ps = src->spheres[id].p;
                 const float m[3] = { pd.x - ps.x, pd.y - ps.y, pd.z - ps.z };
-                for (int c = 0; c < 3; ++c) Pp[c] = (o[c] + d[c] * t) - m[c];
+                for (int c = 0; c < 3; ++c) P[c] = o[c] + d[c] * t, Pp[c] = P[c] - m[c];
                 // 16. where S saw it
                 v[0] = Pp[0] - camS.orig.x, v[1] = Pp[1] - camS.orig.y, v[2] = Pp[2] - camS.orig.z;
                 const float z = rp_dot(v, sdir);
@@ -550,15 +614,29 @@ int reproject_loops(const char *call, float *out_rgbn, float *out_m, const rt_re
                     }
                 }
             }
-            // 19. the blend (D's plane is not read at pass 0)
+            // 31. the flag: a pixel with history and a newer sample, under a pair whose state at it changed (sw > 0.0f implies id < count)
+            bool flagged = false;
+            if (sw > 0.0f && dst->passes != 0)
+                for (size_t k = 0; k < pairs.size() && !flagged; k += rt::kShadowPairFloats) {
+                    const float *g = pairs.data() + k;
+                    uint32_t lj[2];
+                    memcpy(lj, g + 16, sizeof lj);
+                    if (id == lj[0] || id == lj[1]) continue;
+                    const int before = rt::shadow_state(Pp[0], Pp[1], Pp[2], g[0], g[1], g[2], g[3], g[8], g[9], g[10], g[11]);          // 30.
+                    const int after = rt::shadow_state(P[0], P[1], P[2], g[4], g[5], g[6], g[7], g[12], g[13], g[14], g[15]);
+                    flagged = rt::shadow_changes(before, after);
+                }
+            if (out_k) out_k[at] = flagged ? 1 : 0;
+            // 19. the blend (D's plane is not read at pass 0), with 32. the cap of a flagged pixel
             const float *CD = dst->passes != 0 ? dst->plane + (size_t)cd * at : nullptr;
             float *T = out_rgbn + 4 * at;
-            rt::temporal_blend(T[0], T[1], T[2], T[3], CD ? CD[0] : 0.0f, CD ? CD[1] : 0.0f, CD ? CD[2] : 0.0f, nd, CD != nullptr, sw, sn, sc[0], sc[1], sc[2], q.max_history);
+            rt::temporal_blend_as<true>(T[0], T[1], T[2], T[3], CD ? CD[0] : 0.0f, CD ? CD[1] : 0.0f, CD ? CD[2] : 0.0f, nd, CD != nullptr, sw, sn, sc[0], sc[1], sc[2],
+                                        q.max_history, flagged, sq.keep);
             if (!out_m) continue;
             // 27. the moments' blend
             float *M = out_m + 4 * at;
             const float lD = CD ? rt::luminance(CD[0], CD[1], CD[2]) : 0.0f;
-            rt::moments_blend(M[0], M[1], M[2], M[3], lD, nd, CD != nullptr, sw, sn, s1, s2, sk, q.max_history);
+            rt::moments_blend_as<true>(M[0], M[1], M[2], M[3], lD, nd, CD != nullptr, sw, sn, s1, s2, sk, q.max_history, flagged, sq.keep);
         }
     return RT_OK;
 }
@@ -569,13 +647,19 @@ extern "C" {
 
 int rt_reproject_planes(float *out_rgbn, const rt_reproject_view *dst, const rt_reproject_view *src, uint32_t count, int w, int h,
                         const rt_reproject_params *p) {
-    return reproject_loops("rt_reproject_planes", out_rgbn, nullptr, dst, src, nullptr, count, w, h, p);
+    return rt_reproject_shadow_planes(out_rgbn, nullptr, nullptr, dst, src, nullptr, count, w, h, p, nullptr);
 }
 
 int rt_reproject_moments_planes(float *out_rgbn, float *out_m, const rt_reproject_view *dst, const rt_reproject_view *src, const float *src_m, uint32_t count, int w,
                                 int h, const rt_reproject_params *p) {
     if (!out_m) return host_fail("rt_reproject_moments_planes: null argument");
-    return reproject_loops("rt_reproject_moments_planes", out_rgbn, out_m, dst, src, src_m, count, w, h, p);
+    return rt_reproject_shadow_planes(out_rgbn, out_m, nullptr, dst, src, src_m, count, w, h, p, nullptr);
+}
+
+int rt_reproject_shadow_planes(float *out_rgbn, float *out_m, uint8_t *out_k, const rt_reproject_view *dst, const rt_reproject_view *src, const float *src_m,
+                               uint32_t count, int w, int h, const rt_reproject_params *p, const rt_shadow_history_params *sp) {
+    const char *const call = sp ? "rt_reproject_shadow_planes" : out_m ? "rt_reproject_moments_planes" : "rt_reproject_planes";     // (each refusal keeps its caller's name)
+    return reproject_loops(call, out_rgbn, out_m, out_k, dst, src, src_m, count, w, h, p, sp);
 }
 
 }  // extern "C"

@@ -190,6 +190,8 @@ struct Scene {
 //   filtered, _px  [h][w][3], packed                   rt_denoise_pair*_async: this half filtered with the other half's weights (rt_compare_filtered reads _px)
 //   temporal, _px  [h][w][4] (rgb, n), packed          rt_reproject_async INTO this context
 //   moments        [h][w][4] (m1, m2, k, v)            ... while the moments setting of this context is on
+//   flags          [h][w] bytes, 0 or 1                ... while the shadow-history setting of this context is on (rule 31; current while flags_formed beside T)
+//   pairs          5 float4 a pair, pairs_cap pairs    ... the same call's pair list (rule 29), staged through pair_stage without a host wait
 //   atrous, _px    [h][w][4] (rgb, variance), packed   rt_atrous_async, like the three below
 //   tmp            [h][w][4]                           the other (rgb, variance) plane the levels alternate with
 //   guide          [h][w][4]                           the normal and the scene index of the feature plane, one aligned texel
@@ -199,6 +201,13 @@ struct Planes {
     uint32_t *filtered_px = nullptr, *temporal_px = nullptr, *atrous_px = nullptr;
     struct { rt_guide_params params{}; bool on = false; } guide_set;        // rt_set_denoise_guide: what the filters of a pair of halves add to their weights
     struct { rt_moments_params params{}; bool on = false; } moments_set;    // rt_set_temporal_moments: what rt_reproject_async into the context and rt_atrous_async of it consult
+    // shadow-aware history (rt_shadow_history.hip; include/rt_api.h "shadow-aware history")
+    uint8_t *flags = nullptr;
+    bool flags_formed = false;          // the reprojection that formed the temporal plane ran with the setting on: K is current while T is
+    float4 *pairs = nullptr;
+    size_t pairs_cap = 0;               // pairs the block holds room for
+    Staged<float4, 4, true> pair_stage;
+    struct { rt_shadow_history_params params{}; bool on = false; } shadow_set;     // rt_set_shadow_history: what rt_reproject_async into the context consults
 };
 
 // the rows of an image of `h` that rank `rank` of `nranks` renders, the image dealt out in tiles of `tile_rows` (api.local_rows_of says the same in Python)
@@ -282,6 +291,7 @@ inline bool features_current(const rt_ctx *c) { return c->scene.state.features_c
 inline bool filtered_current(const rt_ctx *c) { return c->frame.filtered_pair != 0 && c->planes.filtered && c->planes.filtered_px; }
 inline bool temporal_current(const rt_ctx *c) { return c->frame.temporal_current && features_current(c) && c->planes.temporal && c->planes.temporal_px; }
 inline bool moments_current(const rt_ctx *c) { return temporal_current(c) && c->frame.moments_formed && c->planes.moments; }
+inline bool flags_current(const rt_ctx *c) { return temporal_current(c) && c->planes.flags_formed && c->planes.flags; }
 inline bool atrous_current(const rt_ctx *c) { return c->frame.atrous_current && features_current(c) && c->planes.atrous && c->planes.atrous_px; }
 // ... and what a reader of one needs beside that: the name of its buffer in the "is null" refusal (null: the call takes two buffers), what the
 // context "holds no current" of, the plane with its length in floats, and the packed plane of a call that hands out two
@@ -369,6 +379,9 @@ int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guide
 // ---- rt_moments.hip: the kernels with a moments arm, launched for rt_reproject.hip and rt_atrous.hip (which have checked, chained and acquired) ----
 int reproject_moments(rt_ctx *dst, const rt_ctx *src, const rt_reproject_params &q, const PlaneInput &in, hipStream_t stream);
 int atrous_prepare_moments(rt_ctx *c, const PlaneInput &in, float4 *out, bool pack, hipStream_t stream);
+// ---- rt_shadow_history.hip: the kernels with the shadow arm (rules 29-32), launched for rt_reproject.hip likewise; the pair list is built from the two
+// contexts' mirrors and staged here; T, its packed plane, K and -- `moments` -- M of dst on `stream`
+int reproject_shadow(rt_ctx *dst, rt_ctx *src, const rt_reproject_params &q, const PlaneInput &in, bool moments, hipStream_t stream);
 // ---- rt_denoise_guided.hip: the filter kernels under a guide, launched for rt_denoise.hip ----
 struct GuidedFilter {
     const float *img[2];                // the frame, or the two halves

@@ -30,6 +30,12 @@ __global__ void __launch_bounds__(kPlaneLanes) rt_reproject_moments_kernel(float
                                                                            rt::PixelCamera cam_d, rt::PixelCamera cam_s, float k_pos, float max_history, float nd, float ns,
                                                                            int w, int h, int fast) {
     constexpr int kMom = kFromPlane ? kMomentsOfPlane : kMomentsOfLuminance;
+    constexpr bool kShadow = false;                         // the shadow arm (rt_shadow_history.hip) is discarded, as in rt_reproject_kernel
+    constexpr const float4 *pairs = nullptr;
+    constexpr uint32_t n_pairs = 0;
+    constexpr float keep = 0.0f;
+    constexpr uint8_t *out_k = nullptr;
+    constexpr float4 *s_pairs = nullptr;
 #include "rt_reproject_body.inc.h"
 }
 

@@ -16,6 +16,9 @@ constexpr int kPlaneTileW = 32, kPlaneTileH = 8, kPlaneLanes = kPlaneTileW * kPl
 // of U, or from S's moments plane
 enum { kNoMoments = 0, kMomentsOfLuminance = 1, kMomentsOfPlane = 2 };
 
+// The shadow arm of the same statements (rule 31): the pair list goes through LDS in chunks of this many records of five float4 -- 5120 bytes a workgroup
+constexpr int kShadowChunk = RT_SHADOW_PAIR_CHUNK;
+
 struct PlanePixel {
     int x, y;
 };

@@ -7,7 +7,8 @@
 // This unit is compiled with parity's flags (-ffp-contract=off, correctly rounded division and square root): every multiply, add, division and square
 // root below is an operation of its own, in the written order -- whatever rt_set_mode says.
 // The render kernels are not touched, and nothing here writes anything but the two temporal planes -- and, with rt_set_temporal_moments on for dst,
-// its moments plane, through the kernel instances of rt_moments.hip.  The kernel's STATEMENTS are rt_reproject_body.inc.h, shared with that unit.
+// its moments plane, through the kernel instances of rt_moments.hip, and, with rt_set_shadow_history on for dst, its flag plane, through those of
+// rt_shadow_history.hip.  The kernel's STATEMENTS are rt_reproject_body.inc.h, shared with those units.
 #include <hip/hip_runtime.h>
 
 #include "rt_internal.h"
@@ -32,6 +33,12 @@ __global__ void __launch_bounds__(kPlaneLanes) rt_reproject_kernel(float4 *__res
     constexpr int kMom = kNoMoments;                        // the moments arm (rt_moments.hip) is discarded: its two planes are not arguments here
     constexpr float4 *out_m = nullptr;
     constexpr const float4 *m_s = nullptr;
+    constexpr bool kShadow = false;                         // ... and so is the shadow arm (rt_shadow_history.hip), with its list, its setting, its plane and its LDS
+    constexpr const float4 *pairs = nullptr;
+    constexpr uint32_t n_pairs = 0;
+    constexpr float keep = 0.0f;
+    constexpr uint8_t *out_k = nullptr;
+    constexpr float4 *s_pairs = nullptr;
 #include "rt_reproject_body.inc.h"
 }
 
@@ -56,6 +63,7 @@ RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_param
     if (dst->scene.tables.n_spheres != src->scene.tables.n_spheres)
         return fail(RT_ERR_STATE, "%s: the destination's scene holds %u records, the source's %u", call, dst->scene.tables.n_spheres, src->scene.tables.n_spheres);
     const bool moments = dst->planes.moments_set.on;       // the setting of dst: M is formed beside T (rules 25-27), from S's M while that is current, else from U's luminance
+    const bool shadow = dst->planes.shadow_set.on;         // ... and K beside T (rules 29-32), through the kernels of rt_shadow_history.hip
     PlaneInput in;
     RT_TRY(filter_input(src, call, "the source", moments, &in));
     RT_TRY(select_device(dst));
@@ -68,7 +76,8 @@ RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_param
     RT_TRY(chain_all(stream, { dst, src }));
     RT_TRY(refresh_tables(dst, stream));
     RT_TRY(refresh_tables(src, stream));
-    if (moments) RT_TRY(reproject_moments(dst, src, q, in, stream));       // rt_moments.hip: the kernel with the moments arm
+    if (shadow) RT_TRY(reproject_shadow(dst, src, q, in, moments, stream));   // rt_shadow_history.hip: the kernels with the shadow arm, or -- no pair -- one below
+    else if (moments) RT_TRY(reproject_moments(dst, src, q, in, stream));     // rt_moments.hip: the kernel with the moments arm
     else {
         const auto kernel = in.channels == 4 ? rt_reproject_kernel<4> : rt_reproject_kernel<3>;
         hipLaunchKernelGGL(kernel, plane_grid(dst->w, dst->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(pl.temporal), pl.temporal_px,
@@ -78,6 +87,7 @@ RT_API int rt_reproject_async(rt_ctx *dst, rt_ctx *src, const rt_reproject_param
         HIP_TRY(hipGetLastError());
     }
     dst->frame.reprojected(moments);
+    pl.flags_formed = shadow;
     return RT_OK;
 }
 

@@ -1,6 +1,6 @@
 // rt_rules.h -- the arithmetic of the numbered rules of include/rt_api.h's extensions (feature planes, NL-means and its guide, temporal reprojection,
-// the a-trous filter, temporal luminance moments), stated ONCE: the plain loops of rt_host.cpp (rt_*_planes) and the kernels (rt_features.hip,
-// rt_reproject.hip, rt_atrous.hip, rt_moments.hip, rt_denoise.inc.h) call these functions, so the two sides the GPU tests hold together bit for bit cannot drift apart by a copied line.  Usable from plain
+// the a-trous filter, temporal luminance moments, shadow-aware history), stated ONCE: the plain loops of rt_host.cpp (rt_*_planes) and the kernels (rt_features.hip,
+// rt_reproject.hip, rt_atrous.hip, rt_moments.hip, rt_shadow_history.hip, rt_denoise.inc.h) call these functions, so the two sides the GPU tests hold together bit for bit cannot drift apart by a copied line.  Usable from plain
 // C++ and from HIP, like rt_bvh_layout.h, whose RT_HD it takes.  Every unit that includes it is compiled with -ffp-contract=off: every multiply, add,
 // division and square root below is an operation of its own, in the written order and parenthesisation -- which is part of the rule.
 // What is NOT here: loops, staging, clamping, and whether a tap that does not count is skipped or predicated.  Those belong to each side.
@@ -133,14 +133,52 @@ RT_RULE float atrous_edge(float np0, float np1, float np2, float nq0, float nq1,
 RT_RULE float atrous_centre_weight(float n) { return (0.375f * 0.375f) * n; }
 RT_RULE float atrous_tap_weight(float hj, float hi, float g, float n) { return ((hj * hi) * falloff(g)) * n; }
 
+// rule 29: a record that is a LIGHT -- the library's own light test (rt_scene.hip light_test; .cl:135-138,266)
+RT_RULE bool light_record(const rt_sphere &s) { return !((s.e.x == 0.f) && (s.e.z == 0.f)); }
+
+// rule 29: a pair of the list as both sides hold it -- S's and D's {centre, radius} of the light l, then of the occluder j, then l and j as words and
+// two zero words: five aligned texels
+constexpr int kShadowPairFloats = 20;
+
+// rule 30: the state of a pair at the point X -- where the occluder {c, r} stands in the cone from X to the light's bounding sphere {L, rl}:
+// 0 clear, 1 penumbra, 2 umbra.  No square root; a NaN past the first test fails every comparison and so gives 1
+RT_RULE int shadow_state(float x0, float x1, float x2, float l0, float l1, float l2, float rl, float c0, float c1, float c2, float r) {
+    const float g0 = l0 - x0, g1 = l1 - x1, g2 = l2 - x2;
+    const float ll = dot3(g0, g1, g2, g0, g1, g2);
+    if (!(ll > 0.0f)) return 0;
+    float s = dot3(c0 - x0, c1 - x1, c2 - x2, g0, g1, g2) / ll;
+    if (!(s > 0.0f)) s = 0.0f;
+    if (s > 1.0f) s = 1.0f;
+    const float e0 = (x0 + g0 * s) - c0, e1 = (x1 + g1 * s) - c1, e2 = (x2 + g2 * s) - c2;
+    const float d2 = dot3(e0, e1, e2, e0, e1, e2), pen = rl * s, a = r + pen, b = r - pen;
+    if (d2 > a * a) return 0;
+    if (b > 0.0f && d2 < b * b) return 2;
+    return 1;
+}
+// rule 31: a pair CHANGES a pixel whose states before and after the move are these
+RT_RULE bool shadow_changes(int before, int after) { return before != after || before == 1 || after == 1; }
+// rule 32: the cap of a flagged pixel's history, after rule 18's (hk: rule 26's frames, capped in proportion; a colour-only caller passes a dummy)
+RT_RULE void shadow_cap(float &nh, float &hk, float keep) {
+    if (nh > keep) {
+        hk = hk * (keep / nh);
+        nh = keep;
+    }
+}
+
 // rule 19: the blend of D's colour (c at nd samples; have_d false at pass 0: c is 0 and not counted) with the history of rule 18's sums, into
 // (t0, t1, t2) at tn samples.  (Four references, not a struct or an array: either reaches the kernel as a vector and moves its schedule.)
-RT_RULE void temporal_blend(float &t0, float &t1, float &t2, float &tn, float c0, float c1, float c2, float nd, bool have_d, float sw, float sn, float sc0, float sc1,
-                            float sc2, float max_history) {
+// kShadow: rule 32 between the cap and the blend, for a pixel that rule 31 `flagged`; without it the two last arguments are not read.
+template <bool kShadow>
+RT_RULE void temporal_blend_as(float &t0, float &t1, float &t2, float &tn, float c0, float c1, float c2, float nd, bool have_d, float sw, float sn, float sc0,
+                               float sc1, float sc2, float max_history, [[maybe_unused]] bool flagged, [[maybe_unused]] float keep) {
     t0 = c0, t1 = c1, t2 = c2, tn = nd;
     if (sw > 0.0f) {
         float nh = sn / sw;
         if (nh > max_history) nh = max_history;
+        if constexpr (kShadow) {
+            float hk = 0.0f;
+            if (flagged) shadow_cap(nh, hk, keep);
+        }
         const float h0 = sc0 / sw, h1 = sc1 / sw, h2 = sc2 / sw;
         if (!have_d) t0 = h0, t1 = h1, t2 = h2, tn = nh;
         else {
@@ -148,6 +186,10 @@ RT_RULE void temporal_blend(float &t0, float &t1, float &t2, float &tn, float c0
             t0 = (c0 * nd + h0 * nh) * inv, t1 = (c1 * nd + h1 * nh) * inv, t2 = (c2 * nd + h2 * nh) * inv, tn = nd + nh;
         }
     }
+}
+RT_RULE void temporal_blend(float &t0, float &t1, float &t2, float &tn, float c0, float c1, float c2, float nd, bool have_d, float sw, float sn, float sc0, float sc1,
+                            float sc2, float max_history) {
+    temporal_blend_as<false>(t0, t1, t2, tn, c0, c1, c2, nd, have_d, sw, sn, sc0, sc1, sc2, max_history, false, 0.0f);
 }
 
 // rule 27: the variance of a temporal mean from its moments m1 and m2 over k frames; 0 below two frames, never negative (a NaN fails both tests)
@@ -157,9 +199,10 @@ RT_RULE float moments_variance(float m1, float m2, float k) {
 }
 
 // rules 26-27: the blend of D's luminance ld (at nd samples; have_d false at pass 0: ld is not counted) with the history of rule 18's sums sw and sn
-// and rule 26's sums s1, s2 and sk, into (m1, m2, k, v).  nh and inv are formed as temporal_blend forms them.
-RT_RULE void moments_blend(float &m1, float &m2, float &k, float &v, float ld, float nd, bool have_d, float sw, float sn, float s1, float s2, float sk,
-                           float max_history) {
+// and rule 26's sums s1, s2 and sk, into (m1, m2, k, v).  nh and inv are formed as temporal_blend forms them -- rule 32 included, under kShadow.
+template <bool kShadow>
+RT_RULE void moments_blend_as(float &m1, float &m2, float &k, float &v, float ld, float nd, bool have_d, float sw, float sn, float s1, float s2, float sk,
+                              float max_history, [[maybe_unused]] bool flagged, [[maybe_unused]] float keep) {
     m1 = have_d ? ld : 0.0f, m2 = have_d ? ld * ld : 0.0f, k = have_d ? 1.0f : 0.0f;
     if (sw > 0.0f) {
         float nh = sn / sw;
@@ -169,6 +212,9 @@ RT_RULE void moments_blend(float &m1, float &m2, float &k, float &v, float ld, f
             hk = hk * (max_history / nh);                          // frames are capped in proportion to samples
             nh = max_history;
         }
+        if constexpr (kShadow) {
+            if (flagged) shadow_cap(nh, hk, keep);
+        }
         if (!have_d) m1 = h1, m2 = h2, k = hk;
         else {
             const float inv = 1.0f / (nd + nh);
@@ -176,6 +222,10 @@ RT_RULE void moments_blend(float &m1, float &m2, float &k, float &v, float ld, f
         }
     }
     v = moments_variance(m1, m2, k);
+}
+RT_RULE void moments_blend(float &m1, float &m2, float &k, float &v, float ld, float nd, bool have_d, float sw, float sn, float s1, float s2, float sk,
+                           float max_history) {
+    moments_blend_as<false>(m1, m2, k, v, ld, nd, have_d, sw, sn, s1, s2, sk, max_history, false, 0.0f);
 }
 
 // rule 28: V0 of a pixel whose moments texel holds k frames and the estimate v, where rule 21 gives v21

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "rt_internal.h"
+#include "rt_rules.h"
 
 #ifndef RT_DIAGNOSTICS
 #define RT_DIAGNOSTICS 0
@@ -64,7 +65,7 @@ namespace rt {
 
 // ---- scene storage -------------------------------------------------------------------------
 
-static bool light_test(const rt_sphere &s) { return !((s.e.x == 0.f) && (s.e.z == 0.f)); }   // .cl:135-138,266
+static bool light_test(const rt_sphere &s) { return rt::light_record(s); }   // .cl:135-138,266; stated in rt_rules.h, where rule 29 reads it too
 
 int ensure_scene_capacity(rt_ctx *c, uint32_t count) {
     if (count <= c->scene.cap && c->scene.d_tables) return RT_OK;

@@ -6,6 +6,7 @@
 //            [--no-doubling] [--out frame.ppm] [--oneshot K] [--gpus N]
 //            [--stream N] [--save-state FILE] [--load-state FILE] [--until-psnr DB [--check-every N] [--adaptive [--min-passes M]]
 //             [--denoise [--denoise-radius R]] [--filtered [--live-checks]] [--guided]] [--atrous [--atrous-levels N] [--moments [--moments-kmin K]]]
+//            [--shadow-history [--shadow-keep N]]
 //   --oneshot K   render through the headline call rt_render(scene, cam, out, w, h, spp) K times instead of a
 //                 context (prints the wall time of every call: the first builds the device state, the rest reuse it)
 //   --gpus N      a multi-device context (rt_create_multi: N GPUs of this process, one RCCL gather per frame)
@@ -41,6 +42,11 @@
 //                       mode take turns for four frames of two passes each on seed streams of their own, reprojecting with the setting on;
 //                       the frame's context then reprojects from the last of them, and the filter runs over ITS TEMPORAL PLANE -- the frame
 //                       blended with those eight older passes -- not over its colour plane.  The line gains the setting and the history
+//   --shadow-history    shadow-aware history (rt_set_shadow_history; --shadow-keep N: the samples a flagged pixel keeps, default 2).  A moved
+//                       sphere has to exist for that: a helper context holds the scene as it was one step earlier -- its last record that is
+//                       no light stands two units to the right -- at four passes of a seed stream of its own; the frame's context reprojects
+//                       from it with the setting on, and --atrous then filters ITS TEMPORAL PLANE.  A further line gives the setting, the
+//                       pairs of rule 29 and the share of pixels flagged.  Not with --moments, --until-psnr, --gpus, --rehearse or --oneshot
 //
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
@@ -89,6 +95,43 @@ static int history_moments(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n, co
            (double)reached / (double)(m.size() / 4));
     rt_destroy(hist[0]);
     rt_destroy(hist[1]);
+    return 0;
+}
+
+// --shadow-history: the scene one step earlier in a helper context, then `ctx` reprojects from it with the setting on
+static int history_shadow(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n, const rt_camera& cam, int w, int h, int mode, const rt_shadow_history_params& sp) {
+    std::vector<rt_sphere> before(spheres, spheres + n);
+    int moved = -1;
+    for (uint32_t i = 0; i < n; ++i)
+        if (spheres[i].rad != 0.0f && spheres[i].rad < 100.0f && spheres[i].e.x == 0.f && spheres[i].e.z == 0.f) moved = (int)i;
+    if (moved < 0) {
+        fprintf(stderr, "--shadow-history: the scene holds no record to move\n");
+        return 1;
+    }
+    before[(size_t)moved].p.x += 2.0f;
+    rt_ctx* was = nullptr;
+    if (rt_create(&was, w, h) != RT_OK) return die("rt_create");
+    const auto fail = [&](const char* what) {               // the helper goes on every way out
+        const int rc = die(what);
+        rt_destroy(was);
+        return rc;
+    };
+    if (rt_set_scene(was, before.data(), n) != RT_OK) return fail("rt_set_scene");
+    if (rt_set_camera(was, &cam) != RT_OK) return fail("rt_set_camera");
+    if (rt_set_mode(was, mode) != RT_OK) return fail("rt_set_mode");
+    if (rt_seed_stream_async(was, 100, rt_stream(was)) != RT_OK) return fail("rt_seed_stream_async");
+    if (rt_render_async(was, 4, rt_stream(was)) != RT_OK) return fail("rt_render_async");
+    if (rt_features_async(was, rt_stream(was)) != RT_OK) return fail("rt_features_async");
+    if (rt_set_shadow_history(ctx, &sp) != RT_OK) return fail("rt_set_shadow_history");
+    if (rt_features_async(ctx, rt_stream(ctx)) != RT_OK) return fail("rt_features_async");
+    if (rt_reproject_async(ctx, was, nullptr, rt_stream(ctx)) != RT_OK) return fail("rt_reproject_async");
+    std::vector<uint8_t> k(static_cast<size_t>(w) * h);
+    if (rt_read_history_flags(ctx, k.data()) != RT_OK) return fail("rt_read_history_flags");      // (blocking: the helper may go)
+    size_t flagged = 0;
+    for (uint8_t v : k) flagged += v;
+    printf("{\"shadow_history\": true, \"keep\": %.3f, \"moved_record\": %d, \"pairs\": %d, \"pixels_flagged\": %.4f}\n", (double)sp.keep, moved,
+           rt_shadow_history_pairs(before.data(), spheres, n, nullptr, 0), (double)flagged / (double)k.size());
+    rt_destroy(was);
     return 0;
 }
 
@@ -145,6 +188,9 @@ int main(int argc, char** argv) {
     bool moments = false;       // --moments: with --atrous, the variance from a pixel's history (history_moments)
     rt_moments_params mp;
     rt_moments_defaults(&mp);
+    bool shadow = false;        // --shadow-history: a moved sphere's shadows end a pixel's history (history_shadow)
+    rt_shadow_history_params shp;
+    rt_shadow_history_defaults(&shp);
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -177,6 +223,8 @@ int main(int argc, char** argv) {
         else if (a == "--atrous-levels") at.levels = atoi(next());
         else if (a == "--moments") moments = true;
         else if (a == "--moments-kmin") mp.k_min = (float)atof(next());
+        else if (a == "--shadow-history") shadow = true;
+        else if (a == "--shadow-keep") shp.keep = (float)atof(next());
         else pos.push_back(argv[i]);
     }
     if (!pos.empty() && atoi(pos[0]) != 2) {
@@ -202,6 +250,10 @@ int main(int argc, char** argv) {
     }
     if (moments && !atrous) {
         fprintf(stderr, "--moments steers the wavelet filter: it needs --atrous\n");
+        return 1;
+    }
+    if (shadow && (moments || until || gpus > 1 || rehearse > 0 || oneshot > 0)) {
+        fprintf(stderr, "--shadow-history reprojects into the frame's one context: not with --moments, --until-psnr, --gpus, --rehearse or --oneshot\n");
         return 1;
     }
     if (atrous && (gpus > 1 || rehearse > 0 || oneshot > 0)) {
@@ -354,6 +406,7 @@ int main(int argc, char** argv) {
     rt_stats st;
     if (rt_get_stats(ctx, &st) != RT_OK) return die("rt_get_stats");
     if (moments && history_moments(ctx, spheres.data(), n, cam, w, h, mode, mp) != 0) return 1;
+    if (shadow && history_shadow(ctx, spheres.data(), n, cam, w, h, mode, shp) != 0) return 1;
     if (atrous && filter_atrous(ctx, at, px) != 0) return 1;
     if (!out.empty() && !write_ppm(out, px, w, h)) fprintf(stderr, "cannot write %s\n", out.c_str());
     if (!save_state.empty() && rt_save_state(ctx, save_state.c_str()) != RT_OK) return die("rt_save_state");

@@ -69,6 +69,35 @@ int main() {
             moments += rt_atrous_moments_planes(out.data(), t2.data(), 4, 0, nullptr, fd.data(), w, h, &at, &mp) == RT_OK;
             printf("moments %dx%d: %d of 6 ok, k %g v %g\n", w, h, moments, m2[2], m2[3]);
         }
+        // shadow-aware history's host statement on the same planes: record 3 moved (one pair), then the light moved too (every record pairs with it),
+        // with and without a moments plane and a flag plane, keep 0 and the default, a pure warp; and the pair list, counted and filled short
+        {
+            rt_sphere moved[6];
+            for (int i = 0; i < 6; ++i) moved[i] = d[i];
+            moved[3].p.x += 7.0f;
+            std::vector<float> t1(4 * px), m1(4 * px);
+            std::vector<uint8_t> k(px);
+            rt_shadow_history_params sp;
+            rt_shadow_history_defaults(&sp);
+            const rt_reproject_view src3{ u3.data(), 3, 16, fs.data(), &cs, d }, src4{ u4.data(), 4, 0, fs.data(), &cs, d };
+            int shadow = 0, flagged = 0;
+            for (int lights = 0; lights <= 1; ++lights) {
+                if (lights) moved[5].p.z -= 4.0f;
+                std::vector<float> fm(8 * px);
+                rt_features_planes(fm.data(), moved, 6, &cd, w, h);
+                const rt_reproject_view dst{ cdp.data(), 3, 2, fm.data(), &cd, moved }, dst0{ nullptr, 3, 0, fm.data(), &cd, moved };
+                shadow += rt_reproject_shadow_planes(t1.data(), m1.data(), k.data(), &dst, &src3, nullptr, 6, w, h, nullptr, &sp) == RT_OK;
+                for (uint8_t v : k) flagged += v;
+                sp.keep = 0.0f;
+                shadow += rt_reproject_shadow_planes(t1.data(), nullptr, k.data(), &dst, &src4, nullptr, 6, w, h, nullptr, &sp) == RT_OK;
+                shadow += rt_reproject_shadow_planes(t1.data(), m1.data(), nullptr, &dst, &src4, u4.data(), 6, w, h, nullptr, &sp) == RT_OK;
+                shadow += rt_reproject_shadow_planes(t1.data(), nullptr, k.data(), &dst0, &src3, nullptr, 6, w, h, nullptr, nullptr) == RT_OK;
+                uint32_t lj[4];
+                shadow += rt_shadow_history_pairs(d, moved, 6, lj, 2) == (lights ? 5 : 1);
+                shadow += rt_shadow_history_pairs(d, moved, 6, nullptr, 0) == (lights ? 5 : 1);
+            }
+            printf("shadow history %dx%d: %d of 12 ok, %d flagged\n", w, h, shadow, flagged);
+        }
         // the NL-means host statements on halves of the same sizes, with and without the guide (the feature plane above), search radius 0 and 2, patch
         // radius 0 and 2: with the calls above, every function of rt_rules.h has run
         std::vector<float> ha(3 * px), hb(3 * px), merged(3 * px), fa(3 * px), fb(3 * px);
