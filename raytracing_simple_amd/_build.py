@@ -43,18 +43,15 @@ UNITS = [
     ("rt_compare.hip", ["-ffp-contract=off"]),
     ("rt_tiles.hip", ["-ffp-contract=off"]),
     ("rt_denoise.hip", ["-ffp-contract=off"]),
-    ("rt_denoise_guided.hip", ["-ffp-contract=off"]),
     ("rt_features.hip", ["-ffp-contract=off"]),
     ("rt_reproject.hip", ["-ffp-contract=off"]),
     ("rt_atrous.hip", ["-ffp-contract=off"]),
-    ("rt_moments.hip", ["-ffp-contract=off"]),
-    ("rt_shadow_history.hip", ["-ffp-contract=off"]),
     ("rt_host.cpp", ["-ffp-contract=off"]),
     ("rt_bvh_host.cpp", ["-ffp-contract=off"]),
     ("rt_build_id.cpp", []),
 ]
 DEPS = ["rt_device.h", "rt_instance.h", "rt_internal.h", "rt_detmath.h", "rt_trace.inc.h", "rt_candidates.h", "rt_shade.inc.h", "rt_walk.inc.h", "rt_sched.inc.h", "rt_opts_reset.h", "rt_tile_order.h", "rt_frame_state.h", "rt_owned.h", "rt_choice.h", "rt_scene_state.h", "rt_denoise.inc.h",
-        "rt_rules.h", "rt_plane.inc.h", "rt_reproject_body.inc.h", "rt_atrous_prepare_body.inc.h", "rt_bvh_layout.h", "rt_bvh_host.h",
+        "rt_rules.h", "rt_plane.inc.h", "rt_bvh_layout.h", "rt_bvh_host.h",
         os.path.join("..", "..", "include", "rt_api.h"), os.path.join("..", "..", "include", "rt_debug.h")]
 
 

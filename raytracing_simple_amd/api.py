@@ -687,7 +687,7 @@ class RtContext:
         """rt_moments_defaults (the module-level moments_defaults)."""
         return moments_defaults()
 
-    # --- shadow-aware history (rt_shadow_history.hip) -----------------------------------------------
+    # --- shadow-aware history (rt_reproject.hip) -----------------------------------------------
     def set_shadow_history(self, shadow=None):
         """rt_set_shadow_history: None switches the setting off; a ShadowHistoryParams or a dict of fields laid over shadow_history_defaults()
         switches it on: reproject_async INTO this context then caps the history of pixels where a changed record's shadow came or went (rules 29-32)

@@ -6,8 +6,8 @@
 // the comments below name the rule a line implements.  The reference filters nothing: this is the library's own extension.
 // This unit is compiled with parity's flags (-ffp-contract=off, correctly rounded division): every multiply, add and division below is an operation of
 // its own, in the written order -- whatever rt_set_mode says.
-// The render kernels are not touched, and nothing here writes anything but the context's five filter planes.  The preparation kernel's STATEMENTS
-// are rt_atrous_prepare_body.inc.h, shared with rt_moments.hip, whose instance takes V0 from the moments plane (rule 28) when the setting is on.
+// The render kernels are not touched, and nothing here writes anything but the context's five filter planes.  The preparation kernel's moments arm
+// takes V0 from the moments plane (rule 28) when rt_set_temporal_moments is on and that plane is current; rt_atrous_moments_planes is its host statement.
 //
 // The shape.  rt_atrous_prepare_kernel evaluates rules 20-21 once: it writes (rgb, V0), a 16-byte guide texel (N, id) and beside it one float that is
 // n for a usable pixel and +0.0f for any other -- so a level reads three aligned words per tap (4, 16 and 16 bytes) instead of picking words 3-5 and 7
@@ -32,15 +32,49 @@ extern "C" int rt_host_atrous_params(const rt_atrous_params *p, rt_atrous_params
 // Rules 20-21, one lane per pixel; x and y are ARRAY coordinates (the colour plane's row order).  kCh: U holds 3 floats a pixel (the colour plane, every
 // pixel at `n_all` samples) or 4 (the temporal plane).  px is null unless levels == 0 (rule 24 on (U's rgb, V0)).  No LDS, no barrier: a lane outside
 // the image leaves at once.
+// THE MOMENTS ARM (kMom; rule 28): U is the temporal plane -- M is current only beside it -- and m its moments plane as float2 pairs: texel `at` is
+// m[2 * at] = (m1, m2) and m[2 * at + 1] = (k, v), of which the second is read and selects between its v and rule 21's result.  Without the arm m and
+// k_min are passed null and zero and not touched.
 // Bounds: the lane's own texel of U and F and its four stores at x < w && y < h; a neighbour's texel of U and word 7 of F only for 0 <= qx < w &&
-// 0 <= qy < h (the test stands before the loads); the packed word at row h - 1 - y < h.
-template <int kCh>
+// 0 <= qy < h (the test stands before the loads); the packed word at row h - 1 - y < h; the arm reads m at `at`, the lane's own pixel: ONE 8-byte load.
+template <int kCh, bool kMom>
 __global__ void __launch_bounds__(kPlaneLanes) rt_atrous_prepare_kernel(float4 *__restrict__ out, float4 *__restrict__ guide, float *__restrict__ n_out, uint32_t *__restrict__ px,
-                                                                        const float *__restrict__ u, const float4 *__restrict__ feat, float n_all, int w, int h, int fast) {
-    constexpr bool kMom = false;                            // the moments arm (rt_moments.hip) is discarded: its plane and k_min are not arguments here
-    constexpr const float2 *m = nullptr;
-    constexpr float k_min = 0.0f;
-#include "rt_atrous_prepare_body.inc.h"
+                                                                        const float *__restrict__ u, const float4 *__restrict__ feat, float n_all, int w, int h, int fast,
+                                                                        const float2 *__restrict__ m, float k_min) {
+    static_assert(!kMom || kCh == 4, "the moments plane is current only beside the temporal plane");
+    const auto [x, y] = plane_pixel();
+    if (x >= w || y >= h) return;
+    const size_t at = (size_t)y * (size_t)w + (size_t)x;
+    const float4 up = plane_texel<kCh>(u, at, n_all);
+    const float4 f_lo = feat[2 * at], f_hi = feat[2 * at + 1];
+    const uint32_t id = __float_as_uint(f_hi.w);
+    // rule 21
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+            const size_t aq = (size_t)qy * (size_t)w + (size_t)qx;
+            if (__float_as_uint(feat[2 * aq + 1].w) != id) continue;
+            const float4 uq = plane_texel<kCh>(u, aq, n_all);
+            if (!rt::usable(uq.x, uq.y, uq.z, uq.w)) continue;
+            const float l = rt::luminance(uq.x, uq.y, uq.z);
+            s0 = s0 + 1.0f;
+            s1 = s1 + l;
+            s2 = s2 + l * l;
+        }
+    float v0 = rt::variance_of_sums(s0, s1, s2);
+    const bool usable = rt::usable(up.x, up.y, up.z, up.w);      // rule 20
+    if constexpr (kMom) {
+        const float2 kv = m[2 * at + 1];                         // (k, v): words 2-3 of M[p]
+        v0 = rt::variance_from_history(usable, kv.x, kv.y, k_min, v0);      // rule 28
+    }
+    out[at] = make_float4(up.x, up.y, up.z, v0);
+    guide[at] = make_float4(f_lo.w, f_hi.x, f_hi.y, f_hi.w);
+    n_out[at] = usable ? up.w : 0.0f;
+    if (px) px[(size_t)(h - 1 - y) * (size_t)w + (size_t)x] = pack_rgb(up.x, up.y, up.z, fast != 0);
 }
 
 // Rule 22, one lane per pixel, 25 taps at step s.  `n` is the preparation kernel's plane: n > 0.0f says usable.  The tap rows run as a loop, the five
@@ -125,14 +159,12 @@ RT_API int rt_atrous_async(rt_ctx *c, const rt_atrous_params *p, void *hip_strea
     float4 *cur = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? pl.atrous : pl.tmp);
     float4 *nxt = reinterpret_cast<float4 *>(q.levels % 2 == 0 ? pl.tmp : pl.atrous);
     float4 *const guide = reinterpret_cast<float4 *>(pl.guide);
-    if (in.m) {                                         // rule 28: the setting on AND M current (which implies the temporal plane); nothing else decides
-        RT_TRY(atrous_prepare_moments(c, in, cur, q.levels == 0, stream));       // rt_moments.hip: the preparation kernel with the moments arm
-    } else {
-        const auto prepare = in.channels == 4 ? rt_atrous_prepare_kernel<4> : rt_atrous_prepare_kernel<3>;
-        hipLaunchKernelGGL(prepare, grid, dim3(kPlaneLanes), 0, stream, cur, guide, pl.n, q.levels == 0 ? pl.atrous_px : (uint32_t *)nullptr, in.u,
-                           reinterpret_cast<const float4 *>(c->scene.d_features), in.passes, c->w, c->h, fast);
-        HIP_TRY(hipGetLastError());
-    }
+    // rule 28's arm: the setting on AND M current (which implies the temporal plane); nothing else decides
+    const auto prepare = in.m ? rt_atrous_prepare_kernel<4, true> : in.channels == 4 ? rt_atrous_prepare_kernel<4, false> : rt_atrous_prepare_kernel<3, false>;
+    hipLaunchKernelGGL(prepare, grid, dim3(kPlaneLanes), 0, stream, cur, guide, pl.n, q.levels == 0 ? pl.atrous_px : (uint32_t *)nullptr, in.u,
+                       reinterpret_cast<const float4 *>(c->scene.d_features), in.passes, c->w, c->h, fast, reinterpret_cast<const float2 *>(in.m),
+                       in.m ? pl.moments_set.params.k_min : 0.0f);
+    HIP_TRY(hipGetLastError());
     const float inv_kn2 = 1.0f / (q.k_normal * q.k_normal), kl2 = q.k_lum * q.k_lum;
     for (int level = 0; level < q.levels; ++level) {
         hipLaunchKernelGGL(rt_atrous_level_kernel, grid, dim3(kPlaneLanes), 0, stream, nxt, level == q.levels - 1 ? pl.atrous_px : (uint32_t *)nullptr, cur, guide,

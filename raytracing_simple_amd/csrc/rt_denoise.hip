@@ -8,9 +8,9 @@
 //   rt_denoise_pair_tiles_async   ... of the groups in the current selection alone (adaptive sampling's groups: rt_tiles.hip), the rest kept
 //   rt_read_filtered         that plane of one context (read_plane, rt_internal.h)
 // (rt_denoise_pair_planes is the host statement; rt_compare.hip compares the packed planes).
-// As rt_host.cpp filters through one nlm_planes(out, img, guide, ...), the device filters through ONE body, dn_body<P, N, kAnyRow>: N = 1 is the frame
-// filtered with its own weights, N = 2 the two halves, each with the other's.  Three kernels give it an origin: the frame, the frame's halves, a list
-// of groups.
+// As rt_host.cpp filters through one nlm_planes(out, img, guide, ...), the device filters through ONE body, dn_body<P, N, kAnyRow, kGuided>: N = 1 is the
+// frame filtered with its own weights, N = 2 the two halves, each with the other's; kGuided adds the guide of rules 13-14 ("feature planes").  Three
+// kernel templates give it an origin -- the frame, the frame's halves, a list of groups -- and ONE function launches them.
 // The render kernels are not touched, and nothing here reads or writes anything but colour planes.
 // This unit is compiled with -ffp-contract=off: every multiply, add and IEEE division below is an operation of its own, in the written order.
 #include <hip/hip_runtime.h>
@@ -51,38 +51,45 @@ __global__ void __launch_bounds__(256) rt_denoise_variance_kernel(float *__restr
     }
 }
 
+// The three kernels.  kGuided (rules 13-14; rt_denoise_guided_planes / rt_denoise_pair_guided_planes are the host statements): the feature plane of the
+// first half beside the colour planes, in `gd`; without it `gd` is passed empty and not touched.
 // ... over the frame: the plane tiled from its row 0, a workgroup per 32x8 pixels -- the merged frame with its own weights,
-template <int P>
-__global__ void __launch_bounds__(kPlaneLanes) rt_denoise_kernel(DnPlanes<1> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk) {
+template <int P, bool kGuided>
+__global__ void __launch_bounds__(kPlaneLanes) rt_denoise_kernel(DnPlanes<1> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, DnGuide gd) {
     extern __shared__ float dn_lds[];
-    dn_body<P, 1, false>(dn_lds, (int)blockIdx.x * kPlaneTileW, (int)blockIdx.y * kPlaneTileH, k, vs, w, h, R, alpha, kk);
+    dn_body<P, 1, false, kGuided>(dn_lds, (int)blockIdx.x * kPlaneTileW, (int)blockIdx.y * kPlaneTileH, k, vs, w, h, R, alpha, kk, gd);
 }
 
 // ... the two halves.  (waves_per_eu: at the default radii, R 5 and P 1 -- the only ones it was measured at -- LDS admits four workgroups a CU, a
 // wavefront of each per SIMD.  Told so, the compiler keeps rule 3's independent divisions interleaved; left to aim for a seventh wavefront, it
 // serialises them in this instance to save two registers, which measured 1.9 % slower at 1920x1080 -- profiles/HISTORY.md.  The hint bounds nothing
 // at run time and the register counts are the same with it, 60 / 74 / 93.  It ALLOWS the compiler 128 registers, though: at small radii (R 1, P 0:
-// nine workgroups a CU by LDS) occupancy is bound by registers, so a body that grows must be looked at again with the hint taken off.)
-template <int P>
+// nine workgroups a CU by LDS) occupancy is bound by registers, so a body that grows must be looked at again with the hint taken off.
+// Looked at again for the body grown by the guide: the guided pair instances take 83 / 91 / 109 vector registers for P = 0 / 1 / 2, no scratch.  At the
+// defaults, R 5 and P 1, the 58 KiB of LDS admit two workgroups a CU, a wavefront of each on every SIMD, and 91 registers would admit five; at R 8, P 2
+// one workgroup fits.  Only at R 1, P 0 does LDS -- 26 KiB, six workgroups -- ask for more wavefronts than the hint's four, and that instance's 83
+// registers admit six.  So the hint is kept for what it was measured to do in the unguided body, keeping rule 3's divisions interleaved, and bounds
+// nothing under the guide.)
+template <int P, bool kGuided>
 __global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kPlaneLanes)
-rt_denoise_pair_kernel(DnPlanes<2> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk) {
+rt_denoise_pair_kernel(DnPlanes<2> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, DnGuide gd) {
     extern __shared__ float dn_lds[];
-    dn_body<P, 2, false>(dn_lds, (int)blockIdx.x * kPlaneTileW, (int)blockIdx.y * kPlaneTileH, k, vs, w, h, R, alpha, kk);
+    dn_body<P, 2, false, kGuided>(dn_lds, (int)blockIdx.x * kPlaneTileW, (int)blockIdx.y * kPlaneTileH, k, vs, w, h, R, alpha, kk, gd);
 }
 
 // ... and the halves over the groups of a selection (rt_tiles.hip): workgroup i takes group list[i] -- g = gy * groups_x + gx in the PIXEL BUFFER's tile
 // rows, row 0 at the bottom -- and covers its pixel rows 8 gy .. 8 gy + 7, which are the plane's rows h - 8 (gy + 1) .. h - 1 - 8 gy: the origin is
 // negative for the top, partial, group row.  Every other pixel of the four output planes keeps its words.  A list entry that names no group is skipped
 // by the whole workgroup, ahead of the first barrier.
-template <int P>
+template <int P, bool kGuided>
 __global__ void __attribute__((amdgpu_waves_per_eu(1, 4))) __launch_bounds__(kPlaneLanes)
 rt_denoise_pair_tiles_kernel(DnPlanes<2> k, const float *__restrict__ vs, int w, int h, int R, float alpha, float kk, const uint32_t *__restrict__ list,
-                             uint32_t groups_x, uint32_t n_groups) {
+                             uint32_t groups_x, uint32_t n_groups, DnGuide gd) {
     extern __shared__ float dn_lds[];
     const uint32_t g = list[blockIdx.x];
     if (g >= n_groups) return;
     const uint32_t gy = g / groups_x, gx = g - gy * groups_x;
-    dn_body<P, 2, true>(dn_lds, (int)gx * kPlaneTileW, h - kPlaneTileH * ((int)gy + 1), k, vs, w, h, R, alpha, kk);
+    dn_body<P, 2, true, kGuided>(dn_lds, (int)gx * kPlaneTileW, h - kPlaneTileH * ((int)gy + 1), k, vs, w, h, R, alpha, kk, gd);
 }
 
 using namespace rt;
@@ -91,10 +98,41 @@ namespace {
 
 std::atomic<uint64_t> g_pair_calls{0};                     // numbers the calls that make cross-filtered planes (FrameState::filtered_pair)
 
-dim3 frame_grid(const rt_ctx *c) { return plane_grid(c->w, c->h); }
-
 int launch_variance(float *var, const float *a, const float *b, int w, int h, hipStream_t stream) {
     hipLaunchKernelGGL(rt_denoise_variance_kernel, dim3((unsigned)((3 * (size_t)w + 255) / 256), (unsigned)std::min(h, 65535)), dim3(256), 0, stream, var, a, b, w, h);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// the guide of a pair of halves whose first is `a` (guide_refuse has passed: both hold the same setting, both feature planes are current; the plane is a's)
+DnGuide guide_of(const rt_ctx *a) {
+    const rt_guide_params &g = a->planes.guide_set.params;
+    return DnGuide{ reinterpret_cast<const float4 *>(a->scene.d_features), 1.0f / (g.k_albedo * g.k_albedo), 1.0f / (g.k_normal * g.k_normal), 1.0f / (g.k_depth * g.k_depth) };
+}
+
+// THE launch of the filter, on c's device (selected) and in c's geometry.  N = 1: rt_denoise_async's frame; 2: the halves, over the frame or (`groups`) over a
+// list of `n_selected` groups.  `guide` null: by colour alone.  Dynamic LDS beyond the 64 KiB every kernel may ask for: the limit is raised for that
+// kernel on the selected device (each kernel by its symbol, as every launch of the library: the limit, then the launch).
+template <int N>
+int launch_filter(const rt_ctx *c, const DnPlanes<N> &k, const float *var, const rt_denoise_params &q, hipStream_t stream, const DnGuide *guide = nullptr,
+                  const uint32_t *groups = nullptr, uint32_t n_selected = 0) {
+    const DnGuide gd = guide ? *guide : DnGuide{};
+    const size_t lds = dn_lds_bytes(N, q.search_radius, q.patch_radius, guide != nullptr);
+    const dim3 grid = plane_grid(c->w, c->h);
+    const float kk = q.k * q.k;
+    hipError_t e = hipSuccess;
+    const auto go = [&](auto kernel, dim3 blocks, auto... list) {       // (list: what the tiles kernel takes between kk and the guide)
+        if (lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
+        if (e == hipSuccess) hipLaunchKernelGGL(kernel, blocks, dim3(kPlaneLanes), lds, stream, k, var, c->w, c->h, q.search_radius, q.alpha, kk, list..., gd);
+    };
+    with_patch_radius(q.patch_radius, [&](auto P) {
+        constexpr int kP = decltype(P)::value;
+        if constexpr (N == 1) go(guide ? rt_denoise_kernel<kP, true> : rt_denoise_kernel<kP, false>, grid);
+        else if (groups)
+            go(guide ? rt_denoise_pair_tiles_kernel<kP, true> : rt_denoise_pair_tiles_kernel<kP, false>, dim3(n_selected), groups, groups_per_row(c), group_count(c));
+        else go(guide ? rt_denoise_pair_kernel<kP, true> : rt_denoise_pair_kernel<kP, false>, grid);
+    });
+    if (e != hipSuccess) return fail(RT_ERR_HIP, "the guided filter's LDS limit: %s", hipGetErrorString(e));
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -136,22 +174,8 @@ int filter_pair(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStream_t st
     if (rc != RT_OK) return rc;
     const Planes &pa = a->planes, &pb = b->planes;
     const DnPlanes<2> k{ { a->d_colors, b->d_colors }, { pa.filtered, pb.filtered }, { pa.filtered_px, pb.filtered_px }, { a->knobs.fast(), b->knobs.fast() } };
-    const size_t lds = dn_lds_bytes(2, q.search_radius, q.patch_radius);
-    const float kk = q.k * q.k;
-    if (a->planes.guide_set.on) {                           // (guide_refuse has passed: b holds the same, both feature planes are current)
-        const GuidedFilter f{ { a->d_colors, b->d_colors }, { pa.filtered, pb.filtered }, { pa.filtered_px, pb.filtered_px }, { a->knobs.fast(), b->knobs.fast() },
-                              pa.var, tiles ? a->tiles.d_groups : nullptr, tiles ? a->frame.counts[0] : 0u };
-        rc = launch_guided_filter(2, f, a, q, stream);
-    } else with_patch_radius(q.patch_radius, [&](auto P) {
-        if (tiles)
-            hipLaunchKernelGGL(rt_denoise_pair_tiles_kernel<decltype(P)::value>, dim3(a->frame.counts[0]), dim3(kPlaneLanes), lds, stream, k, a->planes.var, a->w,
-                               a->h, q.search_radius, q.alpha, kk, a->tiles.d_groups, groups_per_row(a), group_count(a));
-        else
-            hipLaunchKernelGGL(rt_denoise_pair_kernel<decltype(P)::value>, frame_grid(a), dim3(kPlaneLanes), lds, stream, k, a->planes.var, a->w, a->h,
-                               q.search_radius, q.alpha, kk);
-    });
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipGetLastError());
+    const DnGuide gd = guide_of(a);
+    RT_TRY(launch_filter<2>(a, k, pa.var, q, stream, pa.guide_set.on ? &gd : nullptr, tiles ? a->tiles.d_groups : nullptr, tiles ? a->frame.counts[0] : 0u));
     const uint64_t call = g_pair_calls.fetch_add(1) + 1;
     for (rt_ctx *c : { a, b }) tiles ? c->frame.pair_tiles_refreshed(call) : c->frame.pair_filtered(call);
     return RT_OK;
@@ -223,15 +247,8 @@ RT_API int rt_denoise_async(rt_ctx *dst, rt_ctx *a, rt_ctx *b, const rt_denoise_
     if (rc == RT_OK) rc = launch_variance(dst->planes.var, a->d_colors, b->d_colors, dst->w, dst->h, stream);
     if (rc != RT_OK) return rc;
     const DnPlanes<1> k{ { dst->d_colors }, { dst->planes.denoise }, { nullptr }, { 0 } };      // (nothing is packed: rt_read_pixels packs the colour plane)
-    if (guided) {                                           // (the feature plane is a's)
-        const GuidedFilter f{ { dst->d_colors, nullptr }, { dst->planes.denoise, nullptr }, { nullptr, nullptr }, { 0, 0 }, dst->planes.var, nullptr, 0u };
-        rc = launch_guided_filter(1, f, a, q, stream);
-    } else with_patch_radius(q.patch_radius, [&](auto P) {
-        hipLaunchKernelGGL(rt_denoise_kernel<decltype(P)::value>, frame_grid(dst), dim3(kPlaneLanes), dn_lds_bytes(1, q.search_radius, q.patch_radius), stream, k,
-                           dst->planes.var, dst->w, dst->h, q.search_radius, q.alpha, q.k * q.k);
-    });
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipGetLastError());
+    const DnGuide gd = guide_of(a);                         // (the feature plane is a's)
+    RT_TRY(launch_filter<1>(dst, k, dst->planes.var, q, stream, guided ? &gd : nullptr));
     std::swap(dst->d_colors, dst->planes.denoise);          // the filtered plane IS the colour plane now; the old one is the next call's scratch
     dst->frame.colours_replaced();                          // rt_read_pixels packs the filtered plane
     return RT_OK;

@@ -1,9 +1,8 @@
 // rt_denoise.inc.h -- the NL-means device body the filter kernels share (include/rt_api.h, "denoising", "the error of the filtered frame", "feature
-// planes"): included by rt_denoise.hip, whose kernels filter by colour alone, and by rt_denoise_guided.hip, whose kernels add the guide of rules 13-14.
-// Two units, so that the code object of the first holds exactly the kernels it held before the guide existed, at the addresses they had.
+// planes"): included by rt_denoise.hip, whose kernels filter by colour alone or, kGuided, add the guide of rules 13-14.
 // The workgroup's shape and the pack are rt_plane.inc.h's (a workgroup's 32x8 output pixels: a row of 32 per half-wave here); the arithmetic of rules
 // 3, 5 and 13 is rt_rules.h's.
-// Both units are compiled with -ffp-contract=off: every multiply, add and IEEE division below is an operation of its own, in the written order.
+// The unit is compiled with -ffp-contract=off: every multiply, add and IEEE division below is an operation of its own, in the written order.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -40,7 +40,7 @@ struct FrameState {
     // The edge-avoiding wavelet filter (rt_atrous.hip): the filtered plane was formed by rt_atrous_async from the temporal plane -- or, where none was
     // current, from the colour plane -- and neither has moved since.  CURRENT while this holds and the scene's feature plane is current too
     bool atrous_current = false;
-    // Temporal luminance moments (rt_moments.hip): the reprojection that formed the temporal plane formed the moments plane too.  CURRENT while both hold
+    // Temporal luminance moments (rt_reproject.hip): the reprojection that formed the temporal plane formed the moments plane too.  CURRENT while both hold
     bool moments_formed = false;
 
     // at pass 0 the next launch would read the default stream (nothing but a custom stream or a written state puts another one there)

@@ -477,7 +477,7 @@ int rt_host_shadow_history_params(const rt_shadow_history_params *p, rt_shadow_h
 
 // rule 29: the pair list of the records S and D, `count` each, in its order; the first `cap` pairs into `out` (rt::kShadowPairFloats floats each: S's and
 // D's {centre, radius} of l, then of j, then l and j as words and two zero words), or nothing (out null).  Returns how many pairs there are.  Hidden:
-// the host loops below and rt_reproject_async (rt_shadow_history.hip, over the two contexts' mirrors) build their lists with it
+// the host loops below and rt_reproject_async (rt_reproject.hip, over the two contexts' mirrors) build their lists with it
 size_t rt_host_shadow_pairs(const rt_sphere *S, const rt_sphere *D, uint32_t count, float *out, size_t cap) {
     const auto changed = [&](uint32_t j) { return memcmp(&S[j], &D[j], 4 * sizeof(float)) != 0; };        // {rad, p}: the record's first four words
     const auto phantom = [&](uint32_t j) { return S[j].rad == 0.0f && D[j].rad == 0.0f; };

@@ -201,7 +201,7 @@ struct Planes {
     uint32_t *filtered_px = nullptr, *temporal_px = nullptr, *atrous_px = nullptr;
     struct { rt_guide_params params{}; bool on = false; } guide_set;        // rt_set_denoise_guide: what the filters of a pair of halves add to their weights
     struct { rt_moments_params params{}; bool on = false; } moments_set;    // rt_set_temporal_moments: what rt_reproject_async into the context and rt_atrous_async of it consult
-    // shadow-aware history (rt_shadow_history.hip; include/rt_api.h "shadow-aware history")
+    // shadow-aware history (rt_reproject.hip; include/rt_api.h "shadow-aware history")
     uint8_t *flags = nullptr;
     bool flags_formed = false;          // the reprojection that formed the temporal plane ran with the setting on: K is current while T is
     float4 *pairs = nullptr;
@@ -376,23 +376,6 @@ int denoise_pair_tiles(rt_ctx *a, rt_ctx *b, const rt_denoise_params &q, hipStre
 int features_refuse(const rt_ctx *c, const char *call, const char *lead = "", const char *of_whom = "");
 // the guide of a pair of halves (rt_set_denoise_guide): RT_ERR_STATE when the two settings differ, or -- on -- a feature plane is not current.  *guided: on
 int guide_refuse(const rt_ctx *a, const rt_ctx *b, const char *call, bool *guided = nullptr);
-// ---- rt_moments.hip: the kernels with a moments arm, launched for rt_reproject.hip and rt_atrous.hip (which have checked, chained and acquired) ----
-int reproject_moments(rt_ctx *dst, const rt_ctx *src, const rt_reproject_params &q, const PlaneInput &in, hipStream_t stream);
-int atrous_prepare_moments(rt_ctx *c, const PlaneInput &in, float4 *out, bool pack, hipStream_t stream);
-// ---- rt_shadow_history.hip: the kernels with the shadow arm (rules 29-32), launched for rt_reproject.hip likewise; the pair list is built from the two
-// contexts' mirrors and staged here; T, its packed plane, K and -- `moments` -- M of dst on `stream`
-int reproject_shadow(rt_ctx *dst, rt_ctx *src, const rt_reproject_params &q, const PlaneInput &in, bool moments, hipStream_t stream);
-// ---- rt_denoise_guided.hip: the filter kernels under a guide, launched for rt_denoise.hip ----
-struct GuidedFilter {
-    const float *img[2];                // the frame, or the two halves
-    float *out[2];
-    uint32_t *px[2];                    // the halves: the packed planes
-    int fast[2];                        // ... and which toInt packs them
-    const float *var;                   // rule 2's plane
-    const uint32_t *groups;             // non-null: the halves over this list of selected groups ...
-    uint32_t n_selected;                // ... of this many entries
-};
-int launch_guided_filter(int n_images, const GuidedFilter &f, const rt_ctx *a, const rt_denoise_params &q, hipStream_t stream);
 
 // ---- rt_tiles.hip: the subset launch's device side ----
 int tiles_refuse(const rt_ctx *c, const char *call);                  // RT_ERR_ARG for the contexts the adaptive calls do not take (null, multi-device, sharded)

@@ -12,11 +12,11 @@ namespace {
 
 constexpr int kPlaneTileW = 32, kPlaneTileH = 8, kPlaneLanes = kPlaneTileW * kPlaneTileH;      // a workgroup's pixels: four wavefronts, as the render kernels'
 
-// The moments arm of the reprojection kernel's statements (rt_reproject_body.inc.h; include/rt_api.h, rule 25): none, a tap's moments from the luminance
-// of U, or from S's moments plane
+// The moments arm of the reprojection kernel (rt_reproject.hip; include/rt_api.h, rule 25): none, a tap's moments from the luminance of U, or from S's
+// moments plane
 enum { kNoMoments = 0, kMomentsOfLuminance = 1, kMomentsOfPlane = 2 };
 
-// The shadow arm of the same statements (rule 31): the pair list goes through LDS in chunks of this many records of five float4 -- 5120 bytes a workgroup
+// The shadow arm of the same kernel (rule 31): the pair list goes through LDS in chunks of this many records of five float4 -- 5120 bytes a workgroup
 constexpr int kShadowChunk = RT_SHADOW_PAIR_CHUNK;
 
 struct PlanePixel {

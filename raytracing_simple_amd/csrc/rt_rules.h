@@ -1,6 +1,6 @@
 // rt_rules.h -- the arithmetic of the numbered rules of include/rt_api.h's extensions (feature planes, NL-means and its guide, temporal reprojection,
 // the a-trous filter, temporal luminance moments, shadow-aware history), stated ONCE: the plain loops of rt_host.cpp (rt_*_planes) and the kernels (rt_features.hip,
-// rt_reproject.hip, rt_atrous.hip, rt_moments.hip, rt_shadow_history.hip, rt_denoise.inc.h) call these functions, so the two sides the GPU tests hold together bit for bit cannot drift apart by a copied line.  Usable from plain
+// rt_reproject.hip, rt_atrous.hip, rt_denoise.inc.h) call these functions, so the two sides the GPU tests hold together bit for bit cannot drift apart by a copied line.  Usable from plain
 // C++ and from HIP, like rt_bvh_layout.h, whose RT_HD it takes.  Every unit that includes it is compiled with -ffp-contract=off: every multiply, add,
 // division and square root below is an operation of its own, in the written order and parenthesisation -- which is part of the rule.
 // What is NOT here: loops, staging, clamping, and whether a tap that does not count is skipped or predicated.  Those belong to each side.

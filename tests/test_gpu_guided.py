@@ -1,4 +1,4 @@
-"""NL-means guided by feature planes on the device (include/rt_api.h "feature planes", rules 13-14; csrc/rt_denoise_guided.hip).  Every comparison
+"""NL-means guided by feature planes on the device (include/rt_api.h "feature planes", rules 13-14; csrc/rt_denoise.hip).  Every comparison
 is of bits: the three filter calls under a guide against rt_denoise_guided_planes / rt_denoise_pair_guided_planes on the same colour planes and the
 feature plane the context itself formed (tests/test_guided_cpu.py holds the host functions to a numpy restatement; tests/test_gpu_feature_planes.py
 holds the plane to rt_features_planes); then the guide's settings, the plane's currency as the filters see it, and the two adaptive loops."""

@@ -1,4 +1,4 @@
-"""Temporal luminance moments on the device (include/rt_api.h "temporal luminance moments", csrc/rt_moments.hip).  Every comparison is of bits:
+"""Temporal luminance moments on the device (include/rt_api.h "temporal luminance moments", csrc/rt_reproject.hip, csrc/rt_atrous.hip).  Every comparison is of bits:
 rt_read_temporal and rt_read_moments after rt_reproject_async against rt_reproject_moments_planes on the read-back inputs, rt_read_atrous after
 rt_atrous_async against rt_atrous_moments_planes (tests/test_moments_cpu.py holds both to a numpy restatement of rules 25-28); then the invariants
 the header states, the plane's currency, the refusals, what the calls leave alone, and the interactive loop with the setting on and off."""

@@ -1,4 +1,4 @@
-"""Shadow-aware history on the device (include/rt_api.h "shadow-aware history", csrc/rt_shadow_history.hip).  Every comparison is of bits:
+"""Shadow-aware history on the device (include/rt_api.h "shadow-aware history", csrc/rt_reproject.hip).  Every comparison is of bits:
 rt_read_temporal, rt_read_moments and rt_read_history_flags after rt_reproject_async against rt_reproject_shadow_planes on the read-back inputs
 (tests/test_shadow_history_cpu.py holds that function to a numpy restatement of rules 29-32) -- every kernel instance, partial workgroups both ways, a
 one-lane image, pair lists of no pair, one pair, exactly one LDS chunk and one pair more -- then the setting turned off again, the flag plane's

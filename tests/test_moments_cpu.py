@@ -1,4 +1,4 @@
-"""Temporal luminance moments (include/rt_api.h "temporal luminance moments", csrc/rt_moments.hip), the part that needs no device: a numpy restatement
+"""Temporal luminance moments (include/rt_api.h "temporal luminance moments", csrc/rt_reproject.hip, csrc/rt_atrous.hip), the part that needs no device: a numpy restatement
 of rules 25-28 in whole-plane float32 operations, written independently of rt_host.cpp's loops; rt_reproject_moments_planes and
 rt_atrous_moments_planes against it bit for bit on the geometries of tests/test_reproject_cpu.py; the cases the rules single out (no history, NaNs, the
 cap); the invariants; the refusals; and the quality the header quotes, with frames of the oracle alone.  tests/test_gpu_moments.py compares the device

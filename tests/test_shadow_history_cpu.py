@@ -1,4 +1,4 @@
-"""Shadow-aware history (include/rt_api.h "shadow-aware history", csrc/rt_shadow_history.hip), the part that needs no device: a numpy restatement of
+"""Shadow-aware history (include/rt_api.h "shadow-aware history", csrc/rt_reproject.hip), the part that needs no device: a numpy restatement of
 rules 29-32 in whole-plane float32 operations, written independently of rt_host.cpp's loops; rt_reproject_shadow_planes against it bit for bit on the
 geometries of tests/test_reproject_cpu.py with records moved, resized and broken; the invariants; the pair order; the refusals; and the quality the
 header quotes, with frames of the oracle alone.  tests/test_gpu_shadow_history.py compares the device with the host function."""

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """`python tools/isa_compare.py A.so B.so`: every gfx950 kernel of two builds of the library, disassembled (llvm-objdump of the code objects inside),
-addresses and encodings stripped, compared instruction for instruction -- which kernels a change of the sources touched.
-`--by-name`: kernels are paired by demangled name without the parameter list (a renamed parameter type changes the mangled name and nothing else)."""
+addresses and encodings stripped, compared instruction for instruction -- which kernels a change of the sources touched.  Per side: the number of
+instructions, and how many of them are not scalar (their mnemonic does not begin with `s_`).
+`--by-name`: kernels are paired by demangled name without the parameter list (a renamed parameter type changes the mangled name and nothing else).
+`--map OLD=NEW` (repeatable, with --by-name): A's kernel OLD is paired with B's kernel NEW, both named that way -- a kernel and its renamed successor."""
 import subprocess, sys, os, re, tempfile, shutil, hashlib
 def kernels(lib):
     tmp = tempfile.mkdtemp()
@@ -27,11 +29,23 @@ def by_name(ks):
     short = {n: re.sub(r"^void ", "", re.sub(r"\((?:[^()]|\([^()]*\))*\)( \[clone [^\]]*\])?$", "", n)) for n in ks}
     seen = list(short.values())
     return {(s if seen.count(s) == 1 else n): ks[n] for n, s in short.items()}
-args = [v for v in sys.argv[1:] if v != "--by-name"]
-BY_NAME = len(args) < len(sys.argv) - 1
+def counts(ins):
+    return "%6s %6s" % (len(ins), sum(1 for i in ins if not i.startswith("s_")))
+args, renamed = [], {}
+argv = sys.argv[1:]
+while argv:
+    v = argv.pop(0)
+    if v == "--map":
+        old, new = argv.pop(0).split("=", 1)
+        renamed[old] = new
+    elif v != "--by-name": args.append(v)
+BY_NAME = "--by-name" in sys.argv[1:]
 a = kernels(args[0]); b = kernels(args[1])
 if BY_NAME: a, b = by_name(a), by_name(b)
+for old, new in renamed.items():
+    if old not in a or new not in b: sys.exit("--map %s=%s: %s" % (old, new, "A holds no such kernel" if old not in a else "B holds no such kernel"))
+    a[old + " -> " + new] = a.pop(old); b[old + " -> " + new] = b.pop(new)
 for k in sorted(set(a) | set(b)):
     ha = hashlib.md5("\n".join(a.get(k, [])).encode()).hexdigest()[:8] if k in a else None
     hb = hashlib.md5("\n".join(b.get(k, [])).encode()).hexdigest()[:8] if k in b else None
-    print("%-60s %6s %6s %s" % (k[:60], len(a.get(k, [])), len(b.get(k, [])), "same" if ha == hb else "DIFFERENT"))
+    print("%-60s %s %s %s" % (k if " -> " in k else k[:60], counts(a.get(k, [])), counts(b.get(k, [])), "same" if ha == hb else "DIFFERENT"))
