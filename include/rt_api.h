@@ -450,6 +450,8 @@ RT_API int rt_select_tiles(rt_ctx *ctx, const uint32_t *err_dev, uint32_t above,
  * selected groups' tiles in heavy-first order where one exists, else in image order -- once per selection, order and tile shape; another
  * adds n_samples to the pass count of every tile of every selected group.  Afterwards rt_current_sample has grown by n_samples, the
  * launch count by one, rt_last_kernel names the instance, and the context is ragged unless the selection held every group of the image.
+ * A launch from pass 0 that leaves groups out leaves them as a 0-pass render holds them: the seeds of the context's stream and a colour
+ * plane of zeros (one fill of the plane ahead of the launch), whatever frame rt_reset_async had left there; their packed pixels stay unspecified.
  * RT_ERR_STATE: no selection; no scene or camera; a kernel instance whose tile is wider than a group (the diagnostics library's
  * two-pixels-per-lane rows).  RT_ERR_ARG: n_samples < 0 or a pass counter overflow; a null, multi-device or sharded context.            */
 RT_API int rt_render_tiles_async(rt_ctx *ctx, int n_samples, void *hip_stream);

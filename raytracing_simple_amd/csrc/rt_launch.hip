@@ -307,6 +307,11 @@ int launch_tiles(rt_ctx *c, int n_samples, hipStream_t stream) {
         c->frame.default_seeds_copied();
         p.seeds_in = c->d_seeds;
     }
+    if (frame.current_sample == 0 && !all) {
+        // ... and the colours of a 0-pass render, zeros: rt_reset_async, rt_seed_stream_async and a state written at pass 0 leave an old frame in the
+        // plane, and pass 0 overwrites it in the tiles this launch renders only.  (The packed pixels of those tiles stay unspecified: include/rt_api.h.)
+        HIP_TRY(hipMemsetAsync(c->d_colors, 0, color_floats(c) * sizeof(float), stream));
+    }
     p.order = c->tiles.d_list;
     p.tile_cost = nullptr;
     RT_TRY(queue_instance(*inst, p, grid, lds_use, stream));

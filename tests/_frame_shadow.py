@@ -153,6 +153,8 @@ class Shadow:
         if n == 0 or self.counts[0] == 0:
             return ACCEPTED
         every = self.counts[0] == self.ty * self.gx
+        if self.cur == 0 and not every:                      # from pass 0 the groups left out hold a 0-pass render: the plane is cleared ahead of the launch
+            self.colors = np.zeros(3 * self.w * self.h, np.float32)
         self.passes = self.tile_map().copy()
         self._render(T.tiles_of(self.mask, self.w, self.h), n)
         self.ragged = not every
