@@ -674,9 +674,17 @@ RT_API int rt_render_adaptive_filtered_tiles(rt_ctx *a, rt_ctx *b, double tile_p
  *  12. the values.  On a hit P = o + d * t, n = vnorm(P - p_id) (.cl:346-347, NOT turned towards the ray), albedo = c_id + e_id per channel,
  *      word 6 = t, word 7 = id.  On a miss seven 0.0f and 0xFFFFFFFF.  Non-finite records behave as in the reference: a NaN discriminant never
  *      hits; a zero-radius hit gives a NaN normal, which is stored as it is.
- * The kernel is a plain sweep, pixels x records tests, made ONCE per scene and camera: one lane per pixel over 8x8 tiles, the geometry table staged
- * in LDS in chunks of 1024 records with a barrier between chunks, so any count up to RT_MAX_SPHERES works.  THE HIERARCHY IS DELIBERATELY NOT USED:
- * the plane is formed once where a frame takes hundreds of passes, and the sweep's answer is the reference's by construction.
+ * WHAT IT COSTS.  One lane per pixel over 8x8 tiles, by one of two kernels that give the same words (rt_last_features_kernel says which ran):
+ *   SWEPT -- scenes without a hierarchy (fewer than 56 small, finite spheres that repeat no earlier record): pixels x records tests, the geometry
+ *   table staged in LDS in chunks of 1024 records with a barrier between chunks, so any count up to RT_MAX_SPHERES works; the reference's Intersect
+ *   by construction.
+ *   WALKED -- every scene that has a hierarchy, from 56 records on (the count was measured: walked, the plane was the faster one at every probed
+ *   count that has a hierarchy): the few large records (the hierarchy's always-list) swept, then ONE closest-hit query per pixel through the hierarchy
+ *   the render kernels walk, with their tie rule (lowest scene index among equal distances) and their three table placements: tables in LDS
+ *   (rt_features_pairs), pairs in LDS and slots in HBM / L2 (_pairs_m), everything in HBM / L2 (_pairs_g).  The hierarchy only selects candidates;
+ *   every test that is made is rule 11's arithmetic.  An interactive host forms the plane every frame (rt_set_camera and rt_update_spheres_async end
+ *   it): walked, the plane cost less than ONE pass of the same scene at every count measured, where the sweep cost 6 passes at 8192 records and 39
+ *   at 262 144.  Measured, profiles/r35_features_walk.jsonl (tools/features_probe.py: both curves and the count); no time is promised.
  *
  * THE GUIDE.  Rules 13-14 extend rules 1-9; the symbols are those of the denoising sections.
  *  13. the feature distance of a pixel p and q = p + o inside the image.  ia = 1.0f / (k_albedo * k_albedo), in and id alike.
@@ -708,8 +716,8 @@ RT_API int rt_render_adaptive_filtered_tiles(rt_ctx *a, rt_ctx *b, double tile_p
  * 58 KiB for the pair kernel at the defaults, 92 KiB at R 8, P 2 (the dynamic-LDS limit is raised for it).
  * MEASURED on an MI355X by tools/guided_probe.py (profiles/r21_guided.jsonl; device time between two events, medians; NO TIME IS PROMISED):
  *   rt_features_async, 800x600 / 1920x1080, beside ONE pass of the same scene:  Demo 0.010 / 0.022 ms (a pass 0.042 / 0.10);  1024 spheres 0.26 / 0.92
- *   (0.22 / 0.58);  8192 spheres 1.96 / 6.04 (0.42 / 1.02);  262 144 spheres 60 / 193 (2.0 / 4.9).  The plain sweep costs one pass at a thousand records
- *   and forty at RT_MAX_SPHERES -- once per scene and camera, where a frame takes hundreds of passes.
+ *   (0.22 / 0.58);  8192 spheres 1.96 / 6.04 (0.42 / 1.02);  262 144 spheres 60 / 193 (2.0 / 4.9).  That was the plain sweep, then the only kernel:
+ *   one pass at a thousand records and forty at RT_MAX_SPHERES.  Scenes with a hierarchy are walked since (WHAT IT COSTS, above).
  *   the filters at 1920x1080, unguided / guided:  rt_denoise_async 0.94 / 1.42 ms;  rt_denoise_pair_async 1.58 / 2.79;  rt_denoise_pair_tiles_async with
  *   half of the groups selected 0.85 / 1.45.  The unguided kernels are the machine code they were before the guide existed.
  *   the table above from rendered contexts, filtered on the device: unguided / guided 27.62 / 27.83 and 31.46 / 31.57 (Demo, 4 and 16 passes),
@@ -725,6 +733,11 @@ RT_API void rt_guide_defaults(rt_guide_params *g);
  * resets, merges and filters do not touch it: it depends on scene and camera alone.  Nothing else of the context changes.
  * RT_ERR_STATE without scene or camera; RT_ERR_ARG for a null, multi-device or sharded context.                                               */
 RT_API int rt_features_async(rt_ctx *ctx, void *hip_stream);
+
+/* The symbol of the kernel the context's last rt_features_async launched: "rt_features_kernel" (swept), "rt_features_pairs", "rt_features_pairs_m" or
+ * "rt_features_pairs_g" (walked, by table placement).  "" before any such call and for a null context.  Like rt_last_kernel for the render path, the
+ * only way to see the choice: it depends on the scene, never the result.                                                                         */
+RT_API const char *rt_last_features_kernel(const rt_ctx *ctx);
 
 /* The context's feature plane, 8 words per pixel, into HOST memory.  Blocking.  RT_ERR_STATE when the plane is not current; RT_ERR_ARG for a null,
  * multi-device or sharded context or a null buffer.                                                                                            */

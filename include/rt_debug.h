@@ -61,7 +61,12 @@ RT_API int rt_debug_set_bvh(rt_ctx *ctx, int min_spheres, int lds_limit);
 RT_API int rt_debug_set_tree_shape(rt_ctx *ctx, int by_area);        /* the hierarchy's shape: 1 (default) by surface area -- uploads below 1500 tree spheres on the host, larger ones and every device-resident update on the device; 2: on the device for every upload too; 0: the fixed (halved) shape everywhere */
 RT_API int rt_debug_set_bvh_layout(rt_ctx *ctx, int top_pairs, int packed);   /* the pair table's layout for the A/B walks: top_pairs > 0 renumbers the top of the tree breadth-first to the front (the root becomes pair 0; at most 255 pairs -- rt_trace_*_pairs_gt, _gtp stage them), packed != 0 writes the packed pair table behind the blob (_gq, _gtp).  Default 0, 0: the builders' numbering, no packed table -- the product library's layout.  Applies from the next rt_set_scene or rebuild; RT_TOP_PAIRS overrides the count where a top is promoted.  rt_set_mode of an instance that reads one of these tables asks for it the same way and rebuilds the current scene's tables */
 RT_API int rt_debug_set_walk(rt_ctx *ctx, int steps, int gate, int forced);   /* steps: TAIL LANES since round 5, 0..63 -- a trip's walk phase ends once no more than `steps` lanes still walk, their walks go on in the next trip (0, the default: every walk runs to its end within the trip; an experiment's knob); gate: ready lanes that make a wavefront shade (0 = keep); forced 0 = hierarchy or plain sweep by estimate / measurement (default), 1 = the hierarchy whenever the scene has one */
-RT_API int rt_debug_set_walk_round(rt_ctx *ctx, int steps);   /* pair steps a lane takes in a row before the leaf step of the lanes that hold a leaf (default 3; large = until every lane has one) */
+/* which kernel rt_features_async launches: 0 = the rule (csrc/rt_instance.h features_form), 1 = the sweep, 2 = the hierarchy, at the placement the LDS
+ * limits give (rt_debug_set_bvh's lds_limit forces one).  RT_ERR_ARG for anything else.  With 2 on a scene without a hierarchy rt_features_async returns
+ * RT_ERR_STATE before it queues anything: plane, currency and rt_last_features_kernel stay (only where rt_update_spheres_async left the tables stale
+ * does their pending rebuild run first -- whether the moved records have a hierarchy is known behind it). */
+RT_API int rt_debug_set_features_form(rt_ctx *ctx, int form);
+RT_API int rt_debug_set_walk_round(rt_ctx *ctx, int steps);  /* pair steps a lane takes in a row before the leaf step of the lanes that hold a leaf (default 3; large = until every lane has one) */
 /* n_rays rays { o.xyz, t_max, d.xyz, shadow != 0 } (8 floats each; the last as a bit pattern) through the hierarchy walk
  * AND the plain sweep, one lane per ray; out4 (4 words per ray) = the walk's answer, then the sweep's -- closest hit:
  * distance bits and scene index (~0 for a miss); shadow ray: the first blocking scene index (the sphere count for

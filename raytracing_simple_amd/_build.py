@@ -189,7 +189,8 @@ def build(force=False, verbose=False, diag=True):
 
 
 def build_harness(cc, force=False, verbose=False):
-    """The native hosts on the C ABI: tools/rt_bench (the reference's Main.cpp without the window),
+    """The native hosts on the C ABI (rt_bench also asks the HIP runtime for the two events that time rt_features_async; rt_inflight for its own):
+    tools/rt_bench (the reference's Main.cpp without the window),
     tools/rt_inflight (bench.py's frames-in-flight loop), tools/rt_view (the display component, built
     only where freeglut's library exists -- its sources are syntax-checked by tests/test_adapter.py)."""
     inc = "-I" + os.path.join(ROOT, "include")

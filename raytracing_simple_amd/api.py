@@ -27,7 +27,7 @@ SYMBOLS = ["rt_render", "rt_release_cache", "rt_create", "rt_create_multi", "rt_
            "rt_denoise_defaults", "rt_denoise_async", "rt_denoise_planes",
            "rt_denoise_pair_async", "rt_denoise_pair_planes", "rt_read_filtered", "rt_compare_filtered_async", "rt_compare_filtered",
            "rt_render_converged_filtered", "rt_render_adaptive_filtered", "rt_denoise_pair_tiles_async", "rt_render_adaptive_filtered_tiles",
-           "rt_guide_defaults", "rt_features_async", "rt_read_features", "rt_features_planes", "rt_set_denoise_guide",
+           "rt_guide_defaults", "rt_features_async", "rt_last_features_kernel", "rt_read_features", "rt_features_planes", "rt_set_denoise_guide",
            "rt_denoise_guided_planes", "rt_denoise_pair_guided_planes",
            "rt_reproject_defaults", "rt_reproject_async", "rt_read_temporal", "rt_reproject_planes",
            "rt_atrous_defaults", "rt_atrous_async", "rt_read_atrous", "rt_atrous_planes",
@@ -38,7 +38,7 @@ DEBUG_SYMBOLS = ["rt_debug_variant_count", "rt_debug_instance", "rt_debug_instan
                  "rt_debug_rcp_probe", "rt_debug_set_regen_gate", "rt_debug_set_mat_lds_limit", "rt_debug_set_persist",
                  "rt_debug_set_ncus", "rt_debug_set_coop_min", "rt_debug_set_bvh", "rt_debug_set_tree_shape", "rt_debug_set_bvh_layout", "rt_debug_set_walk", "rt_debug_set_walk_round", "rt_debug_bvh_pick", "rt_debug_tree_estimate", "rt_debug_set_choice_estimate", "rt_debug_create_breakdown", "rt_debug_walk_rays", "rt_debug_read_bvh", "rt_debug_read_packed_pairs", "rt_debug_set_direct_camera", "rt_debug_tile_candidates", "rt_debug_set_tile_order", "rt_debug_read_tile_order", "rt_debug_read_tile_list", "rt_debug_set_wg_waves", "rt_debug_counters", "rt_debug_counters_raw",
                  "rt_debug_reset_by_copy", "rt_debug_probe_seeds", "rt_debug_sidelog_read", "rt_debug_timelog_enable", "rt_debug_timelog_tag",
-                 "rt_debug_timelog_read", "rt_debug_wavelog_read"]
+                 "rt_debug_timelog_read", "rt_debug_wavelog_read", "rt_debug_set_features_form"]
 
 
 class RtError(RuntimeError):
@@ -217,6 +217,7 @@ def load_library(diag=False):
         "rt_render_adaptive_filtered_tiles": (i32, [vp, vp, C.c_double, i32, i32, i32, C.POINTER(DenoiseParams), C.POINTER(FrameError), C.POINTER(i32)]),
         "rt_guide_defaults": (None, [C.POINTER(GuideParams)]),
         "rt_features_async": (i32, [vp, vp]),
+        "rt_last_features_kernel": (C.c_char_p, [vp]),
         "rt_read_features": (i32, [vp, vp]),
         "rt_features_planes": (i32, [vp, vp, u32, vp, i32, i32]),
         "rt_set_denoise_guide": (i32, [vp, C.POINTER(GuideParams)]),
@@ -274,6 +275,7 @@ def load_library(diag=False):
             "rt_debug_create_breakdown": (i32, [C.POINTER(C.c_double)]),
             "rt_debug_walk_rays": (i32, [vp, vp, u32, vp]),
             "rt_debug_set_walk_round": (i32, [vp, i32]),
+            "rt_debug_set_features_form": (i32, [vp, i32]),
             "rt_debug_read_bvh": (i32, [vp, vp, u32, vp]),
             "rt_debug_read_packed_pairs": (i32, [vp, vp, u32, C.POINTER(u32)]),
             "rt_debug_set_tile_order": (i32, [vp, i32]),
@@ -619,6 +621,10 @@ class RtContext:
     def features_async(self, stream=None):
         """rt_features_async: the feature plane of this context's scene and camera, formed on the device (read_features)."""
         self._check(self._lib.rt_features_async(self._h, C.c_void_p(stream or 0)))
+
+    def last_features_kernel(self):
+        """Symbol of the kernel the last features_async launched (rt_last_features_kernel): the sweep's, or the hierarchy's by table placement."""
+        return self._lib.rt_last_features_kernel(self._h).decode()
 
     def read_features(self):
         """rt_read_features: the feature plane, float32 [h][w][8] in the colour plane's row order: albedo, normal, distance and -- word 7, view it as

@@ -351,6 +351,13 @@ RT_API int rt_debug_set_walk_round(rt_ctx *c, int steps) {
     return dbg_apply(c, dbg_set_walk_round, steps);
 }
 
+// which kernel forms the feature plane: 0 = the rule (rt_instance.h features_form), 1 = the sweep, 2 = the hierarchy at the placement the LDS limits
+// give (rt_debug_set_bvh forces a placement).  2 on a scene without a hierarchy makes rt_features_async return RT_ERR_STATE
+RT_API int rt_debug_set_features_form(rt_ctx *c, int form) {
+    if (!c || c->multi || form < 0 || form > 2) return fail(RT_ERR_ARG, "rt_debug_set_features_form: form %d (0 the rule, 1 the sweep, 2 the hierarchy) on a null / multi-device context?", form);
+    c->knobs.features_form = form;
+    return RT_OK;
+}
 static int dbg_set_walk_forced(rt_ctx *c, int v) { c->knobs.walk_forced = v ? 1 : 0; c->choice.knob_set(); return RT_OK; }
 // rt_walk.inc.h: pair steps per lane per loop trip, ready lanes that make a wavefront shade (0 = keep either), and
 // forced: 0 = hierarchy or plain sweep by measurement (the library's behaviour), 1 = the hierarchy whenever the scene has one

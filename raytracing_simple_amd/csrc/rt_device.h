@@ -8,6 +8,7 @@
 #include "../../include/rt_api.h"
 #include "rt_bvh_layout.h"     // kBvhLeaf, kBvhLeafRef, the offsets into the hierarchy's blob
 #include "rt_instance.h"       // what an instance is (tables, role, flags), the LDS it needs, kMaxK2Table, kBvhTopPairs, kLdsMax: shared with the HIP-free rule
+#include "rt_rules.h"          // PixelCamera: what rule 10 reads of a camera
 
 namespace rt {
 
@@ -119,6 +120,18 @@ struct Instance {
     uint8_t role;           // InstanceRole (with `waves`, what launch() selects by)
     uint8_t flags;          // InstanceFlags
 };
+// The feature plane through the hierarchy (rt_walk.inc.h rt_features_pairs / _pairs_m / _pairs_g, instantiated in rt_kernel_parity.hip ONLY: the plane is
+// parity's arithmetic whatever the mode): what the kernel reads, and the launch by placement (rt_instance.h FeaturesForm; never kFeaturesSweep --
+// that one is rt_features.hip's own kernel)
+struct FeaturesWalkParams {
+    float4 *out;            // [h][w][2], the plane's row order
+    const float4 *geom, *emis, *colr;       // the scene tables, by scene index (rule 12 reads them at the winner's)
+    BvhTables bvh;
+    PixelCamera cam;
+    int w, h;
+};
+hipError_t launch_features_walk(int form, const FeaturesWalkParams &p, dim3 grid, size_t lds, hipStream_t stream);
+const char *features_walk_name(int form);     // the kernel's symbol ("" for a form that walks nothing)
 const Instance *parity_instances(int *count);
 const Instance *fast_instances(int *count);
 hipError_t launch_instance(const Instance &inst, const LaunchParams &p, dim3 grid, size_t lds, hipStream_t stream);

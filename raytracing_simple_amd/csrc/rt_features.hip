@@ -6,8 +6,10 @@
 // the comments below name the rule a line implements.  The reference hands out no such plane: this is the library's own extension.
 // This unit is compiled with parity's flags (-ffp-contract=off, correctly rounded division and square root): every multiply, add, division and square
 // root below is an operation of its own, in the written order -- whatever rt_set_mode says.
-// A PLAIN SWEEP, pixels x records tests: the plane is formed once per scene and camera, where a frame takes hundreds of passes over the same scene, and
-// the sweep's answer is the reference's Intersect by construction.  The hierarchy is deliberately not used.
+// Two ways to the same words (rt_instance.h features_form says which a call takes; rt_last_features_kernel names it): the PLAIN SWEEP below, pixels x
+// records tests, whose answer is the reference's Intersect by construction -- scenes without a hierarchy, or of fewer than kFeaturesWalkMin records --
+// and ONE closest-hit query per pixel THROUGH THE HIERARCHY (rt_walk.inc.h rt_features_pairs / _pairs_m / _pairs_g, parity's unit), which an interactive
+// host that forms the plane every frame needs on large scenes.  The hierarchy only selects candidates: every test made is the same arithmetic.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -102,6 +104,10 @@ RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
     int rc = tiles_refuse(c, "rt_features_async");
     if (rc != RT_OK) return rc;
     if (!c->scene.state.renderable()) return fail(RT_ERR_STATE, "rt_features_async: rt_set_scene and rt_set_camera come first");
+    // (the hierarchy forced on a scene that has none: refused here, before anything is queued, where the tables say so already; a scene whose
+    // tables an update left stale is asked again behind their rebuild, below)
+    const char *no_hierarchy = "rt_features_async: the hierarchy is forced (rt_debug_set_features_form) and the scene has none (fewer than %d small spheres?)";
+    if (c->knobs.features_form == 2 && !c->scene.state.needs_refresh() && !c->scene.state.has_hierarchy()) return fail(RT_ERR_STATE, no_hierarchy, c->knobs.bvh_min);
     rc = select_device(c);
     if (rc != RT_OK) return rc;
     RT_TRY(ensure_device(c->owned, &c->scene.d_features, 8 * image_pixels(c)));
@@ -110,13 +116,29 @@ RT_API int rt_features_async(rt_ctx *c, void *hip_stream) {
     rc = chain(c, stream);
     if (rc == RT_OK) rc = refresh_tables(c, stream);
     if (rc != RT_OK) return rc;
-    hipLaunchKernelGGL(rt_features_kernel, plane_grid(c->w, c->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(c->scene.d_features), c->scene.tables.geom,
-                       c->scene.tables.emis, c->scene.tables.colr, c->scene.tables.n_spheres, pixel_camera(c->cam), c->w, c->h);
-    HIP_TRY(hipGetLastError());
+    // which kernel: the rule, of the scene as the refresh left it
+    const SceneFacts facts = scene_facts(c);
+    const int form = features_form(c->knobs, facts);
+    if (c->knobs.features_form == 2 && !features_walks(form)) return fail(RT_ERR_STATE, no_hierarchy, c->knobs.bvh_min);
+    if (features_walks(form)) {
+        const FeaturesWalkParams p{ reinterpret_cast<float4 *>(c->scene.d_features), c->scene.tables.geom, c->scene.tables.emis, c->scene.tables.colr, c->scene.bvh,
+                                    pixel_camera(c->cam), c->w, c->h };
+        const size_t lds = features_lds(form, facts);
+        if (lds > kLdsMax) return fail(RT_ERR_ARG, "rt_features_async: %s needs %zu B of LDS for this scene (limit %zu)", features_walk_name(form), lds, kLdsMax);
+        HIP_TRY(launch_features_walk(form, p, plane_grid(c->w, c->h), lds, stream));
+        c->last_features_kernel = features_walk_name(form);
+    } else {
+        hipLaunchKernelGGL(rt_features_kernel, plane_grid(c->w, c->h), dim3(kPlaneLanes), 0, stream, reinterpret_cast<float4 *>(c->scene.d_features), c->scene.tables.geom,
+                           c->scene.tables.emis, c->scene.tables.colr, c->scene.tables.n_spheres, pixel_camera(c->cam), c->w, c->h);
+        HIP_TRY(hipGetLastError());
+        c->last_features_kernel = "rt_features_kernel";
+    }
     if (!c->scene.state.features_current) c->frame.features_reformed();     // (a temporal plane formed under the plane that ended stays ended)
     c->scene.state.features_formed();
     return RT_OK;
 }
+
+RT_API const char *rt_last_features_kernel(const rt_ctx *c) { return c ? c->last_features_kernel : ""; }
 
 RT_API int rt_read_features(rt_ctx *c, float *out_host) { return read_plane(c, "rt_read_features", Plane::Features, out_host); }
 

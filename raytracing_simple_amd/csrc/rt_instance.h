@@ -109,6 +109,8 @@ struct Knobs {
                                         // (round 4, this kernel: 2 / 3 / 4 / 6 in a row = 5.42 / 5.37 / 5.22 / 5.45 ms on C3, profiles/r04k_walk_sweep.jsonl)
     int walk_tail = 0;                  // lanes that may be left walking when a trip's walk phase ends (0 = none: every walk runs to its end within the trip)
     int walk_forced = 0;                // 0 = measured choice (rt_ctx::choice); diagnostics: 1 = the hierarchy whenever the scene has one
+    // ---- the feature plane ----
+    int features_form = 0;              // 0 = the rule (features_form below); diagnostics (rt_debug_set_features_form): 1 = the sweep, 2 = the hierarchy
 
     // ---- what `mode` means, said once: RT_MODE_PARITY / RT_MODE_FAST, or (diagnostics build; rt_set_mode checks the range) a row of the parity
     // table as 100 + row, of the fast table as 200 + row ----
@@ -191,6 +193,39 @@ inline Shape pick_shape(const Knobs &k, const SceneFacts &s, int n_samples, Form
         out.waves = 4;
     }
     return out;
+}
+
+// ---- the feature plane (rt_features_async) -------------------------------------------------------------
+// Which kernel forms it: the plain sweep of rt_features.hip, pixels x records, or ONE closest-hit query per pixel through the hierarchy
+// (rt_walk.inc.h rt_features_pairs*), at the table placement the render walk's LDS limits give.  The plane is one query per pixel and times nothing:
+// workgroup shape, persistent wavefronts and the render path's hierarchy-against-sweep measurement do not enter.
+enum FeaturesForm : int {
+    kFeaturesSweep = 0,     // rt_features_kernel
+    kFeaturesPairs,         // rt_features_pairs: header, pairs, slots and stacks in LDS
+    kFeaturesPairsM,        // rt_features_pairs_m: the pairs staged, the slots where they lie in HBM / L2
+    kFeaturesPairsG,        // rt_features_pairs_g: pairs and slots where they lie
+};
+// Scenes of at least this many records that have a hierarchy form their plane through it.  MEASURED (tools/features_probe.py,
+// profiles/r35_features_walk.jsonl: the smallest probed count from which the hierarchy is faster at 800x600 and at 1920x1080 and stays faster at
+// every larger probed count).  The hierarchy never lost, from 57 records -- the smallest random scene that has one -- to 262 144: so this is 56,
+// the fewest tree spheres a hierarchy is built from (Knobs::bvh_min), and the rule's first clause decides alone
+constexpr uint32_t kFeaturesWalkMin = 56;
+inline bool features_walks(int form) { return form != kFeaturesSweep; }
+// `s` describes the scene AFTER refresh_tables (has_hierarchy: the blob describes the records as they are).  Knobs::features_form forces either side
+// (diagnostics): 2 on a scene without a hierarchy still answers kFeaturesSweep, and rt_features_async refuses
+inline FeaturesForm features_form(const Knobs &k, const SceneFacts &s) {
+    if (!s.has_hierarchy || k.features_form == 1) return kFeaturesSweep;
+    if (k.features_form != 2 && s.n_spheres < kFeaturesWalkMin) return kFeaturesSweep;
+    const size_t all = lds_bytes_pairs(0, 0, false, 0, s.n_leaves, s.n_slots, s.stack_depth, 256);
+    const size_t pairs = lds_bytes_pairs(0, 0, false, 0, s.n_leaves, 0, s.stack_depth, 256);
+    return all <= (size_t)k.bvh_lds_limit ? kFeaturesPairs : (k.bvh_mixed != 0 && pairs <= (size_t)k.bvh_lds_limit ? kFeaturesPairsM : kFeaturesPairsG);
+}
+// the dynamic LDS of a form that walks: hdr | pairs | slots | stacks, what is not staged left out (a workgroup is 256 lanes)
+inline size_t features_lds(int form, const SceneFacts &s) {
+    return form == kFeaturesPairs    ? lds_bytes_pairs(0, 0, false, 0, s.n_leaves, s.n_slots, s.stack_depth, 256)
+           : form == kFeaturesPairsM ? lds_bytes_pairs(0, 0, false, 0, s.n_leaves, 0, s.stack_depth, 256)
+           : form == kFeaturesPairsG ? lds_bytes_pairs(0, 0, false, 0, 1, 0, s.stack_depth, 256)
+                                     : 0;
 }
 
 // The dynamic LDS an instance of table kind `tables` needs for the scene, checked against what the scene has

@@ -248,6 +248,7 @@ struct rt_ctx {
     rt::TileOrder order;                // heavy-first tile schedule (rt_tile_order.h; rt_trace.inc.h reads and writes its arrays)
     rt::Knobs knobs;                    // what a launch is made of besides: arithmetic mode, thresholds, the hierarchy's and the walk's knobs, diagnostics knobs (rt_instance.h)
     const char *last_kernel = "";       // symbol of the instance the last launch used
+    const char *last_features_kernel = "";      // ... of the kernel the last rt_features_async launched (rt_features.hip)
     unsigned long long debug_counters[24] = {};   // diagnostic instances only
     hipStream_t stream = nullptr;       // the context's own (non-blocking) stream
     hipStream_t last_stream = nullptr;  // stream of the most recent launch / update (what readers wait for)

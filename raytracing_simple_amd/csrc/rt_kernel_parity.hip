@@ -60,6 +60,7 @@
 #define RT_NS parity_pairs           /* large scenes: the walk over sibling pairs, nearer child first (rt_walk.inc.h) */
 #define RT_KERNEL_NAME rt_trace_parity_pairs
 #define RT_WALK_RAYS_KERNEL_NAME rt_walk_rays_parity   /* diagnostics build: rays through the walk and the sweep */
+#define RT_FEATURES_KERNEL_NAME rt_features_pairs      /* both builds: the feature plane through the hierarchy, at this placement */
 #define RT_OPT_WALK 1
 #define RT_OPT_MINWAVES 5
 #include "rt_trace.inc.h"
@@ -67,6 +68,7 @@
 
 #define RT_NS parity_pairs_g         /* tables too large for LDS: the same walk over pairs and slots where they lie in HBM / L2 */
 #define RT_KERNEL_NAME rt_trace_parity_pairs_g
+#define RT_FEATURES_KERNEL_NAME rt_features_pairs_g
 #define RT_OPT_WALK 1
 #define RT_OPT_GLOBAL_TABLES 1
 #define RT_OPT_MINWAVES 5
@@ -75,6 +77,7 @@
 
 #define RT_NS parity_pairs_m          /* tables beyond LDS whose PAIRS still fit it: pairs staged, slots where they lie in HBM / L2 */
 #define RT_KERNEL_NAME rt_trace_parity_pairs_m
+#define RT_FEATURES_KERNEL_NAME rt_features_pairs_m
 #define RT_OPT_WALK 1
 #define RT_OPT_GLOBAL_TABLES 2
 #define RT_OPT_MINWAVES 5
@@ -278,6 +281,20 @@ hipError_t launch_pack_parity(const LaunchParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// The feature plane through the hierarchy (rt_instance.h FeaturesForm): one row per placement, the render walk's own
+static const struct { void (*fn)(const FeaturesWalkParams); const char *name; } kFeaturesWalk[] = {
+    { nullptr, "" },
+    { parity_pairs::rt_features_pairs, "rt_features_pairs" },
+    { parity_pairs_m::rt_features_pairs_m, "rt_features_pairs_m" },
+    { parity_pairs_g::rt_features_pairs_g, "rt_features_pairs_g" },
+};
+const char *features_walk_name(int form) { return form > kFeaturesSweep && form <= kFeaturesPairsG ? kFeaturesWalk[form].name : ""; }
+hipError_t launch_features_walk(int form, const FeaturesWalkParams &p, dim3 grid, size_t lds, hipStream_t stream) {
+    if (form <= kFeaturesSweep || form > kFeaturesPairsG || lds > kLdsMax) return hipErrorInvalidValue;      // (the dynamic-LDS limit: prepare_parity, once)
+    hipLaunchKernelGGL(kFeaturesWalk[form].fn, grid, dim3(256), lds, stream, p);
+    return hipGetLastError();
+}
+
 #if RT_DIAGNOSTICS
 hipError_t launch_walk_rays(const LaunchParams &p, const float4 *rays, uint32_t n_rays, uint4 *out, size_t lds, hipStream_t stream) {
     if (n_rays == 0) return hipSuccess;
@@ -315,6 +332,10 @@ hipError_t prepare_parity() {
     for (const Instance &k : kParityInstances) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+        if (e != hipSuccess) return e;
+    }
+    for (int form = kFeaturesPairs; form <= kFeaturesPairsG; ++form) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kFeaturesWalk[form].fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -5,6 +5,7 @@
 #undef RT_SCHED_KERNEL_NAME
 #undef RT_PACK_KERNEL_NAME
 #undef RT_WALK_RAYS_KERNEL_NAME
+#undef RT_FEATURES_KERNEL_NAME
 #undef RT_OPT_WG_WAVES
 #undef RT_OPT_COOP
 #undef RT_OPT_WALK

@@ -1033,3 +1033,78 @@ extern "C" __global__ void __launch_bounds__(256) RT_WALK_RAYS_KERNEL_NAME(const
     }
 }
 #endif
+
+#if RT_OPT_WALK == 1 && defined(RT_FEATURES_KERNEL_NAME)
+// The feature plane through the hierarchy (include/rt_api.h, "feature planes", rules 10-12; rt_instance.h features_form says which scenes): one lane per
+// pixel over rt_plane.inc.h's 32x8 workgroups, ONE closest-hit query a pixel -- the rays kernel's closest branch between rule 10's ray and rule 12's
+// words.  Built in the product library too, in parity's unit only; the tables lie where this instance's render kernel has them (RT_OPT_GLOBAL_TABLES).
+// EVERY lane stays to the end: the sweep over the always-list and the leaf steps use wave ballots.  A lane outside the image traces the ray of the
+// nearest pixel inside it and stores nothing.
+// Bounds: staged are pairs [0, 4 (n_leaves - 1)) and slots [0, n_slots) of the blob, into the LDS the launch sized by the same counts
+// (rt_instance.h features_lds); a lane's stack is s_stack[level * 256 + tid], level < stack_depth; the winner's slot is < n_slots and its scene index
+// < n_spheres (the builders' tables), read on a hit only; the store is guarded by x < w && y < h.
+extern "C" __global__ void __launch_bounds__(256, RT_OPT_MINWAVES) RT_FEATURES_KERNEL_NAME(const FeaturesWalkParams P) {
+    constexpr int kThreads = 256;
+    extern __shared__ float4 lds[];
+    const uint32_t n_always = P.bvh.n_always, n_slots = P.bvh.n_slots;
+    const uint32_t *g_index = reinterpret_cast<const uint32_t *>(P.bvh.blob + bvh_index_at(n_slots));
+    const int tid = threadIdx.x;
+    float4 *s_hdr = lds;
+    if (tid < 2) s_hdr[tid] = P.bvh.blob[tid];
+#if RT_OPT_GLOBAL_TABLES == 1
+    const float4 *s_pairs = P.bvh.blob + bvh_pairs_at(n_slots);
+    const float4 *s_slots = P.bvh.blob + bvh_slots_at();
+    uint16_t *s_stack = reinterpret_cast<uint16_t *>(s_hdr + 2);
+#else
+    const uint32_t n_pairs = P.bvh.n_leaves - 1u;
+    float4 *s_pairs = s_hdr + 2;
+    {
+        const float4 *g_pairs = P.bvh.blob + bvh_pairs_at(n_slots);
+        for (uint32_t i = tid; i < 4u * n_pairs; i += kThreads) s_pairs[i] = g_pairs[i];
+    }
+#if RT_OPT_GLOBAL_TABLES == 2
+    const float4 *s_slots = P.bvh.blob + bvh_slots_at();
+    uint16_t *s_stack = reinterpret_cast<uint16_t *>(s_pairs + 4 * n_pairs);
+#else
+    float4 *s_slots = s_pairs + 4 * n_pairs;
+    {
+        const float4 *g_slots = P.bvh.blob + bvh_slots_at();
+        for (uint32_t i = tid; i < n_slots; i += kThreads) s_slots[i] = g_slots[i];
+    }
+    uint16_t *s_stack = reinterpret_cast<uint16_t *>(s_slots + n_slots);
+#endif
+#endif
+    __syncthreads();
+
+    // rule 10: the ray through the pixel's centre (rt_plane.inc.h plane_pixel's mapping: a wavefront on an 8x8 tile, the four tiles side by side)
+    const int x = (int)blockIdx.x * 32 + (tid >> 6) * 8 + (tid & 7), y = (int)blockIdx.y * 8 + ((tid & 63) >> 3);
+    const PixelRay r = pixel_ray(P.cam, x < P.w ? x : P.w - 1, y < P.h ? y : P.h - 1, 1.f / (float)P.w, 1.f / (float)P.h);
+    const V3 o = mk(r.ox, r.oy, r.oz), d = mk(r.dx, r.dy, r.dz);
+
+    // rule 11: the nearest record, the lowest scene index among equals -- the always-list swept, the tree walked
+    unsigned long long roots = 0;
+    float t = 1e20f;
+    uint32_t slot = 0;
+    sweep_closest(s_slots, n_always, o, d, t, slot, roots);
+    const BvhRay R = bvh_ray(s_hdr, o, d);
+    uint32_t cur = bvh_root(s_hdr), w_slot = slot, w_idx = 0xffffffffu;
+    int sp = 0;
+    float w_far = t;
+    walk_pairs(s_pairs, s_slots, g_index, s_stack + tid, kThreads, n_always, o, d, R, false, 3, cur, sp, w_far, w_idx, w_slot, nullptr, nullptr);     // (3 pair steps a round, as the rays kernel)
+
+    // rule 12: the values
+    float4 lo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+    if (w_far < 1e20f) {
+        const uint32_t id = g_index[w_slot];
+        const float4 g = P.geom[id], e = P.emis[id], c = P.colr[id];
+        const Float3 nrm = hit_normal(r, w_far, g.x, g.y, g.z);
+        lo = make_float4(c.x + e.x, c.y + e.y, c.z + e.z, nrm.x);
+        hi = make_float4(nrm.y, nrm.z, w_far, __uint_as_float(id));
+    }
+    if (x < P.w && y < P.h) {
+        const size_t at = (size_t)(P.h - 1 - y) * (size_t)P.w + (size_t)x;
+        P.out[2 * at] = lo;
+        P.out[2 * at + 1] = hi;
+    }
+}
+#endif

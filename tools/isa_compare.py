@@ -3,7 +3,10 @@
 addresses and encodings stripped, compared instruction for instruction -- which kernels a change of the sources touched.  Per side: the number of
 instructions, and how many of them are not scalar (their mnemonic does not begin with `s_`).
 `--by-name`: kernels are paired by demangled name without the parameter list (a renamed parameter type changes the mangled name and nothing else).
-`--map OLD=NEW` (repeatable, with --by-name): A's kernel OLD is paired with B's kernel NEW, both named that way -- a kernel and its renamed successor."""
+`--map OLD=NEW` (repeatable, with --by-name): A's kernel OLD is paired with B's kernel NEW, both named that way -- a kernel and its renamed successor.
+`--pc-relative`: the displacement of a program-counter-relative address -- the literal of the `s_add_u32` (and, where it is one, of the `s_addc_u32`) that
+follows an `s_getpc_b64` on the same register pair -- is left out of the comparison.  It is the distance from the instruction to a constant table of the
+code object, and moves for EVERY kernel of a translation unit when the unit gains or loses a kernel; nothing else of an instruction is left out."""
 import subprocess, sys, os, re, tempfile, shutil, hashlib
 def kernels(lib):
     tmp = tempfile.mkdtemp()
@@ -13,13 +16,19 @@ def kernels(lib):
     for f in sorted(os.listdir(tmp)):
         if "amdgcn" not in f: continue
         txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d"] + (["--demangle"] if BY_NAME else []) + [f], cwd=tmp, check=True, capture_output=True, text=True).stdout
-        cur = None
+        cur = None; pc_pair = None; pc_left = 0
         for line in txt.split("\n"):
             m = re.match(r"^[0-9a-f]+ <(.+)>:", line)
             if m: cur = m.group(1); out[cur] = []; continue
             if cur and "//" in line:
                 ins = line.split("//")[0].strip()
                 ins = re.sub(r"<[^>]+>", "", ins)
+                if PC_RELATIVE:
+                    m = re.match(r"s_getpc_b64 s\[(\d+):(\d+)\]", ins)
+                    if m: pc_pair = (m.group(1), m.group(2)); pc_left = 2
+                    elif pc_left and re.match(r"s_add_u32 s%s, s%s, " % (pc_pair[0], pc_pair[0]), ins): ins = re.sub(r", [^,]+$", ", pc-relative", ins); pc_left -= 1
+                    elif pc_left and re.match(r"s_addc_u32 s%s, s%s, " % (pc_pair[1], pc_pair[1]), ins): ins = re.sub(r", [^,]+$", ", pc-relative", ins); pc_left = 0
+                    else: pc_left = 0
                 out[cur].append(ins)
     shutil.rmtree(tmp)
     return out
@@ -38,8 +47,9 @@ while argv:
     if v == "--map":
         old, new = argv.pop(0).split("=", 1)
         renamed[old] = new
-    elif v != "--by-name": args.append(v)
+    elif v not in ("--by-name", "--pc-relative"): args.append(v)
 BY_NAME = "--by-name" in sys.argv[1:]
+PC_RELATIVE = "--pc-relative" in sys.argv[1:]
 a = kernels(args[0]); b = kernels(args[1])
 if BY_NAME: a, b = by_name(a), by_name(b)
 for old, new in renamed.items():

@@ -35,7 +35,8 @@
 //                       figure of its own last check
 //   --atrous            the context the frame ends in -- the one context, or with --until-psnr the merged (and filtered) one -- forms its
 //                       feature plane and runs the edge-avoiding wavelet filter over its colour plane (rt_features_async, rt_atrous_async;
-//                       --atrous-levels N: 0 .. 5, default 3); --out is written from the filtered frame.  A further line gives the
+//                       --atrous-levels N: 0 .. 5, default 3); --out is written from the filtered frame.  A further line names the kernel that formed
+//                       the plane and its device time between two events (a large .scn scene: what the plane cost beside the pass), and gives the
 //                       parameters and the wall time of the two calls and the read-back.  Not with --gpus / --rehearse
 //   --moments           with --atrous: the filter takes its variance from a pixel's history (rt_set_temporal_moments; --moments-kmin K: the
 //                       frames a pixel needs, default 4).  A history has to exist for that: two helper contexts of the same scene, view and
@@ -51,6 +52,8 @@
 // The four positional arguments are the reference's; only framework ID 2 (the slot
 // Config.cpp:63-65 leaves empty) is served, GPU = 1, memory type 0 (Buffer).
 // Prints one JSON line with frame time and ray throughput.
+#include <hip/hip_runtime_api.h>
+
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -135,14 +138,26 @@ static int history_shadow(rt_ctx* ctx, const rt_sphere* spheres, uint32_t n, con
     return 0;
 }
 
-// --atrous: the feature plane, the filter, and the filtered frame's packed words into `px`; prints its line
+// --atrous: the feature plane, the filter, and the filtered frame's packed words into `px`; prints its line -- with the kernel that formed the plane
+// (rt_last_features_kernel: swept, or walked through the hierarchy) and its device time between two events, what the plane cost beside the pass
 static int filter_atrous(rt_ctx* ctx, const rt_atrous_params& at, std::vector<uint32_t>& px) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (rt_features_async(ctx, rt_stream(ctx)) != RT_OK) return die("rt_features_async");
-    if (rt_atrous_async(ctx, &at, rt_stream(ctx)) != RT_OK) return die("rt_atrous_async");
+    hipStream_t stream = static_cast<hipStream_t>(rt_stream(ctx));
+    struct Events {                                     // (given back on every way out)
+        hipEvent_t ev[2] = { nullptr, nullptr };
+        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+        hipEvent_t& operator[](int k) { return ev[k]; }
+    } ev;
+    float features_ms = 0.f;
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess || hipEventRecord(ev[0], stream) != hipSuccess) return die("hipEventRecord");
+    if (rt_features_async(ctx, stream) != RT_OK) return die("rt_features_async");
+    if (hipEventRecord(ev[1], stream) != hipSuccess) return die("hipEventRecord");
+    if (rt_atrous_async(ctx, &at, stream) != RT_OK) return die("rt_atrous_async");
     if (rt_read_atrous(ctx, nullptr, px.data()) != RT_OK) return die("rt_read_atrous");
-    printf("{\"atrous\": true, \"levels\": %d, \"k_lum\": %.3f, \"k_normal\": %.3f, \"atrous_wall_ms\": %.4f}\n", at.levels, (double)at.k_lum,
-           (double)at.k_normal, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (hipEventSynchronize(ev[1]) != hipSuccess || hipEventElapsedTime(&features_ms, ev[0], ev[1]) != hipSuccess) return die("hipEventElapsedTime");
+    printf("{\"atrous\": true, \"levels\": %d, \"k_lum\": %.3f, \"k_normal\": %.3f, \"features_kernel\": \"%s\", \"features_device_ms\": %.4f, \"atrous_wall_ms\": %.4f}\n",
+           at.levels, (double)at.k_lum, (double)at.k_normal, rt_last_features_kernel(ctx), (double)features_ms,
+           std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return 0;
 }
 

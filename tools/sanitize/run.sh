@@ -4,8 +4,8 @@
 # good, truncated and missing files, seed stream, camera basis), the hierarchy's host builders,
 # the record of a context's resources (rt_owned.h, with a recorder in owned_free's place), the
 # record of which form renders a scene (rt_choice.h, with a log in the launches' place), the
-# rule that says which kernel instance a launch gets (rt_instance.h) and the record of what a
-# context holds of its scene (rt_scene_state.h).
+# rule that says which kernel instance a launch gets and which kernel forms the feature plane
+# (rt_instance.h) and the record of what a context holds of its scene (rt_scene_state.h).
 # Run from the repository root.
 set -eu
 R=$(cd "$(dirname "$0")/../.." && pwd)
@@ -37,6 +37,10 @@ $T/choice_san
 # which kernel instance a launch gets (rt_instance.h alone): the thresholds from either side, the LDS of every table kind, recorded real scenes
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/instance_main.cpp -o $T/instance_san
 $T/instance_san
+# which kernel forms the feature plane (rt_instance.h features_form, features_lds): no hierarchy, the count and the LDS limits from either side
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -ffp-contract=off -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/features_main.cpp \
+    $R/raytracing_simple_amd/csrc/rt_bvh_host.cpp -o $T/features_san
+$T/features_san
 # what a context holds of its scene (rt_scene_state.h alone), driven in the order the API's calls report to it
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I$R/raytracing_simple_amd/csrc $R/tools/sanitize/scene_main.cpp -o $T/scene_san
 $T/scene_san
